@@ -32,9 +32,23 @@ flight each, >= 1 s of timed work.
              cache level holds it) and ONE request carries 4 M candidates drawn from all of them - the gather of the
              assembly kernel against real HBM.  No CPU baseline / latency leg (the oracle does not hold 8 M items).
 
-One JSON line is printed by rank 0 (contract in the task statement) with two extra objects:
+One JSON line is printed by rank 0: metric, value, unit, higher_is_better, dtype, ms_per_step (one timed step), the
+configuration and the provenance of the build.  A plain run does only that: set up, warm up, time `--steps` steps, print.
+
+--full   everything else the benchmark measures, after the timed steps, in the same line:
+  kernels      per-kernel HIP-event times (a profiled loop of its own)
   roofline     dominant kernel, algorithmic bytes / HIP-event time vs the 8 TB/s HBM peak
-  cpu_baseline the CPU oracle (a scalar port of the reference's read path) on a bounded sample
+  e2e          the serving loop with fresh requests (above), Python and native host threads
+  latency      single-request latency, the reference's latency protocol (`--latency-sweep`), concurrent callers
+  encoder      c5: the other encoder precision, its parity with the headline one
+  multi_gpu_projection  c4 / c4x on one GPU: the ceiling of item sharding from this run's kernel split
+  cpu_baseline the CPU oracle (a scalar port of the reference's read path) on a bounded sample, parity of the GPU results with it
+
+--dump-outputs DIR   after the timed steps, what the last timed step computed, as the caller of the path receives it:
+  scores_stream<k>.npy (f64), order_stream<k>.npy (within-request positions, f32 - exact below 2^24) and
+  status_stream<k>.npy (per request) for every batch the last step ran, and c5's embeddings_stream<k>.npy (f32, the
+  forward pass of the step's queries).  At most 64 MB in all: beyond that every array is cut to the same fixed, seeded
+  sample of its flat positions.  The inputs are seeded: the same arguments give the same inputs in every run.
 """
 from __future__ import annotations
 
@@ -107,7 +121,14 @@ def main():
     ap.add_argument("--concurrent-requests", type=int, default=400, help="... requests per caller")
     ap.add_argument("--latency-sweep", type=int, default=None,
                     help="sequential requests per size of the reference's latency protocol (sizes 25..300; default 5000 for the default c2 run, 0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need (per-kernel times, roofline, e2e, latency, the encoder's "
+                         "other precision, CPU baseline and parity): the options above that steer those legs act only with --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (scores, order, status; c5: embeddings) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     wl = args.workload
     if args.requests is None:
         args.requests = {"c2": 3840, "c3": 384, "c4": 1, "c4x": 1, "c5": 3840}[wl]
@@ -217,7 +238,7 @@ def main():
 
     # ---- state: one generation pass feeds the device store (and the CPU oracle on rank 0, N=1)
     oracle = None
-    do_cpu = rank == 0 and n_gpus == 1 and args.cpu_sample > 0
+    do_cpu = args.full and rank == 0 and n_gpus == 1 and args.cpu_sample > 0
     if do_cpu:
         from oracle.assembly import OraclePlan, OracleStore, sort_order
         from oracle.forest import OracleForest
@@ -322,11 +343,12 @@ def main():
             ctx.comm_barrier()
 
     cur_enc = [enc]   # c5: the encoder whose forward pass a step runs (the other precision is timed after the main region)
+    last_emb = {}     # c5: the embeddings the latest forward pass of each stream's queries returned (--dump-outputs)
 
     def run_one(i):
         bt = batches[i % n_streams]
         if qtok is not None:
-            cur_enc[0].embed_ids(*qtok[i % n_streams])
+            last_emb[i % n_streams] = cur_enc[0].embed_ids(*qtok[i % n_streams])
         if sharded:   # this rank's slice -> one in-place RCCL all-gather of the f64 scores -> order (csrc/comm.cpp)
             bt.run_sharded(booster) if use_dist else bt.run(booster)
         else:
@@ -365,6 +387,58 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     value = total_items * bps * (1 if sharded else n_gpus) * args.steps / elapsed
     ms_per_batch = ms_per_step / bps
+
+    if args.dump_outputs and rank == 0:
+        arrays = {}
+        for k in sorted({((args.steps - 1) * bps + j) % n_streams for j in range(bps)}):   # the batches the last timed step ran
+            sc, od, _ = batches[k].fetch()
+            arrays[f"scores_stream{k}"] = sc
+            arrays[f"order_stream{k}"] = od
+            arrays[f"status_stream{k}"] = batches[k].status()
+            if k in last_emb:
+                arrays[f"embeddings_stream{k}"] = last_emb[k]
+        dump_outputs(args.dump_outputs, arrays)
+        log(f"outputs of the last timed step: {', '.join(sorted(arrays))} -> {args.dump_outputs}")
+
+    # the headline: what a plain run prints (--full adds its legs' objects to the same line)
+    head = {
+        "metric": f"ranked items/sec (feature assembly + {args.trees}-tree LambdaMART + ordering), Ranklens-shaped {args.items}-item requests",
+        "value": value, "unit": "items/s", "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": ms_per_step, "ms_per_device_batch": ms_per_batch, "higher_is_better": True, "scaling": "strong" if sharded else "weak", "vs_baseline": None,
+        "dtype": "f64" if args.backend == "lightgbm" else "f32", "data": "synthetic", "full": args.full,
+        "config": {"workload": f"ranklens-{args.items}item-{dim}col-{args.trees}tree-" + (args.backend if args.backend == "lightgbm" else f"xgboost-depth{args.depth}"), "requests_per_step_per_gpu": args.requests,
+                   "items_per_request": args.items, "device_batches_per_step": bps, "items_per_device_batch": total_items, "items_per_step_per_gpu": total_items * bps, "catalogue_items": n_catalogue, "item_table_bytes": int(n_catalogue) * ranker.item_stride(),
+                   "sessions": args.sessions, "columns": dim, "split_candidates_per_column": args.quantiles, "trees": info["n_trees"], "leaves_per_tree": 16 if args.backend == "lightgbm" else 2 ** args.depth, "backend": args.backend,
+                   "scorer": "bit-vector" if info["bitvector"] else "tree walk",
+                   "tile_columns": info["tile_columns"], "batches_in_flight": n_streams,
+                   "parallelism": (f"item-sharded x{n_gpus}" if sharded else f"request-sharded x{n_gpus}") +
+                                  (", RCCL all-gather of scores" if n_gpus > 1 else "")},
+        "value_is": "device-resident throughput: the requests of a step are resolved and in HBM before the clock starts (bench contract); "
+                    "the end-to-end serving rate with fresh requests per batch is `e2e` (--full)",
+        # WHICH code this run measured: the library's source digest and the key (hash of the translation unit) of every
+        # specialised kernel loaded for the model.  tools/pmc_summary.py copies the same object out of the profiled run's
+        # output into each committed summary; counters of another build or another kernel are dropped (--full), not quoted.
+        "provenance": {"build_id": M.lib().mrk_build_id().decode(), "jit_kernels": ranker.kernel_keys(model_name)},
+    }
+    provenance = head["provenance"]
+
+    def finish():
+        for bt in batches:
+            bt.close()
+        booster.close()
+        if use_dist:
+            ctx.comm_barrier()
+            if rank == 0 and n_gpus > 1:
+                try:
+                    os.remove(f"/tmp/mrk_comm_{comm_key}.id")
+                except OSError:
+                    pass
+
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(head), flush=True)
+        finish()
+        return
 
     # ---- per-kernel HIP-event timing (outside the timed region, one batch at a time: the events add a little
     #      overhead and overlapping batches would stretch each other's kernels)
@@ -436,10 +510,6 @@ def main():
     valu_issue = {}
     pmc_stale = None   # None: no committed counters for this shape; True: they were collected on OTHER code and are not quoted
     jit_on = os.environ.get("MRK_RANK_JIT", "1") not in ("0",)
-    # WHICH code this run measured: the library's source digest and the key (hash of the translation unit) of every
-    # specialised kernel loaded for the model.  tools/pmc_summary.py copies the same object out of the profiled run's
-    # output into each committed summary; counters of another build or another kernel are dropped here, not quoted.
-    provenance = {"build_id": M.lib().mrk_build_id().decode(), "jit_kernels": ranker.kernel_keys(model_name)}
     # the kernel behind `dominant` in the newest committed summary of this workload (names change with the batch shape:
     # mrk_jit_rank_cells / _split / mrk_jit_assemble_cells; qs_score_wave_kernel / qs_score_split_kernel)
     prefixes = {"rank_fused": ("mrk_jit_rank_fused_score", "rank_fused_score"), "score": ("qs_score",), "assemble": ("mrk_jit_rank_cells", "mrk_jit_assemble_cells") if jit_on else ("rank_fused_cells", "assemble_cells")}
@@ -1006,40 +1076,34 @@ def main():
             assert np.array_equal(scores[lo:hi], chk[r][0]) and np.array_equal(order[lo:hi], chk[r][1]), f"parity broke at request {r}"
 
     if rank == 0:
-        out = {
-            "metric": f"ranked items/sec (feature assembly + {args.trees}-tree LambdaMART + ordering), Ranklens-shaped {args.items}-item requests",
-            "value": value, "unit": "items/s", "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms_per_step, "ms_per_device_batch": ms_per_batch, "higher_is_better": True, "scaling": "strong" if sharded else "weak", "vs_baseline": None,
-            "dtype": "f64" if args.backend == "lightgbm" else "f32", "data": "synthetic",
-            "config": {"workload": f"ranklens-{args.items}item-{dim}col-{args.trees}tree-" + (args.backend if args.backend == "lightgbm" else f"xgboost-depth{args.depth}"), "requests_per_step_per_gpu": args.requests,
-                       "items_per_request": args.items, "device_batches_per_step": bps, "items_per_device_batch": total_items, "items_per_step_per_gpu": total_items * bps, "catalogue_items": n_catalogue, "item_table_bytes": int(n_catalogue) * ranker.item_stride(),
-                       "sessions": args.sessions, "columns": dim, "split_candidates_per_column": args.quantiles, "trees": info["n_trees"], "leaves_per_tree": 16 if args.backend == "lightgbm" else 2 ** args.depth, "backend": args.backend,
-                       "scorer": "bit-vector" if info["bitvector"] else "tree walk",
-                       "tile_columns": V, "batches_in_flight": n_streams,
-                       "parallelism": (f"item-sharded x{n_gpus}" if sharded else f"request-sharded x{n_gpus}") +
-                                      (", RCCL all-gather of scores" if n_gpus > 1 else "")},
-            "value_is": "device-resident throughput: the requests of a step are resolved and in HBM before the clock starts (bench contract); "
-                        "the end-to-end serving rate with fresh requests per batch is `e2e`",
-            "e2e": e2e,
-            "latency": latency,
-            "encoder": encoder_out,
-            "kernels": kernels,
-            "multi_gpu_projection": projection,
-            "roofline": roofline,
-            "cpu_baseline": cpu,
-            "provenance": provenance,
-        }
+        out = dict(head, e2e=e2e, latency=latency, encoder=encoder_out, kernels=kernels, multi_gpu_projection=projection,
+                   roofline=roofline, cpu_baseline=cpu)
         print(json.dumps(out), flush=True)
-    for bt in batches:
-        bt.close()
-    booster.close()
-    if use_dist:
-        ctx.comm_barrier()
-        if rank == 0 and n_gpus > 1:
-            try:
-                os.remove(f"/tmp/mrk_comm_{comm_key}.id")
-            except OSError:
-                pass
+    finish()
+
+
+def dump_outputs(out_dir, arrays, limit=60_000_000):   # under 64 MB with the .npy headers, in either unit
+    """arrays {name: ndarray} -> out_dir/<name>.npy: floating arrays keep their precision (f64 / f32), integers become f32
+    (exact below 2^24) or f64.  Over `limit` bytes in all, every array is cut to the same fixed, seeded sample of its flat
+    positions (the same positions for the same shapes in every run)."""
+    os.makedirs(out_dir, exist_ok=True)
+    conv = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.dtype.kind == "f":
+            a = a.astype(np.float64 if a.dtype.itemsize > 4 else np.float32, copy=False)
+        else:
+            small = a.size == 0 or int(np.abs(a.astype(np.int64)).max()) < (1 << 24)
+            a = a.astype(np.float32 if small else np.float64)
+        conv[name] = a
+    total = sum(a.nbytes for a in conv.values())
+    for name in sorted(conv):
+        a = conv[name]
+        if total > limit:
+            keep = max(min(a.size, 1), a.size * limit // total)
+            pos = np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))
+            a = a.reshape(-1)[pos]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 if __name__ == "__main__":

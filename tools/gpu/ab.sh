@@ -3,7 +3,7 @@ cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 O=gpurun_out/${TAG:-ab}
 mkdir -p $O
 for rep in 1 2; do for v in $VARIANTS; do for w in ${WL:-c2}; do
-  MRK_LIB=$PWD/ab/$v/libmrk_hip.so timeout 300 python bench.py --workload $w --steps 10 --warmup 2 --cpu-sample 0 --latency-requests ${LAT:-0} --e2e-seconds 0 > $O/${v}_${w}_$rep.json 2> $O/${v}_${w}_$rep.log || tail -3 $O/${v}_${w}_$rep.log
+  MRK_LIB=$PWD/ab/$v/libmrk_hip.so timeout 300 python bench.py --full --workload $w --steps 10 --warmup 2 --cpu-sample 0 --latency-requests ${LAT:-0} --e2e-seconds 0 > $O/${v}_${w}_$rep.json 2> $O/${v}_${w}_$rep.log || tail -3 $O/${v}_${w}_$rep.log
   python - $v $w $rep $O/${v}_${w}_$rep.json <<'PY'
 import json, sys
 try:

@@ -1,10 +1,10 @@
 #!/bin/bash
 # ablation of the assembly kernel by feature family (bench.py --drop-features), one line per variant
-cd "$GRAFT_REPO_ROOT"; mkdir -p gpurun_out/ablate
-run() { tag=$1; shift; timeout 300 python bench.py --steps 10 --warmup 2 --cpu-sample 0 --latency-requests 0 --streams 1 "$@" > gpurun_out/ablate/$tag.json 2> gpurun_out/ablate/$tag.log || tail -5 gpurun_out/ablate/$tag.log
+cd "$(dirname "$0")/../.."; export BENCH_OUT=${BENCH_OUT:-bench_out}; mkdir -p $BENCH_OUT/ablate
+run() { tag=$1; shift; timeout 300 python bench.py --full --steps 10 --warmup 2 --cpu-sample 0 --latency-requests 0 --streams 1 "$@" > $BENCH_OUT/ablate/$tag.json 2> $BENCH_OUT/ablate/$tag.log || tail -5 $BENCH_OUT/ablate/$tag.log
 python - <<PY
 import json
-d=json.load(open("gpurun_out/ablate/$tag.json"))
+d=json.load(open("$BENCH_OUT/ablate/$tag.json"))
 print("$tag".ljust(14), round(d['value']/1e6,1),'M items/s', round(d['ms_per_step'],3),'ms', {k:round(v['avg_ms']*v['launches_per_step'],3) for k,v in d['kernels'].items()}, d['config']['columns'], d['config']['tile_columns'])
 PY
 }

@@ -17,10 +17,10 @@ PY
 }
 for v in "regs1" "regs0:MRK_JIT_REGS=0" "regs1w3:MRK_JIT_WAVES=3" "regs1w4:MRK_JIT_WAVES=4" "regs0w4:MRK_JIT_REGS=0 MRK_JIT_WAVES=4"; do
   name=${v%%:*}; envs=""; [[ "$v" == *:* ]] && envs=${v#*:}
-  env $envs timeout 600 python bench.py --workload c2 $Q > $O/c2_$name.json 2> $O/c2_$name.log || tail -3 $O/c2_$name.log
+  env $envs timeout 600 python bench.py --full --workload c2 $Q > $O/c2_$name.json 2> $O/c2_$name.log || tail -3 $O/c2_$name.log
   show "c2 $name" $O/c2_$name.json
-  env $envs timeout 900 python bench.py --workload c4x --clones 19 --items 2000000 $Q > $O/c4x_$name.json 2> $O/c4x_$name.log || tail -3 $O/c4x_$name.log
+  env $envs timeout 900 python bench.py --full --workload c4x --clones 19 --items 2000000 $Q > $O/c4x_$name.json 2> $O/c4x_$name.log || tail -3 $O/c4x_$name.log
   show "c4x(2M of 2M) $name" $O/c4x_$name.json
 done
-env MRK_RANK_JIT=0 timeout 900 python bench.py --workload c4x --clones 19 --items 2000000 $Q > $O/c4x_nojit.json 2> $O/c4x_nojit.log
+env MRK_RANK_JIT=0 timeout 900 python bench.py --full --workload c4x --clones 19 --items 2000000 $Q > $O/c4x_nojit.json 2> $O/c4x_nojit.log
 show "c4x(2M of 2M) nojit" $O/c4x_nojit.json

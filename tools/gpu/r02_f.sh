@@ -15,9 +15,9 @@ except Exception as e:
     print(sys.argv[1], 'FAILED', e)
 PY
 }
-timeout 600 python bench.py --workload c2 --backend xgboost --trees 100 --depth 6 $Q > $O/c2_xgb_d6.json 2> $O/c2_xgb_d6.log; show "c2 xgb 100x d6" $O/c2_xgb_d6.json
-env MRK_BENCH_FORCE_DIST=1 timeout 600 python bench.py --workload c2 $Q > $O/c2_dist1.json 2> $O/c2_dist1.log || tail -5 $O/c2_dist1.log; show "c2 through RCCL (world 1)" $O/c2_dist1.json
-env MRK_BENCH_FORCE_DIST=1 timeout 600 python bench.py --workload c4 $Q > $O/c4_dist1.json 2> $O/c4_dist1.log || tail -5 $O/c4_dist1.log; show "c4 through RCCL (world 1)" $O/c4_dist1.json
-timeout 600 python bench.py --workload c4 $Q > $O/c4.json 2> $O/c4.log; show "c4" $O/c4.json
+timeout 600 python bench.py --full --workload c2 --backend xgboost --trees 100 --depth 6 $Q > $O/c2_xgb_d6.json 2> $O/c2_xgb_d6.log; show "c2 xgb 100x d6" $O/c2_xgb_d6.json
+env MRK_BENCH_FORCE_DIST=1 timeout 600 python bench.py --full --workload c2 $Q > $O/c2_dist1.json 2> $O/c2_dist1.log || tail -5 $O/c2_dist1.log; show "c2 through RCCL (world 1)" $O/c2_dist1.json
+env MRK_BENCH_FORCE_DIST=1 timeout 600 python bench.py --full --workload c4 $Q > $O/c4_dist1.json 2> $O/c4_dist1.log || tail -5 $O/c4_dist1.log; show "c4 through RCCL (world 1)" $O/c4_dist1.json
+timeout 600 python bench.py --full --workload c4 $Q > $O/c4.json 2> $O/c4.log; show "c4" $O/c4.json
 MRK_DEFINES=MRK_PHASE_CLOCKS python -c "from metarank_amd import _native; _native.build(force=True)" > $O/phase_build.log 2>&1
 MRK_DEFINES=MRK_PHASE_CLOCKS timeout 600 python tools/phase_clocks.py c2 > $O/phase_c2.txt 2>&1; tail -40 $O/phase_c2.txt

@@ -16,19 +16,19 @@ except Exception as e:
 PY
 }
 for w in c2 c3 c4 c5 c4x; do
-  timeout 900 python bench.py --workload $w > $O/bench_$w.json 2> $O/bench_$w.log || tail -5 $O/bench_$w.log
+  timeout 900 python bench.py --full --workload $w > $O/bench_$w.json 2> $O/bench_$w.log || tail -5 $O/bench_$w.log
   show $w $O/bench_$w.json
 done
-timeout 900 python bench.py --backend xgboost --trees 100 --depth 6 > $O/bench_c2_xgb100_d6.json 2> $O/bench_c2_xgb100_d6.log; show "config 2 as written (xgboost 100 x depth 6)" $O/bench_c2_xgb100_d6.json
-timeout 900 python bench.py --backend xgboost --trees 100 --depth 8 --cpu-sample 0 > $O/bench_c2_xgb100_d8.json 2> $O/bench_c2_xgb100_d8.log; show "xgboost 100 x depth 8" $O/bench_c2_xgb100_d8.json
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_c2 -o s -- python bench.py --steps 2 --warmup 1 --cpu-sample 0 --latency-requests 0 --e2e-seconds 0 > $O/stats_c2.log 2>&1
+timeout 900 python bench.py --full --backend xgboost --trees 100 --depth 6 > $O/bench_c2_xgb100_d6.json 2> $O/bench_c2_xgb100_d6.log; show "config 2 as written (xgboost 100 x depth 6)" $O/bench_c2_xgb100_d6.json
+timeout 900 python bench.py --full --backend xgboost --trees 100 --depth 8 --cpu-sample 0 > $O/bench_c2_xgb100_d8.json 2> $O/bench_c2_xgb100_d8.log; show "xgboost 100 x depth 8" $O/bench_c2_xgb100_d8.json
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_c2 -o s -- python bench.py --full --steps 2 --warmup 1 --cpu-sample 0 --latency-requests 0 --e2e-seconds 0 > $O/stats_c2.log 2>&1
 PMC="--steps 3 --warmup 1 --batches-per-step 1 --streams 1 --cpu-sample 0 --latency-requests 0 --e2e-seconds 0"
-run() { w=$1; name=$2; shift 2; timeout 900 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $O/pmc_${w}_$name -o s -- python bench.py --workload $w $PMC > $O/pmc_${w}_$name.log 2>&1; }
+run() { w=$1; name=$2; shift 2; timeout 900 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $O/pmc_${w}_$name -o s -- python bench.py --full --workload $w $PMC > $O/pmc_${w}_$name.log 2>&1; }
 for w in c2 c3 c4x; do
 run $w fetch FETCH_SIZE
 run $w write WRITE_SIZE
 run $w wait SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats1_$w -o s -- python bench.py --workload $w $PMC > $O/stats1_$w.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats1_$w -o s -- python bench.py --full --workload $w $PMC > $O/stats1_$w.log 2>&1
 python tools/pmc_summary.py $O/pmc_${w}_fetch $O/pmc_${w}_write $O/pmc_${w}_wait $O/stats1_$w > $O/pmc_${w}_summary.json
 python - <<PY
 import json

@@ -14,9 +14,9 @@ except Exception as e:
     print(sys.argv[1], 'FAILED', e)
 PY
 }
-timeout 600 python bench.py --workload c2 $Q > $O/c2.json 2> $O/c2.log; show "c2" $O/c2.json
-timeout 600 python bench.py --workload c3 $Q > $O/c3.json 2> $O/c3.log; show "c3" $O/c3.json
-timeout 600 python bench.py --workload c4 $Q > $O/c4.json 2> $O/c4.log; show "c4" $O/c4.json
-timeout 900 python bench.py --workload c4x --clones 19 --items 2000000 $Q > $O/c4x.json 2> $O/c4x.log; show "c4x(2M of 2M)" $O/c4x.json
+timeout 600 python bench.py --full --workload c2 $Q > $O/c2.json 2> $O/c2.log; show "c2" $O/c2.json
+timeout 600 python bench.py --full --workload c3 $Q > $O/c3.json 2> $O/c3.log; show "c3" $O/c3.json
+timeout 600 python bench.py --full --workload c4 $Q > $O/c4.json 2> $O/c4.log; show "c4" $O/c4.json
+timeout 900 python bench.py --full --workload c4x --clones 19 --items 2000000 $Q > $O/c4x.json 2> $O/c4x.log; show "c4x(2M of 2M)" $O/c4x.json
 MRK_DEFINES=MRK_PHASE_CLOCKS python -c "from metarank_amd import _native; _native.build(force=True)" > $O/phase_build.log 2>&1
 MRK_DEFINES=MRK_PHASE_CLOCKS timeout 600 python tools/phase_clocks.py c2 > $O/phase_c2.txt 2>&1; tail -32 $O/phase_c2.txt

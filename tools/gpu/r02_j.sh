@@ -4,7 +4,7 @@ TAG=${TAG:-r02_j}
 O=gpurun_out/$TAG
 mkdir -p $O
 timeout 900 python -m pytest tests/test_encoder_gpu.py -m gpu -x -q > $O/pytest.log 2>&1; grep -E "passed|failed|rror" $O/pytest.log | tail -5
-timeout 900 python bench.py --workload c5 --cpu-sample 0 > $O/bench_c5.json 2> $O/bench_c5.log || tail -5 $O/bench_c5.log
+timeout 900 python bench.py --full --workload c5 --cpu-sample 0 > $O/bench_c5.json 2> $O/bench_c5.log || tail -5 $O/bench_c5.log
 python - <<PY
 import json
 d = json.load(open("$O/bench_c5.json"))

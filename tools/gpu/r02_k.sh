@@ -13,12 +13,12 @@ except Exception as e:
     print(sys.argv[1], 'FAILED', e)
 PY
 }
-timeout 900 python bench.py --cpu-sample 0 > $O/bench_c2.json 2> $O/bench_c2.log; show c2 $O/bench_c2.json
-env MRK_FUSED_SPLIT=1 MRK_QS_SPLIT=8 timeout 900 python bench.py --cpu-sample 0 --e2e-seconds 0 --steps 2 --warmup 1 > $O/bench_c2_nosplit.json 2> $O/bench_c2_nosplit.log; show "c2 (no op split, 8-way trees)" $O/bench_c2_nosplit.json
-env MRK_FUSED_SPLIT=2 timeout 900 python bench.py --cpu-sample 0 --e2e-seconds 0 --steps 2 --warmup 1 > $O/bench_c2_split2.json 2> $O/bench_c2_split2.log; show "c2 (op split 2)" $O/bench_c2_split2.json
-timeout 900 python bench.py --workload c3 --cpu-sample 0 --e2e-seconds 0 --steps 2 --warmup 1 > $O/bench_c3.json 2> $O/bench_c3.log; show c3 $O/bench_c3.json
-timeout 900 python bench.py --workload c5 --cpu-sample 0 > $O/bench_c5.json 2> $O/bench_c5.log; show c5 $O/bench_c5.json
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/lat -o s -- python bench.py --steps 1 --warmup 1 --batches-per-step 1 --cpu-sample 0 --e2e-seconds 0 --latency-requests 300 > $O/lat.json 2> $O/lat.log
+timeout 900 python bench.py --full --cpu-sample 0 > $O/bench_c2.json 2> $O/bench_c2.log; show c2 $O/bench_c2.json
+env MRK_FUSED_SPLIT=1 MRK_QS_SPLIT=8 timeout 900 python bench.py --full --cpu-sample 0 --e2e-seconds 0 --steps 2 --warmup 1 > $O/bench_c2_nosplit.json 2> $O/bench_c2_nosplit.log; show "c2 (no op split, 8-way trees)" $O/bench_c2_nosplit.json
+env MRK_FUSED_SPLIT=2 timeout 900 python bench.py --full --cpu-sample 0 --e2e-seconds 0 --steps 2 --warmup 1 > $O/bench_c2_split2.json 2> $O/bench_c2_split2.log; show "c2 (op split 2)" $O/bench_c2_split2.json
+timeout 900 python bench.py --full --workload c3 --cpu-sample 0 --e2e-seconds 0 --steps 2 --warmup 1 > $O/bench_c3.json 2> $O/bench_c3.log; show c3 $O/bench_c3.json
+timeout 900 python bench.py --full --workload c5 --cpu-sample 0 > $O/bench_c5.json 2> $O/bench_c5.log; show c5 $O/bench_c5.json
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/lat -o s -- python bench.py --full --steps 1 --warmup 1 --batches-per-step 1 --cpu-sample 0 --e2e-seconds 0 --latency-requests 300 > $O/lat.json 2> $O/lat.log
 python - <<PY
 import csv
 for r in csv.DictReader(open("$O/lat/s_kernel_stats.csv")):

@@ -14,11 +14,11 @@ except Exception as e:
 PY
 }
 for nw in 1 2 4 8 16; do
-  env MRK_QS_SPLIT=$nw timeout 600 python bench.py --workload c2 $Q > $O/c2_nw$nw.json 2> $O/c2_nw$nw.log; show "c2 trees split $nw" $O/c2_nw$nw.json
+  env MRK_QS_SPLIT=$nw timeout 600 python bench.py --full --workload c2 $Q > $O/c2_nw$nw.json 2> $O/c2_nw$nw.log; show "c2 trees split $nw" $O/c2_nw$nw.json
 done
 for nw in 4 8; do
-  env MRK_QS_SPLIT=$nw timeout 600 python bench.py --workload c3 $Q > $O/c3_nw$nw.json 2> $O/c3_nw$nw.log; show "c3 trees split $nw" $O/c3_nw$nw.json
-  env MRK_QS_SPLIT=$nw timeout 600 python bench.py --workload c2 --streams 1 $Q > $O/c2s1_nw$nw.json 2> $O/c2s1_nw$nw.log; show "c2 one stream, trees split $nw" $O/c2s1_nw$nw.json
+  env MRK_QS_SPLIT=$nw timeout 600 python bench.py --full --workload c3 $Q > $O/c3_nw$nw.json 2> $O/c3_nw$nw.log; show "c3 trees split $nw" $O/c3_nw$nw.json
+  env MRK_QS_SPLIT=$nw timeout 600 python bench.py --full --workload c2 --streams 1 $Q > $O/c2s1_nw$nw.json 2> $O/c2s1_nw$nw.log; show "c2 one stream, trees split $nw" $O/c2s1_nw$nw.json
 done
-env MRK_QS_SPLIT=8 timeout 900 python bench.py --workload c4x --clones 19 --items 2000000 $Q > $O/c4x_nw8.json 2> $O/c4x_nw8.log; show "c4x(2M) trees split 8" $O/c4x_nw8.json
-env MRK_QS_SPLIT=8 timeout 600 python bench.py --workload c2 --backend xgboost --trees 500 --depth 4 $Q > $O/c2_xgbd4_nw8.json 2> $O/c2_xgbd4_nw8.log; show "c2 xgb 500 x d4 (f32 bit-vector), split 8" $O/c2_xgbd4_nw8.json
+env MRK_QS_SPLIT=8 timeout 900 python bench.py --full --workload c4x --clones 19 --items 2000000 $Q > $O/c4x_nw8.json 2> $O/c4x_nw8.log; show "c4x(2M) trees split 8" $O/c4x_nw8.json
+env MRK_QS_SPLIT=8 timeout 600 python bench.py --full --workload c2 --backend xgboost --trees 500 --depth 4 $Q > $O/c2_xgbd4_nw8.json 2> $O/c2_xgbd4_nw8.log; show "c2 xgb 500 x d4 (f32 bit-vector), split 8" $O/c2_xgbd4_nw8.json

@@ -16,9 +16,9 @@ except Exception as e:
 PY
 }
 for t in 512 256; do
-  env MRK_WALK_TILE=$t timeout 600 python bench.py --backend xgboost --trees 100 --depth 6 $Q > $O/xgb6_t$t.json 2> $O/xgb6_t$t.log; show "config 2, walk tile $t" $O/xgb6_t$t.json
-  env MRK_WALK_TILE=$t timeout 600 python bench.py --backend xgboost --trees 100 --depth 8 $Q > $O/xgb8_t$t.json 2> $O/xgb8_t$t.log; show "xgb depth 8, walk tile $t" $O/xgb8_t$t.json
+  env MRK_WALK_TILE=$t timeout 600 python bench.py --full --backend xgboost --trees 100 --depth 6 $Q > $O/xgb6_t$t.json 2> $O/xgb6_t$t.log; show "config 2, walk tile $t" $O/xgb6_t$t.json
+  env MRK_WALK_TILE=$t timeout 600 python bench.py --full --backend xgboost --trees 100 --depth 8 $Q > $O/xgb8_t$t.json 2> $O/xgb8_t$t.log; show "xgb depth 8, walk tile $t" $O/xgb8_t$t.json
 done
 for nb in 2 4 6; do
-  timeout 600 python bench.py --cpu-sample 0 --latency-requests 0 --steps 3 --warmup 1 --e2e-batches $nb > $O/e2e_nb$nb.json 2> $O/e2e_nb$nb.log; show "c2 e2e, $nb batches in flight" $O/e2e_nb$nb.json
+  timeout 600 python bench.py --full --cpu-sample 0 --latency-requests 0 --steps 3 --warmup 1 --e2e-batches $nb > $O/e2e_nb$nb.json 2> $O/e2e_nb$nb.log; show "c2 e2e, $nb batches in flight" $O/e2e_nb$nb.json
 done

@@ -16,7 +16,7 @@ except Exception as e:
 PY
 }
 for s in 0 1 2 3 4; do
-  env MRK_FUSED_SLICES=$s timeout 600 python bench.py --workload c3 $Q > $O/c3_s$s.json 2> $O/c3_s$s.log; show "c3, slices $s" $O/c3_s$s.json
+  env MRK_FUSED_SLICES=$s timeout 600 python bench.py --full --workload c3 $Q > $O/c3_s$s.json 2> $O/c3_s$s.log; show "c3, slices $s" $O/c3_s$s.json
 done
-timeout 600 python bench.py --workload c2 $Q > $O/c2.json 2> $O/c2.log; show "c2" $O/c2.json
-env MRK_FUSED_SLICES=2 MRK_FUSED_THREADS=64 timeout 600 python bench.py --workload c2 $Q > $O/c2_s2.json 2> $O/c2_s2.log; show "c2, 64 lanes x 2 slices" $O/c2_s2.json
+timeout 600 python bench.py --full --workload c2 $Q > $O/c2.json 2> $O/c2.log; show "c2" $O/c2.json
+env MRK_FUSED_SLICES=2 MRK_FUSED_THREADS=64 timeout 600 python bench.py --full --workload c2 $Q > $O/c2_s2.json 2> $O/c2_s2.log; show "c2, 64 lanes x 2 slices" $O/c2_s2.json

@@ -15,8 +15,8 @@ PY
 }
 for rep in 1 2; do
 for wl in c2 c3; do
-  env MRK_LIB=$PWD/metarank_amd/libmrk_hip_head.so timeout 600 python bench.py --workload $wl $Q > $O/${wl}_head$rep.json 2> $O/${wl}_head$rep.log; show "$wl head" $O/${wl}_head$rep.json
-  env MRK_FUSED_SLICES=1 timeout 600 python bench.py --workload $wl $Q > $O/${wl}_new$rep.json 2> $O/${wl}_new$rep.log; show "$wl new, slices off" $O/${wl}_new$rep.json
+  env MRK_LIB=$PWD/metarank_amd/libmrk_hip_head.so timeout 600 python bench.py --full --workload $wl $Q > $O/${wl}_head$rep.json 2> $O/${wl}_head$rep.log; show "$wl head" $O/${wl}_head$rep.json
+  env MRK_FUSED_SLICES=1 timeout 600 python bench.py --full --workload $wl $Q > $O/${wl}_new$rep.json 2> $O/${wl}_new$rep.log; show "$wl new, slices off" $O/${wl}_new$rep.json
 done
 done
 rocm-smi --showclocks 2>/dev/null | grep -E "sclk|mclk|fclk" | head

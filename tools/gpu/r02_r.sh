@@ -15,9 +15,9 @@ PY
 }
 for st in 1 2; do
 for s in 1 2 3 4; do
-  env MRK_FUSED_SLICES=$s timeout 600 python bench.py --workload c3 --streams $st $Q > $O/c3_st${st}_s$s.json 2> $O/c3_st${st}_s$s.log; show "c3, streams $st, slices $s" $O/c3_st${st}_s$s.json
+  env MRK_FUSED_SLICES=$s timeout 600 python bench.py --full --workload c3 --streams $st $Q > $O/c3_st${st}_s$s.json 2> $O/c3_st${st}_s$s.log; show "c3, streams $st, slices $s" $O/c3_st${st}_s$s.json
 done
 done
-env MRK_FUSED_SLICES=2 timeout 600 python bench.py --workload c3 --requests 96 --streams 1 $Q > $O/c3_96_s2.json 2> $O/c3_96_s2.log; show "c3 96 req, slices 2" $O/c3_96_s2.json
-env MRK_FUSED_SLICES=4 timeout 600 python bench.py --workload c3 --requests 96 --streams 1 $Q > $O/c3_96_s4.json 2> $O/c3_96_s4.log; show "c3 96 req, slices 4" $O/c3_96_s4.json
-env MRK_FUSED_SLICES=1 timeout 600 python bench.py --workload c3 --requests 96 --streams 1 $Q > $O/c3_96_s1.json 2> $O/c3_96_s1.log; show "c3 96 req, slices 1" $O/c3_96_s1.json
+env MRK_FUSED_SLICES=2 timeout 600 python bench.py --full --workload c3 --requests 96 --streams 1 $Q > $O/c3_96_s2.json 2> $O/c3_96_s2.log; show "c3 96 req, slices 2" $O/c3_96_s2.json
+env MRK_FUSED_SLICES=4 timeout 600 python bench.py --full --workload c3 --requests 96 --streams 1 $Q > $O/c3_96_s4.json 2> $O/c3_96_s4.log; show "c3 96 req, slices 4" $O/c3_96_s4.json
+env MRK_FUSED_SLICES=1 timeout 600 python bench.py --full --workload c3 --requests 96 --streams 1 $Q > $O/c3_96_s1.json 2> $O/c3_96_s1.log; show "c3 96 req, slices 1" $O/c3_96_s1.json

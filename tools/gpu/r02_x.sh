@@ -15,7 +15,7 @@ except Exception as e:
 PY
 }
 for l in 1 0 1 0; do
-  env MRK_PREPASS_LDS=$l timeout 600 python bench.py --workload c4 $Q > $O/c4_l$l.json 2> $O/c4_l$l.log; show "c4, pre-pass tables in LDS=$l" $O/c4_l$l.json
+  env MRK_PREPASS_LDS=$l timeout 600 python bench.py --full --workload c4 $Q > $O/c4_l$l.json 2> $O/c4_l$l.log; show "c4, pre-pass tables in LDS=$l" $O/c4_l$l.json
 done
-env MRK_RANK_FUSED=0 timeout 600 python bench.py --workload c2 $Q > $O/c2_unfused.json 2> $O/c2_unfused.log; show "c2 unfused, LDS pre-pass" $O/c2_unfused.json
-env MRK_RANK_FUSED=0 MRK_PREPASS_LDS=0 timeout 600 python bench.py --workload c2 $Q > $O/c2_unfused_l0.json 2> $O/c2_unfused_l0.log; show "c2 unfused, HBM pre-pass" $O/c2_unfused_l0.json
+env MRK_RANK_FUSED=0 timeout 600 python bench.py --full --workload c2 $Q > $O/c2_unfused.json 2> $O/c2_unfused.log; show "c2 unfused, LDS pre-pass" $O/c2_unfused.json
+env MRK_RANK_FUSED=0 MRK_PREPASS_LDS=0 timeout 600 python bench.py --full --workload c2 $Q > $O/c2_unfused_l0.json 2> $O/c2_unfused_l0.log; show "c2 unfused, HBM pre-pass" $O/c2_unfused_l0.json

@@ -15,5 +15,5 @@ except Exception as e:
 PY
 }
 for w in c2 c3 c4 c5; do
-  timeout 600 python bench.py --workload $w $Q > $O/$w.json 2> $O/$w.log; show "$w" $O/$w.json
+  timeout 600 python bench.py --full --workload $w $Q > $O/$w.json 2> $O/$w.log; show "$w" $O/$w.json
 done

@@ -5,7 +5,7 @@ O=gpurun_out/$TAG
 mkdir -p $O
 timeout 900 python -m pytest tests -m gpu -x -q > $O/pytest.log 2>&1; grep -E "passed|failed|rror" $O/pytest.log | tail -3
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2
-timeout 600 python bench.py > $O/bench_c2.json 2> $O/bench_c2.log; tail -c 600 $O/bench_c2.json | head -c 600; echo
+timeout 600 python bench.py --full > $O/bench_c2.json 2> $O/bench_c2.log; tail -c 600 $O/bench_c2.json | head -c 600; echo
 python - <<PY
 import json
 d = json.load(open("$O/bench_c2.json"))

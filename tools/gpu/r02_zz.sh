@@ -5,7 +5,7 @@ mkdir -p $O
 timeout 600 python -m pytest tests/test_score_gpu.py tests/test_rank_parity.py -m gpu -x -q > $O/pytest.log 2>&1; grep -E "passed|failed|rror" $O/pytest.log | tail -3
 Q="--steps 5 --warmup 2 --cpu-sample 0 --e2e-seconds 0 --latency-requests 100"
 for w in c2 c3; do
-  timeout 300 python bench.py --workload $w $Q > $O/$w.json 2> $O/$w.log
+  timeout 300 python bench.py --full --workload $w $Q > $O/$w.json 2> $O/$w.log
   python - <<PY
 import json
 d = json.load(open("$O/$w.json"))

@@ -10,7 +10,7 @@ mkdir -p $O
 tail -12 $O/pip_install.log
 timeout 1200 python -m pytest tests/test_big_sort_gpu.py tests/test_serving_loop.py -m gpu -x -q > $O/pytest_new.log 2>&1; tail -15 $O/pytest_new.log
 for w in c4 c4x; do
-  timeout 600 python bench.py --workload $w --steps 5 --warmup 2 --cpu-sample 0 --latency-requests 0 --e2e-seconds 0 > $O/bench_$w.json 2> $O/bench_$w.log || tail -5 $O/bench_$w.log
+  timeout 600 python bench.py --full --workload $w --steps 5 --warmup 2 --cpu-sample 0 --latency-requests 0 --e2e-seconds 0 > $O/bench_$w.json 2> $O/bench_$w.log || tail -5 $O/bench_$w.log
   python - $w $O/bench_$w.json <<'PY'
 import json, sys
 try:
@@ -20,8 +20,8 @@ except Exception as e:
     print(sys.argv[1], 'FAILED', e)
 PY
 done
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_c4x -o s -- python bench.py --workload c4x --steps 2 --warmup 1 --cpu-sample 0 --latency-requests 0 --e2e-seconds 0 > $O/stats_c4x.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_c4x -o s -- python bench.py --full --workload c4x --steps 2 --warmup 1 --cpu-sample 0 --latency-requests 0 --e2e-seconds 0 > $O/stats_c4x.log 2>&1
 head -25 $O/stats_c4x/*kernel_stats.csv 2>/dev/null | cut -c1-200
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_c4 -o s -- python bench.py --workload c4 --steps 2 --warmup 1 --cpu-sample 0 --latency-requests 0 --e2e-seconds 0 > $O/stats_c4.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_c4 -o s -- python bench.py --full --workload c4 --steps 2 --warmup 1 --cpu-sample 0 --latency-requests 0 --e2e-seconds 0 > $O/stats_c4.log 2>&1
 head -25 $O/stats_c4/*kernel_stats.csv 2>/dev/null | cut -c1-200
 find $O -name "*kernel_trace.csv" -size +1M -delete

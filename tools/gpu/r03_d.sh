@@ -3,7 +3,7 @@ cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 O=gpurun_out/r03_d
 mkdir -p $O
 for w in 4 3; do for s in 2 3 4; do
-  MRK_RANK_JIT=1 MRK_JIT_WAVES=$w timeout 300 python bench.py --streams $s --steps 10 --warmup 2 --cpu-sample 0 --latency-requests 0 --e2e-seconds 0 > $O/b_w${w}_s$s.json 2> $O/b_w${w}_s$s.log || tail -3 $O/b_w${w}_s$s.log
+  MRK_RANK_JIT=1 MRK_JIT_WAVES=$w timeout 300 python bench.py --full --streams $s --steps 10 --warmup 2 --cpu-sample 0 --latency-requests 0 --e2e-seconds 0 > $O/b_w${w}_s$s.json 2> $O/b_w${w}_s$s.log || tail -3 $O/b_w${w}_s$s.log
   python - $w $s $O/b_w${w}_s$s.json <<'PY'
 import json, sys
 try:

@@ -3,7 +3,7 @@ cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 O=gpurun_out/r03_f
 mkdir -p $O
 for w in c2 c3; do for p in 75 60 50 40 30; do
-  MRK_TABLE_LOAD_PCT=$p timeout 300 python bench.py --workload $w --steps 6 --warmup 2 --cpu-sample 0 --latency-requests 0 --e2e-seconds 0 > $O/b_${w}_p$p.json 2> $O/b_${w}_p$p.log || tail -3 $O/b_${w}_p$p.log
+  MRK_TABLE_LOAD_PCT=$p timeout 300 python bench.py --full --workload $w --steps 6 --warmup 2 --cpu-sample 0 --latency-requests 0 --e2e-seconds 0 > $O/b_${w}_p$p.json 2> $O/b_${w}_p$p.log || tail -3 $O/b_${w}_p$p.log
   python - $w $p $O/b_${w}_p$p.json <<'PY'
 import json, sys
 try:

@@ -5,7 +5,7 @@ rm -rf $O; mkdir -p $O
 rocprofv3 -L 2>/dev/null | grep -i -E "LDS|TA_|TCP_" | head -60 > $O/counters.txt; wc -l $O/counters.txt
 ARGS="--streams 1 --steps 2 --warmup 1 --batches-per-step 2 --cpu-sample 0 --latency-requests 0 --e2e-seconds 0"
 run() { tag=$1; shift
-  MRK_RANK_JIT=1 timeout 300 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $O/$tag -o s -- python bench.py $ARGS > $O/$tag.log 2>&1 || tail -3 $O/$tag.log
+  MRK_RANK_JIT=1 timeout 300 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $O/$tag -o s -- python bench.py --full $ARGS > $O/$tag.log 2>&1 || tail -3 $O/$tag.log
 }
 run p1 SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_ADDR_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS SQ_ACTIVE_INST_LDS
 run p2 SQ_WAVES SQ_LDS_UNALIGNED_STALL SQ_LDS_MEM_VIOLATIONS SQ_LDS_ATOMIC_RETURN SQ_WAIT_INST_LDS SQ_INST_CYCLES_VMEM SQ_INSTS_FLAT SQ_INSTS_FLAT_LDS_ONLY

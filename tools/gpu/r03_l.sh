@@ -3,7 +3,7 @@ cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 O=gpurun_out/r03_l
 mkdir -p $O
 for m in 0 23000 27000 32000 40000; do for s in 2 3; do
-  MRK_FUSED_LDS_MIN=$m timeout 300 python bench.py --streams $s --steps 10 --warmup 2 --cpu-sample 0 --latency-requests 0 --e2e-seconds 0 > $O/b_m${m}_s$s.json 2> $O/b_m${m}_s$s.log || tail -3 $O/b_m${m}_s$s.log
+  MRK_FUSED_LDS_MIN=$m timeout 300 python bench.py --full --streams $s --steps 10 --warmup 2 --cpu-sample 0 --latency-requests 0 --e2e-seconds 0 > $O/b_m${m}_s$s.json 2> $O/b_m${m}_s$s.log || tail -3 $O/b_m${m}_s$s.log
   python - $m $s $O/b_m${m}_s$s.json <<'PY'
 import json, sys
 try:

@@ -3,7 +3,7 @@ cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 O=gpurun_out/r03_q
 mkdir -p $O
 for t in 1 2; do for nb in 3 5; do
-  timeout 300 python bench.py --steps 10 --warmup 2 --cpu-sample 0 --latency-requests 0 --e2e-seconds 1.5 --e2e-threads $t --e2e-batches $nb > $O/b_t${t}_n$nb.json 2> $O/b_t${t}_n$nb.log || tail -3 $O/b_t${t}_n$nb.log
+  timeout 300 python bench.py --full --steps 10 --warmup 2 --cpu-sample 0 --latency-requests 0 --e2e-seconds 1.5 --e2e-threads $t --e2e-batches $nb > $O/b_t${t}_n$nb.json 2> $O/b_t${t}_n$nb.log || tail -3 $O/b_t${t}_n$nb.log
   python - $t $nb $O/b_t${t}_n$nb.json <<'PY'
 import json, sys
 try:

@@ -4,7 +4,7 @@ O=gpurun_out/${TAG:-r03_quick}
 mkdir -p $O
 timeout 1200 python -m pytest tests/test_rank_parity.py tests/test_known_answers.py tests/test_rank_one_gpu.py -m gpu -x -q > $O/pytest.log 2>&1; tail -4 $O/pytest.log
 for w in ${WORKLOADS:-c2 c3}; do
-  timeout 300 python bench.py --workload $w --steps 10 --warmup 2 --cpu-sample 0 --latency-requests 200 --e2e-seconds 0 > $O/b_$w.json 2> $O/b_$w.log || tail -3 $O/b_$w.log
+  timeout 300 python bench.py --full --workload $w --steps 10 --warmup 2 --cpu-sample 0 --latency-requests 200 --e2e-seconds 0 > $O/b_$w.json 2> $O/b_$w.log || tail -3 $O/b_$w.log
   python - $w $O/b_$w.json <<'PY'
 import json, sys
 try:

@@ -2,7 +2,7 @@
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 O=gpurun_out/r03_r
 rm -rf $O; mkdir -p $O
-timeout 300 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $O/tr -o s -- python bench.py --steps 2 --warmup 1 --batches-per-step 4 --cpu-sample 0 --latency-requests 0 --e2e-seconds 0.25 > $O/tr.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $O/tr -o s -- python bench.py --full --steps 2 --warmup 1 --batches-per-step 4 --cpu-sample 0 --latency-requests 0 --e2e-seconds 0.25 > $O/tr.log 2>&1
 ls -la $O/tr | head; python - <<'PY'
 import csv, glob, collections
 O = "gpurun_out/r03_r/tr"

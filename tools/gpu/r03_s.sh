@@ -4,7 +4,7 @@ O=gpurun_out/${TAG:-r03_s}
 mkdir -p $O
 timeout 900 python -m pytest tests/test_rank_parity.py tests/test_serving_loop.py -m gpu -x -q > $O/pytest.log 2>&1; grep -E "passed|failed|error" $O/pytest.log | tail -2
 for nb in 3 4; do
-  timeout 300 python bench.py --steps 10 --warmup 2 --cpu-sample 0 --latency-requests 0 --e2e-seconds 1.5 --e2e-batches $nb > $O/b_n$nb.json 2> $O/b_n$nb.log || tail -3 $O/b_n$nb.log
+  timeout 300 python bench.py --full --steps 10 --warmup 2 --cpu-sample 0 --latency-requests 0 --e2e-seconds 1.5 --e2e-batches $nb > $O/b_n$nb.json 2> $O/b_n$nb.log || tail -3 $O/b_n$nb.log
   python - $nb $O/b_n$nb.json <<'PY'
 import json, sys
 try:

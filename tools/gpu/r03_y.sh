@@ -4,7 +4,7 @@ O=gpurun_out/r03_y
 mkdir -p $O
 export MRK_RANK_JIT=1 MRK_JIT_SHIPPED=0
 run() { tag=$1; st=$2; shift 2
-  env "$@" timeout 300 python bench.py --workload ${WLD:-c2} --streams $st --steps 10 --warmup 2 --cpu-sample 0 --latency-requests 0 --e2e-seconds ${E2E:-0} > $O/$tag.json 2> $O/$tag.log || tail -3 $O/$tag.log
+  env "$@" timeout 300 python bench.py --full --workload ${WLD:-c2} --streams $st --steps 10 --warmup 2 --cpu-sample 0 --latency-requests 0 --e2e-seconds ${E2E:-0} > $O/$tag.json 2> $O/$tag.log || tail -3 $O/$tag.log
   python - $tag $O/$tag.json <<'PY'
 import json, sys
 try:

@@ -4,7 +4,7 @@ O=gpurun_out/r03_zc
 mkdir -p $O
 export MRK_RANK_JIT=1 MRK_JIT_SHIPPED=0
 run() { tag=$1; w=$2; shift 2
-  env "$@" timeout 300 python bench.py --workload $w --steps 10 --warmup 2 --cpu-sample 0 --latency-requests 0 --e2e-seconds 0 > $O/${tag}_$w.json 2> $O/${tag}_$w.log || tail -3 $O/${tag}_$w.log
+  env "$@" timeout 300 python bench.py --full --workload $w --steps 10 --warmup 2 --cpu-sample 0 --latency-requests 0 --e2e-seconds 0 > $O/${tag}_$w.json 2> $O/${tag}_$w.log || tail -3 $O/${tag}_$w.log
   python - $tag $w $O/${tag}_$w.json <<'PY'
 import json, sys
 try:

@@ -3,7 +3,7 @@ cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 O=gpurun_out/r03_zd
 mkdir -p $O
 for rep in 1 2; do for p in 0 1; do for s in 2 3; do
-  MRK_SCORE_PRIORITY=$p timeout 300 python bench.py --streams $s --steps 10 --warmup 2 --cpu-sample 0 --latency-requests 0 --e2e-seconds 0 > $O/p${p}_s${s}_$rep.json 2> $O/p${p}_s${s}_$rep.log || tail -3 $O/p${p}_s${s}_$rep.log
+  MRK_SCORE_PRIORITY=$p timeout 300 python bench.py --full --streams $s --steps 10 --warmup 2 --cpu-sample 0 --latency-requests 0 --e2e-seconds 0 > $O/p${p}_s${s}_$rep.json 2> $O/p${p}_s${s}_$rep.log || tail -3 $O/p${p}_s${s}_$rep.log
   python - $p $s $O/p${p}_s${s}_$rep.json <<'PY'
 import json, sys
 try:

@@ -20,7 +20,7 @@ except Exception as e:
     print(sys.argv[1], 'FAILED', e)
 PY
 }
-run() { name=$1; shift; env "$@" timeout 300 python bench.py $B $EXTRA > $O/$name.json 2> $O/$name.log || tail -3 $O/$name.log; show $name $O/$name.json; }
+run() { name=$1; shift; env "$@" timeout 300 python bench.py --full $B $EXTRA > $O/$name.json 2> $O/$name.log || tail -3 $O/$name.log; show $name $O/$name.json; }
 {
 EXTRA="--workload c2 --latency-requests 300" run c2_default A=1
 EXTRA="--workload c3 --latency-requests 0" run c3_default A=1
@@ -35,7 +35,7 @@ run c2_default_again A=1
 } 2>&1 | tee $O/ab.txt
 # PMC: instruction mix and wait cycles of the c2 assembly kernel (separate passes; no trace domains with --pmc)
 ARGS="--workload c2 --streams 1 --steps 3 --warmup 1 --cpu-sample 0 --latency-requests 0 --e2e-seconds 0"
-pmc() { name=$1; shift; timeout 300 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $O/$name -o s -- python bench.py $ARGS > $O/$name.log 2>&1; }
+pmc() { name=$1; shift; timeout 300 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $O/$name -o s -- python bench.py --full $ARGS > $O/$name.log 2>&1; }
 pmc p1 SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_LDS SQ_ACTIVE_INST_VALU
 pmc p2 SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_IFETCH
 python tools/pmc_summary.py $O/p1 $O/p2 > $O/pmc_c2_summary.json

@@ -19,7 +19,7 @@ except Exception as e:
 PY
 }
 B="--steps 10 --warmup 2 --cpu-sample 0 --e2e-seconds 0"
-run() { name=$1; shift; env "$@" timeout 400 python bench.py $B $EXTRA > $O/$name.json 2> $O/$name.log || tail -3 $O/$name.log; show $name $O/$name.json; }
+run() { name=$1; shift; env "$@" timeout 400 python bench.py --full $B $EXTRA > $O/$name.json 2> $O/$name.log || tail -3 $O/$name.log; show $name $O/$name.json; }
 {
 for rep in 1 2; do
   EXTRA="--workload c2 --latency-requests 200" run c2_sig0_$rep MRK_JIT_SIG=0
@@ -36,7 +36,7 @@ EXTRA="--workload c4 --latency-requests 0" run c4_sig1 MRK_JIT_SIG=1
 } 2>&1 | tee $O/ab.txt
 # PMC: instruction mix and wait cycles of the c2 assembly kernel both ways (separate passes; no trace domains with --pmc)
 ARGS="--workload c2 --streams 1 --batches-per-step 1 --steps 3 --warmup 1 --cpu-sample 0 --latency-requests 0 --e2e-seconds 0"
-pmc() { name=$1; sig=$2; shift 2; MRK_JIT_SIG=$sig timeout 300 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $O/$name -o s -- python bench.py $ARGS > $O/$name.log 2>&1; }
+pmc() { name=$1; sig=$2; shift 2; MRK_JIT_SIG=$sig timeout 300 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $O/$name -o s -- python bench.py --full $ARGS > $O/$name.log 2>&1; }
 for sig in 0 1; do
 pmc p1_sig$sig $sig SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_LDS SQ_ACTIVE_INST_VALU
 pmc p2_sig$sig $sig SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_IFETCH

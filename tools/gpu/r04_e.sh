@@ -21,7 +21,7 @@ except Exception as e:
 PY
 }
 B="--steps 10 --warmup 2 --cpu-sample 0 --e2e-seconds 0"
-run() { name=$1; shift; env "$@" timeout 400 python bench.py $B $EXTRA > $O/$name.json 2> $O/$name.log || tail -3 $O/$name.log; show $name $O/$name.json; }
+run() { name=$1; shift; env "$@" timeout 400 python bench.py --full $B $EXTRA > $O/$name.json 2> $O/$name.log || tail -3 $O/$name.log; show $name $O/$name.json; }
 {
 for rep in 1 2; do
   EXTRA="--workload c4x --latency-requests 0" run c4x_arena_$rep MRK_ITEMS_LDS=0

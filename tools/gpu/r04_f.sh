@@ -18,7 +18,7 @@ except Exception as e:
 PY
 }
 B="--steps 10 --warmup 2 --cpu-sample 0 --e2e-seconds 0"
-run() { name=$1; shift; env "$@" timeout 400 python bench.py $B $EXTRA > $O/$name.json 2> $O/$name.log || tail -3 $O/$name.log; show $name $O/$name.json; }
+run() { name=$1; shift; env "$@" timeout 400 python bench.py --full $B $EXTRA > $O/$name.json 2> $O/$name.log || tail -3 $O/$name.log; show $name $O/$name.json; }
 {
 EXTRA="--workload c2 --latency-requests 200" run c2_default A=1
 EXTRA="--workload c2 --latency-requests 0 --streams 3" run c2_streams3 A=1

@@ -16,7 +16,7 @@ done
 for rep in 1 2; do for v in ${VARIANTS:-base e1 e5 e45 e10 e10p e11 e1_10 e1_10p e1_11 e145}; do for w in c2 c3; do
   [ $rep = 2 ] && [ $w = c3 ] && continue   # c3 once, c2 twice
   D="$(cat ab/$v/jit_defines)"
-  MRK_JIT_DEFINES="$D" MRK_LIB=$PWD/ab/$v/libmrk_hip.so timeout 300 python bench.py --workload $w --steps 10 --warmup 2 --cpu-sample 0 \
+  MRK_JIT_DEFINES="$D" MRK_LIB=$PWD/ab/$v/libmrk_hip.so timeout 300 python bench.py --full --workload $w --steps 10 --warmup 2 --cpu-sample 0 \
     --latency-requests $([ $w = c2 ] && echo 300 || echo 0) --e2e-seconds 0 > $O/${v}_${w}_$rep.json 2> $O/${v}_${w}_$rep.log || tail -3 $O/${v}_${w}_$rep.log
   python - $v $w $rep $O/${v}_${w}_$rep.json <<'PY'
 import json, sys
@@ -31,7 +31,7 @@ done; done; done 2>&1 | tee $O/ab.txt
 # the out-of-cache gather (4 M candidates over an 8 M-item table): the lookups of MRK_GET_PAIR are in its kernel too
 for v in base e45 e10p e11; do
   D="$(cat ab/$v/jit_defines)"
-  MRK_JIT_DEFINES="$D" MRK_LIB=$PWD/ab/$v/libmrk_hip.so timeout 300 python bench.py --workload c4x --steps 5 --warmup 1 --cpu-sample 0 --latency-requests 0 --e2e-seconds 0 \
+  MRK_JIT_DEFINES="$D" MRK_LIB=$PWD/ab/$v/libmrk_hip.so timeout 300 python bench.py --full --workload c4x --steps 5 --warmup 1 --cpu-sample 0 --latency-requests 0 --e2e-seconds 0 \
     > $O/${v}_c4x.json 2> $O/${v}_c4x.log || tail -3 $O/${v}_c4x.log
   python -c "
 import json,sys
@@ -40,7 +40,7 @@ done 2>&1 | tee -a $O/ab.txt
 
 # the UNFUSED path (pre-pass kernel + item-parallel assembly: tables through L2) under the same experiments: is the fused kernel still ahead?
 for v in base e1_10p e1_11; do
-  MRK_RANK_FUSED=0 MRK_JIT_DEFINES="$(cat ab/$v/jit_defines)" MRK_LIB=$PWD/ab/$v/libmrk_hip.so timeout 300 python bench.py --workload c2 --steps 10 --warmup 2 --cpu-sample 0 \
+  MRK_RANK_FUSED=0 MRK_JIT_DEFINES="$(cat ab/$v/jit_defines)" MRK_LIB=$PWD/ab/$v/libmrk_hip.so timeout 300 python bench.py --full --workload c2 --steps 10 --warmup 2 --cpu-sample 0 \
     --latency-requests 0 --e2e-seconds 0 > $O/${v}_c2_unfused.json 2> $O/${v}_c2_unfused.log || tail -3 $O/${v}_c2_unfused.log
   python -c "
 import json

@@ -20,7 +20,7 @@ except Exception as e:
 PY
 }
 B="--steps 10 --warmup 2 --cpu-sample 0 --e2e-seconds 1.5"
-run() { name=$1; shift; env "$@" timeout 400 python bench.py $B $EXTRA > $O/$name.json 2> $O/$name.log || tail -3 $O/$name.log; show $name $O/$name.json; }
+run() { name=$1; shift; env "$@" timeout 400 python bench.py --full $B $EXTRA > $O/$name.json 2> $O/$name.log || tail -3 $O/$name.log; show $name $O/$name.json; }
 {
 for rep in 1 2; do
   EXTRA="--workload c2 --latency-requests 0" run c2_old_$rep MRK_SORT_PRIORITY=0 MRK_HOST_THREADS=1
@@ -31,6 +31,6 @@ EXTRA="--workload c2 --latency-requests 100" run c2_default A=1
 EXTRA="--workload c3 --latency-requests 0" run c3_old MRK_SORT_PRIORITY=0 MRK_HOST_THREADS=1
 EXTRA="--workload c3 --latency-requests 0" run c3_default A=1
 } 2>&1 | tee $O/ab.txt
-timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_c2 -o s -- python bench.py --steps 2 --warmup 1 --cpu-sample 0 --latency-requests 0 --e2e-seconds 0 > $O/stats_c2.log 2>&1
+timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_c2 -o s -- python bench.py --full --steps 2 --warmup 1 --cpu-sample 0 --latency-requests 0 --e2e-seconds 0 > $O/stats_c2.log 2>&1
 head -5 $O/stats_c2/s_kernel_stats.csv | cut -c1-160 | tee -a $O/ab.txt
 find $O -name "*kernel_trace.csv" -size +1M -delete

@@ -6,7 +6,7 @@ mkdir -p $O
 timeout 1000 python -m pytest tests -m gpu -q -p no:cacheprovider > $O/pytest.log 2>&1; echo "pytest rc=$?" | tee -a $O/pytest.log
 grep -E "passed|failed|error" $O/pytest.log | tail -3
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; tail -2 $O/smoke.log
-timeout 600 python bench.py > $O/bench_c2.json 2> $O/bench_c2.log || tail -5 $O/bench_c2.log
+timeout 600 python bench.py --full > $O/bench_c2.json 2> $O/bench_c2.log || tail -5 $O/bench_c2.log
 python - $O/bench_c2.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))
@@ -16,7 +16,7 @@ print('roofline', r['kernel'], round(r['frac'], 4), 'traffic', r['traffic'], 'ra
 print('valu_issue', r['valu_issue'])
 print('cpu', d['cpu_baseline']['value'], d['cpu_baseline']['cores'])
 PY
-timeout 600 python bench.py --workload c4x --cpu-sample 0 > $O/bench_c4x.json 2> $O/bench_c4x.log
+timeout 600 python bench.py --full --workload c4x --cpu-sample 0 > $O/bench_c4x.json 2> $O/bench_c4x.log
 python - $O/bench_c4x.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

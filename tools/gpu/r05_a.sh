@@ -11,7 +11,7 @@ f=$(find $O/stats_enc_f32 -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && c
 find $O -name "*kernel_trace.csv" -size +1M -delete
 if [ -z "$SKIP_SUITE" ]; then
 timeout 1500 python -m pytest tests -m gpu -q -p no:cacheprovider -x > $O/pytest_gpu.log 2>&1; echo "gpu suite rc=$? $(grep -E 'passed|failed' $O/pytest_gpu.log | tail -1)"
-timeout 400 python bench.py > $O/bench_c2.json 2> $O/bench_c2.err; echo "bench rc=$?"; python - $O/bench_c2.json <<'PY'
+timeout 400 python bench.py --full > $O/bench_c2.json 2> $O/bench_c2.err; echo "bench rc=$?"; python - $O/bench_c2.json <<'PY'
 import json, sys
 try:
     d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -4,8 +4,8 @@ cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 O=gpurun_out/${TAG:-r05_b}
 mkdir -p $O
 timeout 1500 python -m pytest tests -m gpu -q -p no:cacheprovider -x > $O/pytest_gpu.log 2>&1; echo "gpu suite rc=$? $(grep -E 'passed|failed' $O/pytest_gpu.log | tail -1)"; grep -E "^FAILED|^ERROR|Error" $O/pytest_gpu.log | head -5
-timeout 600 python bench.py > $O/bench_c2.json 2> $O/bench_c2.err; echo "bench c2 rc=$?"
-timeout 600 python bench.py --workload c5 > $O/bench_c5.json 2> $O/bench_c5.err; echo "bench c5 rc=$?"
+timeout 600 python bench.py --full > $O/bench_c2.json 2> $O/bench_c2.err; echo "bench c2 rc=$?"
+timeout 600 python bench.py --full --workload c5 > $O/bench_c5.json 2> $O/bench_c5.err; echo "bench c5 rc=$?"
 python - $O <<'PY'
 import json, sys
 O = sys.argv[1]

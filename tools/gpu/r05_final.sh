@@ -10,7 +10,7 @@ timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_enc
 f=$(find $O/stats_enc_f32 -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $O/enc_f32_kernel_stats.csv
 timeout 300 python tools/encoder_bench.py --quick --precision f16 --json > $O/encoder_bench_f16.json 2>/dev/null
 echo "encoder f32: $(cat $O/encoder_bench_f32.json | tail -1)"; echo "encoder f16: $(cat $O/encoder_bench_f16.json | tail -1)"
-timeout 400 python bench.py --streams 3 --cpu-sample 0 --latency-requests 0 --e2e-seconds 0 > $O/bench_c2_streams3.json 2>/dev/null; python - $O/bench_c2_streams3.json <<'PY'
+timeout 400 python bench.py --full --streams 3 --cpu-sample 0 --latency-requests 0 --e2e-seconds 0 > $O/bench_c2_streams3.json 2>/dev/null; python - $O/bench_c2_streams3.json <<'PY'
 import json, sys
 try:
     d = json.load(open(sys.argv[1])); print("c2 with 3 streams:", round(d["value"] / 1e6, 1), "M items/s")

@@ -5,7 +5,7 @@ O=gpurun_out/${TAG:-r05_g}
 mkdir -p $O
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "smoke rc=$? $(tail -1 $O/smoke.log | cut -c1-200)"
 for w in c2 c4; do
-  MRK_BENCH_FORCE_DIST=1 timeout 400 python bench.py --workload $w --cpu-sample 0 --latency-requests 0 --e2e-seconds 0 > $O/bench_${w}_rccl_world1.json 2> $O/bench_${w}_rccl.err
+  MRK_BENCH_FORCE_DIST=1 timeout 400 python bench.py --full --workload $w --cpu-sample 0 --latency-requests 0 --e2e-seconds 0 > $O/bench_${w}_rccl_world1.json 2> $O/bench_${w}_rccl.err
   python - $O/bench_${w}_rccl_world1.json <<'PY'
 import json, sys
 try:
@@ -14,7 +14,7 @@ except Exception as e:
     print("failed", e)
 PY
 done
-timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_torchrun_n1.json 2> $O/bench_torchrun_n1.err; echo "torchrun rc=$?"
+timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_torchrun_n1.json 2> $O/bench_torchrun_n1.err; echo "torchrun rc=$?"
 python - $O/bench_torchrun_n1.json <<'PY'
 import json, sys
 try:

@@ -2,7 +2,7 @@
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 O=gpurun_out/r06_ao; mkdir -p $O
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -3 | tee $O/smoke.txt
-timeout 600 python bench.py > $O/bench_default.json 2> $O/bench_default.log; echo "bench rc=$?" | tee -a $O/smoke.txt
+timeout 600 python bench.py --full > $O/bench_default.json 2> $O/bench_default.log; echo "bench rc=$?" | tee -a $O/smoke.txt
 python - <<'PY' | tee -a $O/smoke.txt
 import json
 d=json.loads(open("gpurun_out/r06_ao/bench_default.json").read().strip().splitlines()[-1])

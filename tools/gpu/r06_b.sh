@@ -9,7 +9,7 @@ for rows in 384000 100000 4000000; do
   done
 done | tee $O/score_ab.txt
 for v in "MRK_QS_PIPE=0" "MRK_QS_PIPE=4" "MRK_QS_PIPE=0" "MRK_QS_PIPE=4"; do
-  env $v timeout 300 python bench.py --cpu-sample 0 --latency-requests 0 --e2e-seconds 0 > $O/bench_c2_$v.json 2>$O/bench_err.txt
+  env $v timeout 300 python bench.py --full --cpu-sample 0 --latency-requests 0 --e2e-seconds 0 > $O/bench_c2_$v.json 2>$O/bench_err.txt
   python - $O/bench_c2_$v.json "$v" <<'PY'
 import json, sys
 try:

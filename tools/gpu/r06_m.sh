@@ -5,7 +5,7 @@ export MRK_RANK_JIT=1
 timeout 1200 python -m pytest tests -m gpu -x -q -k "rank_parity or known_answers or write_path or big or serving" 2>&1 | tail -3 | tee $O/pytest_k.log
 for wl in c2 c3 c4; do
 for v in "MRK_LIB=$PWD/ab/base/libmrk_hip.so MRK_JIT_DEFINES=MRK_GET_K=1" "MRK_X=1" "MRK_LIB=$PWD/ab/base/libmrk_hip.so MRK_JIT_DEFINES=MRK_GET_K=1" "MRK_X=1"; do
-  env $v timeout 600 python bench.py --workload $wl --steps 5 --warmup 2 --cpu-sample 0 --latency-requests 100 --latency-sweep 0 --e2e-seconds 0 --concurrent-callers '' 2>$O/$wl.log | python -c "
+  env $v timeout 600 python bench.py --full --workload $wl --steps 5 --warmup 2 --cpu-sample 0 --latency-requests 100 --latency-sweep 0 --e2e-seconds 0 --concurrent-callers '' 2>$O/$wl.log | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('$wl ${v:0:12}', round(d['value']/1e6,1), 'M items/s', {k: round(x['avg_ms'],4) for k,x in d['kernels'].items()}, 'p50', (d.get('latency') or {}).get('p50_ms'))"
 done

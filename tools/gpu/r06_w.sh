@@ -3,7 +3,7 @@
 O=gpurun_out/r06_w; mkdir -p $O
 for wl in c2 c3 c4x; do
 for qn in 49 254; do
-  timeout 600 python bench.py --workload $wl --quantiles $qn --steps 5 --warmup 2 --cpu-sample 0 --latency-requests 200 --latency-sweep 0 --e2e-seconds 0 --concurrent-callers '' 2>$O/$wl.log | python -c "
+  timeout 600 python bench.py --full --workload $wl --quantiles $qn --steps 5 --warmup 2 --cpu-sample 0 --latency-requests 200 --latency-sweep 0 --e2e-seconds 0 --concurrent-callers '' 2>$O/$wl.log | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('$wl quantiles=$qn', round(d['value']/1e6,1), 'M items/s', {k: round(x['avg_ms'],4) for k,x in d['kernels'].items()}, 'p50', (d.get('latency') or {}).get('p50_ms'), 'tile columns', d['config'].get('tile_columns'))"
 done
