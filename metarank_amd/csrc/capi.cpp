@@ -64,6 +64,7 @@ static Switches read_switches() {
   s.jit_prepass = flag("MRK_JIT_PREPASS", true);
   s.qs_split = num("MRK_QS_SPLIT", -1);
   s.qs_kernel = num("MRK_QS_KERNEL", 1);
+  s.qs_byte = flag("MRK_QS_BYTE", true);
   s.qs_r = num("MRK_QS_R", 2);
   s.walk_tile = num("MRK_WALK_TILE", 0);
   s.encoder_graph = flag("MRK_ENCODER_GRAPH", false);
@@ -233,6 +234,7 @@ static void upload_model(mrk_ctx *ctx, mrk_model *m) {
   m->qs = pack_forest_qs(m->forest, m->forest.n_features);
   if (m->qs.ok) {
     up(m->d_qs_nodes, m->qs.nodes.data(), m->qs.nodes.size() * 4);
+    if (m->qs.byte_ok) up(m->d_qs_bnodes, m->qs.bnodes.data(), m->qs.bnodes.size() * 4);
     up(m->d_qs_leaves, m->qs.leaves.data(), m->qs.leaves.size());
     {  // the assembly kernel stages tables with 1 KiB wave-loads that may run past a table's end: slack after the last one
       std::vector<double> padded(m->qs.thr);

@@ -98,6 +98,9 @@ MRK_HD inline uint64_t id_hash_bytes(const uint8_t *s, size_t len) {
 constexpr int QS_SLOTS = 16;
 constexpr int QS_LEAVES = 16;
 constexpr int QS_TREE_WORDS = QS_SLOTS * 2;
+// byte mode (forest.hpp PackedForestQS::bnodes): three arrays of QS_SLOTS dwords per tree
+constexpr int QS_BYTE_TREE_WORDS = QS_SLOTS * 3;
+constexpr uint32_t QS_BYTE_KMAX = 254;  // largest threshold index of a byte-mode forest (cells are clamped to 255)
 constexpr int QS_MAX_VIEWS = 255;
 constexpr uint16_t QS_RIGHT = 0x7FFF;
 constexpr uint32_t QS_STAGE_CHUNK = 128;  // doubles one global_load_lds_dwordx4 of a wavefront moves (64 lanes x 16 B)

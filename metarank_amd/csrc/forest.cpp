@@ -867,6 +867,8 @@ PackedForestQS pack_forest_qs(const Forest &f, int n_cols) {
 
   if (pf.views.size() > (size_t)QS_MAX_VIEWS) return fail("more than 255 tile columns");
   pf.nodes.assign((size_t)(pf.n_trees + 1) * QS_TREE_WORDS, 0);
+  pf.bnodes.assign((size_t)(pf.n_trees + 1) * QS_BYTE_TREE_WORDS, 0);
+  bool byte_ok = true;
   pf.leaves.assign((size_t)pf.n_trees * QS_LEAVES * leaf_sz, 0);
   std::vector<int> lo, hi;  // per internal node: leaf positions [lo, hi) of its left subtree
   for (size_t ti = 0; ti < f.trees.size(); ++ti) {
@@ -909,6 +911,11 @@ PackedForestQS pack_forest_qs(const Forest &f, int n_cols) {
       }
     }
     uint32_t slot = 0, n_cat = 0;
+    uint32_t *bd = pf.bnodes.data() + ti * QS_BYTE_TREE_WORDS;
+    bd[QS_SLOTS - 1] = cat_first;
+    struct ByteSlot { uint32_t kv, ma, mb; };
+    ByteSlot groups[3][QS_SLOTS];  // A-only, crossing, B-only
+    uint32_t n_group[3] = {0, 0, 0};
     for (size_t i = 0; i < ni; ++i) {
       const int kind = node_kind(t, i);
       const uint32_t view = (uint32_t)view_ids.at({t.feat[i], kind});
@@ -931,9 +938,24 @@ PackedForestQS pack_forest_qs(const Forest &f, int n_cols) {
       nd[slot] = kbin | (kbin << 16);
       nd[QS_SLOTS + slot] = m | (view << 24);
       ++slot;
+      if (kbin > QS_BYTE_KMAX) byte_ok = false;
+      const uint32_t ma = m & 0xffu, mb = m >> 8;
+      const int g = mb == 0 ? 0 : (ma == 0 ? 2 : 1);
+      groups[g][n_group[g]++] = ByteSlot{kbin | (view << 24), (ma << 8) | (ma << 24), (mb << 8) | (mb << 24)};
     }
     nd[QS_SLOTS - 1] = cat_first | (n_cat << 24);
+    bd[QS_SLOTS - 1] = nd[QS_SLOTS - 1];
+    uint32_t bs = 0;
+    for (int g = 0; g < 3; ++g)
+      for (uint32_t j = 0; j < n_group[g]; ++j, ++bs) {
+        bd[bs] = groups[g][j].kv;
+        bd[QS_SLOTS + bs] = groups[g][j].ma;
+        bd[2 * QS_SLOTS + bs] = groups[g][j].mb;
+      }
+    bd[2 * QS_SLOTS - 1] = n_group[0] | ((n_group[0] + n_group[1]) << 8);  // (the A array's last word)
   }
+  pf.byte_ok = byte_ok;
+  if (!byte_ok) pf.bnodes.clear();
   pf.ok = true;
   return pf;
 }

@@ -154,6 +154,23 @@ PackedForest pack_forest(const Forest &f, uint32_t chunk_bytes);
 // words} and are tested against their bitset one by one.  One all-zero tree is appended so that the
 // scorer's prefetch of "the next tree" never leaves the array.
 // Leaves are stored in left-to-right position order, QS_LEAVES per tree.
+//
+// BYTE MODE: when every numerical node's k is <= QS_BYTE_KMAX (254: at most 255 distinct thresholds per numerical column,
+// LightGBM with max_bin <= 256) and the scorer clamps every cell to 255, d = k - cell lies in [-255, 254], so the high byte
+// of each 16-bit half of one v_pk_sub_i16 is already the node's 0xFF (false: left subtree removed) / 0x00 mask - no shift.
+// Eight bits cannot hold 16 leaves: removed leaves 0-7 are ORed into one accumulator, 8-15 into another, each in bits 8-15 /
+// 24-31 (the two rows), and one v_perm_b32 gathers the four high bytes into the 16-bit-per-row vector of the format above.
+// A node's left subtree [l, r) touches the first accumulator ("A-only", r <= 8), the second ("B-only", l >= 8) or both
+// ("crossing": an ancestor of leaves 7 and 8, at most 7 per tree).  `bnodes` holds per tree QS_BYTE_TREE_WORDS dwords,
+// three arrays of QS_SLOTS (three s_load_dwordx16), slots ordered [A-only | crossing | B-only | unused]:
+//   [0, 16)   k | view << 24: k for both halves (v_pk_sub_i16 op_sel_hi:[0,1]), `word >> 16` the view's M0;
+//             [15]: the categorical word (as in `nodes`)
+//   [16, 32)  A mask: leaves 0-7 of the left subtree in bits 8-15 and 24-31;  [31]: x | a << 8, x = A-only nodes,
+//             a = x + crossing nodes
+//   [32, 48)  B mask: leaves 8-15 of the left subtree, the same bits
+// so a tree ORs slots [0, a) into A and [x, 15) into B; an A-only slot's B mask and a B-only or unused slot's A mask are 0.
+// Categorical nodes keep the side list (their cells are not clamped).
+// One all-zero tree follows the last, as in `nodes`.
 // (constants and device structs of this format: device_types.hpp)
 
 struct PackedForestQS {
@@ -163,6 +180,8 @@ struct PackedForestQS {
   int n_trees = 0;
   std::vector<uint32_t> nodes;   // (n_trees + 1) * QS_SLOTS * 2
   std::vector<uint8_t> leaves;   // n_trees * QS_LEAVES * (8 | 4)
+  bool byte_ok = false;          // byte mode applies (every numerical node's k <= QS_BYTE_KMAX): `bnodes` is filled
+  std::vector<uint32_t> bnodes;  // (n_trees + 1) * QS_BYTE_TREE_WORDS
   std::vector<double> thr;
   // the same tables once more, COMPACT: back to back at their exact lengths (no 128-entry chunks, no padding) - a model with
   // 50 distinct thresholds per column is 9 KB here and 24 KB in `thr`; what the resident-table sinks keep in LDS.
@@ -174,7 +193,7 @@ struct PackedForestQS {
   std::vector<QsCatNode> cat_nodes;
   std::vector<uint32_t> cat_bits;
   size_t device_bytes() const {
-    return nodes.size() * 4 + leaves.size() + (thr.size() + thr_rt.size()) * 8 + feats.size() * 16 + views.size() * 4 + cat_nodes.size() * 16 + cat_bits.size() * 4;
+    return (nodes.size() + bnodes.size()) * 4 + leaves.size() + (thr.size() + thr_rt.size()) * 8 + feats.size() * 16 + views.size() * 4 + cat_nodes.size() * 16 + cat_bits.size() * 4;
   }
 };
 

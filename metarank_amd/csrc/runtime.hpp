@@ -158,6 +158,7 @@ struct Switches {
   int big_sort_tile = 0;       // MRK_BIG_SORT_TILE: candidates per workgroup of its classify / scatter passes (0: n / 512, at least 1 024)
   int qs_split = -1;           // MRK_QS_SPLIT
   int qs_kernel = 1;           // MRK_QS_KERNEL
+  bool qs_byte = true;         // MRK_QS_BYTE=0: the split scorer keeps the 16-bit node test for forests that qualify for byte mode (A/B runs)
   int qs_r = 2;                // MRK_QS_R
   int walk_tile = 0;           // MRK_WALK_TILE=256: the tree-walk scorer's rows per workgroup (default: 512 where the tile fits)
   bool encoder_graph = false;  // MRK_ENCODER_GRAPH
@@ -253,6 +254,7 @@ struct mrk_model {
   // bit-vector image (forests of <= 16-leaf trees); qs.ok == false => tree-walk kernel only
   mrk::PackedForestQS qs;
   mrk::QsSignature qs_sig;             // the image's view signature (forest.hpp): part of the key of the specialised assembly kernels
+  mrk::DevBuf d_qs_bnodes;             // byte-mode node image (qs.byte_ok)
   mrk::DevBuf d_qs_nodes, d_qs_leaves, d_qs_thr, d_qs_feats, d_qs_views, d_qs_catnodes, d_qs_cat;
 };
 

@@ -393,6 +393,120 @@ qs_score_split_kernel(const uint32_t *__restrict__ nodes, const uint8_t *__restr
   if (tid < QS_TILE_ROWS && row < rows) out[row] = F64 ? acc64 : (double)acc32;
 }
 
+// BYTE MODE of the split kernel (forest.hpp "byte mode", image PackedForestQS::bnodes): the forest's numerical nodes all have
+// k <= 254 and the slab's cells are clamped to 255 while it is staged (v_pk_min_u16), so one v_pk_sub_i16 per node leaves the
+// node's false-mask in the high byte of each row's half - no v_pk_ashrrev_i16.  Removed leaves 0-7 go to acc_a, 8-15 to acc_b
+// (both in bits 8-15 / 24-31), one v_perm_b32 gathers the high bytes into the 16-bit-per-row vector of the other kernels, and
+// the rest - categorical nodes, exit leaf, leaf adds in tree order - is the split kernel's: the exit leaves, hence the scores,
+// are the same bits.  Per tree 15 v_pk_sub_i16 + (a + 15 - x) v_and_or_b32 + 1 v_perm_b32 instead of 15 x 3 + 1.
+// The ladders run in guarded blocks of 4 slots (acc_a: blocks that start below a; acc_b: blocks that end above x): a block
+// may overrun a ladder's bound - an A-only slot's B mask and a B-only or unused slot's A mask are 0 - and costs one s_cmp and
+// one branch, where a fall-through switch on the exact count costs ~3x the scalar work (tools/native/issue_bench.hip).
+// Categorical nodes read their UNCLAMPED cells (category ids) from the global tile, not from the slab.
+template <int B0>
+__device__ __forceinline__ void qs_byte_block(uint32_t &acc, const uint32_t (&d)[QS_SLOTS - 1], const uint32_t (&m)[QS_SLOTS]) {
+#pragma unroll
+  for (int s = B0; s < B0 + 4 && s < QS_SLOTS - 1; ++s) asm("v_and_or_b32 %0, %1, %2, %0" : "+v"(acc) : "v"(d[s]), "s"(m[s]));
+}
+
+template <bool F64, int NW>
+__global__ void __launch_bounds__(NW * 64)
+qs_score_byte_split_kernel(const uint32_t *__restrict__ bnodes, const uint8_t *__restrict__ leaves,
+                           const QsCatNode *__restrict__ cat_nodes, const uint32_t *__restrict__ cat_bits,
+                           const uint16_t *__restrict__ cells, int n_trees, int V, int rows, double base,
+                           double *__restrict__ out) {
+  constexpr int LS = F64 ? 8 : 4;
+  constexpr int TREE_LEAF_BYTES = QS_LEAVES * LS;
+  constexpr int CH = 8 * NW;  // trees per chunk
+  extern __shared__ __align__(16) uint8_t smem[];
+  uint8_t *s_leaf = smem + (size_t)V * 256;
+  uint8_t *s_idx = s_leaf + CH * TREE_LEAF_BYTES;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const long long tile = blockIdx.x;
+  const uint16_t *tile_cells = cells + (size_t)tile * V * QS_TILE_ROWS;
+  {
+    const uint4 *src = (const uint4 *)tile_cells;
+    uint4 *dst = (uint4 *)smem;
+    typedef unsigned short ushort2v __attribute__((ext_vector_type(2)));
+    const ushort2v cap = {255, 255};
+    auto clamp = [&](uint32_t w) {  // v_pk_min_u16: QS_RIGHT -> 255, still above every k <= 254
+      return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_bit_cast(ushort2v, w), cap));
+    };
+    for (int i = tid; i < V * 16; i += NW * 64) {
+      const uint4 v = src[i];
+      dst[i] = make_uint4(clamp(v.x), clamp(v.y), clamp(v.z), clamp(v.w));
+    }
+  }
+  double acc64 = 0.0;
+  float acc32 = (float)base;
+  for (int c0 = 0; c0 < n_trees; c0 += CH) {
+    const int nt = min(CH, n_trees - c0);
+    __syncthreads();  // slab staged / previous chunk consumed
+    {
+      const uint4 *src = (const uint4 *)(leaves + (size_t)c0 * TREE_LEAF_BYTES);
+      uint4 *dst = (uint4 *)s_leaf;
+      for (int i = tid; i < nt * (TREE_LEAF_BYTES / 16); i += NW * 64) dst[i] = src[i];
+    }
+    for (int tt = wave; tt < nt; tt += NW) {
+      const uint32_t *nd = bnodes + (size_t)(c0 + tt) * QS_BYTE_TREE_WORDS;
+      uint32_t kv[QS_SLOTS], ma[QS_SLOTS], mb[QS_SLOTS];  // scalar loads: three s_load_dwordx16
+#pragma unroll
+      for (int s = 0; s < QS_SLOTS; ++s) {
+        kv[s] = nd[s];
+        ma[s] = nd[QS_SLOTS + s];
+        mb[s] = nd[2 * QS_SLOTS + s];
+      }
+      uint32_t d[QS_SLOTS - 1];
+#pragma unroll
+      for (int s = 0; s < QS_SLOTS - 1; ++s)  // (a DS add-TID read needs one wait state after the M0 write)
+        asm volatile("s_lshr_b32 m0, %1, 16\n\ts_nop 0\n\tds_read_addtid_b32 %0" : "=v"(d[s]) : "s"(kv[s]) : "memory");
+      __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): the reads above are invisible to the compiler
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int s = 0; s < QS_SLOTS - 1; ++s) {  // high byte of each half: 0xFF <=> cell > k (k: the word's low half, both rows)
+        const short2v k2 = __builtin_bit_cast(short2v, kv[s]);
+        d[s] = __builtin_bit_cast(uint32_t, __builtin_shufflevector(k2, k2, 0, 0) - __builtin_bit_cast(short2v, d[s]));
+      }
+      const uint32_t x = ma[QS_SLOTS - 1] & 0xffu, a = (ma[QS_SLOTS - 1] >> 8) & 0xffu;
+      uint32_t acc_a = 0, acc_b = 0;
+      qs_byte_block<0>(acc_a, d, ma);  // (a >= 1 for every tree with a node; harmless otherwise)
+      if (a > 4) qs_byte_block<4>(acc_a, d, ma);
+      if (a > 8) qs_byte_block<8>(acc_a, d, ma);
+      if (a > 12) qs_byte_block<12>(acc_a, d, ma);
+      if (x < 4) qs_byte_block<0>(acc_b, d, mb);
+      if (x < 8) qs_byte_block<4>(acc_b, d, mb);
+      if (x < 12) qs_byte_block<8>(acc_b, d, mb);
+      qs_byte_block<12>(acc_b, d, mb);
+      uint32_t accn = __builtin_amdgcn_perm(acc_b, acc_a, 0x07030501u);  // A.byte1, B.byte1, A.byte3, B.byte3
+      const uint32_t catw = kv[QS_SLOTS - 1];
+      if (catw >> 24) {
+        const QsCatNode *cn = cat_nodes + (catw & 0xffffffu);
+        for (uint32_t j = 0; j < (catw >> 24); ++j) {
+          const QsCatNode cnode = cn[j];
+          const uint32_t cc = *(const uint32_t *)(tile_cells + (size_t)(cnode.view_dl & 0xffffu) * QS_TILE_ROWS + lane * 2);
+          accn |= qs_cat_pair<F64>(cnode, cc, cat_bits);
+        }
+      }
+      const uint32_t inv = ~accn;
+      const uint32_t pair = (uint32_t)__builtin_ctz(inv) | ((uint32_t)__builtin_ctz(inv >> 16) << 8);
+      *(uint16_t *)(s_idx + tt * QS_TILE_ROWS + lane * 2) = (uint16_t)pair;  // rows 2 * lane, 2 * lane + 1
+    }
+    __syncthreads();
+    if (tid < QS_TILE_ROWS) {  // row `tid`: the chunk's leaves, in tree order
+      for (int tt = 0; tt < nt; ++tt) {
+        const uint32_t li = s_idx[tt * QS_TILE_ROWS + tid];
+        if constexpr (F64) acc64 += *(const double *)(s_leaf + tt * TREE_LEAF_BYTES + li * 8);
+        else acc32 += *(const float *)(s_leaf + tt * TREE_LEAF_BYTES + li * 4);
+      }
+    }
+  }
+  const long long row = tile * QS_TILE_ROWS + tid;
+  if (tid < QS_TILE_ROWS && row < rows) out[row] = F64 ? acc64 : (double)acc32;
+}
+
 // (Measured and removed, round 6 - commit 4ad2903 has the code: a PIPELINED form of the split kernel - 7 evaluating wavefronts + 1
 // adding wavefront per tile, the exit leaves of chunk k double-buffered against the adds of chunk k - 1, one barrier per chunk,
 // nobody idle.  Same box: 0.226 vs 0.223 ms at 384 000 rows, 1.966 vs 1.908 ms at 4 M rows, bench 1 041 vs 1 142 M items/s
@@ -412,11 +526,14 @@ void launch_wave(mrk_ctx *ctx, mrk_model *m, const uint16_t *d_cells, int rows, 
     const size_t lds = (size_t)V * 256 + (size_t)8 * nw * (QS_LEAVES * (F64 ? 8 : 4) + QS_TILE_ROWS);
     if (lds <= 160 * 1024) {
       ScopedKernelTimer timer(ctx, "score");
+      // byte mode (MRK_QS_BYTE=0: the 16-bit kernels for every forest, A/B runs): same LDS, same residency
+      const bool byte_mode = q.byte_ok && switches().qs_byte;
 #define MRK_SPLIT(NW_)                                                                                                      \
       {                                                                                                                       \
-        auto sk = qs_score_split_kernel<F64, NW_>;                                                                            \
+        auto sk = byte_mode ? qs_score_byte_split_kernel<F64, NW_> : qs_score_split_kernel<F64, NW_>;                        \
         lds_optin(ctx, (const void *)sk);                                                                                     \
-        hipLaunchKernelGGL(sk, dim3((unsigned)n_tiles), dim3(NW_ * 64), lds, ctx->launch, m->d_qs_nodes.as<uint32_t>(),       \
+        hipLaunchKernelGGL(sk, dim3((unsigned)n_tiles), dim3(NW_ * 64), lds, ctx->launch,                                     \
+                           byte_mode ? m->d_qs_bnodes.as<uint32_t>() : m->d_qs_nodes.as<uint32_t>(),                          \
                            m->d_qs_leaves.as<uint8_t>(), m->d_qs_catnodes.as<QsCatNode>(), m->d_qs_cat.as<uint32_t>(), d_cells, \
                            q.n_trees, V, rows, m->forest.base_score, d_out);                                                  \
       }

@@ -187,6 +187,86 @@ __global__ void __launch_bounds__(256) k_tree_m0_only(int iters, uint32_t *out) 
 }
 constexpr int K_TREE_M0_ONLY = 58 + 30 + 15;  // (s_nop counted as an issue slot)
 
+// the byte-mode tree step (score_qs.hip qs_score_byte_split_kernel): cells clamped to 255 and k <= 254, so one v_pk_sub_i16
+// leaves a clean 0xFF / 0x00 high byte per row; leaves 0-7 are ORed into acc_a, 8-15 into acc_b, a node whose left subtree
+// crosses position 8 ("crossing", z per tree) into both; one v_perm_b32 merges them.  Per tree: M0 write + s_nop + read per node,
+// 15 v_pk_sub, (x + z) + (15 - x) = 15 + z v_and_or_b32 entered by wavefront-uniform switches, 1 v_perm, 12 VALU of leaf
+// bookkeeping stand-ins (today's 13 less the acc_a | acc_b merge) = 43 + z VALU + 30 SALU + 15 LDS (+ the switches' SALU)
+// one straight-line ladder per count (no fall-through between cases: the CFG stays a plain multiway branch).  TWO: slots
+// alternate between two accumulators, so that no v_and_or_b32 reads the one before it (the compiler puts an s_nop between
+// dependent inline-asm VALU ops), merged by one v_or_b32 per ladder
+template <bool TWO, int B, int E>
+__device__ __forceinline__ void byte_ladder(uint32_t &acc, uint32_t &acc2, const uint32_t (&c)[15], const uint32_t (&m)[15]) {
+#pragma unroll
+  for (int s = B; s < E; ++s) {
+    if (TWO && (s & 1)) asm("v_and_or_b32 %0, %1, %2, %0" : "+v"(acc2) : "v"(c[s]), "s"(m[s]));
+    else asm("v_and_or_b32 %0, %1, %2, %0" : "+v"(acc) : "v"(c[s]), "s"(m[s]));
+  }
+}
+// the same ladders as independent guarded blocks of G slots: A runs blocks that start below a, B blocks that end above x.  A block
+// may overrun the ladder's bound by up to G - 1 slots: harmless, a B-only slot's A mask and an A-only slot's B mask are 0
+template <int G, bool A_SIDE>
+__device__ __forceinline__ void byte_blocks(uint32_t &acc, const uint32_t (&c)[15], const uint32_t (&m)[15], int bound) {
+#pragma unroll
+  for (int b0 = 0; b0 < 15; b0 += G) {
+    if (A_SIDE ? b0 < bound : b0 + G > bound) {
+#pragma unroll
+      for (int s = b0; s < b0 + G && s < 15; ++s) asm("v_and_or_b32 %0, %1, %2, %0" : "+v"(acc) : "v"(c[s]), "s"(m[s]));
+    }
+  }
+}
+#define BYTE_CASES(F) F(0) F(1) F(2) F(3) F(4) F(5) F(6) F(7) F(8) F(9) F(10) F(11) F(12) F(13) F(14) F(15)
+template <int MODE>  // 0 switch, 1 switch + two chains, 2 compile-time x = 6 / a = 8, 4 / 2 guarded blocks of 4 / 2 slots
+__global__ void __launch_bounds__(256) k_tree_byte(int iters, uint32_t *out, int x, int a) {
+  uint32_t acc_a2 = 0, acc_b2 = 0;
+  __shared__ uint32_t slab[64 * 64];
+  for (int i = threadIdx.x; i < 64 * 64; i += 256) slab[i] = (i * 2654435761u) & 0x00ff00ffu;
+  __syncthreads();
+  uint32_t acc_a = 0, acc_b = 0, kk = 0x00400040u, ma[15], mb[15];
+#pragma unroll
+  for (int s = 0; s < 15; ++s) {  // per-slot masks in scalar registers, as the kernel's node loads leave them
+    ma[s] = __builtin_amdgcn_readfirstlane(0x5a005a00u + (s << 9) + x);
+    mb[s] = __builtin_amdgcn_readfirstlane(0x3c003c00u + (s << 9) + a);
+  }
+  const uint32_t voff = (blockIdx.x & 7) << 8;
+  for (int i = 0; i < iters; ++i) {
+    uint32_t c[15];
+#pragma unroll
+    for (int s = 0; s < 15; ++s)
+      asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tds_read_addtid_b32 %0" : "=v"(c[s]) : "s"(voff + (s << 8)) : "memory");
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int s = 0; s < 15; ++s) asm volatile("v_pk_sub_i16 %0, %1, %0" : "+v"(c[s]) : "s"(kk));
+    constexpr bool TWO = MODE == 1;
+    if constexpr (MODE == 2) {
+      byte_ladder<false, 0, 8>(acc_a, acc_a2, c, ma);
+      byte_ladder<false, 6, 15>(acc_b, acc_b2, c, mb);
+    } else if constexpr (MODE == 4 || MODE == 3) {
+      byte_blocks<MODE == 4 ? 4 : 2, true>(acc_a, c, ma, a);
+      byte_blocks<MODE == 4 ? 4 : 2, false>(acc_b, c, mb, x);
+    } else {
+    switch (a) {  // slots [0, a)
+#define CASE_A(n) case n: byte_ladder<TWO, 0, n>(acc_a, acc_a2, c, ma); break;
+      BYTE_CASES(CASE_A)
+#undef CASE_A
+    }
+    switch (x) {  // slots [x, 15)
+#define CASE_B(n) case n: byte_ladder<TWO, n, 15>(acc_b, acc_b2, c, mb); break;
+      BYTE_CASES(CASE_B)
+#undef CASE_B
+    }
+    }
+    if (TWO) {
+      acc_a |= acc_a2;
+      acc_b |= acc_b2;
+    }
+    asm volatile("v_perm_b32 %0, %1, %0, %2" : "+v"(acc_a) : "v"(acc_b), "s"(0x07030501u));
+    REP8(asm volatile("v_xor_b32 %0, %0, %1" : "+v"(acc_a) : "v"(acc_b));)
+    REP4(asm volatile("v_xor_b32 %0, %0, %1" : "+v"(acc_b) : "v"(acc_a));)
+  }
+  out[blockIdx.x * 256 + threadIdx.x] = acc_a ^ acc_b;
+}
+
 // dependent LDS search chain: 8 dependent ds_read_b32 + compare/select (the binning search of the assembly kernel)
 __global__ void __launch_bounds__(256) k_lds_chain(int iters, uint32_t *out) {
   __shared__ uint32_t slab[64 * 64];
@@ -200,8 +280,8 @@ __global__ void __launch_bounds__(256) k_lds_chain(int iters, uint32_t *out) {
 }
 constexpr int K_LDS_CHAIN = 8;
 
-template <typename T, typename K>
-static void run(const char *name, K kern, int k_per_iter, int n_cus, T *d_out) {
+template <typename T, typename K, typename... Extra>
+static void run(const char *name, K kern, int k_per_iter, int n_cus, T *d_out, Extra... extra) {
   const int iters = 4096;
   fprintf(stderr, "%s\n", name);
   for (int w : {1, 2, 4, 8}) {  // 256-thread workgroups per CU = wavefronts per SIMD
@@ -209,12 +289,12 @@ static void run(const char *name, K kern, int k_per_iter, int n_cus, T *d_out) {
     hipEvent_t e0, e1;
     CK(hipEventCreate(&e0));
     CK(hipEventCreate(&e1));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, 0, iters / 8, d_out);  // warm
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, 0, iters / 8, d_out, extra...);  // warm
     CK(hipDeviceSynchronize());
     float best = 1e30f;
     for (int rep = 0; rep < 5; ++rep) {
       CK(hipEventRecord(e0, 0));
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, 0, iters, d_out);
+      hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, 0, iters, d_out, extra...);
       CK(hipEventRecord(e1, 0));
       CK(hipEventSynchronize(e1));
       float ms;
@@ -247,6 +327,17 @@ int main() {
   run("tree step (today)", k_tree_now, K_TREE_NOW, n_cus, (uint32_t *)d);
   run("tree step (m0 only)", k_tree_m0_only, K_TREE_M0_ONLY, n_cus, (uint32_t *)d);
   run("tree step (valu addr)", k_tree_valu_addr, K_TREE_VALU_ADDR, n_cus, (uint32_t *)d);
+  // x = A-only nodes, a = x + z nodes touch acc_a; 43 + z VALU (+ 2: two chains) + 30 SALU + 15 LDS per trip
+  const char *modes[] = {"switch", "switch 2ch", "fixed", "blk2", "blk4"};
+  for (int mode : {0, 1, 3, 4})
+    for (int z : {0, 2, 7}) {
+      const int x = z == 7 ? 0 : 7 - z / 2;
+      char name[48];
+      snprintf(name, sizeof name, "tree step (byte %s z=%d)", modes[mode], z);
+      auto k = mode == 0 ? k_tree_byte<0> : mode == 1 ? k_tree_byte<1> : mode == 3 ? k_tree_byte<3> : k_tree_byte<4>;
+      run(name, k, 43 + z + (mode == 1 ? 2 : 0) + 30 + 15, n_cus, (uint32_t *)d, x, x + z);
+    }
+  run("tree step (byte fixed z=2)", k_tree_byte<2>, 43 + 2 + 30 + 15, n_cus, (uint32_t *)d, 6, 8);
   run("lds dependent chain", k_lds_chain, K_LDS_CHAIN, n_cus, (uint32_t *)d);
   CK(hipFree(d));
   return 0;
