@@ -33,12 +33,15 @@
  *   mrk_init(devices, n)       <- HipConfig(inner, devices: List[Int]) next to LightGBMConfig / XGBoostConfig
  *                                 M/config/BoosterConfig.scala:96-104 (SURVEY.md 8b touch point 1): one context per device,
  *                                 all inside the one host process (M/main/command/Serve.scala:72-128)
+ *   mrk_index_*                <- KnnIndexWriter.write / KnnIndexReader.lookup  M/ml/recommend/embedding/HnswJavaIndex.scala:23-87,
+ *                                 EmbeddingSimilarityModel.predict  M/ml/recommend/MFRecommender.scala:66-80
  *   mrk_encoder_*              <- OnnxSession / OnnxBiEncoder / OnnxCrossEncoder  M/ml/onnx/sbert/ (OnnxSession, OnnxBiEncoder, OnnxCrossEncoder .scala)
  *
  * ABI 8 (round 5): mrk_init creates n contexts; mrk_device_count; mrk_comm_init_local; mrk_model_inspect; mrk_serve_stats takes
  * the length of its output array; mrk_store_put_binary_at / mrk_store_expire; mrk_encoder_load is f32 (MRK_ENCODER_AUTO = F32).
  * ABI 9 (round 6): mrk_model_weights / mrk_model_inspect_weights (Booster.weights()), mrk_abi_layout.  Same ABI, new behaviour:
  * the serving queue's slots are launched in gangs (64 slots on 8 streams) and mrk_rank answers through a started queue.
+ * Still ABI 9, new symbols only: mrk_index_* (the similar-items index of /recommend).
  */
 #ifndef MRK_H
 #define MRK_H
@@ -555,6 +558,49 @@ void mrk_encoder_free(mrk_encoder *enc);
  * mrk_rank / mrk_batch_prepare encode the request's `rankingField` text with this encoder (queries are cached by
  * text, as EmbeddingCache does) instead of expecting a host-computed embedding. */
 int mrk_config_bind_encoder(mrk_ctx *ctx, const char *feature, mrk_encoder *enc);
+
+/* ---- similar items (POST /recommend/<model>): an exact nearest-neighbour index on the device ----------------------------
+ * Replaces the HNSW index behind the reference's `similar` (ALS factors) and `semantic` (BERT embeddings) recommenders:
+ * M/ml/recommend/embedding/HnswJavaIndex.scala:23-59 (KnnIndexReader.lookup), :68-87 (KnnIndexWriter.write),
+ * M/ml/recommend/MFRecommender.scala:66-80 (EmbeddingSimilarityModel.predict), M/ml/Recommender.scala:36-44.  The distance is
+ * hnswlib-core's DOUBLE_COSINE_DISTANCE, in f64, every sum walked in dimension order with separate multiplies and adds:
+ *   dot += u[i]*v[i]; nru += u[i]*u[i]; nrv += v[i]*v[i];   distance = 1.0 - dot / (sqrt(nru) * sqrt(nrv))
+ * The device scans the whole table, so the result is the TRUE n nearest rows (HNSW approximates them), ordered by
+ * java.lang.Double.compare on the distance (-0.0 before 0.0, NaN last) and, among equal distances, by ascending row (HNSW
+ * defines no tie order; this one is the library's).  Zero vectors are legal (their distance is NaN, returned as the canonical
+ * NaN 0x7ff8000000000000); non-finite values follow IEEE arithmetic, nothing is refused.  Results are independent of how many
+ * queries share a call.  Limits (MRK_ERR_INVALID_ARG): n + n_items <= 2048, 1 <= cols <= 4096, rows < 2^31.
+ * There is no save / load: the host rebuilds the index from its EmbeddingMap (KnnIndex.write / load). */
+typedef struct mrk_index mrk_index;
+/* KnnIndexWriter.write(EmbeddingMap) -- HnswJavaIndex.scala:68-87: ids[rows] (each stored once), values row-major rows x cols,
+ * elem_bytes 4 (float) or 8 (double).  Everything is copied.  The table is stored as f32 when every value survives
+ * double -> float -> double unchanged (always true for encoder embeddings, which the reference widens from floats,
+ * M/ml/recommend/BertSemanticRecommender.scala:61-66) and as f64 otherwise; both widths give the same bits. */
+int mrk_index_build(mrk_ctx *ctx, const char *const *ids, const void *values, int elem_bytes, int64_t rows, int cols, mrk_index **out);
+/* EmbeddingMap.rows / .cols, the stored width (4 or 8) and the bytes held on the device; any output may be NULL */
+int mrk_index_info(mrk_index *ix, int64_t *rows, int *cols, int *stored_elem_bytes, int64_t *device_bytes);
+/* EmbeddingMap.ids(row): NULL when out of range; valid until mrk_index_free */
+const char *mrk_index_id(mrk_index *ix, int64_t row);
+/* index.get(id) -- HnswJavaIndex.scala:29: the row of an id, -1 when unknown */
+int64_t mrk_index_row(mrk_index *ix, const char *id);
+/* HnswIndexReader.lookupOne = index.findNearest(vector, n) -- HnswJavaIndex.scala:56-59 -- for n_queries raw vectors
+ * (n_queries x cols doubles): out_rows / out_dist are n_queries x n row-major, the first out_n[q] = min(n, rows) entries of
+ * row q are filled, nearest first.  Calls of any size are cut into launches inside the library. */
+int mrk_index_search(mrk_index *ix, const double *queries, int n_queries, int n, int32_t *out_rows, double *out_dist, int32_t *out_n);
+/* KnnIndexReader.lookup(items, n) -- HnswJavaIndex.scala:25-38: no items -> nothing; one item -> the neighbours of its stored
+ * vector, nothing when the id is unknown; several -> unknown ids are dropped, duplicates kept, and the query is the centroid
+ * (:40-54: per dimension the f64 sum in request order divided by the number kept).  When NO id of a several-item request is
+ * known the reference searches for a NaN centroid, whose result is undefined; here that returns nothing.  out_rows / out_dist
+ * hold n entries, *out_n are filled. */
+int mrk_index_lookup(mrk_index *ix, const char *const *item_ids, int n_items, int n, int32_t *out_rows, double *out_dist, int32_t *out_n);
+/* EmbeddingSimilarityModel.predict -- MFRecommender.scala:67-77 -- and the ordering of Recommender.recommend --
+ * Recommender.scala:42: lookup(items, count + n_items), drop every result that is one of the request's items, take(count),
+ * then the stable sortBy(-score) with score = distance: the response is the `count` nearest items FARTHEST FIRST (NaN scores
+ * last).  That is what the reference answers; it is reproduced, not corrected.  out_rows / out_score hold count entries.
+ * No items -> MRK_ERR_INVALID_ARG ("similar items recommender requires request.items to be non-empty", :69); nothing left
+ * after the filter -> MRK_ERR_NOT_FOUND ("empty response from the recommender", :74). */
+int mrk_index_recommend(mrk_index *ix, const char *const *item_ids, int n_items, int count, int32_t *out_rows, double *out_score, int32_t *out_n);
+void mrk_index_free(mrk_index *ix);
 
 #ifdef __cplusplus
 }

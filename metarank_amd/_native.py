@@ -241,6 +241,14 @@ SIGNATURES = {
     "mrk_encoder_score_ids": (_I, [_V, _P, _P, _P, _I, _I, _P]),
     "mrk_encoder_free": (None, [_V]),
     "mrk_config_bind_encoder": (_I, [_V, _S, _V]),
+    "mrk_index_build": (_I, [_V, C.POINTER(_S), _P, _I, C.c_int64, _I, C.POINTER(_V)]),
+    "mrk_index_info": (_I, [_V, C.POINTER(C.c_int64), C.POINTER(_I), C.POINTER(_I), C.POINTER(C.c_int64)]),
+    "mrk_index_id": (_S, [_V, C.c_int64]),
+    "mrk_index_row": (C.c_int64, [_V, _S]),
+    "mrk_index_search": (_I, [_V, _P, _I, _I, _P, _P, _P]),
+    "mrk_index_lookup": (_I, [_V, C.POINTER(_S), _I, _I, _P, _P, _P]),
+    "mrk_index_recommend": (_I, [_V, C.POINTER(_S), _I, _I, _P, _P, _P]),
+    "mrk_index_free": (None, [_V]),
 }
 
 _lib = None
