@@ -559,6 +559,33 @@ void mrk_encoder_free(mrk_encoder *enc);
  * text, as EmbeddingCache does) instead of expecting a host-computed embedding. */
 int mrk_config_bind_encoder(mrk_ctx *ctx, const char *feature, mrk_encoder *enc);
 
+/* ---- field_match term / ngram / bm25 on the device ---------------------------------------------------------------------
+ * M/feature/FieldMatchFeature.scala:60-92, M/feature/matcher/FieldMatcher.scala:15-49, BM25Matcher.scala:26-40.
+ * Opt-in per feature: the library-level key "match": "device" in the feature's JSON, beside the reference's rankingField /
+ * itemField / method {type, language, n, termFreq}.  Without the key a field_match feature is a host-computed column whose
+ * per-item values arrive as item field "__ext:<name>", as before.  With it (method.type term | ngram | bm25, anything else
+ * is MRK_ERR_PARSE; dim 1):
+ *   - state: the item-scope string list "<name>_<itemField.field>" - what FieldMatchFeature.writes puts, matcher.tokenize's
+ *     output, strictly ascending in String.compareTo (UTF-16 code unit) order.  A string list that is not, put into such a
+ *     column through mrk_store_put_string_list or mrk_store_put_binary, is refused with MRK_ERR_UNSUPPORTED.
+ *   - query: matcher.tokenize(request field), computed by the host (the Lucene analyzers stay on the JVM), as the ranking-level
+ *     MRK_FIELD_STRING_LIST field "__tokens:<name>".  Absent field (or another type): every item 0.0.  Tokens that are not
+ *     strictly ascending fail the request with MRK_ERR_INVALID_ARG; more than MRK_MATCH_MAX_QUERY_TOKENS (term / ngram) or
+ *     MRK_MATCH_MAX_QUERY_TOKENS_BM25 (bm25) with MRK_ERR_UNSUPPORTED - a query is never truncated.
+ *   - value: term / ngram |Q n D| / |Q u D| (0.0 for an empty query, an unknown item, missing or non-list state, an empty
+ *     list); bm25 the sum over the query tokens present in the list, in query order, of
+ *     (idf * 2.2) / (1.0 + 1.2 * (0.25 + 0.75 * (len / avgdl))), every operation rounded on its own, idf =
+ *     log(1.0 + (docs - gtf + 0.5) / (gtf + 0.5)) with the host's libm log. */
+#define MRK_MATCH_MAX_QUERY_TOKENS 128
+#define MRK_MATCH_MAX_QUERY_TOKENS_BM25 64
+/* BM25MatcherType.create's TermFreqDic.fromFile: `json_bytes` is the dictionary's JSON {"language", "fields", "docs", "avgdl",
+ * "termfreq": {term: count}} (BM25Matcher.scala:45), read - and un-gzipped - by the host.  Binds it to the device-matched bm25
+ * feature `feature`; may be called again to replace it (requests in flight finish with the old one).  MRK_ERR_PARSE: malformed
+ * JSON, a missing key, docs < 0, avgdl not finite or not positive, a count that is not an Int >= 0; MRK_ERR_NOT_FOUND: unknown
+ * feature; MRK_ERR_UNSUPPORTED: not a device-matched bm25 field_match.  Ranking a model whose bm25 feature has no
+ * dictionary fails with MRK_ERR_INVALID_ARG.  No device needed. */
+int mrk_config_bind_termfreq(mrk_ctx *ctx, const char *feature, const char *json_bytes, size_t len);
+
 /* ---- similar items (POST /recommend/<model>): an exact nearest-neighbour index on the device ----------------------------
  * Replaces the HNSW index behind the reference's `similar` (ALS factors) and `semantic` (BERT embeddings) recommenders:
  * M/ml/recommend/embedding/HnswJavaIndex.scala:23-59 (KnnIndexReader.lookup), :68-87 (KnnIndexWriter.write),

@@ -241,6 +241,7 @@ SIGNATURES = {
     "mrk_encoder_score_ids": (_I, [_V, _P, _P, _P, _I, _I, _P]),
     "mrk_encoder_free": (None, [_V]),
     "mrk_config_bind_encoder": (_I, [_V, _S, _V]),
+    "mrk_config_bind_termfreq": (_I, [_V, _S, _P, C.c_size_t]),
     "mrk_index_build": (_I, [_V, C.POINTER(_S), _P, _I, C.c_int64, _I, C.POINTER(_V)]),
     "mrk_index_info": (_I, [_V, C.POINTER(C.c_int64), C.POINTER(_I), C.POINTER(_I), C.POINTER(C.c_int64)]),
     "mrk_index_id": (_S, [_V, C.c_int64]),

@@ -710,6 +710,13 @@ int mrk_model_dim(mrk_ctx *ctx, const char *model_name) {
   return rc == MRK_OK ? dim : rc;
 }
 
+int mrk_config_bind_termfreq(mrk_ctx *ctx, const char *feature, const char *json_bytes, size_t len) {
+  return guard([&] {
+    if (!ctx || !feature || !json_bytes) throw StatusError(MRK_ERR_INVALID_ARG, "mrk_config_bind_termfreq: null argument");
+    bind_termfreq(ctx, feature, json_bytes, len);
+  });
+}
+
 #define STORE_PUT(call)                                   \
   return guard([&] {                                      \
     if (!key) throw StatusError(MRK_ERR_INVALID_ARG, "null key"); \

@@ -15,8 +15,11 @@
 #include "encoder.hpp"
 #include "jit.hpp"
 #include "json.hpp"
+#include "match_host.hpp"
 
 namespace mrk {
+
+static_assert(MATCH_MAX_QUERY == MRK_MATCH_MAX_QUERY_TOKENS && MATCH_MAX_QUERY_BM25 == MRK_MATCH_MAX_QUERY_TOKENS_BM25, "include/mrk.h names the limits");
 
 namespace {
 
@@ -317,6 +320,26 @@ std::unique_ptr<FeatureDef> parse_feature(const json::Value &o) {
     f->position = (double)need(o, "position", nm).as_int();
   } else if (type == "relevancy") {
     f->type = FType::Relevancy;
+  } else if (type == "field_match" && o.find("match") && !o.at("match").is_null()) {
+    // library-level opt-in "match": "device": the term / ngram / bm25 score is computed on the device from the stored
+    // token list and the request's query tokens "__tokens:<name>" (FieldMatchFeature.scala:60-92); without the key the
+    // feature stays a host-computed "__ext:<name>" column (below)
+    if (!o.at("match").is_string() || o.at("match").as_string() != "device")
+      bad("feature '" + nm + "': 'match' must be \"device\" when present");
+    const json::Value &method = need(o, "method", nm);
+    const json::Value *mt = method.find("type");
+    const std::string m = mt && mt->is_string() ? mt->as_string() : "";
+    if (m == "term") f->match_method = MATCH_TERM;
+    else if (m == "ngram") f->match_method = MATCH_NGRAM;
+    else if (m == "bm25") f->match_method = MATCH_BM25;
+    else bad("feature '" + nm + "': device matching supports method.type term | ngram | bm25, not '" + m + "'");
+    f->type = FType::FieldMatch;
+    f->ext_field = "__tokens:" + nm;
+    f->field = parse_field_name(need(o, "rankingField", nm).as_string()).field;
+    const FieldName item = parse_field_name(need(o, "itemField", nm).as_string());
+    if (item.event != "item") bad("feature '" + nm + "': itemField must be an item field");
+    f->match_column = nm + "_" + item.field;
+    f->dim = 1;
   } else if (type == "field_match" && o.find("method") && o.at("method").find("type") &&
              o.at("method").at("type").as_string() == "bi-encoder") {
     f->type = FType::Biencoder;
@@ -442,6 +465,10 @@ void declare_columns(const FeatureDef &f, Store &st) {
     case FType::ItemAge: case FType::Biencoder:
       st.add_column(SC_ITEM, f.name, COL_SCALAR, 0);
       break;
+    case FType::FieldMatch:
+      st.add_column(SC_ITEM, f.match_column, COL_SCALAR, 0, "", /*expect_list=*/true);
+      st.require_sorted_lists(SC_ITEM, f.match_column);
+      break;
     default: break;
   }
 }
@@ -566,6 +593,15 @@ void build_program(Program &p, const std::vector<const FeatureDef *> &feats, con
         op.i0 = p.n_consts;
         p.n_consts += 1 + f->qdim;
         break;
+      case FType::FieldMatch:
+        op.kind = OP_FIELD_MATCH;
+        op.scope = SC_ITEM;
+        op.c0 = col_ref(st, SC_ITEM, f->match_column);
+        ho.const_idx = p.n_consts;
+        op.i0 = p.n_consts;
+        op.i1 = f->match_method == MATCH_BM25 ? 1 : 0;
+        p.n_consts += match_const_count(f->match_method);
+        break;
     }
     dst += f->dim;
     p.ops.push_back(op);
@@ -617,6 +653,22 @@ void unbind_encoders(mrk_ctx *ctx) {
         if (f->encoder) { drop.push_back(f->encoder); f->encoder = nullptr; }
   }
   for (mrk_encoder *e : drop) encoder_release(e);
+}
+
+void bind_termfreq(mrk_ctx *ctx, const char *feature, const char *json_bytes, size_t len) {
+  std::shared_ptr<TermFreqDic> dic(new TermFreqDic());
+  const std::string err = termfreq_parse(json_bytes, len, *dic);   // before the lock: dictionaries are large
+  if (!err.empty()) throw StatusError(MRK_ERR_PARSE, std::string("mrk_config_bind_termfreq: ") + err);
+  StoreWriteLock lk(ctx);  // resolve_requests reads FeatureDef::termfreq under the shared lock
+  if (!ctx->registry) throw StatusError(MRK_ERR_INVALID_ARG, "mrk_config_bind_termfreq: load a config first");
+  for (auto &f : ctx->registry->features)
+    if (f->name == feature) {
+      if (f->type != FType::FieldMatch || f->match_method != MATCH_BM25)
+        throw StatusError(MRK_ERR_UNSUPPORTED, std::string("feature ") + feature + " is not a device-matched bm25 field_match");
+      f->termfreq = std::move(dic);
+      return;
+    }
+  throw StatusError(MRK_ERR_NOT_FOUND, std::string("feature ") + feature + " is not configured");
 }
 
 void bind_encoder(mrk_ctx *ctx, const char *feature, mrk_encoder *enc) {
@@ -1063,7 +1115,7 @@ void resolve_requests(const Program &prog, Store &store, const mrk_request *reqs
     const bool per_request = (f.type == FType::Number && f.scope == SC_RANKING) || (f.type == FType::WordCount && f.scope == SC_RANKING) ||
                              (f.type == FType::String && f.field_is_ranking) || f.type == FType::LocalTime || f.type == FType::Position ||
                              f.type == FType::ExternalRanking || f.type == FType::Biencoder || (f.type == FType::Rate && f.scope == SC_IRF) ||
-                             f.type == FType::InteractedWith || f.type == FType::Diversity;
+                             f.type == FType::InteractedWith || f.type == FType::Diversity || f.type == FType::FieldMatch;
     if (per_request) request_ops.push_back(&ho);
   }
   const Table &item_table = store.tables[SC_ITEM];
@@ -1187,6 +1239,30 @@ void resolve_requests(const Program &prog, Store &store, const mrk_request *reqs
               for (size_t k = 0; k < q.size(); ++k) cs[ho.const_idx + 1 + k] = (double)q[k];
             }
           }
+          break;
+        }
+        case FType::FieldMatch: {
+          // matcher.tokenize(request field) arrives from the host as the string list "__tokens:<name>" (the analyzers stay on
+          // the JVM); a missing field is FieldMatchFeature.scala:63's `case None`: every item 0.0
+          if (f.match_method == MATCH_BM25 && !f.termfreq)
+            throw StatusError(MRK_ERR_INVALID_ARG, "feature " + f.name + ": bm25 matching needs its term-frequency dictionary (mrk_config_bind_termfreq)");
+          const mrk_field *fl = fields_map_get(rq, f.ext_field);
+          std::string_view toks[MATCH_MAX_QUERY];
+          const std::string_view *q = nullptr;
+          int nq = 0;
+          if (fl && fl->type == MRK_FIELD_STRING_LIST) {
+            if (fl->n < 0 || (fl->n > 0 && !fl->strs)) throw StatusError(MRK_ERR_INVALID_ARG, "bad string list " + f.ext_field);
+            nq = fl->n;
+            q = toks;
+            for (int k = 0; k < nq && k < MATCH_MAX_QUERY; ++k) toks[k] = fl->strs[k] ? std::string_view(fl->strs[k]) : std::string_view("");
+          }
+          const int cap = f.match_method == MATCH_BM25 ? MATCH_MAX_QUERY_BM25 : MATCH_MAX_QUERY;
+          const MatchPack rc = nq > cap ? MATCH_PACK_TOO_MANY
+                                        : match_pack_query(f.match_method, f.termfreq.get(), q, nq, [&](std::string_view s) { return store.find_token(s); }, cs + ho.const_idx);
+          if (rc == MATCH_PACK_TOO_MANY)
+            throw StatusError(MRK_ERR_UNSUPPORTED, "feature " + f.name + ": " + std::to_string(nq) + " query tokens, " + std::to_string(cap) + " are supported");
+          if (rc == MATCH_PACK_NOT_ASCENDING)
+            throw StatusError(MRK_ERR_INVALID_ARG, "feature " + f.name + ": the query tokens are not strictly ascending in UTF-16 order (matcher.tokenize sorts and dedups)");
           break;
         }
         case FType::Rate:

@@ -16,9 +16,11 @@ struct mrk_encoder;
 
 namespace mrk {
 
+struct TermFreqDic;
+
 enum class FType {
   Number, Boolean, WordCount, Vector, String, InteractionCount, WindowCount, Rate, InteractedWith, Diversity,
-  ItemAge, LocalTime, Position, Relevancy, Biencoder, ExternalRanking, ExternalItem
+  ItemAge, LocalTime, Position, Relevancy, Biencoder, ExternalRanking, ExternalItem, FieldMatch
 };
 
 struct FeatureDef {
@@ -46,6 +48,9 @@ struct FeatureDef {
   int64_t list_duration_ms = 24LL * 3600 * 1000;
   bool cross = false;                   // field_match / cross-encoder: per-item logits of (query, item text) pairs
   mrk_encoder *encoder = nullptr;       // bi-encoder with `method.model`: bound by mrk_config_bind_encoder (one reference held)
+  int match_method = 0;                 // field_match with "match": "device": MatchMethod (match_host.hpp); ext_field = "__tokens:<name>"
+  std::string match_column;             // ... its item column "<name>_<itemField.field>" (FieldMatchFeature.scala:31)
+  std::shared_ptr<const TermFreqDic> termfreq;   // ... bm25: bound by mrk_config_bind_termfreq
 };
 
 // host-side description of what a request has to supply for one op

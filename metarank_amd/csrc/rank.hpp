@@ -22,7 +22,27 @@ enum OpKind : int32_t {
                          // ranking-scoped number/word_count/string, ua/referer columns)
   OP_FILL_NAN = 12,      // relevancy / host-computed per-item features: NaN unless an override arrives
   OP_BIENCODER = 13,     // field_match bi-encoder cosine                      (FieldMatchBiencoderFeature.scala:80-109)
+  OP_FIELD_MATCH = 14,   // field_match term / ngram / bm25 against the request's query tokens (FieldMatchFeature.scala:60-92)
 };
+
+enum MatchMethod : int32_t { MATCH_TERM = 0, MATCH_NGRAM = 1, MATCH_BM25 = 2 };
+
+constexpr int MATCH_MAX_QUERY = 128;       // include/mrk.h MRK_MATCH_MAX_QUERY_TOKENS
+constexpr int MATCH_MAX_QUERY_BM25 = 64;   // include/mrk.h MRK_MATCH_MAX_QUERY_TOKENS_BM25 (one bit of a 64-bit mask per query position)
+
+// OP_FIELD_MATCH: the feature's const block (f64 per request; filled by match_host.cpp match_pack_query, read by rank_device.hpp):
+//   [0]  number of query tokens the store knows (= used id slots), or -1: no query / an empty one (every item 0.0)
+//   [1]  |Q|: every query token, known to the store or not
+//   term / ngram:  [2 .. 2 + 128)   the known tokens' interned ids, ascending, padded with MATCH_PAD
+//   bm25:          [2]              avgdl
+//                  [3 .. 3 + 64)    id * 64 + (position in query order), ascending, padded with MATCH_PAD
+//                  [67 .. 67 + 64)  idf * w of the token at each query position (0.0 past |Q|)
+// u32 ids are exact in f64, and so is id * 64 + position (< 2^38).
+constexpr double MATCH_PAD = 1099511627776.0;   // 2^40: above every id and every id * 64 + position
+constexpr int MATCH_TERM_IDS = 2, MATCH_BM25_AVGDL = 2, MATCH_BM25_IDS = 3, MATCH_BM25_W = MATCH_BM25_IDS + MATCH_MAX_QUERY_BM25;
+constexpr int match_const_count(int method) {
+  return method == MATCH_BM25 ? MATCH_BM25_W + MATCH_MAX_QUERY_BM25 : MATCH_TERM_IDS + MATCH_MAX_QUERY;
+}
 
 enum RateMode : int32_t { RATE_ITEM = 0, RATE_ITEM_FIELD = 1, RATE_RANKING_FIELD = 2 };
 enum NormMode : int32_t { NORM_NOOP = 0, NORM_MINMAX = 1, NORM_POSITION = 2 };

@@ -1146,17 +1146,61 @@ __device__ __forceinline__ Cell rec_cell(const IR &ir, ColRef c, int idx = 0) {
   return out;
 }
 
+// ---- OP_FIELD_MATCH (FieldMatcher.scala:15-49, BM25Matcher.scala:26-40; const block: rank.hpp MATCH_*)
+// index of the first element >= key in a[0, P) - P a power of two, the tail padded with MATCH_PAD - or P - 1 when there is none
+__device__ __forceinline__ int match_lower_bound(const double *a, int P, double key) {
+  int base = 0;
+  for (int s = P >> 1; s >= 1; s >>= 1) base += a[base + s - 1] < key ? s : 0;
+  return base;
+}
+
+// The score of one candidate whose stored list has `len` tokens (0: nothing to match): `head` holds the first TOK_BATCH of
+// them (fetched ahead), `toks` the whole list.  Both lists are sets (strictly ascending strings, checked where they enter),
+// so the merge walk's intersection is the number of list tokens found among the query's ids.
+__device__ __forceinline__ double field_match_value(const double *cs, bool bm25, uint32_t len, const uint32_t *toks, const uint32_t (&head)[TOK_BATCH]) {
+  if (len == 0u) return 0.0;
+  const int cap = bm25 ? MATCH_MAX_QUERY_BM25 : MATCH_MAX_QUERY;
+  const int known = (int)cs[0] < cap ? (int)cs[0] : cap;
+  if (known < 0) return 0.0;
+  const int P = known <= 1 ? 1 : 1 << (32 - __clz(known - 1));   // <= 128 (term / ngram), <= 64 (bm25): inside the block
+  const double *ids = cs + (bm25 ? MATCH_BM25_IDS : MATCH_TERM_IDS);
+  uint32_t hits = 0;
+  unsigned long long present = 0;   // bm25: bit p = the query's p-th token is in the list
+  auto probe = [&](uint32_t tok) __attribute__((always_inline)) {
+    const double key = bm25 ? (double)tok * 64.0 : (double)tok;
+    const double e = ids[match_lower_bound(ids, P, key)];
+    if (!bm25) hits += e == key ? 1u : 0u;
+    else if (e >= key && e < key + 64.0) present |= 1ull << (int)(e - key);
+  };
+#pragma unroll
+  for (int t = 0; t < TOK_BATCH; ++t)
+    if ((uint32_t)t < len) probe(head[t]);
+  for (uint32_t j = TOK_BATCH; j < len; ++j) probe(toks[j]);
+  if (!bm25) return (double)hits / (double)((uint32_t)cs[1] + len - hits);   // intersection.toDouble / union.toDouble
+  // sum += termIDF * (1 * (K1 + 1.0)) / (1 + K1 * (1.0 - B + B * (doc.length / avgdl))) for the present tokens, in query order
+  // (an absent one adds +-0.0); idf * w comes from the host, K1 = 1.2, B = 0.75, 1.0 - B = 0.25 exactly
+  const double den = __dadd_rn(1.0, __dmul_rn(1.2, __dadd_rn(0.25, __dmul_rn(0.75, __ddiv_rn((double)len, cs[MATCH_BM25_AVGDL])))));
+  double sum = 0.0;
+  while (present != 0ull) {
+    const int p = __ffsll((long long)present) - 1;
+    present &= present - 1ull;
+    sum = __dadd_rn(sum, __ddiv_rn(cs[MATCH_BM25_W + p], den));
+  }
+  return sum;
+}
+
 // ops whose first load is the cell of their primary column op.c0
 __device__ __forceinline__ constexpr bool op_has_primary(const Op &op) {
   const int kind = op.kind;
   if (kind == OP_RATE) return op.i0 == RATE_ITEM_FIELD;  // the link cell
   return kind == OP_SCALAR_DOUBLE || kind == OP_SCALAR_BOOL || kind == OP_VECTOR || kind == OP_STRING_INDEX || kind == OP_STRING_ONEHOT ||
-         kind == OP_COUNTER || kind == OP_WINDOW || kind == OP_DIVERSITY || kind == OP_ITEM_AGE || kind == OP_BIENCODER;
+         kind == OP_COUNTER || kind == OP_WINDOW || kind == OP_DIVERSITY || kind == OP_ITEM_AGE || kind == OP_BIENCODER ||
+         kind == OP_FIELD_MATCH;
 }
 // ... and whether that column lives in the candidate's own record
 __device__ __forceinline__ constexpr bool op_primary_in_item(const Op &op) {
   const int kind = op.kind;
-  if (kind == OP_DIVERSITY || kind == OP_BIENCODER || kind == OP_RATE) return true;
+  if (kind == OP_DIVERSITY || kind == OP_BIENCODER || kind == OP_RATE || kind == OP_FIELD_MATCH) return true;
   return op.scope == SC_ITEM;
 }
 
@@ -1185,7 +1229,7 @@ struct OpPre {
 __device__ __forceinline__ constexpr int op_pre_weight(const Op &op) {
   switch (op.kind) {
     case OP_INTERACTED: return 8 * (op.dim < IW_BATCH ? op.dim : IW_BATCH) + IW_TOK * (op.dim < IW_BATCH ? op.dim : IW_BATCH);
-    case OP_DIVERSITY: return TOK_BATCH;
+    case OP_DIVERSITY: case OP_FIELD_MATCH: return TOK_BATCH;
     case OP_RATE: return 4 * (op.dim < RATE_BATCH ? op.dim : RATE_BATCH) * (op.i3 != 0 ? 2 : 1) + 4;
     case OP_VECTOR: return 2 * (op.dim < PRE_F64 ? op.dim : PRE_F64);
     case OP_STRING_INDEX: return 1;
@@ -1221,6 +1265,7 @@ __device__ __forceinline__ constexpr int op_cost(const Op &op) {
     case OP_DIVERSITY: return 7;
     case OP_RATE: return (op.i0 == RATE_ITEM ? 3 : 6) * op.dim;
     case OP_BIENCODER: return 40;
+    case OP_FIELD_MATCH: return 12;   // a title-sized list, each token a binary search of a few steps (the length is state, not program: LOG.md round 9 has the 200-token case)
     default: return op.dim > 0 ? op.dim : 1;
   }
 }
@@ -1288,7 +1333,7 @@ __device__ __forceinline__ void assemble_item_rec(const StoreDev &st, const Prog
         if (pc.tag == TAG_STRING_LIST && pc.hi() > 0) pre.tok[0] = list_tokens(st, primary_list_record(op), pc.lo())[0];
         break;
       }
-      case OP_DIVERSITY: {
+      case OP_DIVERSITY: case OP_FIELD_MATCH: {
         const uint32_t len = pc.tag == TAG_STRING_LIST ? pc.hi() : 0u;
         const uint32_t *toks = list_tokens(st, irec, pc.lo());
 #pragma unroll
@@ -1637,6 +1682,16 @@ __device__ __forceinline__ void assemble_item_rec(const StoreDev &st, const Prog
             v = top / (sqrt(a) * sqrt(bs));
           }
         }
+        sink.put(dst + 0, v);
+        break;
+      }
+      case OP_FIELD_MATCH: {
+        const Cell c = pc;
+        const uint32_t len = c.tag == TAG_STRING_LIST ? c.hi() : 0u;   // unknown item, no state, another type, empty list: 0.0
+        uint32_t head[TOK_BATCH];
+#pragma unroll
+        for (int t = 0; t < TOK_BATCH; ++t) head[t] = pre.tok[t];
+        const double v = field_match_value(b.consts + (size_t)r * prog.n_consts + op.i0, op.i1 != 0, len, list_tokens(st, irec, c.lo()), head);
         sink.put(dst + 0, v);
         break;
       }

@@ -291,6 +291,8 @@ void comm_allgather_f64(mrk_ctx *ctx, const double *send, double *recv, size_t c
 void comm_allgather_i32(mrk_ctx *ctx, const int32_t *send, int32_t *recv, size_t count, hipStream_t stream);
 // features.cpp: drops the encoder references mrk_config_bind_encoder took
 void unbind_encoders(mrk_ctx *ctx);
+// features.cpp: mrk_config_bind_termfreq (parses BM25Matcher.TermFreqDic JSON, binds it to a device-matched bm25 field_match)
+void bind_termfreq(mrk_ctx *ctx, const char *feature, const char *json_bytes, size_t len);
 
 // score.hip
 void launch_score(mrk_ctx *ctx, mrk_model *m, const double *d_x, int rows, int cols, double *d_out,

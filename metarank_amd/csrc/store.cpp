@@ -5,6 +5,8 @@
 #include <cmath>
 #include <cstring>
 
+#include "match_host.hpp"
+
 namespace mrk {
 
 Store::Store() {
@@ -105,6 +107,12 @@ uint32_t Store::intern(const std::string &s) {
 uint32_t Store::find_token(const std::string &s) const {
   auto it = token_of.find(s);
   return it == token_of.end() ? 0 : it->second;
+}
+
+uint32_t Store::find_token(std::string_view s) const {
+  thread_local std::string key;   // token_of is keyed by std::string: one buffer per thread, reused across lookups
+  key.assign(s.data(), s.size());
+  return find_token(key);
 }
 
 uint32_t Store::slot(ScopeId scope, const char *id, size_t len, bool create) {
@@ -332,6 +340,11 @@ bool Store::put_string_list(const KeyRef &k, const std::string_view *v, int n) {
   if (!locate(k, c)) return false;
   kind_check(c.c, COL_SCALAR, k);
   if (n < 0 || (n > 0 && !v)) throw StatusError(MRK_ERR_INVALID_ARG, "bad string list");
+  // FieldMatchFeature.writes stores matcher.tokenize(..) - sorted, unique (FieldMatcher.unique); the device's matching
+  // counts on it, so anything else is refused here (the binary loader comes through this function too)
+  if (c.c->sorted_lists && !utf16_strictly_ascending(v, n))
+    throw StatusError(MRK_ERR_UNSUPPORTED, "string list of '" + c.c->name + "' is not strictly ascending in UTF-16 order: a device-matched field_match reads "
+                                           "this column and FieldMatchFeature never writes such a list");
   std::vector<uint32_t> toks((size_t)n);
   for (int i = 0; i < n; ++i) toks[(size_t)i] = intern(std::string(v[i]));
   put_tokens(c, toks.data(), (uint32_t)n);
@@ -714,6 +727,16 @@ void Store::set_list_config(ScopeId scope, const std::string &name, int64_t coun
   if (it == t.col_of.end()) return;
   t.cols[it->second].list_count = count;
   t.cols[it->second].list_duration_ms = duration_ms;
+}
+
+void Store::require_sorted_lists(ScopeId scope, const std::string &name) {
+  // Only while the layout is open: no slot exists before freeze_layout(), so no list can be in the column yet and every
+  // list that ever gets there has passed put_string_list's check.  The flag is never cleared - a store keeps its layout.
+  if (frozen) throw StatusError(MRK_ERR_INVALID_ARG, "store layout is frozen");
+  Table &t = tables[scope];
+  auto it = t.col_of.find(name);
+  if (it == t.col_of.end()) throw StatusError(MRK_ERR_INVALID_ARG, "state '" + name + "' is not declared");
+  t.cols[it->second].sorted_lists = true;
 }
 
 bool Store::increment_periodic(const char *key, int64_t ts_ms, int64_t inc) {

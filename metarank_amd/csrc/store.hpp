@@ -45,6 +45,7 @@ struct Column {
   int val_off = 0;           // byte offset of the first value cell inside the record
   std::string link_field;    // SString scalar whose value is also a key into the FIELD table ("field=<link_field>:<value>")
   bool expect_list = false;  // the feature that reads it stores string lists here: the record's inline heap is sized for it
+  bool sorted_lists = false; // read by a device-matched field_match: a string list put here must be strictly ascending in UTF-16 order
   // write path (raw state): PeriodicCounterConfig(period, sumPeriodRanges = periods.map(PeriodRange(_, 0))),
   // model/Feature.scala:196-209; BoundedListConfig(count, duration), model/Feature.scala:100-108
   int64_t period_ms = 0;            // COL_PERIODIC: bucket length; 0 = no write-path config (values arrive by put only)
@@ -267,6 +268,7 @@ struct Store {
 
   uint32_t intern(const std::string &s);
   uint32_t find_token(const std::string &s) const;  // 0 if never seen
+  uint32_t find_token(std::string_view s) const;    // ... without a std::string per call
   uint32_t slot(ScopeId scope, const std::string &id, bool create) { return slot(scope, id.data(), id.size(), create); }
   uint32_t slot(ScopeId scope, const char *id, size_t len, bool create);
   static constexpr uint32_t NO_SLOT = 0xffffffffu;
@@ -307,6 +309,7 @@ struct Store {
   // ---- write path (raw Writes of flow/FeatureValueFlow.scala:44-62; the FeatureValue is derived here) ----
   void set_periodic_config(ScopeId scope, const std::string &name, int64_t period_ms, const std::vector<int32_t> &offsets);
   void set_list_config(ScopeId scope, const std::string &name, int64_t count, int64_t duration_ms);
+  void require_sorted_lists(ScopeId scope, const std::string &name);   // a declared column, before freeze_layout()
   // Write.PeriodicIncrement: staged; applied to the device bucket rings (and the window sums recomputed
   // there) at the next flush
   bool increment_periodic(const char *key, int64_t ts_ms, int64_t inc);

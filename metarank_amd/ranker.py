@@ -269,6 +269,12 @@ class HipRanker:
         """mrk_config_bind_encoder: the bi-encoder `feature` embeds its rankingField text on the device from now on"""
         N.check(N.lib().mrk_config_bind_encoder(self.ctx.handle, feature.encode(), encoder.handle))
 
+    def bind_termfreq(self, feature: str, dic):
+        """mrk_config_bind_termfreq: the BM25 term-frequency dictionary (TermFreqDic JSON as bytes / str, or the dict itself)
+        of the device-matched bm25 field_match `feature`"""
+        blob = dic if isinstance(dic, bytes) else (dic if isinstance(dic, str) else json.dumps(dic)).encode()
+        N.check(N.lib().mrk_config_bind_termfreq(self.ctx.handle, feature.encode(), blob, len(blob)))
+
     def serve(self, model_name: str, booster: HipBooster, n_slots: int = 4) -> "Server":
         """mrk_serve_start: the serving queue (persistent workgroups polling slots in pinned memory)"""
         return Server(self, model_name, booster, n_slots)

@@ -13,6 +13,7 @@ import numpy as np
 from ._native import mrk_field, mrk_request
 
 F_STRING, F_NUMBER, F_BOOL, F_STRING_LIST, F_NUMBER_LIST = 0, 1, 2, 3, 4
+TOKENS_PREFIX = "__tokens:"   # include/mrk.h: the query tokens of a device-matched field_match, always a string list
 
 
 def _fill_field(dst: mrk_field, name: str, value, keep: list):
@@ -28,9 +29,10 @@ def _fill_field(dst: mrk_field, name: str, value, keep: list):
         keep.append(b)
         dst.type, dst.str = F_STRING, b
     elif isinstance(value, (list, tuple, np.ndarray)):
-        if len(value) > 0 and isinstance(value[0], str):
+        # an empty list carries no element type: it is a number list, except under a name whose type the library fixes
+        if (len(value) > 0 and isinstance(value[0], str)) or (len(value) == 0 and name.startswith(TOKENS_PREFIX)):
             bs = [v.encode() for v in value]
-            arr = (C.c_char_p * len(bs))(*bs)
+            arr = (C.c_char_p * max(len(bs), 1))(*bs)
             keep.extend([bs, arr])
             dst.type, dst.n, dst.strs = F_STRING_LIST, len(bs), arr
         else:
