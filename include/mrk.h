@@ -181,6 +181,8 @@ int mrk_model_dim(mrk_ctx *ctx, const char *model_name);
  * kernel bins for (1 LightGBM, 0 XGBoost).  what = 0: the HIP source handed to hiprtc; what = 1: the gfx950 code object -
  * of all specialised kernels; `what | (k << 8)`, k = 1..4: of the one kernel the library would compile by itself (1 the
  * workgroup-per-request kernel of full batches, 2 its op-split / sliced form, 3 its f64-matrix form, 4 the item-parallel kernel).
+ * The single-kernel index stops at k = 9 (the kernels mrk_config_precompile's bits 0 .. 8 name): the one-launch kernel and the
+ * persistent workgroup of forests scored by the tree walk (precompile bits 9 / 10) are part of the all-kernels form only.
  * MRK_ERR_INVALID_ARG with *needed set (for what = 1: to an upper bound) when `out` is NULL or `cap` too small; *needed is
  * the exact size on success. */
 int mrk_config_specialize(const char *json, size_t len, const char *model_name, int f64, int what, uint8_t *out, size_t cap,
@@ -189,7 +191,8 @@ int mrk_config_specialize(const char *json, size_t len, const char *model_name, 
 /* Host-only: writes into directory `dir` the gfx950 code object of every specialised kernel in `kernel_mask` (bit k: 0 the
  * workgroup-per-request kernel, 1 its op-split / sliced form, 2 the f64-matrix form, 3 the item-parallel kernel, 4 the
  * one-launch kernel of mrk_rank, 5 the persistent workgroup of the serving queue, 6 the one-launch kernel of FULL batches
- * behind MRK_RANK_FUSED_SCORE=1, 7 the stand-alone pre-pass of requests too large for one workgroup) for this config's model - what a
+ * behind MRK_RANK_FUSED_SCORE=1, 7 the stand-alone pre-pass of requests too large for one workgroup, 9 / 10 the one-launch kernel / the persistent workgroup of
+ * forests scored by the tree walk) for this config's model - what a
  * deployment ships next to libmrk_hip.so (directory `jit_cache`) so that no process ever compiles: the library looks
  * there, then in the user's cache ($MRK_JIT_CACHE_DIR, ~/.cache/mrk_jit), and only then compiles - in the BACKGROUND,
  * ranking with the kernel that interprets the program meanwhile (MRK_RANK_JIT: 0 never specialise, 1 wait for the compiler,
@@ -434,7 +437,11 @@ void mrk_batch_free(mrk_batch *batch);
  * mrk_serve_stats: the first min(n_out, MRK_SERVE_STATS) of {requests through the queue, requests through mrk_rank, workgroup launches; then, summed over the
  * queue's requests, in ns: host resolve + pack, host publish -> acknowledgement, host copy-out, device input copy + cache drops,
  * device ranking, device result write-back; last: the SHADER CYCLES of the device ranking summed the same way - cycles / ns = the
- * clock the requests ran at (a lone workgroup on an otherwise idle device does not see the boost clock)}. */
+ * clock the requests ran at (a lone workgroup on an otherwise idle device does not see the boost clock)}.
+ * Models: any forest.  Trees of <= 16 leaves are scored by the bit-vector scorer; larger trees (XGBoost maxDepth 6 / 8, LightGBM
+ * numLeaves > 16) are walked in the request's workgroup over a matrix it assembles in LDS.  What remains is an LDS limit: that
+ * matrix (columns x 128 rows x 8 bytes LightGBM / 4 bytes XGBoost), the forest's largest chunk (<= 24 KB) and the leaf values of
+ * up to 32 of its trees must fit the workgroup's 128 KB together - else MRK_ERR_UNSUPPORTED, and mrk_last_error names the sizes. */
 typedef struct mrk_server mrk_server;
 int mrk_serve_start(mrk_ctx *ctx, mrk_model *model, const char *model_name, int n_slots, mrk_server **out);
 int mrk_serve_rank(mrk_server *srv, const mrk_request *req, double *out_scores, int32_t *out_order);

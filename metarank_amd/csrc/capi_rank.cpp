@@ -52,6 +52,10 @@ void launch_rank_serve(mrk_ctx *ctx, hipStream_t stream, const StoreDev &st, con
                        int n_slots, int threads, size_t lds, bool f64, void *jit_fn);
 void launch_rank_one(mrk_ctx *ctx, const StoreDev &st, const ProgramDev &prog, const BatchDev &b, uint32_t tab_entries, int vals_cap,
                      int threads, int op_split, const QsDev &q, const QsForestDev &f, const OneOut &out, bool f64, void *jit_fn);
+void launch_rank_one_walk(mrk_ctx *ctx, const StoreDev &st, const ProgramDev &prog, const BatchDev &b, uint32_t tab_entries, int vals_cap,
+                          int threads, int op_split, const WalkDev &w, const OneOut &out, bool f64, size_t lds, void *jit_fn);
+void launch_rank_serve_walk(mrk_ctx *ctx, hipStream_t stream, const StoreDev &st, const ProgramDev &prog, const WalkDev &w, const ServeGangDev &gang,
+                            int n_slots, int threads, size_t lds, bool f64, void *jit_fn);
 int load_feature_values(Store &store, const uint8_t *bytes, size_t len, int64_t now_ms);  // codec.cpp
 void launch_resolve_ids(hipStream_t stream, const IdTableDev &tab, const uint8_t *d_bytes, const uint32_t *d_offs, uint32_t bytes_len, const ReqDev *d_reqs,
                         int n_req, int total, int32_t *d_item_slot, uint32_t *d_item_req, int32_t *d_load_status);  // resolve.hip
@@ -404,6 +408,46 @@ static bool rank_one_applies(const mrk_batch &b, const mrk_model *model, bool ce
   return rank_one_lds_bytes(b.fused_entries, b.fused_vals, b.fused_threads, q.thr_cap, q.n_views, model->forest.backend == Backend::LightGBM, (size_t)q.rt_doubles * 8) <= 96 * 1024;
 }
 
+// ---- forests the bit-vector scorer does not take (trees of more than 16 leaves), and any forest under MRK_SCORER=walk: the
+// one-request kernels that walk the trees in the request's workgroup (rank_device.hpp rank_one_walk_body)
+static WalkDev walk_device_view(const mrk_model *m, int cols) {
+  WalkDev w;
+  w.image = m->d_image.as<uint8_t>();
+  w.trees = m->d_trees.as<TreeRef>();
+  w.chunks = m->d_chunks.as<ChunkRef>();
+  w.cat_bits = m->d_cat.as<uint32_t>();
+  w.n_chunks = (int32_t)m->packed.chunks.size();
+  w.cols = cols;
+  w.chunk_cap = (m->packed.max_chunk_bytes + 15u) & ~15u;
+  w.ref_cap = ((uint32_t)m->packed.max_chunk_trees * (uint32_t)sizeof(TreeRef) + 15u) & ~15u;
+  w.leaf_trees = walk_leaf_trees((int)m->packed.max_chunk_trees);
+  w.pad = 0;
+  w.base = m->forest.base_score;
+  return w;
+}
+static_assert(sizeof(TreeRef) == 12 && WALK_TILE_ROWS == QS_TILE_ROWS, "launch_shape.hpp sizes the TreeRef rows and the matrix of rank_one_walk_body");
+
+static size_t walk_one_lds_bytes(const mrk_model *m, int cols, uint32_t tab_entries, int vals_cap, int threads) {
+  return rank_one_walk_lds_bytes(cols, m->forest.backend == Backend::LightGBM, m->packed.max_chunk_bytes, (int)m->packed.max_chunk_trees,
+                                 walk_leaf_trees((int)m->packed.max_chunk_trees), fused_lds_bytes(tab_entries, vals_cap, threads, 0u, 0, true));
+}
+
+// the model is one the walking one-request kernels are for (the serving queue: unless MRK_RANK_ONE_WALK=0)
+static bool walk_one_model(const mrk_model *model) {
+  const Switches &sw = switches();
+  return model && sw.rank_one_walk != 0 && (!model->qs.ok || sw.scorer_walk);
+}
+
+// mrk_rank's one-launch path for such a model: rank_one_applies' conditions, the walk kernel's LDS
+static bool rank_one_walk_applies(const mrk_batch &b, const mrk_model *model) {
+  const Switches &sw = switches();
+  if (!sw.rank_one || sw.rank_one_walk != 1 || !walk_one_model(model) || b.want_matrix || b.prog->normalises() || !b.fused_ok || b.n_req < 1 || b.n_req > sw.rank_one_max ||
+      b.hb.max_items > QS_TILE_ROWS || b.view.n_overrides > 0)
+    return false;
+  if (b.fused_slices != 1 || b.fused_threads > 512 || b.fused_threads < b.hb.max_items) return false;   // (every candidate has a lane that owns its row)
+  return walk_one_lds_bytes(model, b.prog->dim, b.fused_entries, b.fused_vals, b.fused_threads) <= RANK_ONE_LDS_CAP;
+}
+
 // enqueue the pipeline on the batch's stream for batch items [lo, hi); the caller holds the store (StoreAccess)
 static void run_batch(mrk_batch &b, mrk_model *model, int lo, int hi, bool sort, bool direct = false) {
   mrk_ctx *ctx = b.ctx;
@@ -424,6 +468,7 @@ static void run_batch(mrk_batch &b, mrk_model *model, int lo, int hi, bool sort,
   // the kernel specialised for this model (hiprtc, ~7 s the first time): compiled before the launch lock is taken
   // (the specialised matrix kernel has no op-split form: a split batch of a matrix-scored model runs the interpreting kernel)
   const bool one = direct && sort && lo == 0 && hi == b.total_items && rank_one_applies(b, model, cells);
+  const bool one_walk = !one && !cells && direct && sort && rows > 0 && lo == 0 && hi == b.total_items && rank_one_walk_applies(b, model);
   // full batches of small requests: assembly + forest + ordering in the request's workgroup (one launch, phases of different
   // kinds side by side on every CU)
   const bool fused_score = !one && sort && lo == 0 && hi == b.total_items && cells && sw.rank_fused_score && b.fused_ok && b.fused_split == 1 &&
@@ -431,7 +476,8 @@ static void run_batch(mrk_batch &b, mrk_model *model, int lo, int hi, bool sort,
                            rank_fused_score_lds_bytes(b.fused_entries, b.fused_vals, b.fused_threads, qs_device_view(model).thr_cap, qs_device_view(model).n_views, f64, (size_t)qs_device_view(model).rt_doubles * 8) <= 64 * 1024;
   // (the kernels that write the scorer's tile are keyed by the forest's view signature too: their sinks hold it as constants)
   const QsSignature *sig = cells && sw.thr_stage ? &model->qs_sig : nullptr;
-  void *jit_fn = !cells ? (b.fused_ok && model && b.fused_split == 1 && b.fused_slices == 1 ? jit_matrix_function(*b.prog) : nullptr)  // a model scored from the f64 matrix: the hot path too
+  void *jit_fn = one_walk ? jit_one_walk_function(*b.prog, f64)
+                 : !cells ? (b.fused_ok && model && b.fused_split == 1 && b.fused_slices == 1 ? jit_matrix_function(*b.prog) : nullptr)  // a model scored from the f64 matrix: the hot path too
                         : one ? jit_one_function(*b.prog, f64, sig)
                         : fused_score ? jit_fused_score_function(*b.prog, f64, sig)
                         : !b.fused_ok ? jit_items_function(*b.prog, f64, sig)
@@ -443,14 +489,17 @@ static void run_batch(mrk_batch &b, mrk_model *model, int lo, int hi, bool sort,
   const ProgramDev pd = b.prog->device_view();
   b.fetch_enqueued = false;
   b.direct_out = false;
-  if (one) {
+  if (one || one_walk) {
     b.h_out.reserve(b.out_bytes);
     uint8_t *h = b.h_out.as<uint8_t>();
     const OneOut out{(double *)h, (int32_t *)(h + b.out_order_off), (int32_t *)(h + b.out_status_off),
                      (const int32_t *)(b.d_out.as<uint8_t>() + b.out_status_off) + std::max(b.n_req, 1), std::max(b.n_req, 1)};
     b.view.item_lo = 0;
     b.view.item_hi = b.total_items;
-    launch_rank_one(ctx, st, pd, b.view, b.fused_entries, b.fused_vals, b.fused_threads, b.fused_split, qs_device_view(model), qs_forest_view(model), out, f64, jit_fn);
+    if (one_walk)
+      launch_rank_one_walk(ctx, st, pd, b.view, b.fused_entries, b.fused_vals, b.fused_threads, b.fused_split, walk_device_view(model, pd.dim), out, f64,
+                           walk_one_lds_bytes(model, pd.dim, b.fused_entries, b.fused_vals, b.fused_threads), jit_fn);
+    else launch_rank_one(ctx, st, pd, b.view, b.fused_entries, b.fused_vals, b.fused_threads, b.fused_split, qs_device_view(model), qs_forest_view(model), out, f64, jit_fn);
     b.matrix_valid = false;
     b.direct_out = true;
     b.ran = true;
@@ -569,7 +618,7 @@ int mrk_config_specialize(const char *json, size_t len, const char *model_name, 
   return guard([&] {
     const int kernel = (what >> 8) - 1;  // what = (1 + kernel) << 8 | form: one kernel's translation unit; high byte 0: all kernels
     what &= 0xff;
-    if (!json || !model_name || !needed || (what != 0 && what != 1) || kernel < JIT_ALL || kernel >= JIT_KERNELS)
+    if (!json || !model_name || !needed || (what != 0 && what != 1) || kernel < JIT_ALL || kernel > JIT_ITEMS_RT)  // (the two kernels of forests scored by the tree walk: JIT_ALL shows them, mrk_config_precompile builds them)
       throw StatusError(MRK_ERR_INVALID_ARG, "null argument / unknown `what`");
     Store st;
     std::unique_ptr<Registry> reg = load_config(json, len, st, /*upload=*/false);
@@ -608,7 +657,7 @@ int mrk_config_specialize_for_model(const char *json, size_t len, const char *mo
   return guard([&] {
     const int kernel = (what >> 8) - 1;
     what &= 0xff;
-    if (!json || !model_name || !needed || (what != 0 && what != 1) || kernel < JIT_ALL || kernel >= JIT_KERNELS)
+    if (!json || !model_name || !needed || (what != 0 && what != 1) || kernel < JIT_ALL || kernel > JIT_ITEMS_RT)  // (the two kernels of forests scored by the tree walk: JIT_ALL shows them, mrk_config_precompile builds them)
       throw StatusError(MRK_ERR_INVALID_ARG, "null argument / unknown `what`");
     bool f64 = true;
     const QsSignature sig = signature_of_bytes(backend, model_bytes, model_len, f64);
@@ -788,6 +837,13 @@ int mrk_debug_fused_shape(int n_req, int max_items, int *out3) {
 }
 int mrk_debug_scorer_split(int rows, int views, int f64, int n_cus) {
   return mrk::scorer_waves_per_tile(((long long)rows + mrk::QS_TILE_ROWS - 1) / mrk::QS_TILE_ROWS, views, f64 != 0, n_cus, mrk::QS_LEAVES, mrk::QS_TILE_ROWS);
+}
+
+// launch_shape.hpp rank_one_walk_lds_bytes with the trees per round the library would choose (walk_leaf_trees) (*out_leaf_trees)
+int64_t mrk_debug_walk_lds(int cols, int f64, int64_t chunk_bytes, int chunk_trees, int64_t assembly_bytes, int *out_leaf_trees) {
+  const int lt = mrk::walk_leaf_trees(chunk_trees);
+  if (out_leaf_trees) *out_leaf_trees = lt;
+  return (int64_t)mrk::rank_one_walk_lds_bytes(cols, f64 != 0, (size_t)chunk_bytes, chunk_trees, lt, (size_t)assembly_bytes);
 }
 
 int mrk_debug_clone_items(mrk_ctx *ctx, int copies, int64_t *out_items) {
@@ -1415,6 +1471,7 @@ struct mrk_server {
   std::string model_name;
   const Program *prog = nullptr;
   bool f64 = true;
+  bool walk = false;            // the model is scored by the tree walk (rank_serve_walk_body)
   void *jit_fn = nullptr;
   uint64_t idle_ticks = 0, life_ticks = 0;
   std::vector<std::unique_ptr<ServeSlot>> slots;
@@ -1477,8 +1534,12 @@ void launch_gang(mrk_server &srv, ServeGang &g) {
   d.pad = 0;
   d.idle_ticks = srv.idle_ticks;
   d.life_ticks = srv.life_ticks;
-  launch_rank_serve(ctx, g.stream, ctx->store->device_view(), srv.prog->device_view(), qs_device_view(srv.model), qs_forest_view(srv.model), d,
-                    g.n, SERVE_THREADS, SERVE_LDS, srv.f64, srv.jit_fn);
+  if (srv.walk)
+    launch_rank_serve_walk(ctx, g.stream, ctx->store->device_view(), srv.prog->device_view(), walk_device_view(srv.model, srv.prog->dim), d,
+                           g.n, SERVE_THREADS, SERVE_LDS, srv.f64, srv.jit_fn);
+  else
+    launch_rank_serve(ctx, g.stream, ctx->store->device_view(), srv.prog->device_view(), qs_device_view(srv.model), qs_forest_view(srv.model), d,
+                      g.n, SERVE_THREADS, SERVE_LDS, srv.f64, srv.jit_fn);
   g.launch_id.store(d.launch_id);
   g.running = true;
   if (!g.counted) { g.counted = true; resident_gangs().fetch_add(1, std::memory_order_acq_rel); }
@@ -1582,7 +1643,8 @@ bool serve_fast(mrk_server &srv, const mrk_request *req, double *out_scores, int
   const uint32_t entries = (uint32_t)std::max<uint64_t>(hb.max_req_entries, 1);
   const QsDev q = qs_device_view(srv.model);
   if (!hb.overrides.empty() || (int)prog.prep.size() > fused_max_prep() || hb.max_req_entries > (1u << 20) ||
-      rank_one_lds_bytes(entries, (int)vals, SERVE_THREADS, q.thr_cap, q.n_views, srv.f64, (size_t)q.rt_doubles * 8) > SERVE_LDS)
+      (srv.walk ? walk_one_lds_bytes(srv.model, prog.dim, entries, (int)vals, SERVE_THREADS)
+                : rank_one_lds_bytes(entries, (int)vals, SERVE_THREADS, q.thr_cap, q.n_views, srv.f64, (size_t)q.rt_doubles * 8)) > SERVE_LDS)
     return false;
   // the request's input block: build_batch's arrays, 16-byte aligned
   size_t off = 0;
@@ -1729,8 +1791,25 @@ int mrk_serve_start(mrk_ctx *ctx, mrk_model *model, const char *model_name, int 
     if (!ctx || !model || !model_name || n_slots < 1 || n_slots > 64) throw StatusError(MRK_ERR_INVALID_ARG, "bad arguments (1..64 slots)");
     if (model->ctx != ctx) throw StatusError(MRK_ERR_INVALID_ARG, "model belongs to another context");
     const Program &prog = locked_program(ctx, model_name);
-    if (!model->qs.ok) throw StatusError(MRK_ERR_UNSUPPORTED, "the serving queue scores with the bit-vector scorer (trees of <= 16 leaves); use mrk_rank for this model");
+    // a forest of larger trees is walked in the request's workgroup (rank_serve_walk_body) when its matrix, its largest chunk and
+    // the chunk's leaf values fit the workgroup's LDS next to each other; MRK_RANK_ONE_WALK=0: refused, as before that kernel
+    const bool walk = walk_one_model(model);
+    if (!model->qs.ok && !walk) throw StatusError(MRK_ERR_UNSUPPORTED, "the serving queue scores with the bit-vector scorer (trees of <= 16 leaves); use mrk_rank for this model");
     check_model_fits(model, prog);
+    if (walk) {
+      const bool wf64 = model->forest.backend == Backend::LightGBM;
+      const int lt = walk_leaf_trees((int)model->packed.max_chunk_trees);
+      const size_t need = rank_one_walk_lds_bytes(prog.dim, wf64, model->packed.max_chunk_bytes, (int)model->packed.max_chunk_trees, lt, 0);
+      if (need > SERVE_LDS) {
+        if (model->qs.ok) throw StatusError(MRK_ERR_UNSUPPORTED, "MRK_SCORER=walk: this model's matrix and chunk do not fit the serving workgroup's LDS");
+        throw StatusError(MRK_ERR_UNSUPPORTED, "the serving queue walks this forest in one workgroup's LDS (" + std::to_string(SERVE_LDS) + " bytes) and it does not fit: matrix " +
+                                                   std::to_string(prog.dim) + " columns x 128 rows x " + std::to_string(wf64 ? 8 : 4) + " bytes = " +
+                                                   std::to_string(rank_one_walk_matrix_bytes(prog.dim, wf64)) + ", largest chunk " + std::to_string(model->packed.max_chunk_bytes) +
+                                                   " bytes + leaf values of " + std::to_string(lt) + " trees = " +
+                                                   std::to_string(rank_one_walk_scoring_bytes(wf64, model->packed.max_chunk_bytes, (int)model->packed.max_chunk_trees, lt)) +
+                                                   "; use mrk_rank for this model");
+      }
+    }
     MRK_HIP(hipSetDevice(ctx->device));
     std::unique_ptr<mrk_server> srv(new mrk_server());
     srv->ctx = ctx;
@@ -1740,7 +1819,9 @@ int mrk_serve_start(mrk_ctx *ctx, mrk_model *model, const char *model_name, int 
     srv->f64 = model->forest.backend == Backend::LightGBM;
     srv->idle_ticks = (uint64_t)std::max(1, switches().serve_idle_us) * 100ull;  // wall_clock64: 100 MHz
     srv->life_ticks = (uint64_t)std::max(1, switches().serve_life_us) * 100ull;
-    srv->jit_fn = jit_serve_function(prog, srv->f64, switches().thr_stage ? &model->qs_sig : nullptr);  // warm-up: the compile happens here, not under the first request
+    srv->walk = walk;
+    srv->jit_fn = walk ? jit_serve_walk_function(prog, srv->f64)
+                       : jit_serve_function(prog, srv->f64, switches().thr_stage ? &model->qs_sig : nullptr);  // warm-up: the compile happens here, not under the first request
     srv->front_ns = (int64_t)switches().serve_overload_ms * 1000000;
     // A resident kernel holds its stream's hardware queue for as long as it stays, and streams that share a hardware queue wait
     // for each other: round 5's "collapse at 32 callers" (p99 76 ms) was a slot whose stream had landed behind another slot's

@@ -142,4 +142,27 @@ struct QsSig {
 };
 constexpr uint32_t QS_RT_NONE = 0xffffffffu;
 
+// ---- tree-walk forest image (forest.hpp PackedForest; walked by walk_device.hpp)
+// decision flags of one internal node (already normalised across both libraries)
+enum : uint8_t {
+  NF_CATEGORICAL = 1,   // categorical split, `cat_begin/cat_words` address the bitset
+  NF_DEFAULT_LEFT = 2,  // where "missing" goes
+  NF_MISS_ZERO = 4,     // LightGBM MissingType::Zero  (|v| <= 1e-35 counts as missing)
+  NF_MISS_NAN = 8,      // LightGBM MissingType::NaN / XGBoost (NaN is missing)
+};
+
+struct TreeRef {       // per tree, lives in the chunk header table
+  uint32_t node_off;   // byte offset of the node array inside the chunk image
+  uint32_t leaf_off;   // byte offset of the leaf array inside the chunk image
+  uint16_t n_nodes;    // 0 => single-leaf tree
+  uint16_t depth;
+};
+
+struct ChunkRef {
+  uint32_t byte_off;    // offset of the chunk image in the packed buffer (16 B aligned)
+  uint32_t byte_len;    // multiple of 16
+  uint32_t first_tree;
+  uint32_t n_trees;
+};
+
 }  // namespace mrk

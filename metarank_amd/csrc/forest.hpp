@@ -18,13 +18,7 @@ struct UnsupportedModel : std::runtime_error {
   using std::runtime_error::runtime_error;
 };
 
-// decision flags of one internal node (already normalised across both libraries)
-enum : uint8_t {
-  NF_CATEGORICAL = 1,   // categorical split, `cat_begin/cat_words` address the bitset
-  NF_DEFAULT_LEFT = 2,  // where "missing" goes
-  NF_MISS_ZERO = 4,     // LightGBM MissingType::Zero  (|v| <= 1e-35 counts as missing)
-  NF_MISS_NAN = 8,      // LightGBM MissingType::NaN / XGBoost (NaN is missing)
-};
+// (the decision flags NF_* of one internal node: device_types.hpp)
 
 struct Tree {
   // internal nodes; child >= 0 is an internal node index, child < 0 is ~leaf_index
@@ -97,19 +91,7 @@ struct PackedNode32 {  // XGBoost
 };
 static_assert(sizeof(PackedNode32) == 16, "node32 must be 16 bytes");
 
-struct TreeRef {       // per tree, lives in the chunk header table
-  uint32_t node_off;   // byte offset of the node array inside the chunk image
-  uint32_t leaf_off;   // byte offset of the leaf array inside the chunk image
-  uint16_t n_nodes;    // 0 => single-leaf tree
-  uint16_t depth;
-};
-
-struct ChunkRef {
-  uint32_t byte_off;    // offset of the chunk image in the packed buffer (16 B aligned)
-  uint32_t byte_len;    // multiple of 16
-  uint32_t first_tree;
-  uint32_t n_trees;
-};
+// (TreeRef / ChunkRef - what the walking kernels read of the image's tables: device_types.hpp)
 
 struct PackedForest {
   std::vector<uint8_t> image;     // all chunk images back to back

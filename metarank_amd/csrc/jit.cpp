@@ -102,7 +102,7 @@ std::string jit_source(const Program &prog, bool f64, int kernel, const QsSignat
   // the forest's view signature (forest.hpp): the sinks of the kernels that write the scorer's tile hold it as constants;
   // without one (no bit-vector image, f64-matrix kernels, MRK_JIT_SIG=0) they read the column descriptors from memory
   std::string qs = "mrk::QsDyn";
-  if (sig && sig->ok && kernel != JIT_MATRIX && kernel != JIT_PREPASS) {
+  if (sig && sig->ok && kernel != JIT_MATRIX && kernel != JIT_PREPASS && kernel != JIT_ONE_WALK && kernel != JIT_SERVE_WALK) {
     table("JitSigRows", "QsSig", sig->cols.size(), sig->text);
     s += "struct JitQs {\n  static constexpr bool is_static = true;\n  static constexpr int n_feats = " + std::to_string(sig->cols.size()) +
          ", n_views = " + std::to_string(sig->n_views) + ";\n  static constexpr uint32_t thr_cap = " + std::to_string(sig->thr_cap) +
@@ -173,6 +173,16 @@ std::string jit_source(const Program &prog, bool f64, int kernel, const QsSignat
     s += "extern \"C\" __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2)))\nmrk_jit_rank_serve"
          "(mrk::StoreDev st, mrk::QsDev q, mrk::QsForestDev f, mrk::ServeGangDev gang) {\n"
          "  mrk::rank_serve_body<" + b64 + ", " + qs + ">(st, mrk::JitProg{}, q, f, gang);\n}\n";
+  // the one-launch kernel and the persistent workgroup of forests scored by the tree walk (rank_one_walk_body): the matrix in
+  // LDS, no view signature
+  if (kernel == JIT_ALL || kernel == JIT_ONE_WALK)
+    s += "extern \"C\" __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2)))\nmrk_jit_rank_one_walk"
+         "(mrk::StoreDev st, mrk::BatchDev b, uint32_t tab_entries, int vals_cap, mrk::WalkDev w, int mode, mrk::OneOut out) {\n"
+         "  mrk::rank_one_walk_body<" + b64 + ">(st, mrk::JitProg{}, b, tab_entries, vals_cap, w, mode, out);\n}\n";
+  if (kernel == JIT_ALL || kernel == JIT_SERVE_WALK)
+    s += "extern \"C\" __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2)))\nmrk_jit_rank_serve_walk"
+         "(mrk::StoreDev st, mrk::WalkDev w, mrk::ServeGangDev gang) {\n"
+         "  mrk::rank_serve_walk_body<" + b64 + ">(st, mrk::JitProg{}, w, gang);\n}\n";
   return s;
 }
 
@@ -227,13 +237,15 @@ struct JitKernels {
   std::map<std::string, std::unique_ptr<JitSlotSet>> by_sig;
 };
 
-const char *const JIT_KERNEL_NAME[JIT_KERNELS] = {"mrk_jit_rank_cells", "mrk_jit_rank_cells_split", "mrk_jit_rank_matrix", "mrk_jit_assemble_cells", "mrk_jit_rank_one", "mrk_jit_rank_serve", "mrk_jit_rank_fused_score", "mrk_jit_prepass", "mrk_jit_assemble_cells_rt"};
+const char *const JIT_KERNEL_NAME[JIT_KERNELS] = {"mrk_jit_rank_cells", "mrk_jit_rank_cells_split", "mrk_jit_rank_matrix", "mrk_jit_assemble_cells", "mrk_jit_rank_one", "mrk_jit_rank_serve", "mrk_jit_rank_fused_score", "mrk_jit_prepass", "mrk_jit_assemble_cells_rt", "mrk_jit_rank_one_walk", "mrk_jit_rank_serve_walk"};
 // a kernel that exists only with a forest signature: no program-only stand-in (the caller falls back to another KERNEL meanwhile)
 static inline bool jit_needs_sig(int kernel) { return kernel == JIT_ITEMS_RT; }
 // the resident-table kernel: every table in LDS (<= 64 KB of thresholds leaves room for a request's hash tables and a second workgroup)
 bool jit_items_rt_applies(const QsSignature *sig) { return sig && sig->ok && sig->rt_total > 0 && (size_t)sig->rt_total * 8 <= 64 * 1024 && switches().jit_sig && switches().items_rt; }
 // kernels that neither write the scorer's tile nor depend on the scorer's precision: one per program, kept in slot [kernel][1]
 static inline bool jit_program_only(int kernel) { return kernel == JIT_MATRIX || kernel == JIT_PREPASS; }
+// kernels of forests WITHOUT a view signature: never keyed by one, and no stand-in of a signature's kernel
+static inline bool jit_walk_kind(int kernel) { return kernel == JIT_ONE_WALK || kernel == JIT_SERVE_WALK; }
 
 // 0 off; 1 on: the first rank of a model waits for the compile (a failure falls back to the generic kernel with a warning);
 // 2 required: a failure is an error; 3 async: compile in the background, rank with the generic kernel until it is ready;
@@ -317,7 +329,7 @@ static void *jit_function_locked(const Program &prog, int kernel, bool f64, bool
   if (!prog.jit) prog.jit = new JitKernels();
   JitKernels *k = (JitKernels *)prog.jit;
   if (jit_program_only(kernel)) f64 = true;
-  const bool keyed = sig && sig->ok && !jit_program_only(kernel) && switches().jit_sig;
+  const bool keyed = sig && sig->ok && !jit_program_only(kernel) && !jit_walk_kind(kernel) && switches().jit_sig;
   if (jit_needs_sig(kernel) && (!keyed || !jit_items_rt_applies(sig))) return nullptr;
   // (MRK_JIT_DEFINES is part of the translation unit: a process that flips it - tests, A/B scripts - gets the kernels of the text it asked for)
   std::unique_ptr<JitSlotSet> &set = k->by_sig[(keyed ? sig->text : std::string()) + (switches().jit_defines.empty() ? std::string() : "\n#" + switches().jit_defines)];
@@ -371,7 +383,7 @@ static void *jit_function_locked(const Program &prog, int kernel, bool f64, bool
         void *fallback = nullptr;
         if (keyed && !no_compile) {
           for (int kn = 0; kn < JIT_KERNELS; ++kn) {
-            if (jit_needs_sig(kn)) continue;
+            if (jit_needs_sig(kn) || jit_walk_kind(kn)) continue;
             void *f = jit_function_locked(prog, kn, jit_program_only(kn) ? true : f64, false, nullptr, true);
             if (kn == kernel) fallback = f;
           }
@@ -462,6 +474,8 @@ void *jit_matrix_function(const Program &prog) { return jit_function(prog, JIT_M
 void *jit_prepass_function(const Program &prog) { return jit_function(prog, JIT_PREPASS, true, nullptr); }
 // the one-launch kernel of small requests
 void *jit_one_function(const Program &prog, bool f64, const QsSignature *sig) { return jit_function(prog, JIT_ONE, f64, sig); }
+void *jit_one_walk_function(const Program &prog, bool f64) { return jit_function(prog, JIT_ONE_WALK, f64, nullptr); }
+void *jit_serve_walk_function(const Program &prog, bool f64) { return jit_function(prog, JIT_SERVE_WALK, f64, nullptr, /*wait=*/true); }  // mrk_serve_start IS the warm-up
 void *jit_fused_score_function(const Program &prog, bool f64, const QsSignature *sig) { return jit_function(prog, JIT_FUSED_SCORE, f64, sig); }
 void *jit_serve_function(const Program &prog, bool f64, const QsSignature *sig) { return jit_function(prog, JIT_SERVE, f64, sig, /*wait=*/true); }  // mrk_serve_start IS the warm-up
 

@@ -9,7 +9,7 @@ struct Program;
 struct QsSignature;  // forest.hpp: the forest's view signature - the kernels that write the scorer's tile are keyed by it too
 
 // the specialised kernels of a program; each is compiled (and cached on disk) by itself when a batch first needs it
-enum { JIT_RANK = 0, JIT_SPLIT = 1, JIT_MATRIX = 2, JIT_ITEMS = 3, JIT_ONE = 4, JIT_SERVE = 5, JIT_FUSED_SCORE = 6, JIT_PREPASS = 7, JIT_ITEMS_RT = 8, JIT_KERNELS = 9, JIT_ALL = -1 };
+enum { JIT_RANK = 0, JIT_SPLIT = 1, JIT_MATRIX = 2, JIT_ITEMS = 3, JIT_ONE = 4, JIT_SERVE = 5, JIT_FUSED_SCORE = 6, JIT_PREPASS = 7, JIT_ITEMS_RT = 8, JIT_ONE_WALK = 9, JIT_SERVE_WALK = 10, JIT_KERNELS = 11, JIT_ALL = -1 };
 // the translation unit hiprtc compiles for this model's program: the shared device code + the program as constants +
 // the kernel `kernel` (JIT_ALL: every kernel - inspection tools)
 std::string jit_source(const Program &prog, bool f64, int kernel = JIT_ALL, const QsSignature *sig = nullptr);
@@ -34,6 +34,10 @@ void *jit_prepass_function(const Program &prog);
 void *jit_one_function(const Program &prog, bool f64, const QsSignature *sig);
 // the persistent workgroup of the serving queue (mrk_jit_rank_serve), same conditions
 void *jit_serve_function(const Program &prog, bool f64, const QsSignature *sig);
+// the one-launch kernel and the persistent workgroup of a forest scored by the tree walk (mrk_jit_rank_one_walk,
+// mrk_jit_rank_serve_walk): keyed by the program and the scorer's precision only - such a forest has no view signature
+void *jit_one_walk_function(const Program &prog, bool f64);
+void *jit_serve_walk_function(const Program &prog, bool f64);
 // full batches of small requests: assembly + forest + ordering in one launch (mrk_jit_rank_fused_score)
 void *jit_fused_score_function(const Program &prog, bool f64, const QsSignature *sig);
 int jit_precompile(const Program &prog, bool f64, unsigned kernel_mask, const std::string &dir, const QsSignature *sig = nullptr);

@@ -72,4 +72,23 @@ inline int scorer_waves_per_tile(long long n_tiles, int V, bool f64, int n_cus, 
   return std::max(nw, fill);
 }
 
+// LDS of the one-request kernel of forests the bit-vector scorer does not take (rank_device.hpp rank_one_walk_body):
+//   [matrix: cols x 128 rows x (8 | 4) B][status word, 16 B][max(assembly regions, scoring regions)]
+// scoring regions = the largest chunk of the tree-walk image (rounded up to 16 B) + its TreeRef rows (12 B a tree, rounded up) +
+// the leaf values of `leaf_trees` trees x 128 rows x (8 | 4) B (at least the 1 KB the 128 sort keys take there afterwards).
+// A chunk's trees are walked walk_leaf_trees() at a time: 24 KB of 16-leaf LightGBM trees are 65 trees, whose leaf values alone
+// (65 KB) would push a 24-column model past the 96 KB the one-launch kernels keep to; 32 trees are 4 rounds of 8 wavefronts x WALK_U.
+constexpr int WALK_TILE_ROWS = 128;
+constexpr int WALK_LEAF_TREES_MAX = 32;
+inline int walk_leaf_trees(int chunk_trees) { return std::max(1, std::min(chunk_trees, WALK_LEAF_TREES_MAX)); }
+inline size_t rank_one_walk_matrix_bytes(int cols, bool f64) { return (size_t)std::max(cols, 0) * WALK_TILE_ROWS * (f64 ? 8 : 4); }
+inline size_t rank_one_walk_scoring_bytes(bool f64, size_t chunk_bytes, int chunk_trees, int leaf_trees) {
+  const size_t chunk = (chunk_bytes + 15) & ~(size_t)15, refs = ((size_t)std::max(chunk_trees, 0) * 12 + 15) & ~(size_t)15;
+  return chunk + refs + std::max<size_t>((size_t)std::max(leaf_trees, 1) * WALK_TILE_ROWS * (f64 ? 8 : 4), (size_t)WALK_TILE_ROWS * 8);
+}
+inline size_t rank_one_walk_lds_bytes(int cols, bool f64, size_t chunk_bytes, int chunk_trees, int leaf_trees, size_t assembly_bytes) {
+  return rank_one_walk_matrix_bytes(cols, f64) + 16 + std::max(assembly_bytes, rank_one_walk_scoring_bytes(f64, chunk_bytes, chunk_trees, leaf_trees));
+}
+constexpr size_t RANK_ONE_LDS_CAP = 96 * 1024;   // what mrk_rank's one-launch kernels keep to (capi_rank.cpp rank_one_applies)
+
 }  // namespace mrk

@@ -88,6 +88,20 @@ rank_serve_kernel(StoreDev st, ProgramDev prog, QsDev q, QsForestDev f, ServeGan
   rank_serve_body<F64>(st, prog, q, f, gang);
 }
 
+// the one-launch kernel and the persistent workgroup of forests the bit-vector scorer does not take (rank_device.hpp
+// rank_one_walk_body: the request's f64 / f32 matrix in LDS, the tree walk of score.hip in the request's workgroup)
+template <bool F64>
+__global__ void __launch_bounds__(512)
+rank_one_walk_kernel(StoreDev st, ProgramDev prog, BatchDev b, uint32_t tab_entries, int vals_cap, WalkDev w, int mode, OneOut out) {
+  rank_one_walk_body<F64>(st, prog, b, tab_entries, vals_cap, w, mode, out);
+}
+
+template <bool F64>
+__global__ void __launch_bounds__(512)
+rank_serve_walk_kernel(StoreDev st, ProgramDev prog, WalkDev w, ServeGangDev gang) {
+  rank_serve_walk_body<F64>(st, prog, w, gang);
+}
+
 __global__ void override_kernel(BatchDev b, int dim) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= b.n_overrides) return;
@@ -443,6 +457,29 @@ void launch_rank_one(mrk_ctx *ctx, const StoreDev &st, const ProgramDev &prog, c
   }
 }
 
+// the same for a forest scored by the tree walk (rank_one_walk_body); `lds`: launch_shape.hpp rank_one_walk_lds_bytes;
+// jit_fn: the specialised mrk_jit_rank_one_walk of this program, or nullptr = the interpreting kernel.
+void launch_rank_one_walk(mrk_ctx *ctx, const StoreDev &st, const ProgramDev &prog, const BatchDev &b, uint32_t tab_entries, int vals_cap,
+                          int threads, int op_split, const WalkDev &w, const OneOut &out, bool f64, size_t lds, void *jit_fn) {
+  if (b.n_req <= 0) return;
+  int mode = op_split > 1 ? op_split : 1;
+  ScopedKernelTimer timer(ctx, "rank_one_walk");
+  if (jit_fn) {
+    StoreDev a_st = st;
+    BatchDev a_b = b;
+    WalkDev a_w = w;
+    OneOut a_out = out;
+    int a_vals = vals_cap;
+    void *args[] = {&a_st, &a_b, &tab_entries, &a_vals, &a_w, &mode, &a_out};
+    MRK_HIP(hipModuleLaunchKernel((hipFunction_t)jit_fn, (unsigned)b.n_req, 1, 1, (unsigned)threads, 1, 1, (unsigned)lds, ctx->launch, args, nullptr));
+  } else {
+    lds_optin(ctx, f64 ? (const void *)rank_one_walk_kernel<true> : (const void *)rank_one_walk_kernel<false>);
+    if (f64) hipLaunchKernelGGL(rank_one_walk_kernel<true>, dim3(b.n_req), dim3(threads), lds, ctx->launch, st, prog, b, tab_entries, vals_cap, w, mode, out);
+    else hipLaunchKernelGGL(rank_one_walk_kernel<false>, dim3(b.n_req), dim3(threads), lds, ctx->launch, st, prog, b, tab_entries, vals_cap, w, mode, out);
+    MRK_HIP(hipGetLastError());
+  }
+}
+
 size_t rank_fused_score_lds_bytes(uint32_t tab_entries, int vals_cap, int threads, uint32_t thr_cap, int n_views, bool f64, size_t rt_bytes) {
   const size_t nw = (size_t)threads / 64;
   const size_t scoring = (size_t)n_views * QS_TILE_ROWS * 2 + 16 + 8 * nw * (QS_LEAVES * (f64 ? 8 : 4) + QS_TILE_ROWS) + QS_TILE_ROWS * 8;
@@ -487,6 +524,23 @@ void launch_rank_serve(mrk_ctx *ctx, hipStream_t stream, const StoreDev &st, con
   lds_optin(ctx, f64 ? (const void *)rank_serve_kernel<true> : (const void *)rank_serve_kernel<false>);
   if (f64) hipLaunchKernelGGL(rank_serve_kernel<true>, dim3(n_slots), dim3(threads), lds, stream, st, prog, q, f, gang);
   else hipLaunchKernelGGL(rank_serve_kernel<false>, dim3(n_slots), dim3(threads), lds, stream, st, prog, q, f, gang);
+  MRK_HIP(hipGetLastError());
+}
+
+// ... of a forest scored by the tree walk (rank_serve_walk_body)
+void launch_rank_serve_walk(mrk_ctx *ctx, hipStream_t stream, const StoreDev &st, const ProgramDev &prog, const WalkDev &w, const ServeGangDev &gang,
+                            int n_slots, int threads, size_t lds, bool f64, void *jit_fn) {
+  if (jit_fn) {
+    StoreDev a_st = st;
+    WalkDev a_w = w;
+    ServeGangDev a_s = gang;
+    void *args[] = {&a_st, &a_w, &a_s};
+    MRK_HIP(hipModuleLaunchKernel((hipFunction_t)jit_fn, (unsigned)n_slots, 1, 1, (unsigned)threads, 1, 1, (unsigned)lds, stream, args, nullptr));
+    return;
+  }
+  lds_optin(ctx, f64 ? (const void *)rank_serve_walk_kernel<true> : (const void *)rank_serve_walk_kernel<false>);
+  if (f64) hipLaunchKernelGGL(rank_serve_walk_kernel<true>, dim3(n_slots), dim3(threads), lds, stream, st, prog, w, gang);
+  else hipLaunchKernelGGL(rank_serve_walk_kernel<false>, dim3(n_slots), dim3(threads), lds, stream, st, prog, w, gang);
   MRK_HIP(hipGetLastError());
 }
 

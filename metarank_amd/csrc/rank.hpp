@@ -148,6 +148,21 @@ struct OneOut {
   int32_t n_req_pad;     // max(n_req, 1)
 };
 
+// what the one-request kernels read of a forest's tree-walk image (forest.hpp PackedForest; rank_device.hpp rank_one_walk_body)
+struct WalkDev {
+  const uint8_t *image;
+  const TreeRef *trees;
+  const ChunkRef *chunks;
+  const uint32_t *cat_bits;
+  int32_t n_chunks;
+  int32_t cols;            // matrix columns = the program's dim
+  uint32_t chunk_cap;      // LDS bytes of the largest chunk / of its TreeRef rows, 16-byte multiples
+  uint32_t ref_cap;
+  int32_t leaf_trees;      // trees of a chunk whose leaf values the kernel holds at once (launch_shape.hpp walk_leaf_trees)
+  int32_t pad;
+  double base;             // XGBoost base margin
+};
+
 // ---- the serving queue (rank_device.hpp rank_serve_body, capi_rank.cpp mrk_serve_*): one persistent workgroup per slot,
 // launched in GANGS - one kernel of up to SERVE_GANG workgroups on one stream, workgroup i serving slot i of the gang - so
 // that 64 slots take 8 streams (a resident kernel holds its stream's hardware queue, and a process has few of those).

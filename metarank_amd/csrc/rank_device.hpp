@@ -10,6 +10,7 @@
 #include "rank.hpp"
 #include "sort_device.hpp"
 #include "table_device.hpp"
+#include "walk_device.hpp"
 #include "wave_device.hpp"
 
 #ifdef MRK_PHASE_CLOCKS
@@ -2055,6 +2056,119 @@ __device__ __forceinline__ void rank_one_body(const StoreDev &st, const Prog &pr
   }
 }
 
+// ---- the same for a forest the bit-vector scorer does not take (trees of more than 16 leaves; MRK_SCORER=walk): the request's
+// matrix is assembled in LDS in the tree-walk scorer's feature-major layout (score.hip: rows[f * 128 + row], f64 LightGBM /
+// f32 XGBoost, every value through prep<F64> - the status the request gets is what score_kernel raises), the forest's
+// tree-walk image streams through LDS in its chunks of whole trees, over the assembly's dead regions; the workgroup's
+// wavefronts share a chunk's trees between them - a wavefront takes (WALK_U trees) x (64 of the 128 rows) at a time, every
+// lane walking WALK_U trees of its row at once (walk_device.hpp walk_trees) - and write the exit leaves' VALUES to LDS; after
+// a barrier the row's owner adds them in tree order into its running score: score_kernel's sequence of additions, the same
+// bits.  A chunk's trees are taken `leaf_trees` at a time (what the leaf-value region holds).  Ordering and outputs: rank_one_body's.
+// Dynamic LDS: [matrix: cols x 128 x (8 | 4)][the request's status word, 16 B][the regions of rank_fused_body | afterwards:
+// the chunk, its TreeRef rows, leaf values of leaf_trees x 128 rows (then the 128 sort keys)].
+template <bool F64>
+struct WalkSink {
+  typename RowT<F64>::type *col0;   // the candidate's element of column 0
+  int32_t *status;
+  bool active;
+  __device__ __forceinline__ void begin() const {}
+  __device__ __forceinline__ void finish() const {}
+  __device__ __forceinline__ void put(int col, double v) const {
+    if (active) col0[col * QS_TILE_ROWS] = prep<F64>(v, status, 32);   // (32: "inf met", as score_kernel's per-request status words)
+  }
+};
+
+template <bool F64, typename Prog>
+__device__ __forceinline__ void rank_one_walk_body(const StoreDev &st, const Prog &prog, const BatchDev &b, uint32_t tab_entries, int vals_cap,
+                                                   const WalkDev &w, int mode, const OneOut &out, int blk = -1) {
+  using row_t = typename RowT<F64>::type;
+  constexpr int U = WALK_U;
+  extern __shared__ __align__(16) uint8_t smem_base[];
+  const int tid = threadIdx.x, nthr = blockDim.x;
+  const int r = blk < 0 ? (int)blockIdx.x : blk;
+  const ReqDev rq = b.reqs[r];
+  const uint32_t mat_bytes = (uint32_t)w.cols * (QS_TILE_ROWS * (uint32_t)sizeof(row_t));
+  for (uint32_t i = tid; i < mat_bytes / 4 + 4; i += nthr) ((uint32_t *)smem_base)[i] = 0u;  // rows past the request's last candidate: zeros; the status word
+  row_t *s_rows = (row_t *)smem_base;
+  int32_t *s_status = (int32_t *)(smem_base + mat_bytes);
+  BatchDev bl = b;
+  bl.status = s_status - r;   // &bl.status[r] is the LDS word
+  __syncthreads();
+  rank_fused_body<true>(st, prog, bl, tab_entries, vals_cap, 0u, mode & 255, [&](int gi, int rr, bool active, qs_lds_double *, qs_lds_double *) {
+    return WalkSink<F64>{s_rows + (gi - rq.item_begin), &bl.status[rr], active};
+  }, mat_bytes + 16, nullptr, 0, r);
+  uint8_t *s_chunk = smem_base + mat_bytes + 16;
+  TreeRef *s_refs = (TreeRef *)(s_chunk + w.chunk_cap);
+  row_t *s_leafv = (row_t *)(s_chunk + w.chunk_cap + w.ref_cap);
+  const int n = rq.n_items;
+  const int halves = n > 64 ? 2 : 1;   // 64-row halves of the tile that hold candidates
+  const int wave = tid >> 6, lane = tid & 63, nw = nthr >> 6;
+  double acc64 = 0.0;
+  float acc32 = (float)w.base;  // XGBoost: predictions start at the base margin, f32
+  for (int ci = 0; ci < w.n_chunks; ++ci) {
+    const ChunkRef ch = w.chunks[ci];
+    __syncthreads();  // the matrix is complete and the assembly's regions are dead (first chunk); the previous chunk is consumed
+    {
+      const uint4 *src = (const uint4 *)(w.image + ch.byte_off);
+      uint4 *dst = (uint4 *)s_chunk;
+      const int n16 = (int)(ch.byte_len >> 4);
+      for (int i = tid; i < n16; i += nthr) dst[i] = src[i];
+      const uint32_t *rsrc = (const uint32_t *)(w.trees + ch.first_tree);
+      uint32_t *rdst = (uint32_t *)s_refs;
+      const int nwords = (int)ch.n_trees * 3;
+      for (int i = tid; i < nwords; i += nthr) rdst[i] = rsrc[i];
+    }
+    __syncthreads();
+    const int nt = (int)ch.n_trees;
+    for (int tb = 0; tb < nt; tb += w.leaf_trees) {
+      const int te = min(nt, tb + w.leaf_trees);   // trees [tb, te) of the chunk
+      const int units = (te - tb + U - 1) / U * halves;
+      for (int unit = wave; unit < units; unit += nw) {   // (wavefront-uniform)
+        const int h = halves == 2 ? (unit & 1) : 0;
+        const int t0 = tb + (halves == 2 ? (unit >> 1) : unit) * U;
+        const int row = h * 64 + lane;
+        int node[U];
+        uint32_t lbase[U];
+        walk_trees<F64, U>(s_chunk, s_refs, t0, te, w.cat_bits, [&](uint32_t feat, bool) -> row_t { return s_rows[feat * QS_TILE_ROWS + row]; }, node, lbase);
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+          if (t0 + u < te) s_leafv[(t0 + u - tb) * QS_TILE_ROWS + row] = *(const row_t *)(s_chunk + lbase[u] + (uint32_t)(~node[u]) * (uint32_t)sizeof(row_t));
+      }
+      __syncthreads();
+      if (tid < halves * 64) {   // the row's owner: leaves are added strictly in tree order
+        for (int t = 0; t < te - tb; ++t) {
+          if constexpr (F64) acc64 += s_leafv[t * QS_TILE_ROWS + tid];
+          else acc32 += s_leafv[t * QS_TILE_ROWS + tid];
+        }
+      }
+      if (te < nt) __syncthreads();   // (the next chunk's first barrier otherwise)
+    }
+  }
+  double score;
+  if constexpr (F64) score = acc64;
+  else score = (double)acc32;
+  __syncthreads();   // the leaf values are consumed (no chunk at all: the assembly's regions are dead): their region holds the keys
+  unsigned long long *s_key = (unsigned long long *)s_leafv;
+  if (tid < n) {
+    out.scores[rq.item_begin + tid] = score;
+    s_key[tid] = sort_key(score);
+  }
+  __syncthreads();
+  if (tid < n) {  // the place of candidate `tid`: the pairs (key, index) that precede its own
+    const unsigned long long mine = s_key[tid];
+    int before = 0;
+    for (int j = 0; j < n; ++j) {
+      const unsigned long long kj = s_key[j];
+      before += (kj < mine || (kj == mine && j < tid)) ? 1 : 0;
+    }
+    out.order[rq.item_begin + before] = tid;
+  }
+  if (tid == 0) {
+    out.status[r] = *s_status;
+    out.status[out.n_req_pad + r] = out.load_status ? out.load_status[r] : 0;
+  }
+}
+
 // ---- the same idea for FULL batches of small requests (c2: 3 840 requests x 100 candidates): the request's workgroup
 // assembles its binned tile (one 128-row tile per request, in global memory: the assembly's LDS is full of tables), then
 // pulls the tile back into LDS - over the tables it no longer needs -, scores it with its own wavefronts and orders the
@@ -2124,12 +2238,16 @@ __device__ __forceinline__ void rank_fused_score_body(const StoreDev &st, const 
 // announces `exited` and leaves (a persistent kernel must never outlive its use: hipFree and friends wait for it); the host
 // relaunches it with the next request.  If a request slips in between the announcement and the exit it is still served
 // (device: store exited, fence, read seq; host: store seq, fence, read exited - one side sees the other).
-template <bool F64, typename QS = QsDyn, typename Prog>
-__device__ __forceinline__ void rank_serve_body(const StoreDev &st, const Prog &prog, const QsDev &q, const QsForestDev &f, const ServeGangDev &g) {
+// The loop is templated on the one-request body it runs: WALK false = rank_one_body (the bit-vector scorer; `w` unused), WALK true =
+// rank_one_walk_body (`w`: the forest's tree-walk image; `q` / `f` unused).  `slab_bytes` is what lies in front of the request's status
+// word in that body's LDS layout - the binned slab, or the walking body's matrix; the loop's two words follow the status word at + 8.
+template <bool F64, typename QS = QsDyn, bool WALK = false, typename Prog>
+__device__ __forceinline__ void rank_serve_body(const StoreDev &st, const Prog &prog, const QsDev &q, const QsForestDev &f, const ServeGangDev &g, const WalkDev *w = nullptr) {
   extern __shared__ __align__(16) uint8_t smem_base[];
   const int tid = threadIdx.x, nthr = blockDim.x;
   const ServeSlotDev s = g.slots[blockIdx.x];
-  const uint32_t slab_bytes = (uint32_t)qs_n_views<QS>(q) * (QS_TILE_ROWS * 2);
+  uint32_t slab_bytes = (uint32_t)qs_n_views<QS>(q) * (QS_TILE_ROWS * 2);
+  if constexpr (WALK) slab_bytes = (uint32_t)w->cols * (QS_TILE_ROWS * (F64 ? 8u : 4u));
   volatile uint32_t *s_word = (volatile uint32_t *)(smem_base + slab_bytes + 8);   // [0] seq | STOP, [1] leave after this request
   // the slot's last ANSWERED request: whatever the host has published beyond it is this workgroup's first request (a gang is
   // launched as a whole: most of its slots have nothing pending, the one that asked for the launch has)
@@ -2202,7 +2320,8 @@ __device__ __forceinline__ void rank_serve_body(const StoreDev &st, const Prog &
     asm volatile("s_dcache_inv\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
     const unsigned long long t_in = wall_clock64();
     const unsigned long long c_in = clock64();   // shader cycles next to the 100 MHz wall clock: the clock the request actually ran at
-    rank_one_body<F64, QS>(st, prog, b, tab_entries, (int)vals_cap, q, f, (int)mode, s.out, 0);
+    if constexpr (WALK) rank_one_walk_body<F64>(st, prog, b, tab_entries, (int)vals_cap, *w, (int)mode, s.out, 0);
+    else rank_one_body<F64, QS>(st, prog, b, tab_entries, (int)vals_cap, q, f, (int)mode, s.out, 0);
     const unsigned long long c_ranked = clock64();
     const unsigned long long t_ranked = wall_clock64();
     __threadfence_system();   // every lane's results are in host memory before the acknowledgement
@@ -2223,6 +2342,12 @@ __device__ __forceinline__ void rank_serve_body(const StoreDev &st, const Prog &
     last = seq;
     idle_since = wall_clock64();
   }
+}
+
+// ... of a forest the bit-vector scorer does not take: the same loop around rank_one_walk_body
+template <bool F64, typename Prog>
+__device__ __forceinline__ void rank_serve_walk_body(const StoreDev &st, const Prog &prog, const WalkDev &w, const ServeGangDev &g) {
+  rank_serve_body<F64, QsDyn, true>(st, prog, QsDev{}, QsForestDev{}, g, &w);
 }
 
 }  // namespace

@@ -131,6 +131,8 @@ struct Switches {
   int serve_idle_us = 2000;    // MRK_SERVE_IDLE_US: a serving workgroup without a request for this long leaves its CU (relaunched by the next request)
   bool rank_fused_score = false; // MRK_RANK_FUSED_SCORE=1: full batches of small requests in ONE launch (assembly, forest, ordering per request workgroup) - measured slower than the three launches, kept for A/B
   bool rank_one = true;        // MRK_RANK_ONE=0: mrk_rank's small batches take the three-launch path instead of the one-launch kernel
+  int rank_one_walk = -1;      // MRK_RANK_ONE_WALK: forests scored by the tree walk in ONE workgroup (rank_one_walk_body).  unset: the serving queue takes them, mrk_rank keeps its three launches
+                               // (its one-launch form has not been measured against them yet: LOG.md round 10); 1: mrk_rank takes the one launch too; 0: neither - as before that kernel (same-build A/B)
   int combine_max = 256;       // MRK_RANK_COMBINE_MAX
   int rank_lanes = 3;          // MRK_RANK_LANES: batches of mrk_rank's front in flight at once (1 ... 8)
   int table_load_pct = 75;     // MRK_TABLE_LOAD_PCT

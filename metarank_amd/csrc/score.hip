@@ -20,86 +20,13 @@
 #include <string>
 
 #include "runtime.hpp"
+#include "walk_device.hpp"
 
 namespace mrk {
 
 namespace {
 
-#ifndef MRK_SCORE_U
-#define MRK_SCORE_U 4
-#endif
-constexpr int U = MRK_SCORE_U;  // trees walked concurrently per lane
-
-struct alignas(16) Node16 {
-  uint32_t w0, w1;  // thr (f64) | thr (f32) + feat/flags
-  uint32_t w2, w3;
-};
-
-__device__ __forceinline__ bool in_bitset(const uint32_t *__restrict__ bits, uint32_t begin,
-                                          uint32_t words, int c) {
-  uint32_t w = (uint32_t)c >> 5;
-  if (w >= words) return false;
-  return (bits[begin + w] >> (c & 31)) & 1u;
-}
-
-// LightGBM Tree::NumericalDecision / CategoricalDecision on a value that already went through the
-// dense-row zero flush (|v| <= 1e-35 -> 0.0).  Returns true for "go left".
-__device__ __forceinline__ bool decide64(uint32_t w0, uint32_t w1, uint32_t w2, double v,
-                                         const uint32_t *__restrict__ cat_bits) {
-  const uint32_t flags = (w2 >> 16) & 0xffu;
-  const bool nan_left = (w2 >> 24) & 1u;
-  const bool isn = v != v;
-  if (__builtin_expect(flags & NF_CATEGORICAL, 0)) {
-    if (isn) return false;
-    int iv = (int)v;  // v_cvt_i32_f64 saturates; out-of-range -> not in the bitset / negative
-    if (iv < 0) return false;
-    return in_bitset(cat_bits, w0, w1, iv);
-  }
-  const double thr = __hiloint2double((int)w1, (int)w0);
-  bool left = v <= thr;
-  if ((flags & NF_MISS_ZERO) && v == 0.0) left = (flags & NF_DEFAULT_LEFT) != 0;
-  return isn ? nan_left : left;
-}
-
-// XGBoost RegTree::GetNext with a float feature value; NaN is "missing".
-__device__ __forceinline__ bool decide32(uint32_t w0, uint32_t w1, uint32_t w3, float v,
-                                         const uint32_t *__restrict__ cat_bits) {
-  const uint32_t flags = (w1 >> 16) & 0xffu;
-  const bool def_left = (flags & NF_DEFAULT_LEFT) != 0;
-  if (v != v) return def_left;
-  if (__builtin_expect(flags & NF_CATEGORICAL, 0)) {
-    // common::Decision: invalid category (negative or >= 2^24) or beyond the bitset -> left;
-    // member of the set -> right.
-    if (v < 0.f || v >= 16777216.f) return true;
-    int c = (int)v;
-    return !in_bitset(cat_bits, w0, w3, c);
-  }
-  return v < __uint_as_float(w0);
-}
-
-template <bool F64>
-struct RowT;
-template <>
-struct RowT<true> { using type = double; };
-template <>
-struct RowT<false> { using type = float; };
-
-// dense-row preprocessing applied once per cell when the tile is staged
-template <bool F64>
-__device__ __forceinline__ typename RowT<F64>::type prep(double x, int *flag, int bit = 1) {
-  if constexpr (F64) {
-    // LightGBM RowFunctionFromDenseMatric keeps a cell only if |x| > kZeroThreshold (1e-35f) or NaN;
-    // everything else reads back as 0.0 from the prediction buffer.
-    const double kZero = (double)1e-35f;
-    return (fabs(x) > kZero || x != x) ? x : 0.0;
-  } else {
-    // ltrlib narrows Double -> Float before DMatrix (round-to-nearest-even, overflow -> inf);
-    // XGBoost rejects +-inf when `missing` is NaN ("Input data contains `inf`").
-    float f = (float)x;
-    if (__builtin_isinf(f)) atomicOr(flag, bit);
-    return f;
-  }
-}
+constexpr int U = WALK_U;  // trees walked concurrently per lane (walk_device.hpp)
 
 template <bool F64, int TILE, bool ROWS_LDS>
 __global__ void __launch_bounds__(TILE)
@@ -159,90 +86,14 @@ score_kernel(const uint8_t *__restrict__ image, const TreeRef *__restrict__ tree
 
     const int nt = (int)ch.n_trees;
     for (int t0 = 0; t0 < nt; t0 += U) {
+      // the node decisions and the walk step: walk_device.hpp
       int node[U];
-      uint32_t nbase[U], lbase[U];
-      int maxd = 0;
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int t = min(t0 + u, nt - 1);
-        const TreeRef tr = s_refs[t];
-        nbase[u] = tr.node_off;
-        lbase[u] = tr.leaf_off;
-        const bool live = (t0 + u) < nt && tr.n_nodes != 0;
-        node[u] = live ? 0 : -1;  // -1 == ~0: single-leaf tree (or padding slot, never added)
-        maxd = max(maxd, live ? (int)tr.depth : 0);
-      }
-      for (int d = 0; d < maxd; ++d) {
-        // Phase-structured so that the U dependency chains overlap: all node reads are issued
-        // back to back, then all feature gathers, then the (branch-free) numerical decisions.
-        // Categorical nodes are rare and fixed up afterwards under one wave-level branch.
-        Node16 nd[U];
-        bool walking[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          walking[u] = node[u] >= 0;  // finished lanes re-read node 0; keep their gather in range
-          nd[u] = *(const Node16 *)(s_chunk + nbase[u] + (uint32_t)max(node[u], 0) * 16u);
-        }
-        bool left[U];
-        uint32_t any_flags = 0;
-        if constexpr (F64) {
-          double v[U];
-#pragma unroll
-          for (int u = 0; u < U; ++u) {
-            const uint32_t feat = walking[u] ? (nd[u].w2 & 0xffffu) : 0u;
-            if constexpr (ROWS_LDS) v[u] = s_rows[feat * TILE + tid];
-            else v[u] = (walking[u] && row < rows) ? (row_req ? prep<true>(X[row * cols + feat], flag + row_req[row], 32)
-                                                              : prep<true>(X[row * cols + feat], flag)) : 0.0;
-          }
-#pragma unroll
-          for (int u = 0; u < U; ++u) {
-            const uint32_t flags = (nd[u].w2 >> 16) & 0xffu;
-            any_flags |= walking[u] ? flags : 0u;
-            const double thr = __hiloint2double((int)nd[u].w1, (int)nd[u].w0);
-            bool l = v[u] <= thr;
-            if ((flags & NF_MISS_ZERO) && v[u] == 0.0) l = (flags & NF_DEFAULT_LEFT) != 0;
-            left[u] = (v[u] != v[u]) ? (((nd[u].w2 >> 24) & 1u) != 0) : l;
-          }
-          if (__builtin_expect((any_flags & NF_CATEGORICAL) != 0, 0)) {
-#pragma unroll
-            for (int u = 0; u < U; ++u)
-              if (walking[u] && (((nd[u].w2 >> 16) & NF_CATEGORICAL) != 0))
-                left[u] = decide64(nd[u].w0, nd[u].w1, nd[u].w2, v[u], cat_bits);
-          }
-#pragma unroll
-          for (int u = 0; u < U; ++u) {
-            const int next = left[u] ? (int)(short)(nd[u].w3 & 0xffffu) : (int)(short)(nd[u].w3 >> 16);
-            node[u] = walking[u] ? next : node[u];
-          }
-        } else {
-          float v[U];
-#pragma unroll
-          for (int u = 0; u < U; ++u) {
-            const uint32_t feat = walking[u] ? (nd[u].w1 & 0xffffu) : 0u;
-            if constexpr (ROWS_LDS) v[u] = s_rows[feat * TILE + tid];
-            else v[u] = (walking[u] && row < rows) ? (row_req ? prep<false>(X[row * cols + feat], flag + row_req[row], 32)
-                                                              : prep<false>(X[row * cols + feat], flag)) : 0.f;
-          }
-#pragma unroll
-          for (int u = 0; u < U; ++u) {
-            const uint32_t flags = (nd[u].w1 >> 16) & 0xffu;
-            any_flags |= walking[u] ? flags : 0u;
-            const bool l = v[u] < __uint_as_float(nd[u].w0);
-            left[u] = (v[u] != v[u]) ? ((flags & NF_DEFAULT_LEFT) != 0) : l;
-          }
-          if (__builtin_expect((any_flags & NF_CATEGORICAL) != 0, 0)) {
-#pragma unroll
-            for (int u = 0; u < U; ++u)
-              if (walking[u] && (((nd[u].w1 >> 16) & NF_CATEGORICAL) != 0))
-                left[u] = decide32(nd[u].w0, nd[u].w1, nd[u].w3, v[u], cat_bits);
-          }
-#pragma unroll
-          for (int u = 0; u < U; ++u) {
-            const int next = left[u] ? (int)(short)(nd[u].w2 & 0xffffu) : (int)(short)(nd[u].w2 >> 16);
-            node[u] = walking[u] ? next : node[u];
-          }
-        }
-      }
+      uint32_t lbase[U];
+      walk_trees<F64, U>(s_chunk, s_refs, t0, nt, cat_bits, [&](uint32_t feat, bool walking) -> row_t {
+        if constexpr (ROWS_LDS) return s_rows[feat * TILE + tid];
+        else return (walking && row < rows) ? (row_req ? prep<F64>(X[row * cols + feat], flag + row_req[row], 32)
+                                                      : prep<F64>(X[row * cols + feat], flag)) : (row_t)0;
+      }, node, lbase);
       // leaves are added strictly in tree order
 #pragma unroll
       for (int u = 0; u < U; ++u) {
