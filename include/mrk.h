@@ -318,6 +318,46 @@ int mrk_rank(mrk_ctx *ctx, mrk_model *model, const char *model_name, const mrk_r
  * out_order must have room for `capacity` items (MRK_ERR_INVALID_ARG with out_n_items set if it has more). */
 int mrk_rank_binary(mrk_ctx *ctx, mrk_model *model, const char *model_name, const uint8_t *event, size_t len,
                     int *out_n_items, double *out_scores, int32_t *out_order, int capacity);
+/* ---- training rows: ItemValue.fromState in ValueMode.OfflineTraining ------------------------------------------------
+ * The reference calls ItemValue.fromState from two places: Ranker.makeQuery (OnlineInference, the model's features: mrk_rank)
+ * and TrainBuffer.handleRanking (M/flow/TrainBuffer.scala:51-71: OfflineTraining, EVERY feature of the mapping, once per
+ * ranking event that comes through /feedback or `import`; its result is ClickthroughValues.values, the row a later training
+ * reads).  mrk_values answers the second call.
+ *   model_name  NULL: the MAPPING program - every feature of `features:`, in the order fromState emits values
+ *               (M/model/ItemValue.scala:32-69): the RankingFeatures (local_time, ua, referer) in `features:` order, then the
+ *               ItemFeatures in `features:` order.  ua / referer / random / field_match without "match": "device" are
+ *               "__ext:<name>" inputs with their "dim", as in model programs.  A model's name: that model's columns
+ *               (DatasetDescriptor order, as mrk_rank's matrix).
+ *   mode        0 OnlineInference, 1 OfflineTraining.  The one feature that reads it is `position`
+ *               (M/feature/PositionFeature.scala:32-33): online the configured constant, offline the candidate's index in its
+ *               request (0, 1, 2, ...).  mode 0 with a model's name is mrk_rank(model = NULL, out_matrix)'s matrix.
+ *   out_matrix  n_items x mrk_values_dim() f64, row-major.  A CategoryValue column carries the category's INDEX (what
+ *               ClickthroughQuery.collectFeatureValues reads); CategoryValue.cat is not returned - the host has it as
+ *               values[index - 1] of the feature's schema ("nil" for 0).
+ * Statuses are mrk_rank's (MRK_ERR_DIM_MISMATCH, MRK_ERR_ARITHMETIC of the normalised rate, ...).  Small requests take ONE
+ * kernel launch whose stores go straight into pinned host memory (no forest, no ordering, no copy command); requests of
+ * more than a workgroup's lanes, requests with per-item overrides and programs with a request-normalised column take the
+ * assembly launches and a copy.  Callers of one context are served one at a time; hosts that batch use mrk_batch_load_values.
+ * mrk_values_binary: the same for a request in the reference's binary RankingEventFormat (mrk_rank_binary's decoder);
+ * out_matrix must have room for `capacity` items.
+ * mrk_values_dim: columns of a row (model_name NULL: of the mapping program), <0 on error.
+ * mrk_values_columns: text, one line per feature in column order: "<name>\t<first column>\t<dim>\t<single|vector|category>\n"
+ * - the MValue the reference's feature emits (SingleValue / VectorValue / CategoryValue(index)); NUL-terminated; sizing as
+ * mrk_config_kernel_keys.
+ * mrk_batch_load_values: mrk_batch_load for a values program; mrk_batch_run(batch, NULL) then assembles the rows (scores are
+ * 0.0 and every request keeps its own order, as NoopRanker's), mrk_batch_fetch(out_matrix) / mrk_batch_status read them.
+ * mrk_config_specialize_values: mrk_config_specialize (f64 = 1) for a values program; kernel 12 (what = 12 << 8 | form) is the
+ * one-launch values kernel.  An offline program with a `position` feature holds the item-index op (kind 15); online ones and
+ * programs without `position` do not, and their kernels are the ones mrk_rank runs. */
+int mrk_values(mrk_ctx *ctx, const char *model_name, int mode, const mrk_request *req, double *out_matrix);
+int mrk_values_binary(mrk_ctx *ctx, const char *model_name, int mode, const uint8_t *event, size_t len, int *out_n_items,
+                      double *out_matrix, int capacity);
+int mrk_values_dim(mrk_ctx *ctx, const char *model_name);
+int mrk_values_columns(mrk_ctx *ctx, const char *model_name, char *out, size_t cap, size_t *needed);
+/* host-only (no device, no context), as mrk_config_specialize: the same text for a config that is not loaded anywhere */
+int mrk_config_values_columns(const char *json, size_t len, const char *model_name, char *out, size_t cap, size_t *needed);
+int mrk_config_specialize_values(const char *json, size_t len, const char *model_name, int mode, int what, uint8_t *out,
+                                 size_t cap, size_t *needed);
 /* Warm-up (Serve.maybeWarmup, M/main/command/Serve.scala:130-150): a model loaded with mrk_model_load_container keeps
  * the container's warm-up requests; mrk_model_warmup ranks each of them once (results discarded) and returns the
  * number replayed through out_replayed. */
@@ -365,6 +405,8 @@ typedef struct mrk_item_ids {
  * this batch.  Pageable memory is copied before mrk_batch_load returns and may be reused at once. */
 int mrk_batch_create(mrk_ctx *ctx, mrk_batch **out);
 int mrk_batch_load(mrk_batch *batch, const char *model_name, const mrk_request *reqs, int n_req, const mrk_item_ids *ids);
+int mrk_batch_load_values(mrk_batch *batch, const char *model_name /* NULL: the mapping program */, int mode, const mrk_request *reqs,
+                          int n_req, const mrk_item_ids *ids);   /* see mrk_values */
 int mrk_batch_enqueue_fetch(mrk_batch *batch);
 int mrk_batch_host_outputs(mrk_batch *batch, const double **scores, const int32_t **order, const int32_t **status);
 /* pinned (page-locked) host memory the device can read / write without a staging copy; NULL on failure */

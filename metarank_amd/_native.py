@@ -188,6 +188,13 @@ SIGNATURES = {
     "mrk_store_flush": (_I, [_V]),
     "mrk_rank": (_I, [_V, _V, _S, C.POINTER(mrk_request), _P, _P, _P]),
     "mrk_rank_binary": (_I, [_V, _V, _S, _P, C.c_size_t, C.POINTER(C.c_int), _P, _P, _I]),
+    "mrk_values": (_I, [_V, _S, _I, C.POINTER(mrk_request), _P]),
+    "mrk_values_binary": (_I, [_V, _S, _I, _P, C.c_size_t, C.POINTER(C.c_int), _P, _I]),
+    "mrk_values_dim": (_I, [_V, _S]),
+    "mrk_values_columns": (_I, [_V, _S, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "mrk_config_values_columns": (_I, [_S, C.c_size_t, _S, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "mrk_config_specialize_values": (_I, [_S, C.c_size_t, _S, _I, _I, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "mrk_batch_load_values": (_I, [_V, _S, _I, C.POINTER(mrk_request), _I, _P]),
     "mrk_model_warmup": (_I, [_V, _V, _S, C.POINTER(C.c_int)]),
     "mrk_batch_prepare": (_I, [_V, _S, C.POINTER(mrk_request), _I, C.POINTER(_V)]),
     "mrk_batch_create": (_I, [_V, C.POINTER(_V)]),

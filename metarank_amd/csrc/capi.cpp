@@ -29,6 +29,7 @@ static Switches read_switches() {
   s.prepass_lds = flag("MRK_PREPASS_LDS", true);
   s.rank_combine = flag("MRK_RANK_COMBINE", true);
   s.rank_one = flag("MRK_RANK_ONE", true);
+  s.values_one = flag("MRK_VALUES_ONE", true);
   if (const char *e = getenv("MRK_RANK_ONE_WALK")) s.rank_one_walk = !strcmp(e, "0") ? 0 : !strcmp(e, "1") ? 1 : -1;
   s.rank_fused_score = flag("MRK_RANK_FUSED_SCORE", false);
   s.rank_serve = flag("MRK_RANK_SERVE", true);

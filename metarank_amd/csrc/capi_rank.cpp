@@ -54,6 +54,8 @@ void launch_rank_one(mrk_ctx *ctx, const StoreDev &st, const ProgramDev &prog, c
                      int threads, int op_split, const QsDev &q, const QsForestDev &f, const OneOut &out, bool f64, void *jit_fn);
 void launch_rank_one_walk(mrk_ctx *ctx, const StoreDev &st, const ProgramDev &prog, const BatchDev &b, uint32_t tab_entries, int vals_cap,
                           int threads, int op_split, const WalkDev &w, const OneOut &out, bool f64, size_t lds, void *jit_fn);
+void launch_rank_values(mrk_ctx *ctx, const StoreDev &st, const ProgramDev &prog, const BatchDev &b, uint32_t tab_entries, int vals_cap,
+                        int threads, int op_split, const ValuesOut &out, void *jit_fn);
 void launch_rank_serve_walk(mrk_ctx *ctx, hipStream_t stream, const StoreDev &st, const ProgramDev &prog, const WalkDev &w, const ServeGangDev &gang,
                             int n_slots, int threads, size_t lds, bool f64, void *jit_fn);
 int load_feature_values(Store &store, const uint8_t *bytes, size_t len, int64_t now_ms);  // codec.cpp
@@ -136,13 +138,20 @@ struct mrk_batch {
   // the f64 matrix is materialised only on demand (explain / parity / models without a bit-vector image)
   bool want_matrix = false;
   bool matrix_valid = false;
+  // training rows (mrk_values, mrk_batch_load_values): mrk_batch_run(batch, NULL) assembles the rows of the loaded values program
+  bool values = false;
+  bool values_ran = false;              // the last run was such a run: scores are 0.0 and the order is the request's own (NoopRanker.scala:22-26), filled by the host
+  bool values_direct = false;           // ... by the one-launch values kernel: the device wrote rows and status words into h_vals itself
+  PinBuf h_vals;                        // [rows: T x dim f64][status: n_req i32][load status: n_req i32]
+  size_t vals_status_off = 0;
 };
 
 namespace mrk {
 
 void free_rank_state(mrk_ctx *ctx) {
-  for (int i = 0; i < mrk_ctx::RANK_LANES_MAX; ++i) {
-    mrk_batch *b = (mrk_batch *)ctx->rank_lane[i];
+  for (int i = 0; i <= mrk_ctx::RANK_LANES_MAX; ++i) {   // (the last round: mrk_values' scratch batch)
+    void *&lane = i < mrk_ctx::RANK_LANES_MAX ? ctx->rank_lane[i] : ctx->values_lane;
+    mrk_batch *b = (mrk_batch *)lane;
     if (!b) continue;
     (void)hipSetDevice(ctx->device);
     if (b->stream) {
@@ -150,7 +159,7 @@ void free_rank_state(mrk_ctx *ctx) {
       (void)hipStreamDestroy(b->stream);
     }
     delete b;
-    ctx->rank_lane[i] = nullptr;
+    lane = nullptr;
   }
   delete ctx->registry;
   delete ctx->store;
@@ -321,6 +330,7 @@ static void build_batch(mrk_ctx *ctx, const Program &prog, const mrk_request *re
   b.ran = false;
   b.matrix_valid = false;
   b.fetch_enqueued = false;
+  b.values_ran = b.values_direct = false;
   b.big.clear();
   size_t big_bytes = 0;
   for (int r = 0; r < n_req; ++r)
@@ -489,6 +499,7 @@ static void run_batch(mrk_batch &b, mrk_model *model, int lo, int hi, bool sort,
   const ProgramDev pd = b.prog->device_view();
   b.fetch_enqueued = false;
   b.direct_out = false;
+  b.values_ran = b.values_direct = false;
   if (one || one_walk) {
     b.h_out.reserve(b.out_bytes);
     uint8_t *h = b.h_out.as<uint8_t>();
@@ -552,10 +563,58 @@ static void run_batch(mrk_batch &b, mrk_model *model, int lo, int hi, bool sort,
 
 static void run_batch(mrk_batch &b, mrk_model *model) { run_batch(b, model, 0, b.total_items, true); }
 
+// The training rows of a batch (TrainBuffer.handleRanking: ItemValue.fromState over the loaded values program) on the batch's
+// stream; the caller holds the store (StoreAccess).  Small requests: ONE launch that writes rows and status words straight
+// into the batch's pinned block (rank_device.hpp rank_values_body) - no forest, no ordering, no copy command.  Anything else
+// (requests sliced over several workgroups or too large for one, per-item overrides, a request-normalised column, a caller
+// that asked for the device matrix, MRK_VALUES_ONE=0): today's assembly launch(es) into the device matrix, fetched by a copy.
+// The specialised kernel is used with or without a model.
+static void run_values(mrk_batch &b) {
+  mrk_ctx *ctx = b.ctx;
+  MRK_HIP(hipSetDevice(ctx->device));
+  const Switches &sw = switches();
+  const size_t T = (size_t)b.total_items, R = (size_t)std::max(b.n_req, 1);
+  const bool one = sw.values_one && b.fused_ok && b.n_req >= 1 && T > 0 && b.prog->dim > 0 && b.fused_slices == 1 && b.fused_threads <= 512 &&
+                   b.view.n_overrides == 0 && !b.prog->normalises() && !b.want_matrix;
+  // (before LaunchOn: a first use may compile)
+  void *jit_fn = one ? jit_values_function(*b.prog) : b.fused_ok && b.fused_split == 1 && b.fused_slices == 1 ? jit_matrix_function(*b.prog) : nullptr;
+  LaunchOn on(ctx, b.s());
+  const StoreDev st = ctx->store->device_view();
+  const ProgramDev pd = b.prog->device_view();
+  b.fetch_enqueued = false;
+  b.direct_out = false;
+  b.values_ran = true;
+  b.values_direct = false;
+  b.view.item_lo = 0;
+  b.view.item_hi = b.total_items;
+  if (one) {
+    b.vals_status_off = align_up(T * (size_t)pd.dim * 8, 256);
+    b.h_vals.reserve(b.vals_status_off + 2 * R * 4);
+    uint8_t *h = b.h_vals.as<uint8_t>();
+    const ValuesOut out{(double *)h, (int32_t *)(h + b.vals_status_off), (const int32_t *)(b.d_out.as<uint8_t>() + b.out_status_off) + R, (int32_t)R};
+    launch_rank_values(ctx, st, pd, b.view, b.fused_entries, b.fused_vals, b.fused_threads, b.fused_split, out, jit_fn);
+    b.matrix_valid = false;
+    b.values_direct = true;
+    b.ran = true;
+    return;
+  }
+  MRK_HIP(hipMemsetAsync(b.view.status, 0, R * 4, b.s()));
+  assemble_matrix(b, st, pd, jit_fn);
+  b.ran = true;
+}
+
+// NoopRanker's answer (ml/rank/NoopRanker.scala:22-26) for a values run: every score 0.0, every request in its own order
+static void fill_noop_outputs(const mrk_batch &b, double *scores, int32_t *order) {
+  if (scores) std::fill(scores, scores + b.total_items, 0.0);
+  if (order)
+    for (const ReqDev &rq : b.hb.reqs)
+      for (int i = 0; i < rq.n_items; ++i) order[rq.item_begin + i] = i;
+}
+
 // scores + order + status -> the batch's pinned result buffer, one copy (a copy into pageable caller memory is staged by
 // the runtime anyway, and three small copies cost three round trips); asynchronous
 static void enqueue_fetch(mrk_batch &b, bool scores, bool order) {
-  if (b.direct_out) return;  // the device wrote h_out itself
+  if (b.direct_out || b.values_direct) return;  // the device wrote h_out / h_vals itself
   const size_t T = (size_t)b.total_items;
   b.h_out.reserve(b.out_bytes);
   uint8_t *h = b.h_out.as<uint8_t>();
@@ -574,6 +633,19 @@ static void fetch_batch(mrk_batch &b, double *scores, int32_t *order, double *ma
   mrk_ctx *ctx = b.ctx;
   MRK_HIP(hipSetDevice(ctx->device));
   const size_t T = (size_t)b.total_items;
+  if (b.values_direct) {   // the one-launch values kernel: rows and status words are in the batch's pinned block once the stream is idle
+    MRK_HIP(hipStreamSynchronize(b.s()));
+    const uint8_t *h = b.h_vals.as<uint8_t>();
+    if (matrix && T && b.prog->dim) memcpy(matrix, h, T * b.prog->dim * 8);
+    const int32_t *hs = (const int32_t *)(h + b.vals_status_off), *hl = hs + std::max(b.n_req, 1);
+    for (int r = 0; r < b.n_req; ++r) b.h_status[(size_t)r] = hs[r] | hl[r];
+    fill_noop_outputs(b, scores, order);
+    if (ctx->profile) {
+      std::lock_guard<std::mutex> lk(ctx->mu);
+      drain_profile_events(ctx);
+    }
+    return;
+  }
   if (matrix && T && b.prog->dim && !b.matrix_valid) {
     // the last run assembled straight into the scorer's tile: materialise the f64 matrix now
     LaunchOn on(ctx, b.s());
@@ -588,6 +660,7 @@ static void fetch_batch(mrk_batch &b, double *scores, int32_t *order, double *ma
   const uint8_t *h = b.h_out.as<uint8_t>();
   if (scores && T) memcpy(scores, h, T * 8);
   if (order && T) memcpy(order, h + b.out_order_off, T * 4);
+  if (b.values_ran) fill_noop_outputs(b, scores, order);   // (a values run launches neither scorer nor sort)
   const int32_t *hs = (const int32_t *)(h + b.out_status_off), *hl = hs + std::max(b.n_req, 1);
   for (int r = 0; r < b.n_req; ++r) b.h_status[(size_t)r] = hs[r] | hl[r];
   if (ctx->profile) {
@@ -639,6 +712,30 @@ int mrk_config_specialize(const char *json, size_t len, const char *model_name, 
 }
 
 static const Program &program_of(mrk_ctx *ctx, const char *model_name);
+
+int mrk_config_specialize_values(const char *json, size_t len, const char *model_name, int mode, int what, uint8_t *out, size_t cap, size_t *needed) {
+  return guard([&] {
+    const int kernel = (what >> 8) - 1;  // as mrk_config_specialize; the values kernel (1 + JIT_VALUES) included
+    what &= 0xff;
+    if (!json || !needed || (what != 0 && what != 1) || kernel < JIT_ALL || kernel > JIT_VALUES) throw StatusError(MRK_ERR_INVALID_ARG, "null argument / unknown `what`");
+    if (mode != MODE_ONLINE && mode != MODE_OFFLINE) throw StatusError(MRK_ERR_INVALID_ARG, "mode must be 0 (online) or 1 (offline)");
+    Store st;
+    std::unique_ptr<Registry> reg = load_config(json, len, st, /*upload=*/false);
+    const Program *p = reg->values_program(model_name, mode);
+    if (!p) throw StatusError(MRK_ERR_NOT_FOUND, std::string("model ") + (model_name ? model_name : "<mapping>") + " is not configured");
+    const std::string src = jit_source(*p, true, kernel);
+    std::vector<char> code;
+    if (what == 1 && out) {  // sizing calls (out == NULL) do not compile
+      std::string log;
+      code = jit_compile(src, log);
+    }
+    const char *data = what == 0 ? src.data() : code.data();
+    const size_t n = what == 0 ? src.size() : code.size();
+    *needed = what == 1 && !out ? (size_t)1 << 22 : n;
+    if (cap < n || !out) throw StatusError(MRK_ERR_INVALID_ARG, "output buffer too small (see *needed)");
+    memcpy(out, data, n);
+  });
+}
 
 // host only: the view signature of a serialised booster (what mrk_model_load would key this model's kernels by)
 static QsSignature signature_of_bytes(int backend, const uint8_t *bytes, size_t len, bool &f64) {
@@ -1189,6 +1286,121 @@ static const Program &locked_program(mrk_ctx *ctx, const char *model_name) {
   return program_of(ctx, model_name);
 }
 
+// ---- training rows: what TrainBuffer.handleRanking asks ItemValue.fromState for (flow/TrainBuffer.scala:51-71)
+static const Program &values_program_in(const Registry &reg, const char *model_name, int mode) {
+  if (mode != MODE_ONLINE && mode != MODE_OFFLINE) throw StatusError(MRK_ERR_INVALID_ARG, "mode must be 0 (online) or 1 (offline)");
+  const Program *p = reg.values_program(model_name, mode);
+  if (!p) throw StatusError(MRK_ERR_NOT_FOUND, std::string("model ") + (model_name ? model_name : "<mapping>") + " is not configured");
+  return *p;
+}
+
+static const Program &locked_values_program(mrk_ctx *ctx, const char *model_name, int mode) {
+  if (!ctx) throw StatusError(MRK_ERR_INVALID_ARG, "null argument");
+  std::shared_lock<std::shared_mutex> sl(ctx->store_mu);
+  if (!ctx->registry) throw StatusError(MRK_ERR_INVALID_ARG, "mrk_config_load_json must be called first");
+  const Program &p = values_program_in(*ctx->registry, model_name, mode);
+  if (!p.d_ops.p)
+    throw StatusError(MRK_ERR_UNSUPPORTED, "the mapping needs " + std::to_string(p.prep.size()) + " per-request reductions (interacted_with fields + diversity features); 32 are supported");
+  return p;
+}
+
+int mrk_values(mrk_ctx *ctx, const char *model_name, int mode, const mrk_request *req, double *out_matrix) {
+  return guard([&] {
+    if (!ctx || !req || !out_matrix) throw StatusError(MRK_ERR_INVALID_ARG, "null argument");
+    const Program &prog = locked_values_program(ctx, model_name, mode);
+    std::lock_guard<std::mutex> vl(ctx->values_mu);
+    MRK_HIP(hipSetDevice(ctx->device));
+    if (!ctx->values_lane) {
+      std::unique_ptr<mrk_batch> nb(new mrk_batch());
+      MRK_HIP(hipStreamCreateWithFlags(&nb->stream, hipStreamNonBlocking));
+      ctx->values_lane = nb.release();
+    }
+    mrk_batch &b = *(mrk_batch *)ctx->values_lane;
+    StoreAccess access(ctx, program_mutates_store(prog));
+    if (b.ctx) MRK_HIP(hipStreamSynchronize(b.s()));  // a previous call that failed before its fetch may have left an upload from h_in in flight
+    build_batch(ctx, prog, req, 1, nullptr, b);
+    b.values = true;
+    b.want_matrix = false;
+    run_values(b);
+    if (!b.values_direct) {
+      enqueue_fetch(b, false, false);
+      b.fetch_enqueued = true;
+    }
+    access.release();   // (the rows are assembled: what follows needs no store)
+    fetch_batch(b, nullptr, nullptr, out_matrix);
+    std::string msg;
+    const int code = status_to_code(b.h_status[0], msg);
+    if (code != MRK_OK) throw StatusError(code, msg);
+  });
+}
+
+int mrk_values_binary(mrk_ctx *ctx, const char *model_name, int mode, const uint8_t *event, size_t len, int *out_n_items, double *out_matrix, int capacity) {
+  DecodedRequest dr;
+  int rc = guard([&] {
+    if (out_n_items) *out_n_items = 0;
+    if (!event) throw StatusError(MRK_ERR_INVALID_ARG, "null event");
+    dr.decode(event, len);
+    if (out_n_items) *out_n_items = dr.req.n_items;
+    if (dr.req.n_items > capacity) throw StatusError(MRK_ERR_INVALID_ARG, "the event has more items than the output buffer holds");
+  });
+  if (rc != MRK_OK) return rc;
+  return mrk_values(ctx, model_name, mode, &dr.req, out_matrix);
+}
+
+int mrk_values_dim(mrk_ctx *ctx, const char *model_name) {
+  int dim = -1;
+  int rc = guard([&] {
+    if (!ctx) throw StatusError(MRK_ERR_INVALID_ARG, "null argument");
+    std::shared_lock<std::shared_mutex> lk(ctx->store_mu);
+    if (!ctx->registry) throw StatusError(MRK_ERR_INVALID_ARG, "mrk_config_load_json must be called first");
+    dim = values_program_in(*ctx->registry, model_name, MODE_OFFLINE).dim;
+  });
+  return rc == MRK_OK ? dim : rc;
+}
+
+// "<name>\t<first column>\t<dim>\t<single|vector|category>\n" per feature of a values program, in column order
+static std::string values_columns_text(const Program &prog) {
+  std::string text;
+  for (const HostOp &ho : prog.host_ops) {
+    const FeatureDef &f = *ho.def;
+    // the MValue the reference's feature emits (feature/*.scala): CategoryValue for string encode: index and referer,
+    // VectorValue for the list-valued features whatever their dim, SingleValue for the rest
+    const bool category = f.category || (f.type == FType::String && f.index_encode);
+    const bool vector = f.type == FType::Vector || (f.type == FType::String && !f.index_encode) || f.type == FType::WindowCount || f.type == FType::Rate ||
+                        f.type == FType::InteractedWith || (f.type == FType::ExternalRanking && !f.category) || (f.type == FType::ExternalItem && f.dim > 1);
+    text += f.name + "\t" + std::to_string(ho.dst) + "\t" + std::to_string(f.dim) + "\t" + (category ? "category" : vector ? "vector" : "single") + "\n";
+  }
+  return text;
+}
+
+static void copy_text(const std::string &text, char *out, size_t cap, size_t *needed) {
+  *needed = text.size() + 1;
+  if (!out || cap < text.size() + 1) throw StatusError(MRK_ERR_INVALID_ARG, "output buffer too small (see *needed)");
+  memcpy(out, text.c_str(), text.size() + 1);
+}
+
+int mrk_values_columns(mrk_ctx *ctx, const char *model_name, char *out, size_t cap, size_t *needed) {
+  return guard([&] {
+    if (!ctx || !needed) throw StatusError(MRK_ERR_INVALID_ARG, "null argument");
+    std::string text;
+    {
+      std::shared_lock<std::shared_mutex> lk(ctx->store_mu);
+      if (!ctx->registry) throw StatusError(MRK_ERR_INVALID_ARG, "mrk_config_load_json must be called first");
+      text = values_columns_text(values_program_in(*ctx->registry, model_name, MODE_OFFLINE));
+    }
+    copy_text(text, out, cap, needed);
+  });
+}
+
+int mrk_config_values_columns(const char *json, size_t len, const char *model_name, char *out, size_t cap, size_t *needed) {
+  return guard([&] {
+    if (!json || !needed) throw StatusError(MRK_ERR_INVALID_ARG, "null argument");
+    Store st;
+    std::unique_ptr<Registry> reg = load_config(json, len, st, /*upload=*/false);
+    copy_text(values_columns_text(values_program_in(*reg, model_name, MODE_OFFLINE)), out, cap, needed);
+  });
+}
+
 int mrk_batch_create(mrk_ctx *ctx, mrk_batch **out) {
   return guard([&] {
     if (!out) throw StatusError(MRK_ERR_INVALID_ARG, "out is null");
@@ -1217,6 +1429,21 @@ int mrk_batch_load(mrk_batch *batch, const char *model_name, const mrk_request *
     MRK_HIP(hipStreamSynchronize(batch->s()));  // the previous run may still read the staging buffers
     StoreAccess access(ctx, program_mutates_store(prog));
     build_batch(ctx, prog, reqs, n_req, ids, *batch);
+    batch->values = false;
+  });
+}
+
+int mrk_batch_load_values(mrk_batch *batch, const char *model_name, int mode, const mrk_request *reqs, int n_req, const mrk_item_ids *ids) {
+  return guard([&] {
+    if (!batch || !batch->ctx || n_req < 0 || (n_req > 0 && !reqs)) throw StatusError(MRK_ERR_INVALID_ARG, "bad arguments");
+    mrk_ctx *ctx = batch->ctx;
+    const Program &prog = locked_values_program(ctx, model_name, mode);
+    std::lock_guard<std::mutex> bl(batch->bmu);
+    MRK_HIP(hipSetDevice(ctx->device));
+    MRK_HIP(hipStreamSynchronize(batch->s()));  // the previous run may still read the staging buffers
+    StoreAccess access(ctx, program_mutates_store(prog));
+    build_batch(ctx, prog, reqs, n_req, ids, *batch);
+    batch->values = true;
   });
 }
 
@@ -1251,6 +1478,7 @@ int mrk_batch_run(mrk_batch *batch, mrk_model *model) {
     check_batch(batch, model);
     std::lock_guard<std::mutex> bl(batch->bmu);
     StoreAccess access(batch->ctx, false, /*flush=*/false);  // what the batch resolved against stays what it reads
+    if (batch->values && !model) { run_values(*batch); return; }   // loaded by mrk_batch_load_values: the training rows
     run_batch(*batch, model);
   });
 }
@@ -1384,6 +1612,10 @@ int mrk_batch_host_outputs(mrk_batch *batch, const double **scores, const int32_
       batch->fetch_enqueued = true;
     }
     fetch_batch(*batch, nullptr, nullptr, nullptr);  // waits for the batch; status words -> h_status
+    if (batch->values_ran) {   // (a values run launches neither scorer nor sort)
+      batch->h_out.reserve(batch->out_bytes);
+      fill_noop_outputs(*batch, batch->h_out.as<double>(), (int32_t *)(batch->h_out.as<uint8_t>() + batch->out_order_off));
+    }
     const uint8_t *h = batch->h_out.as<uint8_t>();
     if (scores) *scores = (const double *)h;
     if (order) *order = (const int32_t *)(h + batch->out_order_off);

@@ -372,6 +372,7 @@ std::unique_ptr<FeatureDef> parse_feature(const json::Value &o) {
     f->type = FType::ExternalRanking;
     f->ext_field = "__ext:" + nm;
     f->dim = (int)need(o, "dim", nm).as_int();
+    f->category = type == "referer" && f->dim == 1;   // RefererFeature.scala:109-111: CategoryValue(name, medium, index)
   } else if (type == "field_match" && o.find("method") && o.at("method").find("type") &&
              o.at("method").at("type").as_string() == "cross-encoder") {
     // FieldMatchCrossEncoderFeature: logits of (rankingField text, stored item text) pairs.  Without a bound encoder
@@ -473,8 +474,9 @@ void declare_columns(const FeatureDef &f, Store &st) {
   }
 }
 
-void build_program(Program &p, const std::vector<const FeatureDef *> &feats, const Store &st) {
+void build_program(Program &p, const std::vector<const FeatureDef *> &feats, const Store &st, int mode = MODE_ONLINE) {
   int dst = 0;
+  p.mode = mode;
   p.item_fixed = (int)st.tables[SC_ITEM].heap_off;
   for (const FeatureDef *f : feats) {
     Op op{};
@@ -578,7 +580,11 @@ void build_program(Program &p, const std::vector<const FeatureDef *> &feats, con
         op.scope = SC_ITEM;
         op.c0 = col_ref(st, SC_ITEM, f->name);
         break;
-      case FType::LocalTime: case FType::Position: as_const(1); break;
+      case FType::LocalTime: as_const(1); break;
+      case FType::Position:
+        if (mode == MODE_OFFLINE) op.kind = OP_ITEM_INDEX;   // PositionFeature.scala:33: zipWithIndex
+        else as_const(1);
+        break;
       case FType::ExternalRanking: as_const(f->dim); break;
       case FType::Relevancy: case FType::ExternalItem:
         op.kind = OP_FILL_NAN;
@@ -693,6 +699,13 @@ const Program *Registry::program(const std::string &model) const {
   return it == programs.end() ? nullptr : it->second.get();
 }
 
+const Program *Registry::values_program(const char *model, int mode) const {
+  if (!model) return mapping[mode == MODE_OFFLINE ? MODE_OFFLINE : MODE_ONLINE].get();
+  if (mode != MODE_OFFLINE) return program(model);
+  auto it = offline_programs.find(model);
+  return it == offline_programs.end() ? nullptr : it->second.get();
+}
+
 std::unique_ptr<Registry> load_config(const char *json_text, size_t len, Store &store, bool do_upload) {
   json::Value root = json::parse(json_text, len);
   std::unique_ptr<Registry> reg(new Registry());
@@ -724,8 +737,30 @@ std::unique_ptr<Registry> load_config(const char *json_text, size_t len, Store &
       }
       build_program(*p, ordered, store);
       if (do_upload) upload(*p);
+      std::unique_ptr<Program> off(new Program());
+      off->model = kv.first;
+      off->feature_names = p->feature_names;
+      build_program(*off, ordered, store, MODE_OFFLINE);
+      if (do_upload) upload(*off);
       reg->programs[kv.first] = std::move(p);
+      reg->offline_programs[kv.first] = std::move(off);
     }
+  }
+  // the mapping program: ItemValue.fromState's order over every defined feature (model/ItemValue.scala:36-68)
+  std::vector<const FeatureDef *> emitted;
+  for (int pass = 0; pass < 2; ++pass)
+    for (auto &f : reg->features) {
+      const bool ranking_feature = f->type == FType::LocalTime || f->type == FType::ExternalRanking;   // LocalDateTimeFeature, UserAgentFeature, RefererFeature
+      if (ranking_feature == (pass == 0)) emitted.push_back(f.get());
+    }
+  for (int mode : {MODE_ONLINE, MODE_OFFLINE}) {
+    std::unique_ptr<Program> p(new Program());
+    p->model = "<mapping>";
+    for (const FeatureDef *f : emitted) p->feature_names.push_back(f->name);
+    build_program(*p, emitted, store, mode);
+    // (a mapping with more per-request reductions than the pre-pass holds stays host-only: models that fit are not refused for it)
+    if (do_upload && p->prep.size() <= 32) upload(*p);
+    reg->mapping[mode] = std::move(p);
   }
   return reg;
 }
@@ -1213,7 +1248,9 @@ void resolve_requests(const Program &prog, Store &store, const mrk_request *reqs
           cs[ho.const_idx] = v;
           break;
         }
-        case FType::Position: cs[ho.const_idx] = f.position; break;  // PositionFeature.scala:32
+        case FType::Position:
+          if (ho.const_idx >= 0) cs[ho.const_idx] = f.position;  // PositionFeature.scala:32 (offline programs: the device's OP_ITEM_INDEX)
+          break;
         case FType::ExternalRanking: {
           const mrk_field *fl = fields_map_get(rq, f.ext_field);
           if (fl && fl->type == MRK_FIELD_NUMBER && f.dim == 1) cs[ho.const_idx] = fl->num;

@@ -51,6 +51,7 @@ struct FeatureDef {
   int match_method = 0;                 // field_match with "match": "device": MatchMethod (match_host.hpp); ext_field = "__tokens:<name>"
   std::string match_column;             // ... its item column "<name>_<itemField.field>" (FieldMatchFeature.scala:31)
   std::shared_ptr<const TermFreqDic> termfreq;   // ... bm25: bound by mrk_config_bind_termfreq
+  bool category = false;                // the reference emits a CategoryValue (string encode: index, referer): the column carries its index
 };
 
 // host-side description of what a request has to supply for one op
@@ -62,8 +63,13 @@ struct HostOp {
   int prep_base = -1;   // first pre-pass entry
 };
 
+// ValueMode of ItemValue.fromState (feature/BaseFeature.scala): the only feature that reads it is `position`
+// (PositionFeature.scala:32-33) - online the configured constant, offline the candidate's index in its request (OP_ITEM_INDEX)
+enum ValueMode : int { MODE_ONLINE = 0, MODE_OFFLINE = 1 };
+
 struct Program {
   std::string model;
+  int mode = MODE_ONLINE;
   std::vector<std::string> feature_names;
   std::vector<Op> ops;
   std::vector<HostOp> host_ops;
@@ -95,6 +101,14 @@ struct Registry {
   std::vector<std::unique_ptr<FeatureDef>> features;
   std::map<std::string, std::unique_ptr<Program>> programs;
   const Program *program(const std::string &model) const;
+  // What TrainBuffer.handleRanking asks ItemValue.fromState for (flow/TrainBuffer.scala:51-71): EVERY feature of the mapping, in
+  // the order fromState emits values (model/ItemValue.scala:32-69) - the RankingFeatures (local_time, ua, referer) in `features:`
+  // order, then the ItemFeatures in `features:` order -, in both value modes; and every model's program in offline mode
+  // (DatasetDescriptor order, as online).
+  std::unique_ptr<Program> mapping[2];                                   // [ValueMode]
+  std::map<std::string, std::unique_ptr<Program>> offline_programs;
+  // model == nullptr: the mapping program; nullptr when there is no such model
+  const Program *values_program(const char *model, int mode) const;
   ~Registry();
 };
 

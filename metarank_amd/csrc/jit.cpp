@@ -102,7 +102,7 @@ std::string jit_source(const Program &prog, bool f64, int kernel, const QsSignat
   // the forest's view signature (forest.hpp): the sinks of the kernels that write the scorer's tile hold it as constants;
   // without one (no bit-vector image, f64-matrix kernels, MRK_JIT_SIG=0) they read the column descriptors from memory
   std::string qs = "mrk::QsDyn";
-  if (sig && sig->ok && kernel != JIT_MATRIX && kernel != JIT_PREPASS && kernel != JIT_ONE_WALK && kernel != JIT_SERVE_WALK) {
+  if (sig && sig->ok && kernel != JIT_MATRIX && kernel != JIT_PREPASS && kernel != JIT_ONE_WALK && kernel != JIT_SERVE_WALK && kernel != JIT_VALUES) {
     table("JitSigRows", "QsSig", sig->cols.size(), sig->text);
     s += "struct JitQs {\n  static constexpr bool is_static = true;\n  static constexpr int n_feats = " + std::to_string(sig->cols.size()) +
          ", n_views = " + std::to_string(sig->n_views) + ";\n  static constexpr uint32_t thr_cap = " + std::to_string(sig->thr_cap) +
@@ -140,6 +140,12 @@ std::string jit_source(const Program &prog, bool f64, int kernel, const QsSignat
     s += "extern \"C\" __global__ void __launch_bounds__(256)" + attr + "\nmrk_jit_rank_matrix"
          "(mrk::StoreDev st, mrk::BatchDev b, uint32_t tab_entries, int vals_cap, int mode) {\n"
          "  mrk::rank_fused_matrix_body<false>(st, mrk::JitProg{}, b, tab_entries, vals_cap, mode);\n}\n";
+  // ... and its one-launch form for mrk_values: the rows go straight into the batch's pinned host block (rank_values_body)
+  if (kernel == JIT_VALUES)
+    // (as mrk_jit_rank_one: up to 512 lanes, op-split copies of the item lanes for a handful of requests, two wavefronts per SIMD)
+    s += "extern \"C\" __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2)))\nmrk_jit_rank_values"
+         "(mrk::StoreDev st, mrk::BatchDev b, uint32_t tab_entries, int vals_cap, int mode, mrk::ValuesOut out) {\n"
+         "  mrk::rank_values_body<true>(st, mrk::JitProg{}, b, tab_entries, vals_cap, mode, out);\n}\n";
   // the item-parallel form (requests too large for one workgroup: tables from a previous pre-pass launch, in HBM)
   if (kernel == JIT_ALL || kernel == JIT_ITEMS)
     s += "extern \"C\" __global__ void __launch_bounds__(256)" + attr + "\nmrk_jit_assemble_cells"
@@ -237,13 +243,13 @@ struct JitKernels {
   std::map<std::string, std::unique_ptr<JitSlotSet>> by_sig;
 };
 
-const char *const JIT_KERNEL_NAME[JIT_KERNELS] = {"mrk_jit_rank_cells", "mrk_jit_rank_cells_split", "mrk_jit_rank_matrix", "mrk_jit_assemble_cells", "mrk_jit_rank_one", "mrk_jit_rank_serve", "mrk_jit_rank_fused_score", "mrk_jit_prepass", "mrk_jit_assemble_cells_rt", "mrk_jit_rank_one_walk", "mrk_jit_rank_serve_walk"};
+const char *const JIT_KERNEL_NAME[JIT_KERNELS] = {"mrk_jit_rank_cells", "mrk_jit_rank_cells_split", "mrk_jit_rank_matrix", "mrk_jit_assemble_cells", "mrk_jit_rank_one", "mrk_jit_rank_serve", "mrk_jit_rank_fused_score", "mrk_jit_prepass", "mrk_jit_assemble_cells_rt", "mrk_jit_rank_one_walk", "mrk_jit_rank_serve_walk", "mrk_jit_rank_values"};
 // a kernel that exists only with a forest signature: no program-only stand-in (the caller falls back to another KERNEL meanwhile)
 static inline bool jit_needs_sig(int kernel) { return kernel == JIT_ITEMS_RT; }
 // the resident-table kernel: every table in LDS (<= 64 KB of thresholds leaves room for a request's hash tables and a second workgroup)
 bool jit_items_rt_applies(const QsSignature *sig) { return sig && sig->ok && sig->rt_total > 0 && (size_t)sig->rt_total * 8 <= 64 * 1024 && switches().jit_sig && switches().items_rt; }
 // kernels that neither write the scorer's tile nor depend on the scorer's precision: one per program, kept in slot [kernel][1]
-static inline bool jit_program_only(int kernel) { return kernel == JIT_MATRIX || kernel == JIT_PREPASS; }
+static inline bool jit_program_only(int kernel) { return kernel == JIT_MATRIX || kernel == JIT_PREPASS || kernel == JIT_VALUES; }
 // kernels of forests WITHOUT a view signature: never keyed by one, and no stand-in of a signature's kernel
 static inline bool jit_walk_kind(int kernel) { return kernel == JIT_ONE_WALK || kernel == JIT_SERVE_WALK; }
 
@@ -472,6 +478,7 @@ void *jit_split_function(const Program &prog, bool f64, const QsSignature *sig) 
 // the f64-matrix form of the fused kernel
 void *jit_matrix_function(const Program &prog) { return jit_function(prog, JIT_MATRIX, true, nullptr); }
 void *jit_prepass_function(const Program &prog) { return jit_function(prog, JIT_PREPASS, true, nullptr); }
+void *jit_values_function(const Program &prog) { return jit_function(prog, JIT_VALUES, true, nullptr); }
 // the one-launch kernel of small requests
 void *jit_one_function(const Program &prog, bool f64, const QsSignature *sig) { return jit_function(prog, JIT_ONE, f64, sig); }
 void *jit_one_walk_function(const Program &prog, bool f64) { return jit_function(prog, JIT_ONE_WALK, f64, nullptr); }

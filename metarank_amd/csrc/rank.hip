@@ -61,6 +61,12 @@ rank_fused_matrix_kernel(StoreDev st, ProgramDev prog, BatchDev b, uint32_t tab_
   rank_fused_matrix_body<true>(st, prog, b, tab_entries, vals_cap, mode);
 }
 
+// pre-pass + assembly in ONE launch, the rows stored straight into pinned host memory (rank_device.hpp rank_values_body: mrk_values)
+__global__ void __launch_bounds__(512)
+rank_values_kernel(StoreDev st, ProgramDev prog, BatchDev b, uint32_t tab_entries, int vals_cap, int mode, ValuesOut out) {
+  rank_values_body<true>(st, prog, b, tab_entries, vals_cap, mode, out);
+}
+
 template <bool F64>
 __global__ void __launch_bounds__(512)
 rank_fused_cells_kernel(StoreDev st, ProgramDev prog, BatchDev b, uint32_t tab_entries, int vals_cap, QsDev q, uint16_t *cells, int mode) {
@@ -402,6 +408,31 @@ void launch_rank_fused(mrk_ctx *ctx, const StoreDev &st, const ProgramDev &prog,
     }
   } else {
     launch_override_cells(ctx, b, *q, cells, f64);
+  }
+}
+
+// LDS of the one-launch values kernel: [status word, 16 B][the regions of rank_fused_body, no threshold staging]
+size_t rank_values_lds_bytes(uint32_t tab_entries, int vals_cap, int threads) { return 16 + fused_lds_bytes(tab_entries, vals_cap, threads, 0u, 0, true); }
+
+// One workgroup per request, no slices (`threads` = item lanes x op split, <= 512); jit_fn: the specialised mrk_jit_rank_values of
+// this program, or nullptr = the interpreting kernel.
+void launch_rank_values(mrk_ctx *ctx, const StoreDev &st, const ProgramDev &prog, const BatchDev &b, uint32_t tab_entries, int vals_cap,
+                        int threads, int op_split, const ValuesOut &out, void *jit_fn) {
+  if (b.n_req <= 0) return;
+  int mode = op_split > 1 ? op_split : 1;
+  const size_t lds = rank_values_lds_bytes(tab_entries, vals_cap, threads);
+  ScopedKernelTimer timer(ctx, "rank_values");
+  if (jit_fn) {
+    StoreDev a_st = st;
+    BatchDev a_b = b;
+    ValuesOut a_out = out;
+    int a_vals = vals_cap;
+    void *args[] = {&a_st, &a_b, &tab_entries, &a_vals, &mode, &a_out};
+    MRK_HIP(hipModuleLaunchKernel((hipFunction_t)jit_fn, (unsigned)b.n_req, 1, 1, (unsigned)threads, 1, 1, (unsigned)lds, ctx->launch, args, nullptr));
+  } else {
+    lds_optin(ctx, (const void *)rank_values_kernel);
+    hipLaunchKernelGGL(rank_values_kernel, dim3(b.n_req), dim3(threads), lds, ctx->launch, st, prog, b, tab_entries, vals_cap, mode, out);
+    MRK_HIP(hipGetLastError());
   }
 }
 

@@ -23,6 +23,7 @@ enum OpKind : int32_t {
   OP_FILL_NAN = 12,      // relevancy / host-computed per-item features: NaN unless an override arrives
   OP_BIENCODER = 13,     // field_match bi-encoder cosine                      (FieldMatchBiencoderFeature.scala:80-109)
   OP_FIELD_MATCH = 14,   // field_match term / ngram / bm25 against the request's query tokens (FieldMatchFeature.scala:60-92)
+  OP_ITEM_INDEX = 15,    // position in ValueMode.OfflineTraining: the candidate's index in ITS request (PositionFeature.scala:32-33)
 };
 
 enum MatchMethod : int32_t { MATCH_TERM = 0, MATCH_NGRAM = 1, MATCH_BM25 = 2 };
@@ -143,6 +144,14 @@ constexpr int PREP_MAX_VALUES = 4096;  // diversity numeric: values sorted in LD
 struct OneOut {
   double *scores;        // [total_items], request order
   int32_t *order;        // [total_items], request-local indices in response order
+  int32_t *status;       // [n_req] status words of this run, [n_req_pad .. n_req_pad + n_req) what the id resolution found at load time
+  const int32_t *load_status;   // device copy of the latter (nullptr: zeros)
+  int32_t n_req_pad;     // max(n_req, 1)
+};
+
+// where the one-launch values kernel (rank_device.hpp rank_values_body) leaves a batch's training rows: the batch's pinned block
+struct ValuesOut {
+  double *matrix;        // [total_items x dim], row-major: ClickthroughValues.values of every candidate
   int32_t *status;       // [n_req] status words of this run, [n_req_pad .. n_req_pad + n_req) what the id resolution found at load time
   const int32_t *load_status;   // device copy of the latter (nullptr: zeros)
   int32_t n_req_pad;     // max(n_req, 1)

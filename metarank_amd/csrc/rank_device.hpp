@@ -1696,6 +1696,12 @@ __device__ __forceinline__ void assemble_item_rec(const StoreDev &st, const Prog
         sink.put(dst + 0, v);
         break;
       }
+      case OP_ITEM_INDEX: {
+        // the lane's own request: lanes of one wavefront may belong to different requests (item-parallel kernels), and the
+        // index restarts at 0 in each
+        sink.put(dst + 0, (double)(gi - rq.item_begin));
+        break;
+      }
       default: break;
     }
   };
@@ -1980,6 +1986,29 @@ template <bool SPLIT = false, typename Prog>
 __device__ __forceinline__ void rank_fused_matrix_body(const StoreDev &st, const Prog &prog, const BatchDev &b, uint32_t tab_entries, int vals_cap, int mode = 1) {
   rank_fused_body<SPLIT>(st, prog, b, tab_entries, vals_cap, 0u, mode,
                   [&](int gi, int, bool active, qs_lds_double *, qs_lds_double *) { return MatrixSink{b.matrix + (size_t)gi * prog.dim, active}; });
+}
+
+// ---- ONE launch for the training rows of a batch (mrk_values: TrainBuffer.handleRanking's ItemValue.fromState): pre-pass +
+// assembly in the request's workgroup, every value stored straight into the batch's pinned host block (plain vector stores
+// through MatrixSink) - no forest, no ordering, no copy command.  The status word lives in LDS as in rank_one_body.
+// Dynamic LDS: [the request's status word, 16 B][the regions of rank_fused_body].  `mode` = op_split (SPLIT kernels only).
+template <bool SPLIT = false, typename Prog>
+__device__ __forceinline__ void rank_values_body(const StoreDev &st, const Prog &prog, const BatchDev &b, uint32_t tab_entries, int vals_cap,
+                                                 int mode, const ValuesOut &out) {
+  extern __shared__ __align__(16) uint8_t smem_base[];
+  const int r = (int)blockIdx.x;
+  int32_t *s_status = (int32_t *)smem_base;
+  if (threadIdx.x == 0) *s_status = 0;
+  BatchDev bl = b;
+  bl.status = s_status - r;   // &bl.status[r] is the LDS word
+  __syncthreads();
+  rank_fused_body<SPLIT>(st, prog, bl, tab_entries, vals_cap, 0u, mode & 255,
+                         [&](int gi, int, bool active, qs_lds_double *, qs_lds_double *) { return MatrixSink{out.matrix + (size_t)gi * prog.dim, active}; }, 16);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    out.status[r] = *s_status;
+    out.status[out.n_req_pad + r] = out.load_status ? out.load_status[r] : 0;
+  }
 }
 
 // the hot-path instance of rank_fused_body: straight into the scorer's binned tile

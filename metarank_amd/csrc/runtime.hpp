@@ -131,6 +131,7 @@ struct Switches {
   int serve_idle_us = 2000;    // MRK_SERVE_IDLE_US: a serving workgroup without a request for this long leaves its CU (relaunched by the next request)
   bool rank_fused_score = false; // MRK_RANK_FUSED_SCORE=1: full batches of small requests in ONE launch (assembly, forest, ordering per request workgroup) - measured slower than the three launches, kept for A/B
   bool rank_one = true;        // MRK_RANK_ONE=0: mrk_rank's small batches take the three-launch path instead of the one-launch kernel
+  bool values_one = true;      // MRK_VALUES_ONE=0: mrk_values / values batches take the assembly launch(es) + copy instead of the one-launch values kernel
   int rank_one_walk = -1;      // MRK_RANK_ONE_WALK: forests scored by the tree walk in ONE workgroup (rank_one_walk_body).  unset: the serving queue takes them, mrk_rank keeps its three launches
                                // (its one-launch form has not been measured against them yet: LOG.md round 10); 1: mrk_rank takes the one launch too; 0: neither - as before that kernel (same-build A/B)
   int combine_max = 256;       // MRK_RANK_COMBINE_MAX
@@ -210,6 +211,9 @@ struct mrk_ctx {
   static constexpr int RANK_LANES_MAX = 8;
   void *rank_lane[RANK_LANES_MAX] = {};
   bool lane_busy[RANK_LANES_MAX] = {};
+  // mrk_values' scratch batch (a grow-only mrk_batch on a stream of its own; owned, freed by mrk::free_rank_state): one caller at a time
+  void *values_lane = nullptr;
+  std::mutex values_mu;               // lock order: values_mu before store_mu
   // multi-GPU (comm.cpp): the RCCL communicator this context's device belongs to (ncclComm_t), nullptr = a world of one
   void *comm = nullptr;
   int comm_rank = 0, comm_world = 1;

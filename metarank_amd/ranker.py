@@ -62,6 +62,24 @@ class Batch:
         self.total_items = N.lib().mrk_batch_total_items(self._h)
         self.dim = self.ranker.dim(model_name)
 
+    def load_values(self, rs: "RequestSet | list", model: str | None = None, offline: bool = True):
+        """mrk_batch_load_values: (re)fill the batch for the training rows (TrainBuffer.handleRanking) of the mapping program
+        (model=None) or of a model's program; run(None) then assembles them and fetch(matrix=True) reads them."""
+        name = model.encode() if model is not None else None
+        if isinstance(rs, RequestSet):
+            N.check(N.lib().mrk_batch_load_values(self._h, name, 1 if offline else 0, rs.arr, rs.n_req, C.byref(rs.ids)))
+            self.requests, self.n_req, self.offsets = rs.requests, rs.n_req, rs.offsets_per_request
+            self._keep = rs
+        else:
+            self.requests = [e if isinstance(e, Request) else Request(e) for e in rs]
+            arr = request_array(self.requests)
+            N.check(N.lib().mrk_batch_load_values(self._h, name, 1 if offline else 0, arr, len(self.requests), None))
+            self.n_req = len(self.requests)
+            self.offsets = np.concatenate([[0], np.cumsum([r.n_items for r in self.requests])]).astype(np.int64)
+            self._keep = arr
+        self.total_items = N.lib().mrk_batch_total_items(self._h)
+        self.dim = self.ranker.values_dim(model)
+
     def enqueue_fetch(self):
         N.check(N.lib().mrk_batch_enqueue_fetch(self._h))
 
@@ -232,6 +250,33 @@ class HipRanker:
         if d < 0:
             N.check(d)
         return d
+
+    # ---- ItemValue.fromState for TrainBuffer.handleRanking (ClickthroughValues.values)
+    def values_dim(self, model: str | None = None) -> int:
+        d = N.lib().mrk_values_dim(self.ctx.handle, model.encode() if model is not None else None)
+        if d < 0:
+            N.check(d)
+        return d
+
+    def values(self, request, model: str | None = None, offline: bool = True) -> np.ndarray:
+        """mrk_values: the n_items x values_dim(model) rows of one ranking event - every feature of the mapping in
+        ItemValue.fromState's order (model=None) or a model's columns; offline=True is ValueMode.OfflineTraining
+        (`position` = the item's index in the request).  A category column carries the category's index."""
+        req = request if isinstance(request, Request) else Request(request)
+        mat = np.empty((req.n_items, self.values_dim(model)), dtype=np.float64)
+        N.check(N.lib().mrk_values(self.ctx.handle, model.encode() if model is not None else None, 1 if offline else 0,
+                                   C.byref(req.c), mat.ctypes.data_as(C.c_void_p)))
+        return mat
+
+    def values_columns(self, model: str | None = None) -> list:
+        """mrk_values_columns: [(feature name, first column, dim, "single" | "vector" | "category")] in column order"""
+        name = model.encode() if model is not None else None
+        need = C.c_size_t(0)
+        N.lib().mrk_values_columns(self.ctx.handle, name, None, 0, C.byref(need))
+        buf = C.create_string_buffer(max(need.value, 1))
+        N.check(N.lib().mrk_values_columns(self.ctx.handle, name, buf, len(buf), C.byref(need)))
+        rows = [ln.split("\t") for ln in buf.value.decode().splitlines()]
+        return [(n, int(c), int(d), k) for n, c, d, k in rows]
 
     def load_model(self, blob: bytes, backend: int) -> HipBooster:
         return HipBooster(blob, backend, self.ctx)
