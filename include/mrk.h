@@ -35,6 +35,8 @@
  *                                 all inside the one host process (M/main/command/Serve.scala:72-128)
  *   mrk_index_*                <- KnnIndexWriter.write / KnnIndexReader.lookup  M/ml/recommend/embedding/HnswJavaIndex.scala:23-87,
  *                                 EmbeddingSimilarityModel.predict  M/ml/recommend/MFRecommender.scala:66-80
+ *   mrk_trending_*             <- TrendingPredictor.fit / load, TrendingModel.predict / save
+ *                                 M/ml/recommend/TrendingRecommender.scala:39-133
  *   mrk_encoder_*              <- OnnxSession / OnnxBiEncoder / OnnxCrossEncoder  M/ml/onnx/sbert/ (OnnxSession, OnnxBiEncoder, OnnxCrossEncoder .scala)
  *
  * ABI 8 (round 5): mrk_init creates n contexts; mrk_device_count; mrk_comm_init_local; mrk_model_inspect; mrk_serve_stats takes
@@ -42,6 +44,7 @@
  * ABI 9 (round 6): mrk_model_weights / mrk_model_inspect_weights (Booster.weights()), mrk_abi_layout.  Same ABI, new behaviour:
  * the serving queue's slots are launched in gangs (64 slots on 8 streams) and mrk_rank answers through a started queue.
  * Still ABI 9, new symbols only: mrk_index_* (the similar-items index of /recommend).
+ * Still ABI 9, new symbols only: mrk_trending_* (the trending recommender of /recommend).
  */
 #ifndef MRK_H
 #define MRK_H
@@ -677,6 +680,59 @@ int mrk_index_lookup(mrk_index *ix, const char *const *item_ids, int n_items, in
  * after the filter -> MRK_ERR_NOT_FOUND ("empty response from the recommender", :74). */
 int mrk_index_recommend(mrk_index *ix, const char *const *item_ids, int n_items, int count, int32_t *out_rows, double *out_score, int32_t *out_n);
 void mrk_index_free(mrk_index *ix);
+
+/* ---- trending items (POST /recommend/<model>, type: trending): the fit on the device ---------------------------------------
+ * Replaces TrendingPredictor.fit / load and TrendingModel.predict / save, M/ml/recommend/TrendingRecommender.scala:39-133.
+ * Input: the ordered stream of ItemInteraction(item, type, ts) of :42 - ts is the CLICK-THROUGH's ranking timestamp (ct.ct.ts),
+ * not the interaction's own; the config's `selector` is applied by the host before it hands interactions over.  Semantics,
+ * all bit-exact:
+ *   now    = the maximal ts of ALL interactions (:45), types no weight names included
+ *   items  = the distinct item ids in order of first appearance (:47); one whose interactions match no weight scores 0.0
+ *   per weight w: an interaction counts iff type == w.interaction and ts > now - window.toMillis (:52-53, strict); its bucket is
+ *            (now - ts) / 86 400 000 (:57).  A bucket >= window.toDays - a window that is no whole number of days, or shorter
+ *            than a day - is the JVM's ArrayIndexOutOfBounds (:58-59): the fit fails with MRK_ERR_DIM_MISMATCH naming the
+ *            weight; nothing is clamped or dropped.
+ *   part_w = +0.0 for an item without a counted interaction (:79), else (s = 0.0; for every day i in order: s = s +
+ *            (double)count[i] * pow(decay, i)) * weight (:72-78) - each * and + one IEEE f64 operation, never fused; pow is the
+ *            host libm's.  A day with no count is still visited: 0 * Infinity is NaN, as on the JVM.
+ *   score  = the parts summed left to right in config order starting from the first (Scala 2.13's List.sum as a reduce; 0.0
+ *            for no weights) (:82)
+ *   model  = the items by stable sortBy(-score) (:85): java.lang.Double.compare on the negated score - +0.0 before -0.0, NaN
+ *            last -, ties in order of first appearance.  Recommender.recommend's second sortBy(-score) (M/ml/Recommender.scala:42)
+ *            is the identity on this list, so predict's answer is the response.
+ * Refused rather than imitated: two weights naming one interaction (the reference's .toMap lets the last one's counts feed
+ * both), more than 2^31 - 1 interactions, a count table (4 B x items x sum of window days) that does not fit the device memory
+ * free at fit - all MRK_ERR_UNSUPPORTED.  A finished model is a host object: predict, id, save and load read no device memory. */
+typedef struct mrk_trending_builder mrk_trending_builder;
+typedef struct mrk_trending mrk_trending;
+/* TrendingConfig's decoder, :137-164: {"weights":[{"interaction":"click","weight":1.0,"decay":0.5,"window":"30d"}, ...]} with the
+ * reference's defaults (1.0, 1.0, 30d); durations are ([0-9]+)([smhd]).  MRK_ERR_PARSE for malformed JSON or a bad duration,
+ * MRK_ERR_UNSUPPORTED for a duplicate interaction - both judged before the context is looked at. */
+int mrk_trending_begin(mrk_ctx *ctx, const char *config_json, mrk_trending_builder **out);
+/* The flatMap of :40-44: appends n interactions in order.  item_ids[n]; type_idx[n] indexes THIS call's type_names[n_types];
+ * ts_ms[n].  May be called any number of times; the result does not depend on how the stream is cut into calls.  An index
+ * outside the table or a null id fails the call with MRK_ERR_INVALID_ARG and nothing of it is appended. */
+int mrk_trending_add(mrk_trending_builder *b, const char *const *item_ids, const char *const *type_names, int n_types, const int32_t *type_idx,
+                     const int64_t *ts_ms, int64_t n);
+/* The rest of TrendingPredictor.fit, :45-86.  No interactions: MRK_ERR_NOT_FOUND ("no interactions found").  The builder stays
+ * valid and can take more adds; a later fit covers everything added so far. */
+int mrk_trending_fit(mrk_trending_builder *b, mrk_trending **out);
+void mrk_trending_builder_free(mrk_trending_builder *b);
+/* TrendingPredictor.loadSync, :90-110: big-endian i32 1, i32 size, per item readUTF + f64.  Ids are kept as the bytes readUTF's
+ * length covers (modified UTF-8, as mrk_store_put_binary keeps them).  Another version: MRK_ERR_UNSUPPORTED; size <= 0,
+ * truncation or trailing bytes: MRK_ERR_PARSE.  No device needed; ctx may be NULL. */
+int mrk_trending_load(mrk_ctx *ctx, const uint8_t *bytes, size_t len, mrk_trending **out);
+/* TrendingModel.save, :123-133.  MRK_ERR_INVALID_ARG with *needed set when `out` is NULL or `cap` too small; an id of more than
+ * 65 535 bytes is what writeUTF throws on: MRK_ERR_UNSUPPORTED. */
+int mrk_trending_save(mrk_trending *t, uint8_t *out, size_t cap, size_t *needed);
+/* items of the model, interactions and `now` of its fit (-1 / -1 for a loaded model); any output may be NULL */
+int mrk_trending_info(mrk_trending *t, int64_t *items, int64_t *interactions, int64_t *now_ms);
+/* the id at place `rank` of the model: NULL when out of range; valid until mrk_trending_free */
+const char *mrk_trending_id(mrk_trending *t, int64_t rank);
+/* TrendingModel.predict, :116-121: the scores of the first *out_n = min(count, items) items; their ids are ranks 0 .. *out_n - 1.
+ * count <= 0: MRK_ERR_INVALID_ARG ("count should be greater than 0"). */
+int mrk_trending_predict(mrk_trending *t, int count, double *out_scores, int32_t *out_n);
+void mrk_trending_free(mrk_trending *t);
 
 #ifdef __cplusplus
 }

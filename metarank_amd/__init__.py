@@ -8,3 +8,4 @@ from .booster import LIGHTGBM, XGBOOST, Context, HipBooster, default_context  # 
 from .index import HipIndex  # noqa: F401,E402
 from .ranker import Batch, HipRanker, Server  # noqa: F401,E402
 from .request import Request, RequestSet  # noqa: F401,E402
+from .trending import HipTrending, TrendingBuilder  # noqa: F401,E402

@@ -257,6 +257,16 @@ SIGNATURES = {
     "mrk_index_lookup": (_I, [_V, C.POINTER(_S), _I, _I, _P, _P, _P]),
     "mrk_index_recommend": (_I, [_V, C.POINTER(_S), _I, _I, _P, _P, _P]),
     "mrk_index_free": (None, [_V]),
+    "mrk_trending_begin": (_I, [_V, _S, C.POINTER(_V)]),
+    "mrk_trending_add": (_I, [_V, C.POINTER(_S), C.POINTER(_S), _I, _P, _P, C.c_int64]),
+    "mrk_trending_fit": (_I, [_V, C.POINTER(_V)]),
+    "mrk_trending_builder_free": (None, [_V]),
+    "mrk_trending_load": (_I, [_V, _P, C.c_size_t, C.POINTER(_V)]),
+    "mrk_trending_save": (_I, [_V, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "mrk_trending_info": (_I, [_V, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "mrk_trending_id": (_S, [_V, C.c_int64]),
+    "mrk_trending_predict": (_I, [_V, _I, _P, C.POINTER(C.c_int32)]),
+    "mrk_trending_free": (None, [_V]),
 }
 
 _lib = None

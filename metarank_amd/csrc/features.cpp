@@ -12,6 +12,7 @@
 #include <string_view>
 #include <thread>
 
+#include "duration.hpp"
 #include "encoder.hpp"
 #include "jit.hpp"
 #include "json.hpp"
@@ -98,23 +99,7 @@ int vector_dim(const json::Value *reduce) {
   return d;
 }
 
-// util/DurationJson.scala:9-13: ([0-9]+)([smhd])
-static bool parse_duration_ms(const std::string &s, int64_t &out) {
-  if (s.size() < 2) return false;
-  int64_t n = 0;
-  for (size_t i = 0; i + 1 < s.size(); ++i) {
-    if (s[i] < '0' || s[i] > '9') return false;
-    n = n * 10 + (s[i] - '0');
-    if (n > 100000000000LL) return false;  // (FiniteDuration is bounded too: ~292 years; 1e11 days is far outside)
-  }
-  switch (s.back()) {
-    case 's': out = n * 1000; return true;
-    case 'm': out = n * 60 * 1000; return true;
-    case 'h': out = n * 3600 * 1000; return true;
-    case 'd': out = n * 86400 * 1000; return true;
-    default: return false;
-  }
-}
+// (parse_duration_ms - util/DurationJson.scala:9-13 - lives in duration.hpp: the trending recommender's config reads it too)
 
 // window_count / rate: `bucket` and `periods` (PeriodicCounterConfig(period = bucket, sumPeriodRanges = periods.map(PeriodRange(_, 0))),
 // feature/WindowInteractionCountFeature.scala:25-32, feature/RateFeature.scala:50-90)
