@@ -45,6 +45,7 @@
  * the serving queue's slots are launched in gangs (64 slots on 8 streams) and mrk_rank answers through a started queue.
  * Still ABI 9, new symbols only: mrk_index_* (the similar-items index of /recommend).
  * Still ABI 9, new symbols only: mrk_trending_* (the trending recommender of /recommend).
+ * Still ABI 9, new symbols only: mrk_index_build_texts (the semantic recommender's fit), mrk_index_vectors.
  */
 #ifndef MRK_H
 #define MRK_H
@@ -679,6 +680,24 @@ int mrk_index_lookup(mrk_index *ix, const char *const *item_ids, int n_items, in
  * No items -> MRK_ERR_INVALID_ARG ("similar items recommender requires request.items to be non-empty", :69); nothing left
  * after the filter -> MRK_ERR_NOT_FOUND ("empty response from the recommender", :74). */
 int mrk_index_recommend(mrk_index *ix, const char *const *item_ids, int n_items, int count, int32_t *out_rows, double *out_score, int32_t *out_n);
+/* BertSemanticPredictor.fit -- M/ml/recommend/BertSemanticRecommender.scala:25-79 -- for a whole catalogue: texts[r] is item r's
+ * text fields already joined by the host (" ".join, :54-59); every text is embedded by `enc` (mean pooling, as mrk_encoder_embed)
+ * and becomes row r of an ordinary index of cols = hidden, stored as f32, under ids[r] (each stored once).  The catalogue runs
+ * through the device in pieces: consecutive texts whose token count (one truncated sequence with its special tokens) sums to at
+ * most max_tokens, at most 65 535 texts each, always at least one; 0 = the library's default (131 072), values above 2^24 are
+ * taken as 2^24.  Windows of a few pieces run in length order; every row still lands at its input position.  No embedding passes through host memory, and the host tokenises the next piece while the device works on
+ * the current one.  The encoder's activation scratch grows to min(max_tokens, total tokens) tokens and stays with the handle.
+ * With an encoder of precision f32 (the default) every row has the bits mrk_encoder_embed gives that text alone, whatever
+ * max_tokens is; with precision fp16 that holds against one mrk_encoder_embed call of the same texts when the catalogue is one
+ * piece, and is not promised across pieces.  Other calls on `enc` from other threads are served between two pieces.
+ * MRK_ERR_INVALID_ARG, before any device work: a null ctx / enc / out, an encoder of another context, max_tokens < 0, a null
+ * texts[r] or ids[r] (the message names the row), a duplicate id, rows outside mrk_index_build's limit.  On any error *out is
+ * NULL and the encoder stays usable.  Everything is copied. */
+int mrk_index_build_texts(mrk_ctx *ctx, mrk_encoder *enc, const char *const *ids, const char *const *texts, int64_t rows, int64_t max_tokens,
+                          mrk_index **out);
+/* index.get(id).vector -- HnswJavaIndex.scala:29-31 -- for n rows: out is n x cols doubles, the stored values widened (exact).
+ * A row outside [0, rows) is MRK_ERR_INVALID_ARG and nothing is written. */
+int mrk_index_vectors(mrk_index *ix, const int64_t *rows, int n, double *out);
 void mrk_index_free(mrk_index *ix);
 
 /* ---- trending items (POST /recommend/<model>, type: trending): the fit on the device ---------------------------------------

@@ -256,6 +256,8 @@ SIGNATURES = {
     "mrk_index_search": (_I, [_V, _P, _I, _I, _P, _P, _P]),
     "mrk_index_lookup": (_I, [_V, C.POINTER(_S), _I, _I, _P, _P, _P]),
     "mrk_index_recommend": (_I, [_V, C.POINTER(_S), _I, _I, _P, _P, _P]),
+    "mrk_index_build_texts": (_I, [_V, _V, C.POINTER(_S), C.POINTER(_S), C.c_int64, C.c_int64, C.POINTER(_V)]),
+    "mrk_index_vectors": (_I, [_V, _P, _I, _P]),
     "mrk_index_free": (None, [_V]),
     "mrk_trending_begin": (_I, [_V, _S, C.POINTER(_V)]),
     "mrk_trending_add": (_I, [_V, C.POINTER(_S), C.POINTER(_S), _I, _P, _P, C.c_int64]),

@@ -72,6 +72,7 @@ static Switches read_switches() {
   s.encoder_graph = flag("MRK_ENCODER_GRAPH", false);
   s.encoder_skinny = num("MRK_ENCODER_SKINNY", 15);
   s.encoder_packed = flag("MRK_ENCODER_PACKED", true);
+  s.semantic_window = std::max(0, std::min(64, num("MRK_SEMANTIC_WINDOW", 4)));
   s.encoder_f32_mfma = flag("MRK_ENCODER_F32_MFMA", true);
   return s;
 }

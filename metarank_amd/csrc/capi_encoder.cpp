@@ -9,6 +9,7 @@
 #include <tuple>
 
 #include "encoder.hpp"
+#include "knn.hpp"
 #include "runtime.hpp"
 #include "tokenizer.hpp"
 
@@ -41,8 +42,6 @@ void need(bool ok, const char *what) {
 }
 
 void flatten(const std::vector<Encoding> &rows, int len, int32_t *ids, int32_t *types, int32_t *mask);
-
-enum { MODE_HIDDEN, MODE_POOL, MODE_LOGIT };
 
 uint16_t to_half(float f) {
   const _Float16 h = (_Float16)f;  // round to nearest even, as a checkpoint saved in fp16 would be
@@ -245,20 +244,12 @@ void run_encoder(mrk_encoder &e, const int32_t *ids, const int32_t *types, const
   // encoder's own stream, accumulated under the name "encoder" (bench.py: the dominant launch sequence of config 5)
   hipEvent_t ev_a = nullptr, ev_b = nullptr;
   const bool timed = e.ctx->profile && !(switches().encoder_graph && !e.dev.f32) && hipEventCreate(&ev_a) == hipSuccess && hipEventCreate(&ev_b) == hipSuccess;
-  auto enqueue = [&]() {
-    MRK_HIP(hipMemcpyAsync(e.scratch.ids.p, h, id_words * 4, hipMemcpyHostToDevice, e.stream));
-    if (timed) (void)hipEventRecord(ev_a, e.stream);
-    if (packed) encoder_forward_packed(e.dev, e.scratch, n, f_seq, f_packed, e.stream);
-    else encoder_forward(e.dev, e.scratch, n, seq, e.stream);
-    const float *src = e.scratch.x.as<float>();
-    if (mode != MODE_HIDDEN) {
-      src = e.scratch.out.as<float>();
-      if (mode == MODE_POOL) encoder_meanpool(e.dev, e.scratch, n, f_seq, f_packed, e.scratch.out.as<float>(), e.stream);
-      else encoder_classify(e.dev, e.scratch, n, f_seq, f_packed, e.scratch.out.as<float>(), e.stream);
-    }
-    if (timed) (void)hipEventRecord(ev_b, e.stream);
-    MRK_HIP(hipMemcpyAsync(e.h_out.p, src, out_n * 4, hipMemcpyDeviceToHost, e.stream));
-  };
+  EncoderDest dst;
+  dst.h_out = e.h_out.p;
+  dst.out_n = out_n;
+  EncoderMarks marks;
+  if (timed) { marks.begin = ev_a; marks.end = ev_b; }
+  auto enqueue = [&]() { encoder_enqueue(e, h, id_words, n, f_seq, f_packed, mode, dst, marks); };
   // Small shapes (a request's query, a request's item pairs) are ~40 kernels of a few microseconds each; their launch
   // sequence can be recorded once per (n, seq, mode) as a HIP graph and replayed.
   // Opt-in (MRK_ENCODER_GRAPH=1): measured 0.230 vs 0.240 ms for a 9-token query -- the forward pass of a small batch
@@ -320,6 +311,39 @@ void encode_texts(mrk_encoder &e, const char *const *a, const char *const *b, in
 namespace mrk {
 
 void encoder_retain(mrk_encoder *e) { e->refs.fetch_add(1); }
+
+void encoder_enqueue(mrk_encoder &e, const void *h_ids, size_t id_words, int n, int seq, int M_packed, int mode, const EncoderDest &dst,
+                     const EncoderMarks &marks) {
+  MRK_HIP(hipMemcpyAsync(e.scratch.ids.p, h_ids, id_words * 4, hipMemcpyHostToDevice, e.stream));
+  if (marks.uploaded) MRK_HIP(hipEventRecord(marks.uploaded, e.stream));
+  if (marks.begin) (void)hipEventRecord(marks.begin, e.stream);
+  if (M_packed > 0) encoder_forward_packed(e.dev, e.scratch, n, seq, M_packed, e.stream);
+  else encoder_forward(e.dev, e.scratch, n, seq, e.stream);
+  if (dst.table) {  // pooled rows straight into the index table: no embedding leaves the device
+    if (marks.end) (void)hipEventRecord(marks.end, e.stream);
+    knn_pool_pack(*dst.table, e.scratch.x.as<float>(), e.scratch.ids.as<int32_t>() + 3 * (size_t)M_packed, dst.d_dst_row, dst.row0, n, e.stream);
+    if (marks.packed) (void)hipEventRecord(marks.packed, e.stream);
+    return;
+  }
+  const float *src = e.scratch.x.as<float>();
+  if (mode != MODE_HIDDEN) {
+    src = e.scratch.out.as<float>();
+    if (mode == MODE_POOL) encoder_meanpool(e.dev, e.scratch, n, seq, M_packed, e.scratch.out.as<float>(), e.stream);
+    else encoder_classify(e.dev, e.scratch, n, seq, M_packed, e.scratch.out.as<float>(), e.stream);
+  }
+  if (marks.end) (void)hipEventRecord(marks.end, e.stream);
+  MRK_HIP(hipMemcpyAsync(dst.h_out, src, dst.out_n * 4, hipMemcpyDeviceToHost, e.stream));
+}
+
+bool encoder_calls_in_f32(const mrk_encoder &e) { return call_in_f32(e); }
+
+void encoder_reserve_call(mrk_encoder &e, size_t M, size_t id_words) {
+  const void *before[] = {e.scratch.ids.p, e.scratch.x.p, e.scratch.xh.p, e.scratch.qkv.p, e.scratch.ctx.p, e.scratch.mid.p, e.scratch.y.p};
+  e.scratch.ids.reserve(id_words * 4);
+  encoder_reserve(e.dev, e.scratch, 1, (int)M);
+  const void *after[] = {e.scratch.ids.p, e.scratch.x.p, e.scratch.xh.p, e.scratch.qkv.p, e.scratch.ctx.p, e.scratch.mid.p, e.scratch.y.p};
+  if (memcmp(before, after, sizeof before) != 0) drop_graphs(e);
+}
 
 void encoder_embed_cached(mrk_encoder *e, const std::vector<std::string> &texts, std::vector<std::vector<float>> &out) {
   std::lock_guard<std::mutex> lk(e->mu);

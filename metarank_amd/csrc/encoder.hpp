@@ -78,6 +78,35 @@ void encoder_meanpool(const EncoderDev &enc, EncoderScratch &s, int n, int seq, 
 // pooler + classifier on the [CLS] row: -> out f32 [n] (device)
 void encoder_classify(const EncoderDev &enc, EncoderScratch &s, int n, int seq, int M_packed, float *d_out, hipStream_t stream);
 
+struct KnnTable;  // knn.hpp
+
+// what a forward pass is asked for: hidden states [M, H], pooled embeddings [n, H] or the classifier's logits [n]
+enum { MODE_HIDDEN, MODE_POOL, MODE_LOGIT };
+
+// Where a pass leaves its result: pinned host memory (run_encoder), or - pooled embeddings of a packed batch only - rows of an
+// index table on the device (mrk_index_build_texts): sequence b becomes row d_dst_row[b], or row0 + b when d_dst_row is null.
+struct EncoderDest {
+  void *h_out = nullptr;
+  size_t out_n = 0;                  // floats copied to h_out
+  KnnTable *table = nullptr;
+  int64_t row0 = 0;
+  const int64_t *d_dst_row = nullptr;
+};
+// Optional events of a pass, recorded on the encoder's stream: the ids have left the host buffer | the forward pass (with
+// pooling / classifier when the result goes to the host) starts | ends | the table rows are written.
+struct EncoderMarks {
+  hipEvent_t uploaded = nullptr, begin = nullptr, end = nullptr, packed = nullptr;
+};
+// capi_encoder.cpp: the forward-and-finish step of one call, enqueued on e.stream (nothing is waited for): upload of the id
+// words from pinned h_ids, forward pass (packed when M_packed > 0: seq = the longest sequence), then what `mode` asks for into
+// `dst`.  The caller holds e.mu, has sized every buffer and has set e.dev.f32.
+void encoder_enqueue(mrk_encoder &e, const void *h_ids, size_t id_words, int n, int seq, int M_packed, int mode, const EncoderDest &dst,
+                     const EncoderMarks &marks);
+// ... and what surrounds it for a caller outside capi_encoder.cpp (under e.mu): the arithmetic a handle's calls run in, and
+// the activation buffers + the device id buffer sized for M tokens / id_words words (captured graphs are dropped when one moves)
+bool encoder_calls_in_f32(const mrk_encoder &e);
+void encoder_reserve_call(mrk_encoder &e, size_t M, size_t id_words);
+
 // capi_encoder.cpp / features.cpp
 void encoder_retain(mrk_encoder *e);
 void encoder_release(mrk_encoder *e);

@@ -92,4 +92,19 @@ int knn_recommend_order(int32_t *rows, double *score, int n_found, const std::ve
   return (int)kept.size();
 }
 
+void knn_plan_pieces(const int32_t *lens, int64_t n, int64_t max_tokens, int max_rows, std::vector<int64_t> &starts) {
+  starts.clear();
+  int64_t count = 0, tokens = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    if (count == 0 || !knn_piece_takes(count, tokens, lens[i], max_tokens, max_rows)) {
+      starts.push_back(i);
+      count = 0;
+      tokens = 0;
+    }
+    ++count;
+    tokens += lens[i];
+  }
+  starts.push_back(n);
+}
+
 }  // namespace mrk

@@ -43,4 +43,17 @@ void knn_centroid(const double *vectors, int n, int cols, double *out);
 // farthest first among the nearest, NaN scores last.  Returns how many are left (rows / score are rewritten in place).
 int knn_recommend_order(int32_t *rows, double *score, int n_found, const std::vector<int64_t> &request_rows, int count);
 
+// ---- mrk_index_build_texts: how a catalogue's sequences are cut into forward passes ("pieces")
+// Most sequences of one piece: the packed attention launch of the encoder puts the sequence in grid.z (encoder.hip,
+// forward_impl), which HIP limits to 65 535.
+constexpr int KNN_PIECE_MAX_ROWS = 65535;
+// The rule, one sequence at a time: a piece that holds `count` sequences of `tokens` tokens takes one more of `len` tokens when
+// it is empty (a piece always holds at least one sequence, however small the budget) or when both limits still hold.
+inline bool knn_piece_takes(int64_t count, int64_t tokens, int32_t len, int64_t max_tokens, int max_rows) {
+  return count == 0 || (count < max_rows && tokens + len <= max_tokens);
+}
+// Cuts sequences 0 .. n-1 of `lens` tokens, in order, into pieces: every piece is the longest run the rule above allows.
+// starts = the first sequence of every piece, then n (pieces + 1 entries; {0} for n == 0).
+void knn_plan_pieces(const int32_t *lens, int64_t n, int64_t max_tokens, int max_rows, std::vector<int64_t> &starts);
+
 }  // namespace mrk

@@ -44,6 +44,35 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_pack_kernel(const S *__restri
   vals[knn_offset(row0 + r, d, groups, 16 / (int)sizeof(T))] = (T)src[i];
 }
 
+// The semantic fit (mrk_index_build_texts): mean pooling of the encoder's packed hidden states x [M, H], written as table rows.
+// A lane owns one (sequence, group of 4 dimensions): four f64 sums over the sequence's tokens in token order - meanpool_kernel's
+// arithmetic (encoder.hip), so a row has the bits mrk_encoder_embed gives - with one 16-byte load per token, and ONE 16-byte
+// store, which is exactly one (row, group) element of the blocked layout.  Consecutive lanes are consecutive groups of one
+// sequence (a token's H floats are read as consecutive bytes), consecutive sequences are neighbours in the grid, so the 64
+// stores that make up a group's 1 KiB line meet in L2.  H is a multiple of 64 (capi_encoder.cpp build_encoder): no tail group.
+__global__ __launch_bounds__(KNN_THREADS) void knn_pool_pack_kernel(const float *__restrict__ x, const int32_t *__restrict__ cu,
+                                                                     const int64_t *__restrict__ dst_row, int64_t row0, int n, int64_t rows, int H,
+                                                                     int groups, float *__restrict__ vals) {
+  const int64_t i = (int64_t)blockIdx.x * KNN_THREADS + threadIdx.x;
+  if (i >= (int64_t)n * groups) return;
+  const int b = (int)(i / groups), g = (int)(i - (int64_t)b * groups);
+  const int64_t r = dst_row ? dst_row[b] : row0 + b;
+  if (r < 0 || r >= rows) return;
+  const int first = cu[b], cnt = cu[b + 1] - first;
+  const float4 *p = (const float4 *)(x + (size_t)first * H) + g;
+  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+  for (int j = 0; j < cnt; ++j) {
+    const float4 v = p[(size_t)j * groups];
+    a0 += (double)v.x;
+    a1 += (double)v.y;
+    a2 += (double)v.z;
+    a3 += (double)v.w;
+  }
+  const double c = (double)cnt;
+  const float4 out = make_float4((float)(a0 / c), (float)(a1 / c), (float)(a2 / c), (float)(a3 / c));
+  *(float4 *)(vals + knn_offset(r, g * 4, groups, 4)) = out;
+}
+
 // sqrt(nrv) of every row, the sum walked in the order of the spec
 template <typename T>
 __global__ __launch_bounds__(KNN_THREADS) void knn_norms_kernel(const T *__restrict__ vals, double *__restrict__ snv, int64_t rows, int cols,
@@ -255,6 +284,15 @@ void knn_pack(KnnTable &t, const void *d_src, int src_elem_bytes, int64_t row0, 
     hipLaunchKernelGGL((knn_pack_kernel<double, float>), grid, block, 0, stream, (const double *)d_src, t.d_vals.as<float>(), row0, n, t.cols, t.groups);
   else
     hipLaunchKernelGGL((knn_pack_kernel<double, double>), grid, block, 0, stream, (const double *)d_src, t.d_vals.as<double>(), row0, n, t.cols, t.groups);
+  MRK_HIP(hipGetLastError());
+}
+
+void knn_pool_pack(KnnTable &t, const float *d_x, const int32_t *d_cu, const int64_t *d_dst_row, int64_t row0, int n, hipStream_t stream) {
+  if (n <= 0) return;
+  if (t.elem_bytes != 4 || t.cols % 4 != 0 || (!d_dst_row && (row0 < 0 || row0 + n > t.rows)))
+    throw StatusError(MRK_ERR_INVALID_ARG, "knn_pool_pack: launch outside its limits");
+  const dim3 grid((unsigned)ceil_div((int64_t)n * t.groups, KNN_THREADS)), block(KNN_THREADS);
+  hipLaunchKernelGGL(knn_pool_pack_kernel, grid, block, 0, stream, d_x, d_cu, d_dst_row, row0, n, t.rows, t.cols, t.groups, t.d_vals.as<float>());
   MRK_HIP(hipGetLastError());
 }
 

@@ -26,6 +26,9 @@ struct KnnScratch {
 void knn_table_alloc(KnnTable &t, int64_t rows, int cols, int elem_bytes, hipStream_t stream);
 // rows [row0, row0 + n) of the table from a row-major device copy of the caller's values (src_elem_bytes 4 / 8)
 void knn_pack(KnnTable &t, const void *d_src, int src_elem_bytes, int64_t row0, int64_t n, hipStream_t stream);
+// OnnxBiEncoder.avgpool of n packed sequences straight into the table (f32 storage, cols a multiple of 4): d_x is the encoder's
+// hidden states [M, cols], d_cu the n + 1 token offsets; sequence b becomes row d_dst_row[b], or row0 + b when d_dst_row is null
+void knn_pool_pack(KnnTable &t, const float *d_x, const int32_t *d_cu, const int64_t *d_dst_row, int64_t row0, int n, hipStream_t stream);
 void knn_norms(KnnTable &t, hipStream_t stream);
 // d_out[i * cols + d] = the stored value (row d_rows[i], dimension d) widened to f64
 void knn_fetch_rows(const KnnTable &t, const int64_t *d_rows, int n, double *d_out, hipStream_t stream);

@@ -167,6 +167,7 @@ struct Switches {
   bool encoder_graph = false;  // MRK_ENCODER_GRAPH
   int encoder_skinny = 15;     // MRK_ENCODER_SKINNY
   bool encoder_packed = true;  // MRK_ENCODER_PACKED=0: padded batches for pooled / logit calls too
+  int semantic_window = 4;     // MRK_SEMANTIC_WINDOW=k: mrk_index_build_texts runs windows of about k pieces in length order (rows still land in input order; measured faster); 0: input order
   bool encoder_f32_mfma = true;  // MRK_ENCODER_F32_MFMA=0: the f32 products / attention on the vector unit (the test instrument)
 };
 const Switches &switches();

@@ -48,6 +48,28 @@ class HipIndex:
         embedded by a HipEncoder and the index is built from the float32 result"""
         return cls.build(ids, encoder.embed(list(texts)), ctx or encoder.ctx)
 
+    @classmethod
+    def fit_semantic(cls, encoder, ids, texts, max_tokens: int = 0) -> "HipIndex":
+        """mrk_index_build_texts: BertSemanticPredictor.fit for a whole catalogue.  `texts[r]` is item r's joined text fields; the
+        library cuts the catalogue into forward passes of at most `max_tokens` tokens (0: its default) and writes the pooled
+        embeddings straight into the index table on the device."""
+        ids, texts = list(ids), list(texts)
+        if len(ids) != len(texts):
+            raise N.MrkError(N.ERR_INVALID_ARG, f"{len(texts)} texts do not match {len(ids)} ids")
+        pi, _ki = _strs(ids)
+        pt, _kt = _strs(texts)
+        h = C.c_void_p()
+        N.check(N.lib().mrk_index_build_texts(encoder.ctx.handle, encoder.handle, pi, pt, len(ids), max_tokens, C.byref(h)))
+        return cls(h, encoder.ctx)
+
+    def vectors(self, rows=None) -> np.ndarray:
+        """mrk_index_vectors: the stored vectors of `rows` (default: all of them) as float64, len(rows) x cols"""
+        info = self.info()
+        r = np.arange(info["rows"], dtype=np.int64) if rows is None else np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        out = np.empty((len(r), info["cols"]), dtype=np.float64)
+        N.check(N.lib().mrk_index_vectors(self.handle, r.ctypes.data, len(r), out.ctypes.data))
+        return out
+
     @property
     def handle(self):
         if not self._h:
