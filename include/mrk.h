@@ -37,6 +37,8 @@
  *                                 EmbeddingSimilarityModel.predict  M/ml/recommend/MFRecommender.scala:66-80
  *   mrk_trending_*             <- TrendingPredictor.fit / load, TrendingModel.predict / save
  *                                 M/ml/recommend/TrendingRecommender.scala:39-133
+ *   mrk_als_*                  <- MFPredictor.fit + ALSRecImpl.train  M/ml/recommend/MFRecommender.scala:26-63,
+ *                                 M/ml/recommend/mf/ALSRecImpl.scala:18-81
  *   mrk_encoder_*              <- OnnxSession / OnnxBiEncoder / OnnxCrossEncoder  M/ml/onnx/sbert/ (OnnxSession, OnnxBiEncoder, OnnxCrossEncoder .scala)
  *
  * ABI 8 (round 5): mrk_init creates n contexts; mrk_device_count; mrk_comm_init_local; mrk_model_inspect; mrk_serve_stats takes
@@ -46,6 +48,7 @@
  * Still ABI 9, new symbols only: mrk_index_* (the similar-items index of /recommend).
  * Still ABI 9, new symbols only: mrk_trending_* (the trending recommender of /recommend).
  * Still ABI 9, new symbols only: mrk_index_build_texts (the semantic recommender's fit), mrk_index_vectors.
+ * Still ABI 9, new symbols only: mrk_als_* (the similar-items recommender's fit: eALS factors on the device).
  */
 #ifndef MRK_H
 #define MRK_H
@@ -752,6 +755,66 @@ const char *mrk_trending_id(mrk_trending *t, int64_t rank);
  * count <= 0: MRK_ERR_INVALID_ARG ("count should be greater than 0"). */
 int mrk_trending_predict(mrk_trending *t, int count, double *out_scores, int32_t *out_n);
 void mrk_trending_free(mrk_trending *t);
+
+/* ---- similar items (POST /recommend/<model>, type: als): the fit on the device ---------------------------------------------
+ * Replaces MFPredictor.fit (M/ml/recommend/MFRecommender.scala:26-37) with ALSRecImpl.train (M/ml/recommend/mf/ALSRecImpl.scala:
+ * 18-41): the item factors of an element-wise ALS over the click-through history, written straight into an ordinary mrk_index.
+ * The reference runs librec's EALSRecommender, which is not part of it; what is computed here is the algorithm that class
+ * implements - He, Zhang, Kan, Chua, "Fast Matrix Factorization for Online Recommendation with Implicit Feedback", SIGIR 2016,
+ * Algorithm 1, Eq. 12-13 - with the reference's fixed settings (:20-32): eALS (rec.eals.wrmf.judge = 1), w0 = 128, alpha = 0.4,
+ * every rating and every positive weight 1.  This is a stated definition, not a parity claim against librec (DESIGN.md
+ * section 17, "Unpinned").  Semantics, all f64, every * + / one IEEE operation:
+ *   input  = one (user, item) per line of MFPredictor.uirt (MFRecommender.scala:54-59); the host applies the selector, the
+ *            `interactions` type filter (:61-63) and the no-user rule before it hands pairs over.  Users and items are numbered in
+ *            order of first appearance over all adds; duplicate pairs count once.  R_u = the items of user u ascending, R_i = the
+ *            users of item i ascending, nnz = the distinct pairs, n_i = |R_i|.
+ *   c_i    = (w0 * p_i^alpha) / Z, p_i = n_i / nnz, Z = the p_j^alpha summed in item order; pow is the host libm's.
+ *   init   = the caller's matrices, or value(seed, matrix, row, col) of the library's counter-based generator (Gaussian, mean 0,
+ *            standard deviation 0.01; mrk_als_init_matrix returns the same bytes).
+ *   one iteration = S^q[f][k] = sum_i c_i * (q_if * q_ik);  for every user u: r_j = p_u . q_i (k in order) for its entries, then
+ *            for f = 0 .. K-1 in order:  rf_j = r_j - p_uf * q_if;  num = sum_j (1.0 - (1.0 - c_i) * rf_j) * q_if;
+ *            den = sum_j (1.0 - c_i) * (q_if * q_if);  ks = sum_k (k == f ? 0.0 : p_uk * S^q[f][k]);
+ *            p_uf = (num - ks) / ((den + S^q[f][f]) + lambda_u);  r_j = rf_j + p_uf * q_if.
+ *            Then S^p[f][k] = sum_u p_uf * p_uk and for every item i the same with the roles exchanged and the S terms weighed by
+ *            the row's c_i:  q_if = (num - c_i * ks) / ((den + c_i * S^p[f][f]) + lambda_i).
+ *   order of every sum: a function of its length alone, written out in DESIGN.md section 17 and restated by
+ *            tests/als_reference.py; the result has that restatement's bits and two fits of one input are identical.
+ *   result = an mrk_index of rows = items (in order of first appearance), cols = factors, stored as f64 (EmbeddingMap,
+ *            M/ml/recommend/embedding/EmbeddingMap.scala:10-19); the factors never visit host memory.
+ * Limits, all MRK_ERR_UNSUPPORTED with the sizes in mrk_last_error: factors > 256; more than 2^31 - 1 pairs; more items than an
+ * index has rows; working memory that does not fit what is free on the device at fit.  One device per fit. */
+typedef struct mrk_als_builder mrk_als_builder;
+/* ALSConfig's decoder, ALSRecImpl.scala:60-81, with the reference's defaults (:46-54): iterations 100, factors 100, userReg and
+ * itemReg 0.01f.  The item regulariser is read from the key "itemRef" (:66) - a key "itemReg" is IGNORED, as in the reference;
+ * reproduced, not corrected.  Both regularisers are Java floats: their value in the arithmetic is (double)(float)x.
+ * `interactions`, `store` and `selector` are the host's.  MRK_ERR_PARSE for malformed JSON or a field of the wrong type,
+ * MRK_ERR_INVALID_ARG for factors or iterations < 1 - both judged before the context is looked at. */
+int mrk_als_begin(mrk_ctx *ctx, const char *config_json, mrk_als_builder **out);
+/* The same builder without a context: add, info, config, id and problem work (no device is touched); fit is MRK_ERR_INVALID_ARG. */
+int mrk_als_begin_host(const char *config_json, mrk_als_builder **out);
+/* Appends n pairs, user_ids[n] / item_ids[n], in order (the lines of :54-59).  May be called any number of times; the result does
+ * not depend on how the stream is cut into calls.  A null id fails the call with MRK_ERR_INVALID_ARG and nothing of it is
+ * appended. */
+int mrk_als_add(mrk_als_builder *b, const char *const *user_ids, const char *const *item_ids, int64_t n);
+/* ALSRecImpl.train + KnnIndex.write (MFRecommender.scala:31-32).  init_users (users x factors) and init_items (items x factors),
+ * row-major f64: both or neither (one of the two: MRK_ERR_INVALID_ARG); neither: the generator with `seed`.  out_user_factors
+ * (nullable, users x factors) receives the final user factors, which the reference discards.  No pairs: MRK_ERR_NOT_FOUND.  On
+ * any error *out is NULL.  The builder stays valid for more adds and later fits; *out is freed with mrk_index_free. */
+int mrk_als_fit(mrk_als_builder *b, uint64_t seed, const double *init_users, const double *init_items, double *out_user_factors, mrk_index **out);
+/* distinct users and items, pairs added and distinct pairs so far; any output may be NULL */
+int mrk_als_info(mrk_als_builder *b, int64_t *users, int64_t *items, int64_t *pairs, int64_t *distinct_pairs);
+/* the decoded config: the regularisers as the doubles the arithmetic uses; any output may be NULL */
+int mrk_als_config(mrk_als_builder *b, int *iterations, int *factors, double *lambda_user, double *lambda_item);
+/* the id with inner index `index` of matrix 0 (users) / 1 (items): NULL when out of range; valid until the builder is freed */
+const char *mrk_als_id(mrk_als_builder *b, int matrix, int64_t index);
+/* What a fit would iterate over (host only): R_u as CSR (user_offsets[users + 1], user_items[distinct pairs]), R_i as CSC
+ * (item_offsets[items + 1], item_users[distinct pairs]) and c_i (confidence[items]); any output may be NULL.  No pairs:
+ * MRK_ERR_NOT_FOUND. */
+int mrk_als_problem(mrk_als_builder *b, int32_t *user_offsets, int32_t *user_items, int32_t *item_offsets, int32_t *item_users, double *confidence);
+/* The generator of the initial factors (host only): out = rows x cols values of matrix 0 (users) / 1 (items), each a function of
+ * (seed, matrix, row, column) alone (csrc/als_host.hpp states it). */
+int mrk_als_init_matrix(uint64_t seed, int matrix, int64_t rows, int cols, double *out);
+void mrk_als_builder_free(mrk_als_builder *b);
 
 #ifdef __cplusplus
 }

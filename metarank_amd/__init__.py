@@ -9,3 +9,4 @@ from .index import HipIndex  # noqa: F401,E402
 from .ranker import Batch, HipRanker, Server  # noqa: F401,E402
 from .request import Request, RequestSet  # noqa: F401,E402
 from .trending import HipTrending, TrendingBuilder  # noqa: F401,E402
+from .als import AlsBuilder  # noqa: F401,E402

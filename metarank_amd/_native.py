@@ -269,6 +269,16 @@ SIGNATURES = {
     "mrk_trending_id": (_S, [_V, C.c_int64]),
     "mrk_trending_predict": (_I, [_V, _I, _P, C.POINTER(C.c_int32)]),
     "mrk_trending_free": (None, [_V]),
+    "mrk_als_begin": (_I, [_V, _S, C.POINTER(_V)]),
+    "mrk_als_begin_host": (_I, [_S, C.POINTER(_V)]),
+    "mrk_als_add": (_I, [_V, C.POINTER(_S), C.POINTER(_S), C.c_int64]),
+    "mrk_als_fit": (_I, [_V, C.c_uint64, _P, _P, _P, C.POINTER(_V)]),
+    "mrk_als_info": (_I, [_V, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "mrk_als_config": (_I, [_V, C.POINTER(_I), C.POINTER(_I), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "mrk_als_id": (_S, [_V, _I, C.c_int64]),
+    "mrk_als_problem": (_I, [_V, _P, _P, _P, _P, _P]),
+    "mrk_als_init_matrix": (_I, [C.c_uint64, _I, C.c_int64, _I, _P]),
+    "mrk_als_builder_free": (None, [_V]),
 }
 
 _lib = None

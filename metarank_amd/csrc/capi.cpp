@@ -74,6 +74,7 @@ static Switches read_switches() {
   s.encoder_packed = flag("MRK_ENCODER_PACKED", true);
   s.semantic_window = std::max(0, std::min(64, num("MRK_SEMANTIC_WINDOW", 4)));
   s.encoder_f32_mfma = flag("MRK_ENCODER_F32_MFMA", true);
+  s.als_stage_max = std::max(0, num("MRK_ALS_STAGE_MAX", 0));
   return s;
 }
 static Switches &switches_storage() {

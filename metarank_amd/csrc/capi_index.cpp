@@ -316,6 +316,25 @@ void fit_texts(mrk_ctx *ctx, mrk_encoder *enc, mrk_index *ix, const char *const 
 
 }  // namespace
 
+namespace mrk {
+
+mrk_index *index_from_device_f64(mrk_ctx *ctx, const char *const *ids, const double *d_values, int64_t rows, int cols) {
+  need_ok(knn_check_shape(rows, cols));
+  std::unique_ptr<mrk_index> ix(new mrk_index());
+  need_ok(ix->ids.build(ids, rows));
+  MRK_HIP(hipSetDevice(ctx->device));
+  KnnTable &t = ix->table;
+  knn_table_alloc(t, rows, cols, 8, ctx->stream);
+  knn_pack(t, d_values, 8, 0, rows, ctx->stream);
+  knn_norms(t, ctx->stream);
+  MRK_HIP(hipStreamSynchronize(ctx->stream));
+  ix->ctx = ctx;
+  ctx_retain(ctx);
+  return ix.release();
+}
+
+}  // namespace mrk
+
 extern "C" {
 
 // == KnnIndexWriter.write(EmbeddingMap), HnswJavaIndex.scala:68-87

@@ -40,3 +40,14 @@ void knn_search(mrk_ctx *ctx, const KnnTable &t, KnnScratch &s, const double *d_
                 double *d_out_dist);
 
 }  // namespace mrk
+
+struct mrk_index;
+
+namespace mrk {
+
+// capi_index.cpp: an ordinary index whose rows are the rows x cols f64 matrix at d_values (row-major, on the context's device),
+// stored as f64 under ids[r]; the rows are cut into the table's blocks by knn_pack on ctx->stream and never visit the host.
+// MRK_ERR_INVALID_ARG for a shape outside mrk_index_build's limits or a duplicate id.  Caller holds ctx->mu.
+mrk_index *index_from_device_f64(mrk_ctx *ctx, const char *const *ids, const double *d_values, int64_t rows, int cols);
+
+}  // namespace mrk

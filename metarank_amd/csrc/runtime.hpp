@@ -169,6 +169,7 @@ struct Switches {
   bool encoder_packed = true;  // MRK_ENCODER_PACKED=0: padded batches for pooled / logit calls too
   int semantic_window = 4;     // MRK_SEMANTIC_WINDOW=k: mrk_index_build_texts runs windows of about k pieces in length order (rows still land in input order; measured faster); 0: input order
   bool encoder_f32_mfma = true;  // MRK_ENCODER_F32_MFMA=0: the f32 products / attention on the vector unit (the test instrument)
+  int als_stage_max = 0;       // MRK_ALS_STAGE_MAX=n: the ALS sweeps stage the gathered factor rows of rows of up to n entries in LDS (0: what 16 KiB hold; smaller: tests reach the gather path)
 };
 const Switches &switches();
 void reload_switches();

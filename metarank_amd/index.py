@@ -62,6 +62,23 @@ class HipIndex:
         N.check(N.lib().mrk_index_build_texts(encoder.ctx.handle, encoder.handle, pi, pt, len(ids), max_tokens, C.byref(h)))
         return cls(h, encoder.ctx)
 
+    @classmethod
+    def fit_similar(cls, config, users, items, ctx: Context | None = None, seed: int = 0, init=None, batches: int = 1) -> "HipIndex":
+        """mrk_als_begin + add (the stream cut into `batches` calls) + fit: MFPredictor.fit with ALSRecImpl.train
+        (ml/recommend/MFRecommender.scala:26-37).  `config`: ALSConfig as a dict or JSON text; `users[k]`, `items[k]`: the k-th
+        (user, item) line of MFPredictor.uirt.  The item factors are computed on the device and written straight into the table."""
+        from .als import AlsBuilder
+
+        b = AlsBuilder(config, ctx)
+        try:
+            n = len(users)
+            cuts = [n * k // batches for k in range(batches + 1)]
+            for lo, hi in zip(cuts[:-1], cuts[1:]):
+                b.add(users[lo:hi], items[lo:hi])
+            return b.fit(seed=seed, init=init)
+        finally:
+            b.close()
+
     def vectors(self, rows=None) -> np.ndarray:
         """mrk_index_vectors: the stored vectors of `rows` (default: all of them) as float64, len(rows) x cols"""
         info = self.info()
