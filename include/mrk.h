@@ -816,6 +816,50 @@ int mrk_als_problem(mrk_als_builder *b, int32_t *user_offsets, int32_t *user_ite
 int mrk_als_init_matrix(uint64_t seed, int matrix, int64_t rows, int cols, double *out);
 void mrk_als_builder_free(mrk_als_builder *b);
 
+/* ---- Evaluation on held-out click-throughs: the step that ends every `metarank train` --------------------------------------------
+ * LambdaMARTModel.eval (M/ml/rank/LambdaMARTRanker.scala:406-445, called at :115-123): every group of the test split scored,
+ * ordered by score and reduced to NDCG@k / MAP@k / MRR, beside two baselines - the unchanged request order ("noop") and random
+ * scores.  Groups are sorted and summed on the device (csrc/eval.hip), thousands per launch; new symbols only, no new struct.
+ * PINNED by the reference tree and followed exactly: NDCG(cutoff, nolabels = 1.0, relpow = true) with the default ndcg@10, one
+ * predictMat per group (scoring is per row: one pass over all rows gives the same scores), noopArray(len)(i) = (len - i) /
+ * len.toDouble, the mean over groups.
+ * ASSUMPTION (ltrlib's metric.{NDCG,MAP,MRR} sources are not in the reference tree): the formulas are this
+ * project's.  Per group of n items with scores s and labels y, k = cutoff == 0 ? n : min(cutoff, n):
+ *   order  pi = the stable descending order of sortBy(-score), as /rank answers: NaN scores last, +0.0 before -0.0, ties in
+ *          group order.
+ *   NDCG   ASSUMPTION: gain(y) = y, or 2^y - 1 with MRK_EVAL_RELPOW; dcg = sum over i < k of gain(y[pi(i)]) / log2(i + 2), added
+ *          one after the other for i = 0, 1, ... in f64 (every / and + correctly rounded, never fused; the first term starts the
+ *          sum); idcg = the same sum over the gains sorted descending; the value is `nolabels` when idcg == 0, else dcg / idcg.
+ *          log2 and 2^y are the HOST's libm (std::log2, std::pow): for a label whose 2^y is not exactly representable the value
+ *          follows that libm.
+ *   MAP    ASSUMPTION: an item is relevant when y > 0; ap = (sum over relevant positions i < k of hits_i / (i + 1)) / min(R, k),
+ *          hits_i = relevant items among pi(0..i), R = relevant items of the group; integers converted to f64, the sum in
+ *          position order; 0.0 when R == 0.
+ *   MRR    ASSUMPTION: 1.0 / r, r = the 1-based position in pi of the first relevant item; 0.0 without one.  Ignores the cutoff.
+ *   mean   the per-group values added in group order in f64, divided by n_groups.
+ * Unverifiable here; tests/eval_reference.py restates them and the device agrees with it bit for bit. */
+enum { MRK_METRIC_NDCG = 0, MRK_METRIC_MAP = 1, MRK_METRIC_MRR = 2 };
+enum { MRK_EVAL_RELPOW = 1 }; /* flags: NDCG gain = 2^label - 1 instead of label */
+
+/* One metric of caller-supplied scores.  scores / labels: host f64[group_offsets[n_groups]]; group g is
+ * [group_offsets[g], group_offsets[g + 1]).  out_value: the mean over groups; out_per_group (nullable): n_groups f64.
+ * cutoff == 0: none (the reference's Int.MaxValue).  MRK_ERR_INVALID_ARG, all judged before any device work: a null pointer
+ * where one is required, n_groups < 1, a negative cutoff, an unknown metric or flag, offsets that do not start at 0 or do not
+ * strictly increase (empty groups are refused, as loadDataset filters them out), a non-finite label.  MRK_ERR_UNSUPPORTED: a
+ * group of more than 2^30 items, or arrays that do not fit the device's free memory. */
+int mrk_eval_scores(mrk_ctx *ctx, int metric, int cutoff, int flags, double nolabels, const double *scores, const double *labels,
+                    const int64_t *group_offsets, int64_t n_groups, double *out_value, double *out_per_group);
+
+/* LambdaMARTModel.eval: scores rowmajor (group_offsets[n_groups] rows x cols, host) ONCE with the model - uploaded in pieces of
+ * about 64 MiB, the matrix never has to fit the device -, then every listed metric for the predicted scores, for noopArray and -
+ * if random_scores != NULL (one f64 per row) - for those.  out: n_metrics x 3 f64 (value, noop, random; random = NaN when not
+ * given).  out_scores (nullable): one f64 per row, what mrk_model_predict_f64 gives for the matrix.  Errors as above; a matrix
+ * with fewer columns than the model splits on is MRK_ERR_DIM_MISMATCH and an infinite cell of an XGBoost matrix
+ * MRK_ERR_INVALID_ARG, as predictMat gives. */
+int mrk_model_eval(mrk_model *model, const int *metrics, const int *cutoffs, int n_metrics, int flags, double nolabels,
+                   const double *rowmajor, int cols, const double *labels, const int64_t *group_offsets, int64_t n_groups,
+                   const double *random_scores, double *out, double *out_scores);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,3 +10,4 @@ from .ranker import Batch, HipRanker, Server  # noqa: F401,E402
 from .request import Request, RequestSet  # noqa: F401,E402
 from .trending import HipTrending, TrendingBuilder  # noqa: F401,E402
 from .als import AlsBuilder  # noqa: F401,E402
+from .eval import eval_scores, evaluate, labels_from_interactions  # noqa: F401,E402

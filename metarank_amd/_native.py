@@ -279,6 +279,8 @@ SIGNATURES = {
     "mrk_als_problem": (_I, [_V, _P, _P, _P, _P, _P]),
     "mrk_als_init_matrix": (_I, [C.c_uint64, _I, C.c_int64, _I, _P]),
     "mrk_als_builder_free": (None, [_V]),
+    "mrk_eval_scores": (_I, [_V, _I, _I, _I, C.c_double, _P, _P, _P, C.c_int64, C.POINTER(C.c_double), _P]),
+    "mrk_model_eval": (_I, [_V, _P, _P, _I, _I, C.c_double, _P, _I, _P, _P, C.c_int64, _P, _P, _P]),
 }
 
 _lib = None

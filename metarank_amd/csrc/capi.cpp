@@ -272,6 +272,20 @@ static mrk_model *make_model(mrk_ctx *ctx, int backend, const uint8_t *bytes, si
   return m.release();
 }
 
+// what mrk_model_predict_* and mrk_model_eval ask of a model and a matrix before any device work
+void check_predict_args(mrk_model *model, const void *x, int rows, int cols, const void *out) {
+  if (!model) throw StatusError(MRK_ERR_INVALID_ARG, "null model");
+  if (model->refs.load() <= 0) throw StatusError(MRK_ERR_INVALID_ARG, "model is closed");
+  if (rows < 0 || cols < 0) throw StatusError(MRK_ERR_INVALID_ARG, "negative matrix shape");
+  if (rows > 0 && (!x || !out)) throw StatusError(MRK_ERR_INVALID_ARG, "null matrix / output");
+  int used = 0;
+  for (auto &t : model->forest.trees)
+    for (auto f : t.feat) used = std::max(used, f + 1);
+  if (rows > 0 && cols < used)
+    throw StatusError(MRK_ERR_DIM_MISMATCH, "matrix has " + std::to_string(cols) + " columns but the booster splits on feature " +
+                                                std::to_string(used - 1));
+}
+
 }  // namespace mrk
 
 using namespace mrk;
@@ -387,19 +401,6 @@ int mrk_model_load_container(mrk_ctx *ctx, const uint8_t *blob, size_t len, cons
     if (c.n_warmup > 0) m->warmup_bytes.assign(c.warmup, c.warmup + c.warmup_len);
     *out = m;
   });
-}
-
-static void check_predict_args(mrk_model *model, const void *x, int rows, int cols, const void *out) {
-  if (!model) throw StatusError(MRK_ERR_INVALID_ARG, "null model");
-  if (model->refs.load() <= 0) throw StatusError(MRK_ERR_INVALID_ARG, "model is closed");
-  if (rows < 0 || cols < 0) throw StatusError(MRK_ERR_INVALID_ARG, "negative matrix shape");
-  if (rows > 0 && (!x || !out)) throw StatusError(MRK_ERR_INVALID_ARG, "null matrix / output");
-  int used = 0;
-  for (auto &t : model->forest.trees)
-    for (auto f : t.feat) used = std::max(used, f + 1);
-  if (rows > 0 && cols < used)
-    throw StatusError(MRK_ERR_DIM_MISMATCH, "matrix has " + std::to_string(cols) + " columns but the booster splits on feature " +
-                                                std::to_string(used - 1));
 }
 
 int mrk_model_predict_f64(mrk_model *model, const double *rowmajor, int rows, int cols, double *out_scores) {

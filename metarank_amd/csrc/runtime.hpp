@@ -302,6 +302,9 @@ void unbind_encoders(mrk_ctx *ctx);
 // features.cpp: mrk_config_bind_termfreq (parses BM25Matcher.TermFreqDic JSON, binds it to a device-matched bm25 field_match)
 void bind_termfreq(mrk_ctx *ctx, const char *feature, const char *json_bytes, size_t len);
 
+// capi.cpp: a null / closed model, a negative shape, a null matrix / output, fewer columns than the forest splits on (MRK_ERR_DIM_MISMATCH)
+void check_predict_args(mrk_model *model, const void *x, int rows, int cols, const void *out);
+
 // score.hip
 void launch_score(mrk_ctx *ctx, mrk_model *m, const double *d_x, int rows, int cols, double *d_out,
                   int *d_flag);
