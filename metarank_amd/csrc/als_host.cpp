@@ -5,13 +5,12 @@
 #include <cmath>
 #include <numeric>
 
-#include "../../include/mrk.h"
 #include "json.hpp"
 
 namespace mrk {
 
 AlsConfig als_parse_config(const char *json, size_t len) {
-  auto bad = [](const std::string &m) -> void { throw AlsError(MRK_ERR_PARSE, "als config: " + m); };
+  auto bad = [](const std::string &m) -> void { throw StatusError(MRK_ERR_PARSE, "als config: " + m); };
   json::Value root;
   try {
     root = json::parse(json, len);
@@ -44,19 +43,19 @@ AlsConfig als_parse_config(const char *json, size_t len) {
       for (auto &s : ints->arr)
         if (!s.is_string()) bad("'interactions' holds something that is not a string");
     }
-  if (cfg.factors < 1) throw AlsError(MRK_ERR_INVALID_ARG, "als config: factors = " + std::to_string(cfg.factors) + " (at least 1)");
-  if (cfg.iterations < 1) throw AlsError(MRK_ERR_INVALID_ARG, "als config: iterations = " + std::to_string(cfg.iterations) + " (at least 1)");
+  if (cfg.factors < 1) throw StatusError(MRK_ERR_INVALID_ARG, "als config: factors = " + std::to_string(cfg.factors) + " (at least 1)");
+  if (cfg.iterations < 1) throw StatusError(MRK_ERR_INVALID_ARG, "als config: iterations = " + std::to_string(cfg.iterations) + " (at least 1)");
   return cfg;
 }
 
 void AlsStream::add(const char *const *user_ids, const char *const *item_ids, int64_t n) {
-  if (n < 0) throw AlsError(MRK_ERR_INVALID_ARG, "als: negative pair count");
+  if (n < 0) throw StatusError(MRK_ERR_INVALID_ARG, "als: negative pair count");
   if (n == 0) return;
-  if (!user_ids || !item_ids) throw AlsError(MRK_ERR_INVALID_ARG, "null user_ids / item_ids");
+  if (!user_ids || !item_ids) throw StatusError(MRK_ERR_INVALID_ARG, "null user_ids / item_ids");
   for (int64_t i = 0; i < n; ++i)
     if (!user_ids[i] || !item_ids[i])
-      throw AlsError(MRK_ERR_INVALID_ARG, std::string("null ") + (user_ids[i] ? "item" : "user") + " id at pair " + std::to_string(i));
-  if (n > ALS_MAX_PAIRS - (int64_t)pairs.size()) throw AlsError(MRK_ERR_UNSUPPORTED, "als: more than 2^31 - 1 pairs in one fit");
+      throw StatusError(MRK_ERR_INVALID_ARG, std::string("null ") + (user_ids[i] ? "item" : "user") + " id at pair " + std::to_string(i));
+  if (n > ALS_MAX_PAIRS - (int64_t)pairs.size()) throw StatusError(MRK_ERR_UNSUPPORTED, "als: more than 2^31 - 1 pairs in one fit");
   auto intern = [](std::vector<std::string> &ids, std::unordered_map<std::string, uint32_t> &index_of, const char *id) {
     auto it = index_of.find(id);
     if (it != index_of.end()) return it->second;

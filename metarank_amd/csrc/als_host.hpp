@@ -5,18 +5,13 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
-#include <stdexcept>
 #include <string>
 #include <unordered_map>
 #include <vector>
 
-namespace mrk {
+#include "status.hpp"
 
-// an error with the mrk_status it maps to (this file does not see runtime.hpp's StatusError: that one needs HIP)
-struct AlsError : std::runtime_error {
-  int status;
-  AlsError(int s, const std::string &m) : std::runtime_error(m), status(s) {}
-};
+namespace mrk {
 
 constexpr int ALS_MAX_FACTORS = 256;                        // K: what a sweep's workgroup keeps of its own row in LDS beside the staged rows
 constexpr int64_t ALS_MAX_PAIRS = (int64_t(1) << 31) - 1;   // pairs of one fit (CSR offsets are int32 on the device)

@@ -204,55 +204,38 @@ void ctx_release(mrk_ctx *ctx) {
   delete ctx;
 }
 
-template <typename F>
-static int guard(F &&f) {
-  try {
-    f();
-    return MRK_OK;
-  } catch (const StatusError &e) {
-    set_last_error(e.what());
-    return e.status;
-  } catch (const std::bad_alloc &) {
-    set_last_error("out of host memory");
-    return MRK_ERR_DEVICE;
-  } catch (const UnsupportedModel &e) {
-    set_last_error(e.what());
-    return MRK_ERR_UNSUPPORTED;
-  } catch (const std::exception &e) {
-    set_last_error(e.what());
-    return MRK_ERR_PARSE;
-  }
+Forest parse_booster(int backend, const uint8_t *bytes, size_t len) {
+  if (backend == MRK_BACKEND_LIGHTGBM) return parse_lightgbm_text((const char *)bytes, len);
+  if (backend == MRK_BACKEND_XGBOOST) return parse_xgboost(bytes, len);
+  throw StatusError(MRK_ERR_INVALID_ARG, "unsupported booster tag " + std::to_string(backend));
 }
 
-static void upload_model(mrk_ctx *ctx, mrk_model *m) {
+// packs the forest and puts its images on the device; the caller holds the context (DeviceLock)
+static void upload_model(mrk_model *m, hipStream_t s) {
   m->packed = pack_forest(m->forest, score_chunk_budget());
-  MRK_HIP(hipSetDevice(ctx->device));
-  auto up = [&](DevBuf &b, const void *src, size_t bytes) {
-    b.reserve(bytes ? bytes : 16);
-    if (bytes) MRK_HIP(hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice));
-  };
-  up(m->d_image, m->packed.image.data(), m->packed.image.size());
-  up(m->d_trees, m->packed.trees.data(), m->packed.trees.size() * sizeof(TreeRef));
-  up(m->d_chunks, m->packed.chunks.data(), m->packed.chunks.size() * sizeof(ChunkRef));
-  up(m->d_cat, m->forest.cat_bits.data(), m->forest.cat_bits.size() * 4);
+  upload(m->d_image, m->packed.image, s);
+  upload(m->d_trees, m->packed.trees, s);
+  upload(m->d_chunks, m->packed.chunks, s);
+  upload(m->d_cat, m->forest.cat_bits, s);
   m->qs = pack_forest_qs(m->forest, m->forest.n_features);
+  std::vector<double> padded;   // (outlives the copies)
   if (m->qs.ok) {
-    up(m->d_qs_nodes, m->qs.nodes.data(), m->qs.nodes.size() * 4);
-    if (m->qs.byte_ok) up(m->d_qs_bnodes, m->qs.bnodes.data(), m->qs.bnodes.size() * 4);
-    up(m->d_qs_leaves, m->qs.leaves.data(), m->qs.leaves.size());
-    {  // the assembly kernel stages tables with 1 KiB wave-loads that may run past a table's end: slack after the last one
-      std::vector<double> padded(m->qs.thr);
-      padded.resize(padded.size() + 2 * QS_STAGE_CHUNK, 0.0);
-      // ... and behind the slack the compact tables of the resident-table sinks (score_qs.hip qs_device_view: QsDev::thr_rt)
-      padded.insert(padded.end(), m->qs.thr_rt.begin(), m->qs.thr_rt.end());
-      up(m->d_qs_thr, padded.data(), padded.size() * 8);
-    }
-    up(m->d_qs_feats, m->qs.feats.data(), m->qs.feats.size() * sizeof(QsFeature));
-    up(m->d_qs_views, m->qs.views.data(), m->qs.views.size() * sizeof(QsView));
-    up(m->d_qs_catnodes, m->qs.cat_nodes.data(), m->qs.cat_nodes.size() * sizeof(QsCatNode));
-    up(m->d_qs_cat, m->qs.cat_bits.data(), m->qs.cat_bits.size() * 4);
+    upload(m->d_qs_nodes, m->qs.nodes, s);
+    if (m->qs.byte_ok) upload(m->d_qs_bnodes, m->qs.bnodes, s);
+    upload(m->d_qs_leaves, m->qs.leaves, s);
+    // the assembly kernel stages tables with 1 KiB wave-loads that may run past a table's end: slack after the last one
+    padded = m->qs.thr;
+    padded.resize(padded.size() + 2 * QS_STAGE_CHUNK, 0.0);
+    // ... and behind the slack the compact tables of the resident-table sinks (score_qs.hip qs_device_view: QsDev::thr_rt)
+    padded.insert(padded.end(), m->qs.thr_rt.begin(), m->qs.thr_rt.end());
+    upload(m->d_qs_thr, padded, s);
+    upload(m->d_qs_feats, m->qs.feats, s);
+    upload(m->d_qs_views, m->qs.views, s);
+    upload(m->d_qs_catnodes, m->qs.cat_nodes, s);
+    upload(m->d_qs_cat, m->qs.cat_bits, s);
     m->qs_sig = qs_signature(m->qs, qs_stage_cap(m->qs));
   }
+  MRK_HIP(hipStreamSynchronize(s));
 }
 
 static mrk_model *make_model(mrk_ctx *ctx, int backend, const uint8_t *bytes, size_t len) {
@@ -260,14 +243,11 @@ static mrk_model *make_model(mrk_ctx *ctx, int backend, const uint8_t *bytes, si
   if (!bytes && len) throw StatusError(MRK_ERR_INVALID_ARG, "null model bytes");
   std::unique_ptr<mrk_model> m(new mrk_model());
   m->ctx = ctx;
-  if (backend == MRK_BACKEND_LIGHTGBM) m->forest = parse_lightgbm_text((const char *)bytes, len);
-  else if (backend == MRK_BACKEND_XGBOOST) m->forest = parse_xgboost(bytes, len);
-  else throw StatusError(MRK_ERR_INVALID_ARG, "unsupported booster tag " + std::to_string(backend));
+  m->forest = parse_booster(backend, bytes, len);
   if (m->forest.average_output)
     throw StatusError(MRK_ERR_UNSUPPORTED, "lightgbm: average_output (random forest) models are not supported");
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  if (ctx->closed) throw StatusError(MRK_ERR_INVALID_ARG, "context is shut down");
-  upload_model(ctx, m.get());
+  DeviceLock lk(ctx);
+  upload_model(m.get(), lk.stream);
   ctx_retain(ctx);
   return m.release();
 }
@@ -476,10 +456,7 @@ int mrk_model_weights(mrk_model *model, int importance_type, double *out, int n_
 int mrk_model_inspect_weights(int backend, const uint8_t *bytes, size_t len, int importance_type, double *out, int n_cols) {
   return guard([&] {
     if (!bytes && len) throw StatusError(MRK_ERR_INVALID_ARG, "null argument");
-    Forest f;
-    if (backend == MRK_BACKEND_LIGHTGBM) f = parse_lightgbm_text((const char *)bytes, len);
-    else if (backend == MRK_BACKEND_XGBOOST) f = parse_xgboost(bytes, len);
-    else throw StatusError(MRK_ERR_INVALID_ARG, "unsupported booster tag " + std::to_string(backend));
+    const Forest f = parse_booster(backend, bytes, len);
     importance_checked(f, importance_type, out, n_cols);
   });
 }
@@ -510,10 +487,7 @@ int mrk_abi_layout(int32_t *out, int cap) {
 int mrk_model_inspect(int backend, const uint8_t *bytes, size_t len, mrk_model_info *out) {
   return guard([&] {
     if (!out || (!bytes && len)) throw StatusError(MRK_ERR_INVALID_ARG, "null argument");
-    Forest f;
-    if (backend == MRK_BACKEND_LIGHTGBM) f = parse_lightgbm_text((const char *)bytes, len);
-    else if (backend == MRK_BACKEND_XGBOOST) f = parse_xgboost(bytes, len);
-    else throw StatusError(MRK_ERR_INVALID_ARG, "unsupported booster tag " + std::to_string(backend));
+    const Forest f = parse_booster(backend, bytes, len);
     if (f.average_output) throw StatusError(MRK_ERR_UNSUPPORTED, "lightgbm: average_output (random forest) models are not supported");
     const PackedForest packed = pack_forest(f, score_chunk_budget());
     const PackedForestQS qs = pack_forest_qs(f, f.n_features);

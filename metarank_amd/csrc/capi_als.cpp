@@ -22,36 +22,6 @@ struct mrk_als_builder {
 
 namespace {
 
-template <typename F>
-int guard(F &&f) {
-  try {
-    f();
-    return MRK_OK;
-  } catch (const StatusError &e) {
-    set_last_error(e.what());
-    return e.status;
-  } catch (const AlsError &e) {
-    set_last_error(e.what());
-    return e.status;
-  } catch (const std::bad_alloc &) {
-    set_last_error("out of host memory");
-    return MRK_ERR_DEVICE;
-  } catch (const std::exception &e) {
-    set_last_error(e.what());
-    return MRK_ERR_PARSE;
-  }
-}
-
-void need(bool ok, const char *what) {
-  if (!ok) throw StatusError(MRK_ERR_INVALID_ARG, what);
-}
-
-template <typename T>
-void upload(DevBuf &d, const std::vector<T> &h, hipStream_t s) {
-  d.reserve(std::max<size_t>(h.size() * sizeof(T), 16));
-  if (!h.empty()) MRK_HIP(hipMemcpyAsync(d.p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, s));
-}
-
 double ms_since(std::chrono::steady_clock::time_point t0) {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
@@ -79,10 +49,8 @@ mrk_index *fit_locked(mrk_als_builder *b, uint64_t seed, const double *init_user
   std::vector<const char *> ids((size_t)pr.items);
   for (size_t i = 0; i < ids.size(); ++i) ids[i] = b->st.items[i].c_str();
 
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  if (ctx->closed) throw StatusError(MRK_ERR_INVALID_ARG, "context is shut down");
-  MRK_HIP(hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
+  DeviceLock lk(ctx);
+  hipStream_t s = lk.stream;
   // limit: everything of a fit is resident at once (no chunked fit): both factor matrices, the entries twice (R_u, R_i), r and
   // w - c per entry, the chunk partials of the larger product, and the index table the item factors end in
   const size_t partial_bytes = als_gram_scratch_bytes(std::max(pr.users, pr.items), K);
@@ -140,6 +108,16 @@ mrk_index *fit_locked(mrk_als_builder *b, uint64_t seed, const double *init_user
 
 void check_builder(mrk_als_builder *b) { need(b != nullptr, "null builder"); }
 
+// what both begin entries do: clears *out, a builder with the parsed config and no context
+std::unique_ptr<mrk_als_builder> begin_host(const char *config_json, mrk_als_builder **out) {
+  need(out != nullptr, "out is null");
+  *out = nullptr;
+  need(config_json != nullptr, "null config");
+  std::unique_ptr<mrk_als_builder> b(new mrk_als_builder());
+  b->cfg = als_parse_config(config_json, strlen(config_json));
+  return b;
+}
+
 }  // namespace
 
 extern "C" {
@@ -147,11 +125,7 @@ extern "C" {
 // == ALSConfig's decoder, ALSRecImpl.scala:60-81
 int mrk_als_begin(mrk_ctx *ctx, const char *config_json, mrk_als_builder **out) {
   return guard([&] {
-    need(out != nullptr, "out is null");
-    *out = nullptr;
-    need(config_json != nullptr, "null config");
-    std::unique_ptr<mrk_als_builder> b(new mrk_als_builder());
-    b->cfg = als_parse_config(config_json, strlen(config_json));   // (before the context: a config is judged without a device)
+    std::unique_ptr<mrk_als_builder> b = begin_host(config_json, out);   // (before the context: a config is judged without a device)
     need(ctx != nullptr, "null context");
     b->ctx = ctx;
     ctx_retain(ctx);
@@ -161,11 +135,7 @@ int mrk_als_begin(mrk_ctx *ctx, const char *config_json, mrk_als_builder **out) 
 
 int mrk_als_begin_host(const char *config_json, mrk_als_builder **out) {
   return guard([&] {
-    need(out != nullptr, "out is null");
-    *out = nullptr;
-    need(config_json != nullptr, "null config");
-    std::unique_ptr<mrk_als_builder> b(new mrk_als_builder());
-    b->cfg = als_parse_config(config_json, strlen(config_json));
+    std::unique_ptr<mrk_als_builder> b = begin_host(config_json, out);
     *out = b.release();
   });
 }

@@ -20,27 +20,6 @@ struct mrk_tokenizer {
 };
 
 namespace {
-template <typename F>
-int guard(F &&f) {
-  try {
-    f();
-    return MRK_OK;
-  } catch (const StatusError &e) {
-    set_last_error(e.what());
-    return e.status;
-  } catch (const std::bad_alloc &) {
-    set_last_error("out of host memory");
-    return MRK_ERR_DEVICE;
-  } catch (const std::exception &e) {
-    set_last_error(e.what());
-    return MRK_ERR_PARSE;
-  }
-}
-
-void need(bool ok, const char *what) {
-  if (!ok) throw StatusError(MRK_ERR_INVALID_ARG, what);
-}
-
 void flatten(const std::vector<Encoding> &rows, int len, int32_t *ids, int32_t *types, int32_t *mask);
 
 uint16_t to_half(float f) {

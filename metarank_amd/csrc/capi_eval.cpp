@@ -15,30 +15,6 @@ using namespace mrk;
 
 namespace {
 
-template <typename F>
-int guard(F &&f) {
-  try {
-    f();
-    return MRK_OK;
-  } catch (const StatusError &e) {
-    set_last_error(e.what());
-    return e.status;
-  } catch (const EvalError &e) {
-    set_last_error(e.what());
-    return e.status;
-  } catch (const std::bad_alloc &) {
-    set_last_error("out of host memory");
-    return MRK_ERR_DEVICE;
-  } catch (const std::exception &e) {
-    set_last_error(e.what());
-    return MRK_ERR_PARSE;
-  }
-}
-
-void need(bool ok, const char *what) {
-  if (!ok) throw StatusError(MRK_ERR_INVALID_ARG, what);
-}
-
 // MRK_EVAL_WAVE_MAX / MRK_EVAL_PIECE_ROWS: read per call, never on a launch path of the serving side
 long long env_int(const char *name, long long dflt) {
   const char *e = getenv(name);
@@ -94,27 +70,19 @@ struct EvalRun {
     if (want > (double)free_b)
       throw StatusError(MRK_ERR_UNSUPPORTED, "eval: " + std::to_string(rows) + " rows in " + std::to_string(ng) + " groups need " + std::to_string((unsigned long long)want) +
                                                  " bytes on the device, " + std::to_string(free_b) + " are free");
-    d_gains.reserve(rows * 8);
-    d_rel.reserve(rows);
+    upload(d_gains, ck.gains, s);
+    upload(d_rel, ck.rel, s);
+    upload(d_lg, lg, s);
+    if (!bins.wave.empty()) upload(d_wave, bins.wave, s);
+    if (!bins.group.empty()) upload(d_group, bins.group, s);
+    // (the caller's arrays are no vectors)
     d_off.reserve((size_t)(ng + 1) * 8);
-    d_lg.reserve(lg.size() * 8);
     d_met.reserve((size_t)nm * 4);
     d_cut.reserve((size_t)nm * 4);
     d_out.reserve((size_t)sets * nm * (size_t)ng * 8);
-    MRK_HIP(hipMemcpyAsync(d_gains.p, ck.gains.data(), rows * 8, hipMemcpyHostToDevice, s));
-    MRK_HIP(hipMemcpyAsync(d_rel.p, ck.rel.data(), rows, hipMemcpyHostToDevice, s));
     MRK_HIP(hipMemcpyAsync(d_off.p, group_offsets, (size_t)(ng + 1) * 8, hipMemcpyHostToDevice, s));
-    MRK_HIP(hipMemcpyAsync(d_lg.p, lg.data(), lg.size() * 8, hipMemcpyHostToDevice, s));
     MRK_HIP(hipMemcpyAsync(d_met.p, metrics, (size_t)nm * 4, hipMemcpyHostToDevice, s));
     MRK_HIP(hipMemcpyAsync(d_cut.p, cutoffs, (size_t)nm * 4, hipMemcpyHostToDevice, s));
-    if (!bins.wave.empty()) {
-      d_wave.reserve(bins.wave.size() * 4);
-      MRK_HIP(hipMemcpyAsync(d_wave.p, bins.wave.data(), bins.wave.size() * 4, hipMemcpyHostToDevice, s));
-    }
-    if (!bins.group.empty()) {
-      d_group.reserve(bins.group.size() * 4);
-      MRK_HIP(hipMemcpyAsync(d_group.p, bins.group.data(), bins.group.size() * 4, hipMemcpyHostToDevice, s));
-    }
     if (scratch) d_scratch.reserve(scratch);
     MRK_HIP(hipStreamSynchronize(s));   // lg is a local; the uploads have left the host
     dev.gains = d_gains.as<double>();
@@ -159,9 +127,7 @@ int mrk_eval_scores(mrk_ctx *ctx, int metric, int cutoff, int flags, double nola
     const Checked ck = check_common(&metric, &cutoff, 1, flags, labels, group_offsets, n_groups);
     need(scores != nullptr, "eval: null scores");
     need(ctx != nullptr, "null context");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    if (ctx->closed) throw StatusError(MRK_ERR_INVALID_ARG, "context is shut down");
-    MRK_HIP(hipSetDevice(ctx->device));
+    DeviceLock lk(ctx);
     const size_t rows = (size_t)ck.sh.rows;
     EvalRun run(ctx, ck, &metric, &cutoff, 1, nolabels, group_offsets, n_groups, 1, rows * 8);
     DevBuf d_scores;
@@ -185,9 +151,7 @@ int mrk_model_eval(mrk_model *model, const int *metrics, const int *cutoffs, int
     const std::vector<EvalPiece> pieces = eval_pieces(ck.sh.rows, cols, env_int("MRK_EVAL_PIECE_ROWS", 0));
     check_predict_args(model, rowmajor, pieces.empty() ? 0 : pieces[0].rows, cols, out);   // null / closed model, MRK_ERR_DIM_MISMATCH as predictMat gives
     mrk_ctx *ctx = model->ctx;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    if (ctx->closed) throw StatusError(MRK_ERR_INVALID_ARG, "context is shut down");
-    MRK_HIP(hipSetDevice(ctx->device));
+    DeviceLock lk(ctx);
     const size_t rows = (size_t)ck.sh.rows;
     const size_t piece_bytes = (size_t)pieces[0].rows * (size_t)std::max(cols, 1) * 8;
     const int n_sets = 3;   // predicted, noop, random

@@ -26,26 +26,6 @@ struct mrk_index {
 
 namespace {
 
-template <typename F>
-int guard(F &&f) {
-  try {
-    f();
-    return MRK_OK;
-  } catch (const StatusError &e) {
-    set_last_error(e.what());
-    return e.status;
-  } catch (const std::bad_alloc &) {
-    set_last_error("out of host memory");
-    return MRK_ERR_DEVICE;
-  } catch (const std::exception &e) {
-    set_last_error(e.what());
-    return MRK_ERR_PARSE;
-  }
-}
-
-void need(bool ok, const char *what) {
-  if (!ok) throw StatusError(MRK_ERR_INVALID_ARG, what);
-}
 void need_ok(const std::string &err) {
   if (!err.empty()) throw StatusError(MRK_ERR_INVALID_ARG, err);
 }
@@ -162,8 +142,7 @@ void fit_texts(mrk_ctx *ctx, mrk_encoder *enc, mrk_index *ix, const char *const 
   HipEvent table_ready, packs_done;
   const bool profile = ctx->profile;
   {
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    if (ctx->closed) throw StatusError(MRK_ERR_INVALID_ARG, "context is shut down");
+    DeviceLock lk(ctx);   // (selects the device a second time: the events above are made before the lock is taken)
     knn_table_alloc(t, rows, sh.hidden, 4, ctx->stream);
     MRK_HIP(hipEventRecord(table_ready.ev, ctx->stream));
   }
@@ -349,9 +328,7 @@ int mrk_index_build(mrk_ctx *ctx, const char *const *ids, const void *values, in
     std::unique_ptr<mrk_index> ix(new mrk_index());
     need_ok(ix->ids.build(ids, rows));
     const int stored = elem_bytes == 4 || knn_f32_lossless((const double *)values, (size_t)rows * cols) ? 4 : 8;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    if (ctx->closed) throw StatusError(MRK_ERR_INVALID_ARG, "context is shut down");
-    MRK_HIP(hipSetDevice(ctx->device));
+    DeviceLock lk(ctx);
     KnnTable &t = ix->table;
     knn_table_alloc(t, rows, cols, stored, ctx->stream);
     // the caller's rows go up in pieces of about 64 MiB and are cut into the table's blocks on the device

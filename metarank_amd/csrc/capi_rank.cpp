@@ -62,23 +62,6 @@ int load_feature_values(Store &store, const uint8_t *bytes, size_t len, int64_t 
 void launch_resolve_ids(hipStream_t stream, const IdTableDev &tab, const uint8_t *d_bytes, const uint32_t *d_offs, uint32_t bytes_len, const ReqDev *d_reqs,
                         int n_req, int total, int32_t *d_item_slot, uint32_t *d_item_req, int32_t *d_load_status);  // resolve.hip
 
-template <typename F>
-static int guard(F &&f) {
-  try {
-    f();
-    return MRK_OK;
-  } catch (const StatusError &e) {
-    set_last_error(e.what());
-    return e.status;
-  } catch (const std::bad_alloc &) {
-    set_last_error("out of host memory");
-    return MRK_ERR_DEVICE;
-  } catch (const std::exception &e) {
-    set_last_error(e.what());
-    return MRK_ERR_PARSE;
-  }
-}
-
 static Store &store_of(mrk_ctx *ctx) {
   if (!ctx) throw StatusError(MRK_ERR_INVALID_ARG, "null context");
   if (!ctx->store) throw StatusError(MRK_ERR_INVALID_ARG, "mrk_config_load_json must be called first");
@@ -740,10 +723,7 @@ int mrk_config_specialize_values(const char *json, size_t len, const char *model
 // host only: the view signature of a serialised booster (what mrk_model_load would key this model's kernels by)
 static QsSignature signature_of_bytes(int backend, const uint8_t *bytes, size_t len, bool &f64) {
   if (!bytes || !len) throw StatusError(MRK_ERR_INVALID_ARG, "null model bytes");
-  Forest f;
-  if (backend == MRK_BACKEND_LIGHTGBM) f = parse_lightgbm_text((const char *)bytes, len);
-  else if (backend == MRK_BACKEND_XGBOOST) f = parse_xgboost(bytes, len);
-  else throw StatusError(MRK_ERR_INVALID_ARG, "unsupported booster tag " + std::to_string(backend));
+  const Forest f = parse_booster(backend, bytes, len);
   f64 = f.backend == Backend::LightGBM;
   const PackedForestQS qs = pack_forest_qs(f, f.n_features);
   return qs.ok ? qs_signature(qs, qs_stage_cap(qs)) : QsSignature{};
@@ -1406,13 +1386,9 @@ int mrk_batch_create(mrk_ctx *ctx, mrk_batch **out) {
     if (!out) throw StatusError(MRK_ERR_INVALID_ARG, "out is null");
     *out = nullptr;
     if (!ctx) throw StatusError(MRK_ERR_INVALID_ARG, "null context");
-    {
-      std::lock_guard<std::mutex> lk(ctx->mu);
-      if (ctx->closed) throw StatusError(MRK_ERR_INVALID_ARG, "context is shut down");
-    }
+    { DeviceLock open(ctx); }   // (not held while the stream is made; the device stays selected for this thread)
     std::unique_ptr<mrk_batch> b(new mrk_batch());
     b->ctx = ctx;
-    MRK_HIP(hipSetDevice(ctx->device));
     MRK_HIP(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
     ctx_retain(ctx);
     *out = b.release();

@@ -30,30 +30,6 @@ struct mrk_trending {
 
 namespace {
 
-template <typename F>
-int guard(F &&f) {
-  try {
-    f();
-    return MRK_OK;
-  } catch (const StatusError &e) {
-    set_last_error(e.what());
-    return e.status;
-  } catch (const TrendingError &e) {
-    set_last_error(e.what());
-    return e.status;
-  } catch (const std::bad_alloc &) {
-    set_last_error("out of host memory");
-    return MRK_ERR_DEVICE;
-  } catch (const std::exception &e) {
-    set_last_error(e.what());
-    return MRK_ERR_PARSE;
-  }
-}
-
-void need(bool ok, const char *what) {
-  if (!ok) throw StatusError(MRK_ERR_INVALID_ARG, what);
-}
-
 constexpr int64_t PIECE = int64_t(1) << 20;   // interactions per pinned piece of an upload (16 MiB)
 
 // room for `total` staged interactions; what is staged already moves over.  Caller holds ctx->mu.
@@ -89,10 +65,8 @@ void fit_locked(mrk_trending_builder *b, TrendingModel &out) {
   const int64_t n = b->st.interactions, items = (int64_t)b->st.ids.size();
   const int64_t total_days = cfg.total_days();
   const int n_weights = (int)cfg.weights.size();
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  if (ctx->closed) throw StatusError(MRK_ERR_INVALID_ARG, "context is shut down");
-  MRK_HIP(hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
+  DeviceLock lk(ctx);
+  hipStream_t s = lk.stream;
   // limits: the count table must fit what is free beside the staged interactions (no chunked fit)
   const size_t order_scratch = trending_order_scratch_bytes((int)items);
   const double table_bytes = 4.0 * (double)items * (double)total_days;
@@ -117,16 +91,14 @@ void fit_locked(mrk_trending_builder *b, TrendingModel &out) {
   DevBuf d_table, d_w, d_pow, d_score, d_order, d_scratch, d_err;
   const size_t table_sz = (size_t)items * (size_t)total_days * 4;
   d_table.reserve(table_sz);
-  d_w.reserve(wdev.size() * sizeof(TrendingWeightDev));
-  d_pow.reserve(pow_table.size() * 8);
+  upload(d_w, wdev, s);
+  upload(d_pow, pow_table, s);
   d_score.reserve((size_t)items * 8);
   d_order.reserve((size_t)items * 4);
   d_scratch.reserve(order_scratch);
   d_err.reserve(4);
   if (table_sz) MRK_HIP(hipMemsetAsync(d_table.p, 0, table_sz, s));
   MRK_HIP(hipMemsetAsync(d_err.p, 0, 4, s));
-  if (n_weights) MRK_HIP(hipMemcpyAsync(d_w.p, wdev.data(), wdev.size() * sizeof(TrendingWeightDev), hipMemcpyHostToDevice, s));
-  if (!pow_table.empty()) MRK_HIP(hipMemcpyAsync(d_pow.p, pow_table.data(), pow_table.size() * 8, hipMemcpyHostToDevice, s));
   trending_launch_count(ctx, s, count_mode(), b->d_item.as<uint32_t>(), b->d_widx.as<int32_t>(), b->d_ts.as<long long>(), n, b->st.now_ms,
                         d_w.as<TrendingWeightDev>(), items, d_table.as<uint32_t>(), d_err.as<uint32_t>());
   trending_launch_score(ctx, s, d_table.as<uint32_t>(), d_w.as<TrendingWeightDev>(), n_weights, d_pow.as<double>(), items, d_score.as<double>());
@@ -185,9 +157,7 @@ int mrk_trending_add(mrk_trending_builder *b, const char *const *item_ids, const
     const std::vector<int32_t> weight_of = trending_check_call(b->cfg, b->st, item_ids, type_names, n_types, type_idx, ts_ms, n);
     if (n == 0) return;
     mrk_ctx *ctx = b->ctx;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    if (ctx->closed) throw StatusError(MRK_ERR_INVALID_ARG, "context is shut down");
-    MRK_HIP(hipSetDevice(ctx->device));
+    DeviceLock lk(ctx);
     grow(b, b->st.interactions + n);
     b->pin.reserve((size_t)std::min(n, PIECE) * 16);
     b->broken = true;   // until the call has gone through

@@ -26,20 +26,6 @@ namespace mrk {
       throw ::mrk::StatusError(MRK_ERR_DEVICE, std::string(#expr) + ": " + ncclGetErrorString(_r)); \
   } while (0)
 
-template <typename F>
-static int guard(F &&f) {
-  try {
-    f();
-    return MRK_OK;
-  } catch (const StatusError &e) {
-    set_last_error(e.what());
-    return e.status;
-  } catch (const std::exception &e) {
-    set_last_error(e.what());
-    return MRK_ERR_DEVICE;
-  }
-}
-
 void comm_destroy(mrk_ctx *ctx) {
   if (ctx->comm) {
     (void)hipSetDevice(ctx->device);
@@ -76,6 +62,7 @@ using namespace mrk;
 
 extern "C" {
 
+// (an exception without a status of its own is the device's or the communicator's here: the guards fall back to MRK_ERR_DEVICE)
 int mrk_comm_unique_id(uint8_t *out) {
   return guard([&] {
     if (!out) throw StatusError(MRK_ERR_INVALID_ARG, "null output");
@@ -83,7 +70,7 @@ int mrk_comm_unique_id(uint8_t *out) {
     ncclUniqueId id;
     MRK_NCCL(ncclGetUniqueId(&id));
     memcpy(out, &id, sizeof id);
-  });
+  }, MRK_ERR_DEVICE);
 }
 
 int mrk_comm_init(mrk_ctx *ctx, const uint8_t *id, int rank, int world) {
@@ -100,7 +87,7 @@ int mrk_comm_init(mrk_ctx *ctx, const uint8_t *id, int rank, int world) {
     ctx->comm_rank = rank;
     ctx->comm_world = world;
     ctx->d_comm.reserve(256);
-  });
+  }, MRK_ERR_DEVICE);
 }
 
 // The ranks of a communicator living in ONE process (the JVM with HipConfig(devices = List(0, 1, ...)): mrk_init made the
@@ -155,7 +142,7 @@ int mrk_comm_init_local(mrk_ctx *const *ctxs, int n) {
       throw;
     }
     if (prev_dev >= 0) (void)hipSetDevice(prev_dev);
-  });
+  }, MRK_ERR_DEVICE);
 }
 
 // Host-only shard arithmetic (no context, no device): what mrk_batch_shard_chunk / mrk_batch_run_shard use.
@@ -187,7 +174,7 @@ int mrk_comm_max_f64(mrk_ctx *ctx, double *value) {
     MRK_NCCL(ncclAllReduce(ctx->d_comm.p, ctx->d_comm.p, 1, ncclFloat64, ncclMax, (ncclComm_t)ctx->comm, ctx->stream));
     MRK_HIP(hipMemcpyAsync(value, ctx->d_comm.p, 8, hipMemcpyDeviceToHost, ctx->stream));
     MRK_HIP(hipStreamSynchronize(ctx->stream));
-  });
+  }, MRK_ERR_DEVICE);
 }
 
 int mrk_comm_barrier(mrk_ctx *ctx) {

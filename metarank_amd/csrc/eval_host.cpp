@@ -4,29 +4,27 @@
 #include <algorithm>
 #include <cmath>
 
-#include "../../include/mrk.h"
-
 namespace mrk {
 
 void eval_check_metrics(const int *metrics, const int *cutoffs, int n_metrics) {
-  if (!metrics || !cutoffs) throw EvalError(MRK_ERR_INVALID_ARG, "eval: null metrics / cutoffs");
-  if (n_metrics < 1) throw EvalError(MRK_ERR_INVALID_ARG, "eval: no metric asked for");
+  if (!metrics || !cutoffs) throw StatusError(MRK_ERR_INVALID_ARG, "eval: null metrics / cutoffs");
+  if (n_metrics < 1) throw StatusError(MRK_ERR_INVALID_ARG, "eval: no metric asked for");
   for (int m = 0; m < n_metrics; ++m) {
-    if (metrics[m] < MRK_METRIC_NDCG || metrics[m] > MRK_METRIC_MRR) throw EvalError(MRK_ERR_INVALID_ARG, "eval: unknown metric " + std::to_string(metrics[m]));
-    if (cutoffs[m] < 0) throw EvalError(MRK_ERR_INVALID_ARG, "eval: negative cutoff " + std::to_string(cutoffs[m]));
+    if (metrics[m] < MRK_METRIC_NDCG || metrics[m] > MRK_METRIC_MRR) throw StatusError(MRK_ERR_INVALID_ARG, "eval: unknown metric " + std::to_string(metrics[m]));
+    if (cutoffs[m] < 0) throw StatusError(MRK_ERR_INVALID_ARG, "eval: negative cutoff " + std::to_string(cutoffs[m]));
   }
 }
 
 EvalShape eval_check_groups(const int64_t *off, int64_t n_groups) {
-  if (!off) throw EvalError(MRK_ERR_INVALID_ARG, "eval: null group offsets");
-  if (n_groups < 1) throw EvalError(MRK_ERR_INVALID_ARG, "eval: no groups");
-  if (n_groups > EVAL_MAX_GROUPS) throw EvalError(MRK_ERR_UNSUPPORTED, "eval: more than " + std::to_string(EVAL_MAX_GROUPS) + " groups in one call");
-  if (off[0] != 0) throw EvalError(MRK_ERR_INVALID_ARG, "eval: group offsets do not start at 0");
+  if (!off) throw StatusError(MRK_ERR_INVALID_ARG, "eval: null group offsets");
+  if (n_groups < 1) throw StatusError(MRK_ERR_INVALID_ARG, "eval: no groups");
+  if (n_groups > EVAL_MAX_GROUPS) throw StatusError(MRK_ERR_UNSUPPORTED, "eval: more than " + std::to_string(EVAL_MAX_GROUPS) + " groups in one call");
+  if (off[0] != 0) throw StatusError(MRK_ERR_INVALID_ARG, "eval: group offsets do not start at 0");
   EvalShape sh;
   for (int64_t g = 0; g < n_groups; ++g) {
-    if (off[g + 1] <= off[g]) throw EvalError(MRK_ERR_INVALID_ARG, "eval: group " + std::to_string(g) + " is empty or its offsets decrease");
+    if (off[g + 1] <= off[g]) throw StatusError(MRK_ERR_INVALID_ARG, "eval: group " + std::to_string(g) + " is empty or its offsets decrease");
     const int64_t len = off[g + 1] - off[g];   // (both in [0, INT64_MAX] and ordered: no overflow)
-    if (len > EVAL_MAX_GROUP) throw EvalError(MRK_ERR_UNSUPPORTED, "eval: group " + std::to_string(g) + " has " + std::to_string(len) + " items (limit " + std::to_string(EVAL_MAX_GROUP) + ")");
+    if (len > EVAL_MAX_GROUP) throw StatusError(MRK_ERR_UNSUPPORTED, "eval: group " + std::to_string(g) + " has " + std::to_string(len) + " items (limit " + std::to_string(EVAL_MAX_GROUP) + ")");
     sh.max_len = std::max(sh.max_len, len);
   }
   sh.rows = off[n_groups];
@@ -34,10 +32,10 @@ EvalShape eval_check_groups(const int64_t *off, int64_t n_groups) {
 }
 
 void eval_pack_labels(const double *labels, int64_t rows, bool relpow, double *gains, uint8_t *rel) {
-  if (!labels) throw EvalError(MRK_ERR_INVALID_ARG, "eval: null labels");
+  if (!labels) throw StatusError(MRK_ERR_INVALID_ARG, "eval: null labels");
   for (int64_t i = 0; i < rows; ++i) {
     const double y = labels[i];
-    if (!std::isfinite(y)) throw EvalError(MRK_ERR_INVALID_ARG, "eval: label " + std::to_string(i) + " is not finite");
+    if (!std::isfinite(y)) throw StatusError(MRK_ERR_INVALID_ARG, "eval: label " + std::to_string(i) + " is not finite");
     gains[i] = relpow ? std::pow(2.0, y) - 1.0 : y;
     rel[i] = y > 0.0 ? 1 : 0;
   }

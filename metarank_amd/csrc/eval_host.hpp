@@ -5,17 +5,12 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
-#include <stdexcept>
 #include <string>
 #include <vector>
 
-namespace mrk {
+#include "status.hpp"
 
-// an error with the mrk_status it maps to (this file does not see runtime.hpp's StatusError: that one needs HIP)
-struct EvalError : std::runtime_error {
-  int status;
-  EvalError(int s, const std::string &m) : std::runtime_error(m), status(s) {}
-};
+namespace mrk {
 
 constexpr int EVAL_WAVE_ITEMS = 64;                        // groups of up to this many items: one wavefront each
 constexpr int EVAL_GROUP_ITEMS = 4096;                     // ... up to this many (SORT_MAX_ITEMS): one workgroup each; beyond: bigsort.hip

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "device_types.hpp"
+#include "status.hpp"
 
 namespace mrk {
 
@@ -14,8 +15,8 @@ enum class Backend : int { LightGBM = 0, XGBoost = 1 };
 // a well-formed model that uses something the scorer does not implement (dart, multi-output, vector leaves, a non-identity
 // objective ...): MRK_ERR_UNSUPPORTED at the C ABI, never a silently different score; malformed input is std::runtime_error
 // (MRK_ERR_PARSE)
-struct UnsupportedModel : std::runtime_error {
-  using std::runtime_error::runtime_error;
+struct UnsupportedModel : StatusError {
+  explicit UnsupportedModel(const std::string &m) : StatusError(MRK_ERR_UNSUPPORTED, m) {}
 };
 
 // (the decision flags NF_* of one internal node: device_types.hpp)

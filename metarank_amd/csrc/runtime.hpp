@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 #include <condition_variable>
 #include <cstdint>
@@ -15,15 +16,9 @@
 
 #include "../../include/mrk.h"
 #include "forest.hpp"
+#include "status.hpp"
 
 namespace mrk {
-
-struct StatusError : std::runtime_error {
-  int status;
-  StatusError(int s, const std::string &m) : std::runtime_error(m), status(s) {}
-};
-
-void set_last_error(const std::string &msg);
 
 #define MRK_HIP(expr)                                                                         \
   do {                                                                                        \
@@ -267,6 +262,27 @@ struct mrk_model {
 };
 
 namespace mrk {
+
+// The way into a context for an entry that works on its device: holds ctx->mu (kernel launches, the scratch buffers), refuses
+// a context that mrk_shutdown has closed, and selects the context's device for the calling thread - in that order.
+struct DeviceLock {
+  std::lock_guard<std::mutex> lk;
+  hipStream_t stream;
+  explicit DeviceLock(mrk_ctx *ctx) : lk(ctx->mu), stream(ctx->stream) {
+    if (ctx->closed) throw StatusError(MRK_ERR_INVALID_ARG, "context is shut down");
+    MRK_HIP(hipSetDevice(ctx->device));
+  }
+};
+
+// a host vector into a device buffer on `s` (the caller keeps `h` until the stream has been waited for); never a null pointer
+template <typename T>
+void upload(DevBuf &d, const std::vector<T> &h, hipStream_t s) {
+  d.reserve(std::max<size_t>(h.size() * sizeof(T), 16));
+  if (!h.empty()) MRK_HIP(hipMemcpyAsync(d.p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, s));
+}
+
+// capi.cpp: a serialised booster by its backend tag (MRK_BACKEND_*); an unknown tag is MRK_ERR_INVALID_ARG
+Forest parse_booster(int backend, const uint8_t *bytes, size_t len);
 
 // Times a kernel with HIP events on ctx->stream when profiling is enabled.
 struct ScopedKernelTimer {

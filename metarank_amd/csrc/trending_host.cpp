@@ -5,7 +5,6 @@
 #include <cmath>
 #include <cstring>
 
-#include "../../include/mrk.h"
 #include "duration.hpp"
 #include "json.hpp"
 
@@ -24,7 +23,7 @@ int TrendingConfig::weight_of(const char *type) const {
 }
 
 TrendingConfig trending_parse_config(const char *json, size_t len) {
-  auto bad = [](const std::string &m) -> void { throw TrendingError(MRK_ERR_PARSE, "trending config: " + m); };
+  auto bad = [](const std::string &m) -> void { throw StatusError(MRK_ERR_PARSE, "trending config: " + m); };
   json::Value root;
   try {
     root = json::parse(json, len);
@@ -55,7 +54,7 @@ TrendingConfig trending_parse_config(const char *json, size_t len) {
         w.days = w.window_ms / TRENDING_DAY_MS;
       }
     if (cfg.weight_of(w.interaction.c_str()) >= 0)
-      throw TrendingError(MRK_ERR_UNSUPPORTED, "trending config: two weights name the interaction '" + w.interaction + "'");
+      throw StatusError(MRK_ERR_UNSUPPORTED, "trending config: two weights name the interaction '" + w.interaction + "'");
     cfg.weights.push_back(std::move(w));
   }
   return cfg;
@@ -79,15 +78,12 @@ uint32_t TrendingStream::intern(const char *id) {
 std::vector<int32_t> trending_check_call(const TrendingConfig &cfg, const TrendingStream &st, const char *const *item_ids,
                                          const char *const *type_names, int n_types, const int32_t *type_idx,
                                          const int64_t *ts_ms, int64_t n) {
-  auto need = [](bool ok, const char *what) {
-    if (!ok) throw TrendingError(MRK_ERR_INVALID_ARG, what);
-  };
   need(n >= 0, "trending: negative interaction count");
   need(n_types >= 0, "trending: negative type count");
   need(n == 0 || (item_ids && type_idx && ts_ms), "null item_ids / type_idx / ts_ms");
   need(n_types == 0 || type_names, "null type_names");
   if (n > TRENDING_MAX_INTERACTIONS - st.interactions)
-    throw TrendingError(MRK_ERR_UNSUPPORTED, "trending: more than 2^31 - 1 interactions in one fit");
+    throw StatusError(MRK_ERR_UNSUPPORTED, "trending: more than 2^31 - 1 interactions in one fit");
   std::vector<int32_t> weight_of((size_t)n_types);
   for (int t = 0; t < n_types; ++t) {
     need(type_names[t] != nullptr, "null type name");
@@ -96,7 +92,7 @@ std::vector<int32_t> trending_check_call(const TrendingConfig &cfg, const Trendi
   for (int64_t i = 0; i < n; ++i) {
     need(item_ids[i] != nullptr, "null item id");
     if (type_idx[i] < 0 || type_idx[i] >= n_types)
-      throw TrendingError(MRK_ERR_INVALID_ARG, "trending: type_idx[" + std::to_string(i) + "] = " + std::to_string(type_idx[i]) + " is outside the call's " +
+      throw StatusError(MRK_ERR_INVALID_ARG, "trending: type_idx[" + std::to_string(i) + "] = " + std::to_string(type_idx[i]) + " is outside the call's " +
                                                    std::to_string(n_types) + " type names");
   }
   return weight_of;
@@ -111,7 +107,7 @@ void put_i32(std::vector<uint8_t> &o, uint32_t v) {
 struct Rd {
   const uint8_t *p, *end;
   void need(size_t n) {
-    if ((size_t)(end - p) < n) throw TrendingError(MRK_ERR_PARSE, "trending model: truncated");
+    if ((size_t)(end - p) < n) throw StatusError(MRK_ERR_PARSE, "trending model: truncated");
   }
   int32_t i32() {
     need(4);
@@ -147,7 +143,7 @@ std::vector<uint8_t> trending_save(const TrendingModel &m) {
   size_t bytes = 8;
   for (auto &id : m.ids) {
     if (id.size() > 65535)
-      throw TrendingError(MRK_ERR_UNSUPPORTED, "trending model: an item id of " + std::to_string(id.size()) + " bytes does not fit writeUTF's 65535");
+      throw StatusError(MRK_ERR_UNSUPPORTED, "trending model: an item id of " + std::to_string(id.size()) + " bytes does not fit writeUTF's 65535");
     bytes += 2 + id.size() + 8;
   }
   o.reserve(bytes);
@@ -168,11 +164,11 @@ std::vector<uint8_t> trending_save(const TrendingModel &m) {
 TrendingModel trending_load(const uint8_t *bytes, size_t len) {
   Rd r{bytes, bytes + len};
   const int32_t version = r.i32();
-  if (version != 1) throw TrendingError(MRK_ERR_UNSUPPORTED, "unsupported format " + std::to_string(version));
+  if (version != 1) throw StatusError(MRK_ERR_UNSUPPORTED, "unsupported format " + std::to_string(version));
   const int32_t size = r.i32();
-  if (size <= 0) throw TrendingError(MRK_ERR_PARSE, "trending model: no items found");
+  if (size <= 0) throw StatusError(MRK_ERR_PARSE, "trending model: no items found");
   if ((size_t)size > (size_t)(r.end - r.p) / 10)   // an item takes 10 bytes at least: the count must not size an allocation
-    throw TrendingError(MRK_ERR_PARSE, "trending model: truncated (" + std::to_string(size) + " items do not fit " + std::to_string(r.end - r.p) + " bytes)");
+    throw StatusError(MRK_ERR_PARSE, "trending model: truncated (" + std::to_string(size) + " items do not fit " + std::to_string(r.end - r.p) + " bytes)");
   TrendingModel m;
   m.ids.reserve((size_t)size);
   m.scores.reserve((size_t)size);
@@ -180,12 +176,12 @@ TrendingModel trending_load(const uint8_t *bytes, size_t len) {
     m.ids.push_back(r.utf());
     m.scores.push_back(r.f64());
   }
-  if (r.p != r.end) throw TrendingError(MRK_ERR_PARSE, "trending model: " + std::to_string(r.end - r.p) + " bytes after the last item");
+  if (r.p != r.end) throw StatusError(MRK_ERR_PARSE, "trending model: " + std::to_string(r.end - r.p) + " bytes after the last item");
   return m;
 }
 
 int trending_predict_n(const TrendingModel &m, int count) {
-  if (count <= 0) throw TrendingError(MRK_ERR_INVALID_ARG, "count should be greater than 0");
+  if (count <= 0) throw StatusError(MRK_ERR_INVALID_ARG, "count should be greater than 0");
   return (int)std::min<int64_t>(count, (int64_t)m.ids.size());
 }
 

@@ -6,18 +6,13 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
-#include <stdexcept>
 #include <string>
 #include <unordered_map>
 #include <vector>
 
-namespace mrk {
+#include "status.hpp"
 
-// an error with the mrk_status it maps to (include/mrk.h; this file does not see runtime.hpp's StatusError: that one needs HIP)
-struct TrendingError : std::runtime_error {
-  int status;
-  TrendingError(int s, const std::string &m) : std::runtime_error(m), status(s) {}
-};
+namespace mrk {
 
 constexpr int64_t TRENDING_DAY_MS = 86400000;
 constexpr int64_t TRENDING_MAX_INTERACTIONS = (int64_t(1) << 31) - 1;

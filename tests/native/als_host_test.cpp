@@ -32,7 +32,7 @@ static int status_of(F &&f) {
   try {
     f();
     return MRK_OK;
-  } catch (const AlsError &e) {
+  } catch (const StatusError &e) {
     return e.status;
   }
 }

@@ -24,7 +24,7 @@ static int status_of(F &&f) {
   try {
     f();
     return MRK_OK;
-  } catch (const EvalError &e) {
+  } catch (const StatusError &e) {
     return e.status;
   }
 }

@@ -34,7 +34,7 @@ static int status_of(F &&f) {
   try {
     f();
     return MRK_OK;
-  } catch (const TrendingError &e) {
+  } catch (const StatusError &e) {
     return e.status;
   }
 }

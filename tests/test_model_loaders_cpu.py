@@ -192,3 +192,39 @@ def test_inspect_reports_what_load_would():
     assert inspect(7, blob)[0] == N.ERR_INVALID_ARG
     assert inspect(0, b"not a model")[0] == N.ERR_PARSE
     assert N.lib().mrk_model_inspect(0, None, 0, None) == N.ERR_INVALID_ARG
+
+
+def refused_xgb():
+    d = xgb_doc()
+    d["learner"]["gradient_booster"]["name"] = "dart"
+    return json.dumps(d).encode()
+
+
+def refused_lgbm():
+    return lgbm_text().replace("is_linear=0", "is_linear=1", 1).encode()
+
+
+@pytest.mark.parametrize("backend, refused, says", [(1, refused_xgb, b"only gbtree boosters"), (0, refused_lgbm, b"linear trees are not supported")])
+def test_for_model_entries_refuse_a_booster_as_load_does(backend, refused, says, tmp_path):
+    """mrk_config_specialize_for_model / mrk_config_precompile_for_model parse the booster first, on the host alone: bytes the
+    loader refuses as unsupported are MRK_ERR_UNSUPPORTED with the loader's message - the status mrk_model_inspect (and so
+    mrk_model_load) gives for the same bytes; bytes that are no model at all stay MRK_ERR_PARSE."""
+    L = N.lib()
+    blob = refused()
+    rc, _ = inspect(backend, blob)
+    assert rc == N.ERR_UNSUPPORTED and says in L.mrk_last_error()
+    js = json.dumps({"features": [], "models": {}}).encode()
+    need, n = C.c_size_t(0), C.c_int(-1)
+
+    def specialize(b):
+        return L.mrk_config_specialize_for_model(js, len(js), b"m", backend, b, len(b), 0, None, 0, C.byref(need))
+
+    def precompile(b):
+        return L.mrk_config_precompile_for_model(js, len(js), b"m", backend, b, len(b), 1, str(tmp_path).encode(), C.byref(n))
+
+    for entry in (specialize, precompile):
+        L.mrk_model_inspect(7, blob, len(blob), C.byref(N.mrk_model_info()))   # (another message in between)
+        assert entry(blob) == N.ERR_UNSUPPORTED, (entry.__name__, L.mrk_last_error())
+        assert says in L.mrk_last_error()
+        assert entry(b"not a model") == N.ERR_PARSE, (entry.__name__, L.mrk_last_error())
+    assert n.value == 0 and not list(tmp_path.iterdir())
