@@ -311,26 +311,65 @@ qs_score_wave_kernel(const uint32_t *__restrict__ nodes, const uint8_t *__restri
 // LEAF INDICES are computed in parallel: per chunk of 8 * NW trees every wavefront writes the indices of its
 // trees (tree w, w + NW, ...) to LDS, then the rows' owners add the chunk's leaf values in tree order - the same
 // additions as the one-wavefront kernel, in the same order.
+//
+// LDS of a split workgroup, every offset but the slab's length a compile-time constant of (F64, NW):
+//   [0, IDX)       leaf values of the chunk: CH trees x 16 leaves
+//   [IDX, SLAB)    exit leaf of (tree, row), one byte each: CH x 128 B
+//   [SLAB, ...)    the tile's slab, V x 256 B - read by `ds_read_addtid_b32 offset:SLAB` with M0 = view * 256
+// (The slab came first until round 17, and everything behind it at a run-time offset; the request is the same
+// V * 256 + CH * (16 * LS + 128) bytes.)
+template <bool F64, int NW>
+struct QsSplitLds {
+  static constexpr int LS = F64 ? 8 : 4;
+  static constexpr int TREE_LEAF_BYTES = QS_LEAVES * LS;
+  static constexpr int CH = 8 * NW;  // trees per chunk
+  static constexpr int IDX = CH * TREE_LEAF_BYTES;
+  static constexpr int SLAB = IDX + CH * QS_TILE_ROWS;
+  static_assert(SLAB <= 0xffff && SLAB % 16 == 0, "the slab's offset is a DS instruction's 16-bit immediate");
+};
+
+// the exit leaves of a lane's two rows (16 removed-leaf bits each), one byte per row
+__device__ __forceinline__ uint32_t qs_exit_pair(uint32_t accn) {
+  // exit leaf = lowest position not removed; position nl-1 is in no left subtree, so a zero bit exists
+  const uint32_t inv = ~accn;
+  return (uint32_t)__builtin_ctz(inv) | ((uint32_t)__builtin_ctz(inv >> 16) << 8);
+}
+
+// row `tid` (tid < 128) adds the chunk's leaf values in tree order
+// (Measured and dropped, round 17: this loop unrolled by the chunk over exit leaves stored PRE-SCALED by the leaf size, so that the
+// byte read at `tid + immediate` is the address of the leaf value at another immediate - one VALU op per row-tree instead of
+// two, for one more shift per tree where the byte is made.  Same box, scorer alone, parent / unrolled / this loop: 384 000 rows
+// (NW = 4) 0.209 / 0.207 / - ms, 100 000 rows (NW = 8) 0.076 / 0.092 / 0.074 ms, c4 467 / 420 / 468 M items/s; pipelining the
+// unrolled groups of 8 did not change that (0.089 ms).  LOG.md round 17.)
+template <bool F64, int NW>
+__device__ __forceinline__ void qs_split_add_leaves(const uint8_t *smem, int tid, int nt, double &acc64, float &acc32) {
+  using L = QsSplitLds<F64, NW>;
+  for (int tt = 0; tt < nt; ++tt) {
+    const uint32_t li = smem[L::IDX + tt * QS_TILE_ROWS + tid];
+    if constexpr (F64) acc64 += *(const double *)(smem + tt * L::TREE_LEAF_BYTES + li * 8);
+    else acc32 += *(const float *)(smem + tt * L::TREE_LEAF_BYTES + li * 4);
+  }
+}
+
 template <bool F64, int NW>
 __global__ void __launch_bounds__(NW * 64)
 qs_score_split_kernel(const uint32_t *__restrict__ nodes, const uint8_t *__restrict__ leaves,
                       const QsCatNode *__restrict__ cat_nodes, const uint32_t *__restrict__ cat_bits,
                       const uint16_t *__restrict__ cells, int n_trees, int V, int rows, double base,
                       double *__restrict__ out) {
-  constexpr int LS = F64 ? 8 : 4;
-  constexpr int TREE_LEAF_BYTES = QS_LEAVES * LS;
-  constexpr int CH = 8 * NW;  // trees per chunk
+  using L = QsSplitLds<F64, NW>;
+  constexpr int TREE_LEAF_BYTES = L::TREE_LEAF_BYTES;
+  constexpr int CH = L::CH;
   extern __shared__ __align__(16) uint8_t smem[];
-  // [slab: V x 256 B][leaf values of the chunk: CH x 16 leaves][exit leaf index of (tree, row): CH x 128 B]
-  uint8_t *s_leaf = smem + (size_t)V * 256;
-  uint8_t *s_idx = s_leaf + CH * TREE_LEAF_BYTES;
+  uint8_t *s_idx = smem + L::IDX;
+  const uint8_t *slab = smem + L::SLAB;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // wavefront-uniform: node constants by scalar loads
   const long long tile = blockIdx.x;
   {
     const uint4 *src = (const uint4 *)(cells + (size_t)tile * V * QS_TILE_ROWS);
-    uint4 *dst = (uint4 *)smem;
+    uint4 *dst = (uint4 *)(smem + L::SLAB);
     for (int i = tid; i < V * 16; i += NW * 64) dst[i] = src[i];
   }
   double acc64 = 0.0;
@@ -340,7 +379,7 @@ qs_score_split_kernel(const uint32_t *__restrict__ nodes, const uint8_t *__restr
     __syncthreads();  // slab staged / previous chunk consumed
     {
       const uint4 *src = (const uint4 *)(leaves + (size_t)c0 * TREE_LEAF_BYTES);
-      uint4 *dst = (uint4 *)s_leaf;
+      uint4 *dst = (uint4 *)smem;
       for (int i = tid; i < nt * (TREE_LEAF_BYTES / 16); i += NW * 64) dst[i] = src[i];
     }
     for (int tt = wave; tt < nt; tt += NW) {  // this wavefront's trees of the chunk
@@ -350,8 +389,8 @@ qs_score_split_kernel(const uint32_t *__restrict__ nodes, const uint8_t *__restr
       uint32_t c[QS_SLOTS - 1], mm[QS_SLOTS - 1];
 #pragma unroll
       for (int s = 0; s < QS_SLOTS - 1; ++s)
-        asm volatile("s_lshr_b32 m0, %2, 16\n\ts_pack_ll_b32_b16 %1, %2, %2\n\tds_read_addtid_b32 %0"
-                     : "=v"(c[s]), "=s"(mm[s]) : "s"(r.mv[s]) : "memory");
+        asm volatile("s_lshr_b32 m0, %2, 16\n\ts_pack_ll_b32_b16 %1, %2, %2\n\tds_read_addtid_b32 %0 offset:%3"
+                     : "=v"(c[s]), "=s"(mm[s]) : "s"(r.mv[s]), "n"(L::SLAB) : "memory");
       __builtin_amdgcn_sched_barrier(0);
       __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): the reads above are invisible to the compiler
       __builtin_amdgcn_sched_barrier(0);
@@ -373,21 +412,13 @@ qs_score_split_kernel(const uint32_t *__restrict__ nodes, const uint8_t *__restr
         const QsCatNode *cn = cat_nodes + (catw & 0xffffffu);
         for (uint32_t j = 0; j < (catw >> 24); ++j) {
           const QsCatNode cnode = cn[j];
-          accn |= qs_cat_pair<F64>(cnode, *(const uint32_t *)(smem + ((cnode.view_dl & 0xffffu) << 8) + lane * 4), cat_bits);
+          accn |= qs_cat_pair<F64>(cnode, *(const uint32_t *)(slab + ((cnode.view_dl & 0xffffu) << 8) + lane * 4), cat_bits);
         }
       }
-      const uint32_t inv = ~accn;
-      const uint32_t pair = (uint32_t)__builtin_ctz(inv) | ((uint32_t)__builtin_ctz(inv >> 16) << 8);
-      *(uint16_t *)(s_idx + tt * QS_TILE_ROWS + lane * 2) = (uint16_t)pair;  // rows 2 * lane, 2 * lane + 1
+      *(uint16_t *)(s_idx + tt * QS_TILE_ROWS + lane * 2) = (uint16_t)qs_exit_pair(accn);  // rows 2 * lane, 2 * lane + 1
     }
     __syncthreads();
-    if (tid < QS_TILE_ROWS) {  // row `tid`: the chunk's leaves, in tree order
-      for (int tt = 0; tt < nt; ++tt) {
-        const uint32_t li = s_idx[tt * QS_TILE_ROWS + tid];
-        if constexpr (F64) acc64 += *(const double *)(s_leaf + tt * TREE_LEAF_BYTES + li * 8);
-        else acc32 += *(const float *)(s_leaf + tt * TREE_LEAF_BYTES + li * 4);
-      }
-    }
+    if (tid < QS_TILE_ROWS) qs_split_add_leaves<F64, NW>(smem, tid, nt, acc64, acc32);
   }
   const long long row = tile * QS_TILE_ROWS + tid;
   if (tid < QS_TILE_ROWS && row < rows) out[row] = F64 ? acc64 : (double)acc32;
@@ -403,10 +434,34 @@ qs_score_split_kernel(const uint32_t *__restrict__ nodes, const uint8_t *__restr
 // may overrun a ladder's bound - an A-only slot's B mask and a B-only or unused slot's A mask are 0 - and costs one s_cmp and
 // one branch, where a fall-through switch on the exact count costs ~3x the scalar work (tools/native/issue_bench.hip).
 // Categorical nodes read their UNCLAMPED cells (category ids) from the global tile, not from the slab.
-template <int B0>
+// A block is ONE asm statement (between separate statements the compiler pads with s_nop), and the block that opens a ladder -
+// slots 0-3 of A, slots 12-14 of B: the two that always run - takes the inline constant 0 as its first accumulator, so no
+// accumulator is zero-filled.
+//
+// The tree loop is unrolled by the wavefront's 8 trees of a whole chunk, so the exit leaves' store address is `2 * tid` plus an
+// immediate.
+// (Measured and dropped, round 17: the scalar loads taken off the critical path as in qs_score_wave_kernel - a tree's 16 k-words
+// fetched behind the PREVIOUS tree's subtracts into the same registers, its 32 mask words issued in front of its own cell reads
+// and covered by their wait; 100 SGPRs, no spills.  Same box, 384 000 rows: scorer 0.217 ms against 0.208 without and 0.210
+// before the round; bench 1 091 against 1 113 and 1 104 M items/s (LOG.md round 17).)
+template <int B0, bool FIRST>
 __device__ __forceinline__ void qs_byte_block(uint32_t &acc, const uint32_t (&d)[QS_SLOTS - 1], const uint32_t (&m)[QS_SLOTS]) {
-#pragma unroll
-  for (int s = B0; s < B0 + 4 && s < QS_SLOTS - 1; ++s) asm("v_and_or_b32 %0, %1, %2, %0" : "+v"(acc) : "v"(d[s]), "s"(m[s]));
+  static_assert(B0 % 4 == 0 && B0 < QS_SLOTS - 1 && QS_SLOTS == 16, "blocks of 4 slots, the last one of 3");
+  if constexpr (B0 == 12) {
+    if constexpr (FIRST)
+      asm("v_and_or_b32 %0, %1, %4, 0\n\tv_and_or_b32 %0, %2, %5, %0\n\tv_and_or_b32 %0, %3, %6, %0"
+          : "=&v"(acc) : "v"(d[12]), "v"(d[13]), "v"(d[14]), "s"(m[12]), "s"(m[13]), "s"(m[14]));
+    else
+      asm("v_and_or_b32 %0, %1, %4, %0\n\tv_and_or_b32 %0, %2, %5, %0\n\tv_and_or_b32 %0, %3, %6, %0"
+          : "+v"(acc) : "v"(d[12]), "v"(d[13]), "v"(d[14]), "s"(m[12]), "s"(m[13]), "s"(m[14]));
+  } else {
+    if constexpr (FIRST)
+      asm("v_and_or_b32 %0, %1, %5, 0\n\tv_and_or_b32 %0, %2, %6, %0\n\tv_and_or_b32 %0, %3, %7, %0\n\tv_and_or_b32 %0, %4, %8, %0"
+          : "=&v"(acc) : "v"(d[B0]), "v"(d[B0 + 1]), "v"(d[B0 + 2]), "v"(d[B0 + 3]), "s"(m[B0]), "s"(m[B0 + 1]), "s"(m[B0 + 2]), "s"(m[B0 + 3]));
+    else
+      asm("v_and_or_b32 %0, %1, %5, %0\n\tv_and_or_b32 %0, %2, %6, %0\n\tv_and_or_b32 %0, %3, %7, %0\n\tv_and_or_b32 %0, %4, %8, %0"
+          : "+v"(acc) : "v"(d[B0]), "v"(d[B0 + 1]), "v"(d[B0 + 2]), "v"(d[B0 + 3]), "s"(m[B0]), "s"(m[B0 + 1]), "s"(m[B0 + 2]), "s"(m[B0 + 3]));
+  }
 }
 
 template <bool F64, int NW>
@@ -415,12 +470,10 @@ qs_score_byte_split_kernel(const uint32_t *__restrict__ bnodes, const uint8_t *_
                            const QsCatNode *__restrict__ cat_nodes, const uint32_t *__restrict__ cat_bits,
                            const uint16_t *__restrict__ cells, int n_trees, int V, int rows, double base,
                            double *__restrict__ out) {
-  constexpr int LS = F64 ? 8 : 4;
-  constexpr int TREE_LEAF_BYTES = QS_LEAVES * LS;
-  constexpr int CH = 8 * NW;  // trees per chunk
+  using L = QsSplitLds<F64, NW>;
+  constexpr int TREE_LEAF_BYTES = L::TREE_LEAF_BYTES;
+  constexpr int CH = L::CH;
   extern __shared__ __align__(16) uint8_t smem[];
-  uint8_t *s_leaf = smem + (size_t)V * 256;
-  uint8_t *s_idx = s_leaf + CH * TREE_LEAF_BYTES;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -428,7 +481,7 @@ qs_score_byte_split_kernel(const uint32_t *__restrict__ bnodes, const uint8_t *_
   const uint16_t *tile_cells = cells + (size_t)tile * V * QS_TILE_ROWS;
   {
     const uint4 *src = (const uint4 *)tile_cells;
-    uint4 *dst = (uint4 *)smem;
+    uint4 *dst = (uint4 *)(smem + L::SLAB);
     typedef unsigned short ushort2v __attribute__((ext_vector_type(2)));
     const ushort2v cap = {255, 255};
     auto clamp = [&](uint32_t w) {  // v_pk_min_u16: QS_RIGHT -> 255, still above every k <= 254
@@ -441,67 +494,69 @@ qs_score_byte_split_kernel(const uint32_t *__restrict__ bnodes, const uint8_t *_
   }
   double acc64 = 0.0;
   float acc32 = (float)base;
+  // one tree `t` of this wavefront; the lane's two exit leaves go to `dst`
+  auto step = [&](int t, uint8_t *dst) {
+    const uint32_t *nd = bnodes + (size_t)t * QS_BYTE_TREE_WORDS;
+    uint32_t kv[QS_SLOTS], ma[QS_SLOTS], mb[QS_SLOTS];  // scalar loads: three s_load_dwordx16
+#pragma unroll
+    for (int s = 0; s < QS_SLOTS; ++s) {
+      kv[s] = nd[s];
+      ma[s] = nd[QS_SLOTS + s];
+      mb[s] = nd[2 * QS_SLOTS + s];
+    }
+    uint32_t d[QS_SLOTS - 1];
+#pragma unroll
+    for (int s = 0; s < QS_SLOTS - 1; ++s)  // (a DS add-TID read needs one wait state after the M0 write)
+      asm volatile("s_lshr_b32 m0, %1, 16\n\ts_nop 0\n\tds_read_addtid_b32 %0 offset:%2" : "=v"(d[s]) : "s"(kv[s]), "n"(L::SLAB) : "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): the reads above are invisible to the compiler
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int s = 0; s < QS_SLOTS - 1; ++s) {  // high byte of each half: 0xFF <=> cell > k (k: the word's low half, both rows)
+      const short2v k2 = __builtin_bit_cast(short2v, kv[s]);
+      d[s] = __builtin_bit_cast(uint32_t, __builtin_shufflevector(k2, k2, 0, 0) - __builtin_bit_cast(short2v, d[s]));
+    }
+    const uint32_t x = ma[QS_SLOTS - 1] & 0xffu, a = (ma[QS_SLOTS - 1] >> 8) & 0xffu;
+    uint32_t acc_a, acc_b;
+    qs_byte_block<0, true>(acc_a, d, ma);  // (a >= 1 for every tree with a node; harmless otherwise)
+    if (a > 4) qs_byte_block<4, false>(acc_a, d, ma);
+    if (a > 8) qs_byte_block<8, false>(acc_a, d, ma);
+    if (a > 12) qs_byte_block<12, false>(acc_a, d, ma);
+    qs_byte_block<12, true>(acc_b, d, mb);
+    if (x < 12) qs_byte_block<8, false>(acc_b, d, mb);
+    if (x < 8) qs_byte_block<4, false>(acc_b, d, mb);
+    if (x < 4) qs_byte_block<0, false>(acc_b, d, mb);
+    uint32_t accn = __builtin_amdgcn_perm(acc_b, acc_a, 0x07030501u);  // A.byte1, B.byte1, A.byte3, B.byte3
+    const uint32_t catw = kv[QS_SLOTS - 1];
+    if (catw >> 24) {
+      const QsCatNode *cn = cat_nodes + (catw & 0xffffffu);
+      for (uint32_t j = 0; j < (catw >> 24); ++j) {
+        const QsCatNode cnode = cn[j];
+        const uint32_t cc = *(const uint32_t *)(tile_cells + (size_t)(cnode.view_dl & 0xffffu) * QS_TILE_ROWS + lane * 2);
+        accn |= qs_cat_pair<F64>(cnode, cc, cat_bits);
+      }
+    }
+    const uint32_t pair = qs_exit_pair(accn);
+    *(uint16_t *)dst = (uint16_t)pair;  // rows 2 * lane, 2 * lane + 1
+  };
+  uint8_t *const idx0 = smem + L::IDX + tid * 2;  // tree `wave` of the chunk, rows 2 * lane ..: wave * 128 + lane * 2
   for (int c0 = 0; c0 < n_trees; c0 += CH) {
     const int nt = min(CH, n_trees - c0);
     __syncthreads();  // slab staged / previous chunk consumed
     {
       const uint4 *src = (const uint4 *)(leaves + (size_t)c0 * TREE_LEAF_BYTES);
-      uint4 *dst = (uint4 *)s_leaf;
+      uint4 *dst = (uint4 *)smem;
       for (int i = tid; i < nt * (TREE_LEAF_BYTES / 16); i += NW * 64) dst[i] = src[i];
     }
-    for (int tt = wave; tt < nt; tt += NW) {
-      const uint32_t *nd = bnodes + (size_t)(c0 + tt) * QS_BYTE_TREE_WORDS;
-      uint32_t kv[QS_SLOTS], ma[QS_SLOTS], mb[QS_SLOTS];  // scalar loads: three s_load_dwordx16
+    // this wavefront's trees of the chunk: wave, wave + NW, ...
+    if (nt == CH) {
 #pragma unroll
-      for (int s = 0; s < QS_SLOTS; ++s) {
-        kv[s] = nd[s];
-        ma[s] = nd[QS_SLOTS + s];
-        mb[s] = nd[2 * QS_SLOTS + s];
-      }
-      uint32_t d[QS_SLOTS - 1];
-#pragma unroll
-      for (int s = 0; s < QS_SLOTS - 1; ++s)  // (a DS add-TID read needs one wait state after the M0 write)
-        asm volatile("s_lshr_b32 m0, %1, 16\n\ts_nop 0\n\tds_read_addtid_b32 %0" : "=v"(d[s]) : "s"(kv[s]) : "memory");
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): the reads above are invisible to the compiler
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int s = 0; s < QS_SLOTS - 1; ++s) {  // high byte of each half: 0xFF <=> cell > k (k: the word's low half, both rows)
-        const short2v k2 = __builtin_bit_cast(short2v, kv[s]);
-        d[s] = __builtin_bit_cast(uint32_t, __builtin_shufflevector(k2, k2, 0, 0) - __builtin_bit_cast(short2v, d[s]));
-      }
-      const uint32_t x = ma[QS_SLOTS - 1] & 0xffu, a = (ma[QS_SLOTS - 1] >> 8) & 0xffu;
-      uint32_t acc_a = 0, acc_b = 0;
-      qs_byte_block<0>(acc_a, d, ma);  // (a >= 1 for every tree with a node; harmless otherwise)
-      if (a > 4) qs_byte_block<4>(acc_a, d, ma);
-      if (a > 8) qs_byte_block<8>(acc_a, d, ma);
-      if (a > 12) qs_byte_block<12>(acc_a, d, ma);
-      if (x < 4) qs_byte_block<0>(acc_b, d, mb);
-      if (x < 8) qs_byte_block<4>(acc_b, d, mb);
-      if (x < 12) qs_byte_block<8>(acc_b, d, mb);
-      qs_byte_block<12>(acc_b, d, mb);
-      uint32_t accn = __builtin_amdgcn_perm(acc_b, acc_a, 0x07030501u);  // A.byte1, B.byte1, A.byte3, B.byte3
-      const uint32_t catw = kv[QS_SLOTS - 1];
-      if (catw >> 24) {
-        const QsCatNode *cn = cat_nodes + (catw & 0xffffffu);
-        for (uint32_t j = 0; j < (catw >> 24); ++j) {
-          const QsCatNode cnode = cn[j];
-          const uint32_t cc = *(const uint32_t *)(tile_cells + (size_t)(cnode.view_dl & 0xffffu) * QS_TILE_ROWS + lane * 2);
-          accn |= qs_cat_pair<F64>(cnode, cc, cat_bits);
-        }
-      }
-      const uint32_t inv = ~accn;
-      const uint32_t pair = (uint32_t)__builtin_ctz(inv) | ((uint32_t)__builtin_ctz(inv >> 16) << 8);
-      *(uint16_t *)(s_idx + tt * QS_TILE_ROWS + lane * 2) = (uint16_t)pair;  // rows 2 * lane, 2 * lane + 1
+      for (int j = 0; j < 8; ++j) step(c0 + wave + j * NW, idx0 + j * NW * QS_TILE_ROWS);
+    } else {  // the forest's last chunk
+      for (int tt = wave; tt < nt; tt += NW) step(c0 + tt, idx0 + (tt - wave) * QS_TILE_ROWS);
     }
     __syncthreads();
-    if (tid < QS_TILE_ROWS) {  // row `tid`: the chunk's leaves, in tree order
-      for (int tt = 0; tt < nt; ++tt) {
-        const uint32_t li = s_idx[tt * QS_TILE_ROWS + tid];
-        if constexpr (F64) acc64 += *(const double *)(s_leaf + tt * TREE_LEAF_BYTES + li * 8);
-        else acc32 += *(const float *)(s_leaf + tt * TREE_LEAF_BYTES + li * 4);
-      }
-    }
+    if (tid < QS_TILE_ROWS) qs_split_add_leaves<F64, NW>(smem, tid, nt, acc64, acc32);
   }
   const long long row = tile * QS_TILE_ROWS + tid;
   if (tid < QS_TILE_ROWS && row < rows) out[row] = F64 ? acc64 : (double)acc32;

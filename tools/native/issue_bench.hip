@@ -2,13 +2,15 @@
 // resident wavefronts per SIMD.  The scorer (csrc/score_qs.hip) and the assembly kernels are bound by instruction issue;
 // rounds 1-5 priced every instruction at 4 cycles ("a wavefront issues one instruction per 4 cycles whatever its type").
 // This program measures it instead:
-//   hipcc --offload-arch=gfx950 -O2 -o issue_bench tools/native/issue_bench.hip && ./issue_bench
+//   hipcc --offload-arch=gfx950 -O2 -o issue_bench tools/native/issue_bench.hip && ./issue_bench [substring of the rows to run]
 // Output: one line per (body, waves per SIMD): cycles per instruction per SIMD at the nominal 2.4 GHz.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #define CK(x)                                                                          \
@@ -267,6 +269,97 @@ __global__ void __launch_bounds__(256) k_tree_byte(int iters, uint32_t *out, int
   out[blockIdx.x * 256 + threadIdx.x] = acc_a ^ acc_b;
 }
 
+// The byte-mode step WHOLE, as the kernel issues it, round 7's against round 17's ("lean"): the guarded blocks of 4 above plus what
+// surrounds them.  LEAN = false: two v_mov zero fills, one asm statement per v_and_or_b32 (the compiler pads dependent ones with
+// s_nop), exit leaves by v_not / v_ffbl x 2 / v_lshl_or, the store address by v_lshl_add_u32 from the tree's number, ds_write_b16.
+// LEAN = true: a block is ONE asm statement and the block that opens a ladder (slots 0-3 of A, 12-14 of B: they always run) starts
+// from the inline constant 0; 8 trips are unrolled, so the store goes to a loop-invariant address plus an immediate; the cell
+// reads carry the slab's immediate offset.  (Not modelled: the adding rows and the scalar loads.)
+template <bool FIRST, int B0>
+__device__ __forceinline__ void lean_block(uint32_t &acc, const uint32_t (&c)[15], const uint32_t (&m)[15]) {
+  if constexpr (B0 == 12) {
+    if constexpr (FIRST)
+      asm volatile("v_and_or_b32 %0, %1, %4, 0\n\tv_and_or_b32 %0, %2, %5, %0\n\tv_and_or_b32 %0, %3, %6, %0"
+                   : "=&v"(acc) : "v"(c[12]), "v"(c[13]), "v"(c[14]), "s"(m[12]), "s"(m[13]), "s"(m[14]));
+    else
+      asm volatile("v_and_or_b32 %0, %1, %4, %0\n\tv_and_or_b32 %0, %2, %5, %0\n\tv_and_or_b32 %0, %3, %6, %0"
+                   : "+v"(acc) : "v"(c[12]), "v"(c[13]), "v"(c[14]), "s"(m[12]), "s"(m[13]), "s"(m[14]));
+  } else {
+    if constexpr (FIRST)
+      asm volatile("v_and_or_b32 %0, %1, %5, 0\n\tv_and_or_b32 %0, %2, %6, %0\n\tv_and_or_b32 %0, %3, %7, %0\n\tv_and_or_b32 %0, %4, %8, %0"
+                   : "=&v"(acc) : "v"(c[B0]), "v"(c[B0 + 1]), "v"(c[B0 + 2]), "v"(c[B0 + 3]), "s"(m[B0]), "s"(m[B0 + 1]), "s"(m[B0 + 2]), "s"(m[B0 + 3]));
+    else
+      asm volatile("v_and_or_b32 %0, %1, %5, %0\n\tv_and_or_b32 %0, %2, %6, %0\n\tv_and_or_b32 %0, %3, %7, %0\n\tv_and_or_b32 %0, %4, %8, %0"
+                   : "+v"(acc) : "v"(c[B0]), "v"(c[B0 + 1]), "v"(c[B0 + 2]), "v"(c[B0 + 3]), "s"(m[B0]), "s"(m[B0 + 1]), "s"(m[B0 + 2]), "s"(m[B0 + 3]));
+  }
+}
+template <bool LEAN>
+__global__ void __launch_bounds__(256) k_tree_byte_whole(int iters, uint32_t *out, int x, int a) {
+  constexpr int SLAB = 4096;          // [exit leaves of 8 trees x 4 wavefronts: 4 KB][slab: 16 KB] (LEAN reads the slab at offset:SLAB)
+  __shared__ uint32_t lds[(SLAB + 64 * 64 * 4) / 4];
+  for (int i = threadIdx.x; i < (int)(sizeof(lds) / 4); i += 256) lds[i] = (i * 2654435761u) & 0x00ff00ffu;
+  __syncthreads();
+  uint32_t kk = 0x00400040u, ma[15], mb[15];
+#pragma unroll
+  for (int s = 0; s < 15; ++s) {
+    ma[s] = __builtin_amdgcn_readfirstlane(0x5a005a00u + (s << 9) + x);
+    mb[s] = __builtin_amdgcn_readfirstlane(0x3c003c00u + (s << 9) + a);
+  }
+  const uint32_t voff = (blockIdx.x & 7) << 8;
+  const uint32_t idx0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)lds + threadIdx.x * 2;  // stores stay inside [0, SLAB)
+  uint32_t sink = 0;
+  auto step = [&](auto J, int tt) {
+    constexpr int j = decltype(J)::value;
+    uint32_t c[15], acc_a, acc_b;
+#pragma unroll
+    for (int s = 0; s < 15; ++s) {
+      if constexpr (LEAN) asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tds_read_addtid_b32 %0 offset:%2" : "=v"(c[s]) : "s"(voff + (s << 8)), "n"(SLAB) : "memory");
+      else asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tds_read_addtid_b32 %0" : "=v"(c[s]) : "s"(SLAB + voff + (s << 8)) : "memory");
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int s = 0; s < 15; ++s) asm volatile("v_pk_sub_i16 %0, %1, %0" : "+v"(c[s]) : "s"(kk));
+    if constexpr (LEAN) {
+      lean_block<true, 0>(acc_a, c, ma);
+      if (a > 4) lean_block<false, 4>(acc_a, c, ma);
+      if (a > 8) lean_block<false, 8>(acc_a, c, ma);
+      if (a > 12) lean_block<false, 12>(acc_a, c, ma);
+      lean_block<true, 12>(acc_b, c, mb);
+      if (x < 12) lean_block<false, 8>(acc_b, c, mb);
+      if (x < 8) lean_block<false, 4>(acc_b, c, mb);
+      if (x < 4) lean_block<false, 0>(acc_b, c, mb);
+    } else {
+      asm volatile("v_mov_b32 %0, 0\n\tv_mov_b32 %1, 0" : "=v"(acc_a), "=v"(acc_b));
+      byte_blocks<4, true>(acc_a, c, ma, a);
+      byte_blocks<4, false>(acc_b, c, mb, x);
+    }
+    uint32_t l0, l1, pair;
+    asm volatile("v_perm_b32 %0, %1, %0, %2\n\tv_not_b32 %0, %0" : "+v"(acc_a) : "v"(acc_b), "s"(0x07030501u));
+    asm volatile("v_ffbl_b32 %0, %2\n\tv_ffbl_b32_sdwa %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1" : "=&v"(l0), "=&v"(l1) : "v"(acc_a));
+    if constexpr (LEAN) {
+      asm volatile("v_lshl_or_b32 %0, %2, 8, %1" : "=v"(pair) : "v"(l0), "v"(l1));
+      asm volatile("ds_write_b16 %0, %1 offset:%2" : : "v"(idx0), "v"(pair), "n"(j * 512) : "memory");
+    } else {
+      uint32_t addr;
+      asm volatile("v_lshl_or_b32 %0, %3, 8, %2\n\tv_lshl_add_u32 %1, %4, 9, %5" : "=&v"(pair), "=&v"(addr) : "v"(l0), "v"(l1), "s"(tt), "v"(idx0));
+      asm volatile("ds_write_b16 %0, %1" : : "v"(addr), "v"(pair) : "memory");
+    }
+    sink ^= pair;
+  };
+  if constexpr (LEAN) {
+    for (int i = 0; i < iters; i += 8) {
+      step(std::integral_constant<int, 0>{}, 0); step(std::integral_constant<int, 1>{}, 1);
+      step(std::integral_constant<int, 2>{}, 2); step(std::integral_constant<int, 3>{}, 3);
+      step(std::integral_constant<int, 4>{}, 4); step(std::integral_constant<int, 5>{}, 5);
+      step(std::integral_constant<int, 6>{}, 6); step(std::integral_constant<int, 7>{}, 7);
+    }
+  } else {
+#pragma unroll 1
+    for (int i = 0; i < iters; ++i) step(std::integral_constant<int, 0>{}, i & 7);
+  }
+  out[blockIdx.x * 256 + threadIdx.x] = sink;
+}
+
 // dependent LDS search chain: 8 dependent ds_read_b32 + compare/select (the binning search of the assembly kernel)
 __global__ void __launch_bounds__(256) k_lds_chain(int iters, uint32_t *out) {
   __shared__ uint32_t slab[64 * 64];
@@ -280,9 +373,12 @@ __global__ void __launch_bounds__(256) k_lds_chain(int iters, uint32_t *out) {
 }
 constexpr int K_LDS_CHAIN = 8;
 
+static const char *g_only = nullptr;  // argv[1]: run only the rows whose name contains it
+
 template <typename T, typename K, typename... Extra>
 static void run(const char *name, K kern, int k_per_iter, int n_cus, T *d_out, Extra... extra) {
   const int iters = 4096;
+  if (g_only && !strstr(name, g_only)) return;
   fprintf(stderr, "%s\n", name);
   for (int w : {1, 2, 4, 8}) {  // 256-thread workgroups per CU = wavefronts per SIMD
     const int grid = n_cus * w;
@@ -309,7 +405,8 @@ static void run(const char *name, K kern, int k_per_iter, int n_cus, T *d_out, E
   }
 }
 
-int main() {
+int main(int argc, char **argv) {
+  if (argc > 1) g_only = argv[1];
   setvbuf(stdout, nullptr, _IOLBF, 0);
   fprintf(stderr, "start\n");
   hipDeviceProp_t p;
@@ -338,6 +435,16 @@ int main() {
       run(name, k, 43 + z + (mode == 1 ? 2 : 0) + 30 + 15, n_cus, (uint32_t *)d, x, x + z);
     }
   run("tree step (byte fixed z=2)", k_tree_byte<2>, 43 + 2 + 30 + 15, n_cus, (uint32_t *)d, 6, 8);
+  // round 7's whole step against round 17's: 15 + (blocks' v_and_or_b32) + 8 VALU (r7) / + 5 (lean), 30 SALU, 16 LDS
+  for (int z : {0, 2, 7}) {
+    const int x = z == 7 ? 0 : 7 - z / 2, a = x + z;
+    const int andor = 4 * ((a + 3) / 4 < 4 ? (a + 3) / 4 : 4) - (a > 12 ? 1 : 0) + (15 - 4 * (x / 4));
+    char name[48];
+    snprintf(name, sizeof name, "tree step (r7 whole z=%d)", z);
+    run(name, k_tree_byte_whole<false>, 15 + andor + 8 + 30 + 16, n_cus, (uint32_t *)d, x, a);
+    snprintf(name, sizeof name, "tree step (lean z=%d)", z);
+    run(name, k_tree_byte_whole<true>, 15 + andor + 5 + 30 + 16, n_cus, (uint32_t *)d, x, a);
+  }
   run("lds dependent chain", k_lds_chain, K_LDS_CHAIN, n_cus, (uint32_t *)d);
   CK(hipFree(d));
   return 0;
