@@ -860,6 +860,81 @@ int mrk_model_eval(mrk_model *model, const int *metrics, const int *cutoffs, int
                    const double *rowmajor, int cols, const double *labels, const int64_t *group_offsets, int64_t n_groups,
                    const double *random_scores, double *out, double *out_scores);
 
+/* ---- Training: LambdaMART forests fitted on the device ------------------------------------------------------------------------------
+ * LambdaMARTPredictor.makeBooster (M/ml/rank/LambdaMARTRanker.scala:161-190) for the LightGBM backend: the row matrix mrk_values
+ * wrote stays where it is, the forest comes back as LightGBM's text format (objective=lambdarank) and loads through mrk_model_load
+ * like any other.  New symbols only, no new struct.
+ * ASSUMPTIONS (unpinned): neither LightGBM nor its sources are in the reference tree, so this is NOT LightGBM's bit stream.  The
+ * algorithm below is this project's: LightGBM's lambdarank objective and leaf-wise histogram learner where the rules are public,
+ * and two departures that make every result independent of the order anything arrives in - (a) whatever is summed across rows is
+ * an int64 sum of quantised values (no float atomics anywhere), (b) exp and log2 are the HOST's libm, through tables.
+ * tests/train_reference.py restates it and the device agrees with that to the bit and the byte.  Config keys and [defaults]:
+ * LightGBMConfig's iterations [100], learningRate [0.1], ndcgCutoff [10], maxDepth [8], seed [0], numLeaves [16], sampling [0.8],
+ * debias [false; true is MRK_ERR_UNSUPPORTED], and max_bin [255], truncation [30], sigma [1.0], min_data_in_leaf [20],
+ * min_sum_hessian [1e-3], lambda_l2 [0], early_stopping [20].  An unknown key is MRK_ERR_PARSE.
+ *  1 input     f64 row-major rows x cols; labels integers 0 ... 30; groups under mrk_model_eval's rules, at most 4096 rows each; an
+ *              infinite cell is MRK_ERR_INVALID_ARG; the initial score is 0.
+ *  2 bins      per column, on the host: v = the sorted non-NaN cells (-0.0 is +0.0), m of them.  At most max_bin - 1 distinct
+ *              values: a bound between every two neighbours.  Else for i = 1 ... max_bin - 2 a bound at the first p >=
+ *              floor(i * m / (max_bin - 1)) with v[p] != v[p - 1], duplicates dropped.  The bound between a < b is (a + b) / 2 in
+ *              f64, or a when that is not below b.  bin(x) = the number of bounds < x (so x <= bound goes left, as the scorers
+ *              decide); NaN is bin 255.  A column with one bin never splits.  The validation set uses the same bounds.
+ *  3 gradients per group of n rows: pi = the order of mrk_eval_scores; gain(y) = 2^y - 1; k = min(truncation, n); inv = 1 /
+ *              (sum over i < k of sorted-descending gain_i / lg[i], added in order from 0.0), 0 when that sum is 0; lg[i] =
+ *              log2(i + 2).  A pair of ranks (r, q) counts when the labels differ and min(r, q) < k; with hi / lo the item of the
+ *              higher / lower label: delta = s_hi - s_lo; rho = T[clamp((delta - lo) * f, 0, BINS - 1) truncated];
+ *              w = ((gain_hi - gain_lo) * |1 / lg[r_hi] - 1 / lg[r_lo]|) * inv; lambda = (sigma * rho) * w;
+ *              eta = (((sigma * sigma) * rho) * (1 - rho)) * w; g[hi] -= lambda, g[lo] += lambda, h[both] += eta.  An item adds
+ *              its pairs in ascending partner rank from 0.0.  T[t] = 1 / (1 + exp(sigma * (lo + t / f))), BINS =
+ *              MRK_TRAIN_SIGMOID_BINS, lo = -25 / sigma, f = BINS / (50 / sigma).  Every operation f64, correctly rounded, never
+ *              fused.  No lambdarank_norm, no position debias.
+ *  4 quantise  e_g = 61 - bitlen(rows) - E(max |g|), frexp(x) = m * 2^E; q_g = (int64) nearbyint(ldexp(g, e_g)), ties to even; h
+ *              likewise with max h.  max |g| == 0 ends training.
+ *  5 tree      leaf-wise.  Per leaf and column of the tree's subset a histogram (sum q_g, sum q_h, count) per bin.  Candidates b =
+ *              0 ... nbins - 2, left = bins <= b; NaN goes right, and with rows in bin 255 also left.  Real sums are ldexp((double)
+ *              Q, -e).  Admitted when both counts >= min_data_in_leaf, both hessian sums >= min_sum_hessian, the leaf's depth <
+ *              maxDepth and gain = (GL * GL / (HL + l2) + GR * GR / (HR + l2)) - G * G / (H + l2) > 0.  Best: the highest gain,
+ *              then the lowest column, the lowest b, NaN right.  The leaf with the best gain splits (ties: the lowest leaf) until
+ *              numLeaves leaves or no candidate.  LightGBM's numbering: split s makes node s, the left child keeps the leaf index,
+ *              the right is leaf s + 1.  threshold = the bound of b; decision_type = 8 | (NaN left ? 2 : 0); leaf_value =
+ *              (-G / (H + l2)) * learningRate.  A tree that cannot split ends training and is not emitted.
+ *  6 scores    score[row] += leaf_value, in tree order; validation rows walk the tree by their bins.
+ *  7 subset    per tree min(cols, max(1, floor(cols * sampling + 0.5))) columns: a partial Fisher-Yates shuffle of 0 ... cols - 1
+ *              (position j swaps with j + z % (cols - j), z the next splitmix64 output; state = (uint32) seed << 32 | tree index),
+ *              the first ones taken, ascending.  Made on the host.
+ *  8 stopping  with a validation set: ndcg@ndcgCutoff (relpow, nolabels = 1.0: mrk_eval_scores' number) after every iteration; the
+ *              best iteration is replaced only by a strictly greater value; stops after early_stopping iterations without one;
+ *              the model holds the trees up to the best iteration.  Without one: `iterations` trees. */
+#define MRK_TRAIN_SIGMOID_BINS 65536
+typedef struct mrk_trainer mrk_trainer;
+
+/* Parses the config (errors: above) and creates a trainer on ctx's device.  One GPU per fit. */
+int mrk_train_begin(mrk_ctx *ctx, const char *config_json, mrk_trainer **out);
+/* Hands over a data set: which = 0 the training set, 1 the validation set (optional; after the training set, same cols).  The
+ * matrix is binned on the device, uploaded in pieces of about 64 MiB (MRK_TRAIN_PIECE_ROWS=n: pieces of n rows): it need not fit
+ * the device, and nothing of the caller's is kept.  MRK_ERR_INVALID_ARG: null pointers, a bad `which`, rows / cols < 1, offsets
+ * that do not start at 0 or do not strictly increase, a label that is no integer in 0 ... 30, an infinite cell.
+ * MRK_ERR_UNSUPPORTED, with the sizes in mrk_last_error: cols > 65535, rows >= 2^31, a group of more than 4096 rows, working
+ * memory (bins, gradients, numLeaves x subset x 256 histogram cells) beyond what the device has free. */
+int mrk_train_set(mrk_trainer *t, int which, const double *rowmajor, int64_t rows, int cols, const double *labels, const int64_t *group_offsets,
+                  int64_t n_groups);
+/* Runs the fit (steps 3 - 8). */
+int mrk_train_fit(mrk_trainer *t);
+/* The model text.  *needed: its length in bytes; copies it when cap >= *needed (out may be NULL to ask for the length). */
+int mrk_train_model(mrk_trainer *t, void *out, size_t cap, size_t *needed);
+/* iterations_run: trees grown; best_iteration: trees in the model; out_metric (nullable): the validation metric after each iteration,
+ * min(cap, iterations_run) values (none without a validation set). */
+int mrk_train_history(mrk_trainer *t, int *iterations_run, int *best_iteration, double *out_metric, int cap);
+/* The trainer's own f64 scores of set `which` at the best iteration: what the model predicts for those rows, bit for bit. */
+int mrk_train_scores(mrk_trainer *t, int which, double *out);
+void mrk_train_free(mrk_trainer *t);
+/* Step 3 alone: out_g / out_h, one f64 per row.  Uses sigma and truncation of the config.  Also a device-side custom objective for a
+ * host that keeps lib_lightgbm.  A non-finite score is MRK_ERR_INVALID_ARG. */
+int mrk_train_gradients(mrk_ctx *ctx, const char *config_json, const double *scores, const double *labels, const int64_t *group_offsets,
+                        int64_t n_groups, double *out_g, double *out_h);
+/* Step 2 for one column of n cells (host only, no context): *n_bounds bounds, copied when cap >= *n_bounds. */
+int mrk_train_bins(const char *config_json, const double *column, int64_t n, double *out_bounds, int cap, int *n_bounds);
+
 #ifdef __cplusplus
 }
 #endif

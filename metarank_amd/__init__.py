@@ -11,3 +11,4 @@ from .request import Request, RequestSet  # noqa: F401,E402
 from .trending import HipTrending, TrendingBuilder  # noqa: F401,E402
 from .als import AlsBuilder  # noqa: F401,E402
 from .eval import eval_scores, evaluate, labels_from_interactions  # noqa: F401,E402
+from .train import Trainer, bin_bounds, fit_lambdamart, lambdarank_gradients  # noqa: F401,E402

@@ -1,0 +1,506 @@
+// C ABI (include/mrk.h) of the LambdaMART fit: LambdaMARTPredictor.makeBooster (ml/rank/LambdaMARTRanker.scala:161-190) for the
+// LightGBM backend.  Gradients, histograms, split scans and score updates are train.hip; config, bins, feature subsets, tables, the
+// tree book-keeping and the model text are train_host.cpp; the validation metric is eval.hip's (the number mrk_eval_scores gives).
+// The loop over splits is driven from here: per split one histogram launch, one scan, two records read back.
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <exception>
+#include <memory>
+#include <thread>
+
+#include "eval.hpp"
+#include "eval_host.hpp"
+#include "runtime.hpp"
+#include "train.hpp"
+#include "train_host.hpp"
+
+using namespace mrk;
+
+namespace {
+
+struct TrainSet {
+  bool given = false;
+  int64_t rows = 0, n_groups = 0, max_len = 0;
+  std::vector<uint8_t> labels;
+  std::vector<int64_t> offsets;
+  EvalBins by_size;
+  DevBuf d_bins, d_labels, d_off, d_wave, d_group, d_score, d_best;
+  std::vector<double> gains;        // the validation set: what eval.hip reads (eval_pack_labels, relpow)
+  std::vector<uint8_t> rel;
+  std::vector<double> scores;       // at the best iteration, after the fit
+};
+
+}  // namespace
+
+struct mrk_trainer {
+  mrk_ctx *ctx = nullptr;
+  TrainConfig cfg;
+  std::mutex mu;                    // one set / fit at a time; lock order: mu before ctx->mu
+  int cols = 0;
+  std::vector<std::vector<double>> bounds;
+  std::vector<std::string> infos;
+  DevBuf d_bounds, d_bound_off, d_nbins;
+  TrainSet set[2];
+  bool fitted = false;
+  std::vector<TrainTree> trees;
+  std::vector<double> history;
+  int best_iteration = 0;
+  std::string model;
+};
+
+namespace {
+
+// MRK_TRAIN_PIECE_ROWS: read per call, never on a launch path of the serving side
+long long env_int(const char *name, long long dflt) {
+  const char *e = getenv(name);
+  if (!e || !*e) return dflt;
+  char *end = nullptr;
+  const long long v = strtoll(e, &end, 10);
+  return end && !*end ? v : dflt;
+}
+
+// f(c) for every column on up to 8 host threads; the first exception is rethrown
+template <typename F>
+void for_columns(int cols, F f) {
+  const int hw = (int)std::thread::hardware_concurrency();
+  const int n = std::max(1, std::min({switches().host_threads > 0 ? switches().host_threads : 8, hw > 0 ? hw : 1, cols}));
+  std::atomic<int> next{0};
+  std::exception_ptr err;
+  std::mutex err_mu;
+  auto work = [&] {
+    for (int c; (c = next.fetch_add(1)) < cols;) {
+      try {
+        f(c);
+      } catch (...) {
+        std::lock_guard<std::mutex> lk(err_mu);
+        if (!err) err = std::current_exception();
+      }
+    }
+  };
+  std::vector<std::thread> th;
+  for (int i = 1; i < n; ++i) th.emplace_back(work);
+  work();
+  for (auto &t : th) t.join();
+  if (err) std::rethrow_exception(err);
+}
+
+void check_free(double want, const std::string &what) {
+  size_t free_b = 0, total_b = 0;
+  MRK_HIP(hipMemGetInfo(&free_b, &total_b));
+  if (want > (double)free_b)
+    throw StatusError(MRK_ERR_UNSUPPORTED, "train: " + what + " need " + std::to_string((unsigned long long)want) + " bytes on the device, " + std::to_string(free_b) + " are free");
+}
+
+void set_locked(mrk_trainer *t, int which, const double *x, int64_t rows, int cols, const double *labels, const int64_t *off, int64_t n_groups) {
+  need(which == 0 || which == 1, "train: which is neither 0 (train) nor 1 (validation)");
+  need(!t->fitted, "train: the trainer has been fitted");
+  need(x != nullptr, "train: null matrix");
+  need(rows >= 1 && cols >= 1, "train: rows / cols < 1");
+  if (cols > TRAIN_MAX_COLS) throw StatusError(MRK_ERR_UNSUPPORTED, "train: " + std::to_string(cols) + " columns (limit " + std::to_string(TRAIN_MAX_COLS) + ")");
+  if (rows >= (int64_t(1) << 31)) throw StatusError(MRK_ERR_UNSUPPORTED, "train: " + std::to_string(rows) + " rows (limit 2^31 - 1)");
+  const EvalShape sh = eval_check_groups(off, n_groups);
+  need(sh.rows == rows, "train: the group offsets do not end at `rows`");
+  if (sh.max_len > TRAIN_MAX_GROUP)
+    throw StatusError(MRK_ERR_UNSUPPORTED, "train: a group of " + std::to_string(sh.max_len) + " rows (limit " + std::to_string(TRAIN_MAX_GROUP) + ")");
+  TrainSet &s = t->set[which];
+  s = TrainSet();
+  s.labels = train_check_labels(labels, rows);
+  if (which == 1) {
+    need(t->set[0].given, "train: the validation set comes after the training set");
+    need(cols == t->cols, "train: the validation set has other columns than the training set");
+    s.gains.resize((size_t)rows);
+    s.rel.resize((size_t)rows);
+    eval_pack_labels(labels, rows, true, s.gains.data(), s.rel.data());
+    for (int64_t i = 0; i < rows * cols; ++i)
+      if (std::isinf(x[i])) throw StatusError(MRK_ERR_INVALID_ARG, "train: cell " + std::to_string(i) + " of the validation matrix is infinite");
+  } else {
+    t->set[1] = TrainSet();
+    t->cols = cols;
+    t->bounds.assign((size_t)cols, {});
+    t->infos.assign((size_t)cols, "");
+    for_columns(cols, [&](int c) { t->bounds[(size_t)c] = train_bin_bounds(x + c, rows, cols, t->cfg.max_bin, &t->infos[(size_t)c]); });
+  }
+  s.rows = rows, s.n_groups = n_groups, s.max_len = sh.max_len;
+  s.offsets.assign(off, off + n_groups + 1);
+  s.by_size = eval_bins(off, n_groups, EVAL_WAVE_ITEMS);
+
+  mrk_ctx *ctx = t->ctx;
+  DeviceLock lk(ctx);
+  hipStream_t st = lk.stream;
+  const std::vector<EvalPiece> pieces = eval_pieces(rows, cols, env_int("MRK_TRAIN_PIECE_ROWS", 0));
+  const size_t piece_bytes = (size_t)pieces[0].rows * (size_t)cols * 8;
+  const int n_sub = (int)train_feature_subset(cols, t->cfg.sampling, 0, 0).size();
+  // resident for the fit: the bins, per row g, h, q_g, q_h, score, best score, leaf and label, the lists of groups, the histograms
+  const double fit_bytes = (double)rows * cols + 51.0 * (double)rows + 12.0 * (double)n_groups +
+                           (which == 0 ? 20.0 * 256.0 * (double)n_sub * (double)t->cfg.num_leaves + 2.0 * sizeof(LeafRec) * (double)n_sub : 9.0 * (double)rows + 8.0 * (double)n_groups);
+  check_free(fit_bytes + (double)piece_bytes + 1048576.0, std::to_string(rows) + " rows x " + std::to_string(cols) + " columns in " + std::to_string(n_groups) + " groups, " +
+                                                              std::to_string(t->cfg.num_leaves) + " leaves x " + std::to_string(n_sub) + " columns of histograms");
+  if (which == 0) {
+    std::vector<double> flat;
+    std::vector<int> boff((size_t)cols + 1, 0), nbins((size_t)cols);
+    for (int c = 0; c < cols; ++c) {
+      flat.insert(flat.end(), t->bounds[(size_t)c].begin(), t->bounds[(size_t)c].end());
+      boff[(size_t)c + 1] = (int)flat.size();
+      nbins[(size_t)c] = (int)t->bounds[(size_t)c].size() + 1;
+    }
+    upload(t->d_bounds, flat, st);
+    upload(t->d_bound_off, boff, st);
+    upload(t->d_nbins, nbins, st);
+    MRK_HIP(hipStreamSynchronize(st));   // the vectors are locals
+  }
+  s.d_bins.reserve((size_t)rows * (size_t)cols);
+  DevBuf d_x;
+  d_x.reserve(piece_bytes);
+  for (const EvalPiece &pc : pieces) {
+    MRK_HIP(hipMemcpyAsync(d_x.p, x + (size_t)pc.row0 * (size_t)cols, (size_t)pc.rows * (size_t)cols * 8, hipMemcpyHostToDevice, st));
+    train_launch_bin(ctx, st, d_x.as<double>(), pc.rows, cols, t->d_bounds.as<double>(), t->d_bound_off.as<int>(), s.d_bins.as<uint8_t>(), rows, pc.row0);
+  }
+  upload(s.d_labels, s.labels, st);
+  upload(s.d_off, s.offsets, st);
+  if (!s.by_size.wave.empty()) upload(s.d_wave, s.by_size.wave, st);
+  if (!s.by_size.group.empty()) upload(s.d_group, s.by_size.group, st);
+  s.d_score.reserve((size_t)rows * 8);
+  s.d_best.reserve((size_t)rows * 8);
+  MRK_HIP(hipMemsetAsync(s.d_score.p, 0, (size_t)rows * 8, st));
+  MRK_HIP(hipMemsetAsync(s.d_best.p, 0, (size_t)rows * 8, st));
+  MRK_HIP(hipStreamSynchronize(st));     // the caller's matrix is not kept
+  drain_profile_events(ctx);
+  s.given = true;
+}
+
+// the tables of step 3 on the device
+struct GradTables {
+  DevBuf d_lg, d_invlg, d_sigmoid;
+  SigmoidTable sig;
+  void make(const TrainConfig &cfg, int64_t max_len, hipStream_t st) {
+    sig = train_sigmoid_table(cfg.sigma);
+    const std::vector<double> lg = eval_lg_table(max_len);
+    std::vector<double> invlg(lg.size());
+    for (size_t i = 0; i < lg.size(); ++i) invlg[i] = 1.0 / lg[i];
+    upload(d_lg, lg, st);
+    upload(d_invlg, invlg, st);
+    upload(d_sigmoid, sig.t, st);
+    MRK_HIP(hipStreamSynchronize(st));   // lg and invlg are locals
+  }
+  GradDev dev(const TrainConfig &cfg) const {
+    GradDev d{};
+    d.lg = d_lg.as<double>(), d.invlg = d_invlg.as<double>(), d.sigmoid = d_sigmoid.as<double>();
+    d.lo = sig.lo, d.f = sig.f, d.sigma = cfg.sigma, d.sigma2 = cfg.sigma * cfg.sigma, d.truncation = cfg.truncation;
+    return d;
+  }
+};
+
+void launch_gradients(mrk_ctx *ctx, hipStream_t st, const GradDev &d, const EvalBins &by_size, const DevBuf &d_wave, const DevBuf &d_group) {
+  train_launch_grad_wave(ctx, st, d, d_wave.as<int>(), (int)by_size.wave.size());
+  train_launch_grad_group(ctx, st, d, d_group.as<int>(), (int)by_size.group.size(), (int)by_size.group_max_len);
+}
+
+void fit_locked(mrk_trainer *t) {
+  need(t->set[0].given, "train: no training set");
+  need(!t->fitted, "train: the trainer has been fitted");
+  mrk_ctx *ctx = t->ctx;
+  const TrainConfig &cfg = t->cfg;
+  TrainSet &tr = t->set[0], &va = t->set[1];
+  const int64_t rows = tr.rows;
+  const int cols = t->cols;
+  // ctx->mu is held per iteration, not for the fit: every iteration ends with the stream waited for, so other calls on the context
+  // (/rank among them) get their turn between two trees
+  std::unique_ptr<DeviceLock> lk(new DeviceLock(ctx));
+  hipStream_t st = lk->stream;
+  // a fit starts from score 0, also after one that a device error ended half-way
+  for (TrainSet *s : {&tr, &va})
+    if (s->given) {
+      MRK_HIP(hipMemsetAsync(s->d_score.p, 0, (size_t)s->rows * 8, st));
+      MRK_HIP(hipMemsetAsync(s->d_best.p, 0, (size_t)s->rows * 8, st));
+    }
+
+  GradTables tab;
+  tab.make(cfg, std::max(tr.max_len, va.given ? va.max_len : 0), st);
+  const int n_sub_max = (int)train_feature_subset(cols, cfg.sampling, 0, 0).size();
+  DevBuf d_g, d_h, d_qg, d_qh, d_leaf_of, d_maxes, d_G, d_H, d_C, d_feat_best, d_recs, d_subset;
+  DevBuf d_tcol, d_tbin, d_tnan, d_tleft, d_tright, d_tvalue;
+  d_g.reserve((size_t)rows * 8), d_h.reserve((size_t)rows * 8), d_qg.reserve((size_t)rows * 8), d_qh.reserve((size_t)rows * 8);
+  d_leaf_of.reserve((size_t)rows * 2);
+  d_maxes.reserve(16);
+  const size_t cells = (size_t)cfg.num_leaves * (size_t)n_sub_max * 256;
+  d_G.reserve(cells * 8), d_H.reserve(cells * 8), d_C.reserve(cells * 4);
+  d_feat_best.reserve(2 * (size_t)n_sub_max * sizeof(LeafRec));
+  d_recs.reserve(2 * sizeof(LeafRec));
+  d_subset.reserve((size_t)n_sub_max * 4);
+  for (DevBuf *b : {&d_tcol, &d_tbin, &d_tnan, &d_tleft, &d_tright}) b->reserve((size_t)cfg.num_leaves * 4);
+  d_tvalue.reserve((size_t)cfg.num_leaves * 8);
+  PinBuf h_back;   // what the host reads per iteration / split: two maxima, two records
+  h_back.reserve(16 + 2 * sizeof(LeafRec));
+  unsigned long long *h_maxes = h_back.as<unsigned long long>();
+  LeafRec *h_recs = (LeafRec *)(h_back.as<uint8_t>() + 16);
+
+  // the validation metric: eval.hip's kernels on the validation scores
+  DevBuf d_vgains, d_vrel, d_met, d_cut, d_metric;
+  EvalDev ev{};
+  std::vector<double> per_group;
+  if (va.given) {
+    const int metric = MRK_METRIC_NDCG;
+    upload(d_vgains, va.gains, st);
+    upload(d_vrel, va.rel, st);
+    d_met.reserve(4), d_cut.reserve(4), d_metric.reserve((size_t)va.n_groups * 8);
+    MRK_HIP(hipMemcpyAsync(d_met.p, &metric, 4, hipMemcpyHostToDevice, st));
+    MRK_HIP(hipMemcpyAsync(d_cut.p, &cfg.ndcg_cutoff, 4, hipMemcpyHostToDevice, st));
+    MRK_HIP(hipStreamSynchronize(st));
+    ev.scores = va.d_score.as<double>(), ev.gains = d_vgains.as<double>(), ev.rel = d_vrel.as<uint8_t>(), ev.offsets = va.d_off.as<long long>();
+    ev.lg = tab.d_lg.as<double>(), ev.metrics = d_met.as<int>(), ev.cutoffs = d_cut.as<int>(), ev.n_metrics = 1, ev.need_ideal = 1, ev.nolabels = 1.0;
+    ev.n_groups = va.n_groups, ev.out = d_metric.as<double>();
+    per_group.resize((size_t)va.n_groups);
+  }
+
+  GradDev gd = tab.dev(cfg);
+  gd.scores = tr.d_score.as<double>(), gd.labels = tr.d_labels.as<uint8_t>(), gd.offsets = tr.d_off.as<long long>(), gd.g = d_g.as<double>(), gd.h = d_h.as<double>();
+  const uint8_t *bins = tr.d_bins.as<uint8_t>();
+  uint16_t *leaf_of = d_leaf_of.as<uint16_t>();
+  double best_metric = 0.0;
+  t->trees.clear(), t->history.clear(), t->best_iteration = 0;
+
+  for (int it = 0; it < cfg.iterations; ++it) {
+    if (it > 0) {
+      MRK_HIP(hipStreamSynchronize(st));   // (the copies of a new best iteration)
+      lk.reset();
+      lk.reset(new DeviceLock(ctx));
+    }
+    launch_gradients(ctx, st, gd, tr.by_size, tr.d_wave, tr.d_group);
+    MRK_HIP(hipMemsetAsync(d_maxes.p, 0, 16, st));
+    train_launch_max(ctx, st, gd.g, gd.h, rows, d_maxes.as<unsigned long long>());
+    MRK_HIP(hipMemcpyAsync(h_maxes, d_maxes.p, 16, hipMemcpyDeviceToHost, st));
+    MRK_HIP(hipStreamSynchronize(st));
+    double gmax, hmax;
+    memcpy(&gmax, &h_maxes[0], 8), memcpy(&hmax, &h_maxes[1], 8);
+    if (gmax == 0.0) break;
+    ScanParams sp{train_exponent(gmax, rows), train_exponent(hmax, rows), cfg.min_data_in_leaf, cfg.min_sum_hessian, cfg.lambda_l2};
+    train_launch_quantise(ctx, st, gd.g, gd.h, rows, sp.e_g, sp.e_h, d_qg.as<long long>(), d_qh.as<long long>(), leaf_of);
+    const std::vector<int32_t> subset = train_feature_subset(cols, cfg.sampling, cfg.seed, it);
+    MRK_HIP(hipMemcpyAsync(d_subset.p, subset.data(), subset.size() * 4, hipMemcpyHostToDevice, st));   // (waited for with the root's record)
+    HistDev hd{d_G.as<long long>(), d_H.as<long long>(), d_C.as<unsigned>(), (int)subset.size()};
+
+    auto scan = [&](int leaf_a, int leaf_b, bool small_is_left) {
+      train_launch_scan(ctx, st, hd, d_subset.as<int>(), t->d_nbins.as<int>(), leaf_a, leaf_b, small_is_left, sp, d_feat_best.as<LeafRec>(), d_recs.as<LeafRec>());
+      MRK_HIP(hipMemcpyAsync(h_recs, d_recs.p, 2 * sizeof(LeafRec), hipMemcpyDeviceToHost, st));
+      MRK_HIP(hipStreamSynchronize(st));
+    };
+    TrainTree tree;
+    train_launch_hist(ctx, st, bins, rows, leaf_of, 0, 0, d_qg.as<long long>(), d_qh.as<long long>(), d_subset.as<int>(), hd);
+    scan(0, -1, false);
+    std::vector<LeafRec> cand{h_recs[0]};
+    std::vector<TrainSums> totals{TrainSums{h_recs[0].g, h_recs[0].h, h_recs[0].c}};
+    while (tree.num_leaves() < cfg.num_leaves) {
+      int leaf = -1;
+      for (int l = 0; l < tree.num_leaves(); ++l)
+        if (cand[(size_t)l].valid && tree.depth[(size_t)l] < cfg.max_depth && (leaf < 0 || cand[(size_t)l].gain > cand[(size_t)leaf].gain)) leaf = l;
+      if (leaf < 0) break;
+      const LeafRec c = cand[(size_t)leaf];
+      const TrainSums whole = totals[(size_t)leaf];
+      double weight = 0.0;
+      tree.ivalue.push_back(train_leaf_output(whole, sp.e_g, sp.e_h, cfg.lambda_l2, cfg.learning_rate, &weight));
+      tree.iweight.push_back(weight);
+      tree.icount.push_back(whole.c);
+      const int fresh = tree.split(leaf, c.col, c.bin, t->bounds[(size_t)c.col][(size_t)c.bin], c.nan_left != 0, c.gain);
+      train_launch_split(ctx, st, bins + (size_t)c.col * (size_t)rows, rows, leaf_of, leaf, fresh, c.bin, c.nan_left);
+      const TrainSums left{c.gl, c.hl, c.cl}, right{whole.g - c.gl, whole.h - c.hl, whole.c - c.cl};
+      totals[(size_t)leaf] = left;
+      totals.push_back(right);
+      cand.resize((size_t)fresh + 1);
+      if (tree.num_leaves() >= cfg.num_leaves || tree.depth[(size_t)leaf] >= cfg.max_depth) {   // neither child is split again: no histogram
+        cand[(size_t)leaf].valid = cand[(size_t)fresh].valid = 0;
+        continue;
+      }
+      const bool small_is_left = left.c <= right.c;
+      train_launch_hist(ctx, st, bins, rows, leaf_of, small_is_left ? leaf : fresh, fresh, d_qg.as<long long>(), d_qh.as<long long>(), d_subset.as<int>(), hd);
+      scan(leaf, fresh, small_is_left);
+      cand[(size_t)leaf] = h_recs[0];
+      cand[(size_t)fresh] = h_recs[1];
+    }
+    if (tree.num_leaves() == 1) break;
+    const int nl = tree.num_leaves();
+    tree.value.resize((size_t)nl), tree.weight.resize((size_t)nl), tree.count.resize((size_t)nl);
+    for (int l = 0; l < nl; ++l) {
+      tree.value[(size_t)l] = train_leaf_output(totals[(size_t)l], sp.e_g, sp.e_h, cfg.lambda_l2, cfg.learning_rate, &tree.weight[(size_t)l]);
+      tree.count[(size_t)l] = totals[(size_t)l].c;
+    }
+    std::vector<int32_t> nan_left((size_t)nl - 1);
+    for (int n = 0; n < nl - 1; ++n) nan_left[(size_t)n] = (tree.dt[(size_t)n] & 2) ? 1 : 0;
+    MRK_HIP(hipMemcpyAsync(d_tcol.p, tree.feat.data(), (size_t)(nl - 1) * 4, hipMemcpyHostToDevice, st));
+    MRK_HIP(hipMemcpyAsync(d_tbin.p, tree.bin.data(), (size_t)(nl - 1) * 4, hipMemcpyHostToDevice, st));
+    MRK_HIP(hipMemcpyAsync(d_tnan.p, nan_left.data(), (size_t)(nl - 1) * 4, hipMemcpyHostToDevice, st));
+    MRK_HIP(hipMemcpyAsync(d_tleft.p, tree.left.data(), (size_t)(nl - 1) * 4, hipMemcpyHostToDevice, st));
+    MRK_HIP(hipMemcpyAsync(d_tright.p, tree.right.data(), (size_t)(nl - 1) * 4, hipMemcpyHostToDevice, st));
+    MRK_HIP(hipMemcpyAsync(d_tvalue.p, tree.value.data(), (size_t)nl * 8, hipMemcpyHostToDevice, st));
+    const TreeDev td{d_tcol.as<int>(), d_tbin.as<int>(), d_tnan.as<int>(), d_tleft.as<int>(), d_tright.as<int>(), d_tvalue.as<double>()};
+    train_launch_apply(ctx, st, td, leaf_of, nullptr, rows, tr.d_score.as<double>());
+    if (va.given) {
+      train_launch_apply(ctx, st, td, nullptr, va.d_bins.as<uint8_t>(), va.rows, va.d_score.as<double>());
+      {
+        ScopedKernelTimer timer(ctx, "train_eval");
+        eval_launch_wave(ctx, st, ev, va.d_wave.as<int>(), (int)va.by_size.wave.size());
+        eval_launch_group(ctx, st, ev, va.d_group.as<int>(), (int)va.by_size.group.size(), (int)va.by_size.group_max_len);
+      }
+      MRK_HIP(hipMemcpyAsync(per_group.data(), d_metric.p, per_group.size() * 8, hipMemcpyDeviceToHost, st));
+    }
+    MRK_HIP(hipStreamSynchronize(st));   // the tree's arrays have left the host; the metric has arrived
+    t->trees.push_back(std::move(tree));
+    const int n_trees = (int)t->trees.size();
+    if (!va.given) {
+      t->best_iteration = n_trees;
+      continue;
+    }
+    const double m = eval_mean(per_group.data(), va.n_groups);
+    t->history.push_back(m);
+    if (t->best_iteration == 0 || m > best_metric) {
+      t->best_iteration = n_trees, best_metric = m;
+      MRK_HIP(hipMemcpyAsync(tr.d_best.p, tr.d_score.p, (size_t)rows * 8, hipMemcpyDeviceToDevice, st));
+      MRK_HIP(hipMemcpyAsync(va.d_best.p, va.d_score.p, (size_t)va.rows * 8, hipMemcpyDeviceToDevice, st));
+    } else if (n_trees - t->best_iteration >= cfg.early_stopping) break;
+  }
+  for (TrainSet *s : {&tr, &va}) {
+    if (!s->given) continue;
+    s->scores.resize((size_t)s->rows);
+    MRK_HIP(hipMemcpyAsync(s->scores.data(), va.given ? s->d_best.p : s->d_score.p, (size_t)s->rows * 8, hipMemcpyDeviceToHost, st));
+  }
+  MRK_HIP(hipStreamSynchronize(st));
+  drain_profile_events(ctx);
+  t->model = train_write_model(t->trees, (size_t)t->best_iteration, cols, t->infos, cfg.learning_rate);
+  t->fitted = true;
+}
+
+void check_trainer(mrk_trainer *t) { need(t != nullptr, "null trainer"); }
+
+}  // namespace
+
+extern "C" {
+
+int mrk_train_begin(mrk_ctx *ctx, const char *config_json, mrk_trainer **out) {
+  return guard([&] {
+    need(out != nullptr, "out is null");
+    *out = nullptr;
+    need(config_json != nullptr, "null config");
+    std::unique_ptr<mrk_trainer> t(new mrk_trainer());
+    t->cfg = train_parse_config(config_json, strlen(config_json));
+    need(ctx != nullptr, "null context");
+    ctx_retain(ctx);
+    t->ctx = ctx;
+    *out = t.release();
+  });
+}
+
+int mrk_train_set(mrk_trainer *t, int which, const double *rowmajor, int64_t rows, int cols, const double *labels, const int64_t *group_offsets,
+                  int64_t n_groups) {
+  return guard([&] {
+    check_trainer(t);
+    std::lock_guard<std::mutex> lk(t->mu);
+    set_locked(t, which, rowmajor, rows, cols, labels, group_offsets, n_groups);
+  });
+}
+
+int mrk_train_fit(mrk_trainer *t) {
+  return guard([&] {
+    check_trainer(t);
+    std::lock_guard<std::mutex> lk(t->mu);
+    fit_locked(t);
+  });
+}
+
+int mrk_train_model(mrk_trainer *t, void *out, size_t cap, size_t *needed) {
+  return guard([&] {
+    check_trainer(t);
+    need(needed != nullptr, "needed is null");
+    std::lock_guard<std::mutex> lk(t->mu);
+    if (!t->fitted) throw StatusError(MRK_ERR_NOT_FOUND, "train: not fitted yet");
+    *needed = t->model.size();
+    if (out && cap >= t->model.size()) memcpy(out, t->model.data(), t->model.size());
+  });
+}
+
+int mrk_train_history(mrk_trainer *t, int *iterations_run, int *best_iteration, double *out_metric, int cap) {
+  return guard([&] {
+    check_trainer(t);
+    std::lock_guard<std::mutex> lk(t->mu);
+    if (!t->fitted) throw StatusError(MRK_ERR_NOT_FOUND, "train: not fitted yet");
+    if (iterations_run) *iterations_run = (int)t->trees.size();
+    if (best_iteration) *best_iteration = t->best_iteration;
+    if (out_metric)
+      for (int i = 0; i < cap && i < (int)t->history.size(); ++i) out_metric[i] = t->history[(size_t)i];
+  });
+}
+
+int mrk_train_scores(mrk_trainer *t, int which, double *out) {
+  return guard([&] {
+    check_trainer(t);
+    need(which == 0 || which == 1, "train: which is neither 0 (train) nor 1 (validation)");
+    need(out != nullptr, "out is null");
+    std::lock_guard<std::mutex> lk(t->mu);
+    if (!t->fitted || !t->set[which].given) throw StatusError(MRK_ERR_NOT_FOUND, "train: no scores of that set");
+    memcpy(out, t->set[which].scores.data(), t->set[which].scores.size() * 8);
+  });
+}
+
+void mrk_train_free(mrk_trainer *t) {
+  if (!t) return;
+  mrk_ctx *ctx = t->ctx;
+  {  // (as mrk_trending_builder_free: the buffers go while nothing of this context runs)
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    (void)hipSetDevice(ctx->device);
+    (void)hipStreamSynchronize(ctx->stream);
+    delete t;
+  }
+  ctx_release(ctx);
+}
+
+int mrk_train_gradients(mrk_ctx *ctx, const char *config_json, const double *scores, const double *labels, const int64_t *group_offsets, int64_t n_groups,
+                        double *out_g, double *out_h) {
+  return guard([&] {
+    need(config_json != nullptr, "null config");
+    const TrainConfig cfg = train_parse_config(config_json, strlen(config_json));
+    need(scores != nullptr && out_g != nullptr && out_h != nullptr, "train: null scores / outputs");
+    const EvalShape sh = eval_check_groups(group_offsets, n_groups);
+    const std::vector<uint8_t> y = train_check_labels(labels, sh.rows);
+    for (int64_t i = 0; i < sh.rows; ++i)
+      if (!std::isfinite(scores[i])) throw StatusError(MRK_ERR_INVALID_ARG, "train: score " + std::to_string(i) + " is not finite");
+    if (sh.max_len > TRAIN_MAX_GROUP)
+      throw StatusError(MRK_ERR_UNSUPPORTED, "train: a group of " + std::to_string(sh.max_len) + " rows (limit " + std::to_string(TRAIN_MAX_GROUP) + ")");
+    need(ctx != nullptr, "null context");
+    const EvalBins by_size = eval_bins(group_offsets, n_groups, EVAL_WAVE_ITEMS);
+    DeviceLock lk(ctx);
+    hipStream_t st = lk.stream;
+    const size_t rows = (size_t)sh.rows;
+    check_free(33.0 * (double)rows + 12.0 * (double)n_groups + 16.0 * (double)sh.max_len + 8.0 * TRAIN_SIGMOID_BINS + 65536.0,
+               std::to_string(rows) + " rows in " + std::to_string(n_groups) + " groups");
+    GradTables tab;
+    tab.make(cfg, sh.max_len, st);
+    DevBuf d_scores, d_labels, d_off, d_wave, d_group, d_g, d_h;
+    d_scores.reserve(rows * 8), d_off.reserve((size_t)(n_groups + 1) * 8), d_g.reserve(rows * 8), d_h.reserve(rows * 8);
+    MRK_HIP(hipMemcpyAsync(d_scores.p, scores, rows * 8, hipMemcpyHostToDevice, st));
+    MRK_HIP(hipMemcpyAsync(d_off.p, group_offsets, (size_t)(n_groups + 1) * 8, hipMemcpyHostToDevice, st));
+    upload(d_labels, y, st);
+    if (!by_size.wave.empty()) upload(d_wave, by_size.wave, st);
+    if (!by_size.group.empty()) upload(d_group, by_size.group, st);
+    GradDev gd = tab.dev(cfg);
+    gd.scores = d_scores.as<double>(), gd.labels = d_labels.as<uint8_t>(), gd.offsets = d_off.as<long long>(), gd.g = d_g.as<double>(), gd.h = d_h.as<double>();
+    launch_gradients(ctx, st, gd, by_size, d_wave, d_group);
+    MRK_HIP(hipMemcpyAsync(out_g, d_g.p, rows * 8, hipMemcpyDeviceToHost, st));
+    MRK_HIP(hipMemcpyAsync(out_h, d_h.p, rows * 8, hipMemcpyDeviceToHost, st));
+    MRK_HIP(hipStreamSynchronize(st));
+    drain_profile_events(ctx);
+  });
+}
+
+int mrk_train_bins(const char *config_json, const double *column, int64_t n, double *out_bounds, int cap, int *n_bounds) {
+  return guard([&] {
+    need(config_json != nullptr, "null config");
+    const TrainConfig cfg = train_parse_config(config_json, strlen(config_json));
+    need(n_bounds != nullptr, "n_bounds is null");
+    need(n >= 0 && (column != nullptr || n == 0), "train: null column");
+    const std::vector<double> b = train_bin_bounds(column, n, 1, cfg.max_bin);
+    *n_bounds = (int)b.size();
+    if (out_bounds && cap >= (int)b.size() && !b.empty()) memcpy(out_bounds, b.data(), b.size() * 8);
+  });
+}
+
+}  // extern "C"

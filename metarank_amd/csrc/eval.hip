@@ -12,13 +12,14 @@
 // fused.  A group's values go to its own index: nothing depends on which kernel or workgroup took it, and no float atomics.
 //   n <= 64                  eval_wave_kernel: one wavefront per group, one lane per item, four groups per workgroup.  No sort
 //                            network: a lane's rank is the number of pairs that are pair_lt its own.
-//   n <= SORT_MAX_ITEMS      eval_group_kernel: one workgroup per group, the LDS bitonic of trending.hip on (key, u16 index),
+//   n <= SORT_MAX_ITEMS      eval_group_kernel: one workgroup per group, the LDS bitonic of bitonic_device.hpp on (key, u16 index),
 //                            padded to the next power of two >= n.  44.5 KiB of LDS.
 //   beyond                   bigsort.hip's sample sort for both orders, a gather kernel for step 2, one wavefront for step 4.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
+#include "bitonic_device.hpp"
 #include "eval.hpp"
 #include "eval_host.hpp"
 #include "rank.hpp"
@@ -137,32 +138,6 @@ eval_wave_kernel(EvalDev d, const int *__restrict__ groups, int count) {
   wave_lds_sync();
   for (int m = lane; m < d.n_metrics; m += 64)
     d.out[(long long)m * d.n_groups + g] = metric_value(d.metrics[m], d.cutoffs[m], n, s_t[wave], s_it[wave], &s_rel[wave], d.nolabels);
-}
-
-// the bitonic network of trending_order_kernel over s_key[0, p2) (and, IDX, the indices beside them); the caller has synchronised
-template <bool IDX>
-__device__ void lds_bitonic(u64 *s_key, unsigned short *s_idx, int p2) {
-  const int tid = threadIdx.x, T = blockDim.x;
-  for (int k = 2; k <= p2; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = tid; i < p2; i += T) {
-        const int p = i ^ j;
-        if (p > i) {
-          const u64 ka = s_key[i], kb = s_key[p];
-          const int ia = IDX ? s_idx[i] : 0, ib = IDX ? s_idx[p] : 0;
-          const bool up = (i & k) == 0;
-          if (up ? pair_lt(kb, ib, ka, ia) : pair_lt(ka, ia, kb, ib)) {
-            s_key[i] = kb;
-            s_key[p] = ka;
-            if (IDX) {
-              s_idx[i] = (unsigned short)ib;
-              s_idx[p] = (unsigned short)ia;
-            }
-          }
-        }
-      }
-      __syncthreads();
-    }
 }
 
 // blockDim.x: a multiple of 64 up to 1024

@@ -1,0 +1,84 @@
+// Device half of the LambdaMART fit (train.hip), driven by capi_train.cpp.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+struct mrk_ctx;
+
+namespace mrk {
+
+constexpr int TRAIN_BIN_ROWS = 256;     // rows per workgroup of the binning kernel (one lane per row)
+constexpr int TRAIN_HIST_ROWS = 2048;   // rows per workgroup of the histogram kernel (256 lanes x 8 rows)
+constexpr int TRAIN_HIST_FEATS = 4;     // columns per workgroup of the histogram kernel: 4 LDS histograms of 256 x (i64, i64, u32) = 20 KiB
+constexpr int TRAIN_ROW_THREADS = 256;  // lanes per workgroup of the row-parallel kernels (max, quantise, split, apply)
+
+// what the LambdaRank kernels read and write, in device memory for the whole launch
+struct GradDev {
+  const double *scores;        // per row
+  const uint8_t *labels;       // per row: 0 ... 30
+  const long long *offsets;    // n_groups + 1
+  const double *lg, *invlg;    // log2(i + 2) and 1 / log2(i + 2), up to the longest group (made on the host)
+  const double *sigmoid;       // MRK_TRAIN_SIGMOID_BINS entries (made on the host)
+  double lo, f;                // the table's index: clamp((delta - lo) * f)
+  double sigma, sigma2;
+  int truncation;
+  double *g, *h;               // per row
+};
+// groups[0, count): groups of <= 64 rows, one wavefront each
+void train_launch_grad_wave(mrk_ctx *ctx, hipStream_t s, const GradDev &d, const int *groups, int count);
+// groups[0, count): groups of <= TRAIN_MAX_GROUP rows (the longest has max_len), one workgroup each
+void train_launch_grad_group(mrk_ctx *ctx, hipStream_t s, const GradDev &d, const int *groups, int count, int max_len);
+
+// a piece of the row-major matrix into the column-major byte matrix: bins[c * rows + row0 + i] = the number of bounds of column c
+// below x[i * cols + c], or 255 for NaN.  bounds of column c: bounds[bound_off[c] ... bound_off[c + 1])
+void train_launch_bin(mrk_ctx *ctx, hipStream_t s, const double *x, int piece_rows, int cols, const double *bounds, const int *bound_off, uint8_t *bins,
+                      long long rows, long long row0);
+
+// maxes[0] = max |g| and maxes[1] = max h as bit patterns (both >= 0: the integer order is the order of the values); the caller zeroes them
+void train_launch_max(mrk_ctx *ctx, hipStream_t s, const double *g, const double *h, long long rows, unsigned long long *maxes);
+// q = (int64) rint(ldexp(v, e)); leaf_of = 0
+void train_launch_quantise(mrk_ctx *ctx, hipStream_t s, const double *g, const double *h, long long rows, int e_g, int e_h, long long *qg, long long *qh,
+                           uint16_t *leaf_of);
+
+// a (leaf, subset column, bin) histogram: G and H int64, C uint32, each [leaf][n_sub][256]
+struct HistDev {
+  long long *G, *H;
+  unsigned *C;
+  int n_sub;
+};
+// zeroes slot `slot` and adds the rows of `leaf` to it
+void train_launch_hist(mrk_ctx *ctx, hipStream_t s, const uint8_t *bins, long long rows, const uint16_t *leaf_of, int leaf, int slot, const long long *qg,
+                       const long long *qh, const int *subset, const HistDev &hd);
+
+// the best admitted candidate of a leaf (valid == 0: none) and the leaf's totals
+struct LeafRec {
+  double gain;
+  int valid, col, bin, nan_left;
+  long long gl, hl, cl;        // the left side's sums
+  long long g, h, c;           // the leaf's
+};
+struct ScanParams {
+  int e_g, e_h;
+  int min_data;
+  double min_hess, l2;
+};
+// leaf_b < 0: scans leaf_a alone (the root).  Else slot leaf_b holds the histogram of the smaller child of a split and slot leaf_a its
+// parent's: first leaves both slots with their own leaf's (sibling = parent - small; leaf_a is the left child), then scans both.
+// feat_best: scratch of 2 * n_sub records; out: 2 records (leaf_a, leaf_b)
+void train_launch_scan(mrk_ctx *ctx, hipStream_t s, const HistDev &hd, const int *subset, const int *nbins, int leaf_a, int leaf_b, bool small_is_left,
+                       const ScanParams &p, LeafRec *feat_best, LeafRec *out);
+
+// rows of `leaf` whose bin of column `col` goes right move to leaf `fresh`
+void train_launch_split(mrk_ctx *ctx, hipStream_t s, const uint8_t *col_bins, long long rows, uint16_t *leaf_of, int leaf, int fresh, int bin, int nan_left);
+
+// a finished tree on the device: per internal node (column, bin, nan_left, left, right), children as in the model text (~leaf)
+struct TreeDev {
+  const int *col, *bin, *nan_left, *left, *right;
+  const double *leaf_value;
+};
+// scores[row] += leaf_value[leaf]: leaf_of given (the training rows) or found by walking the tree over the rows' bins (validation)
+void train_launch_apply(mrk_ctx *ctx, hipStream_t s, const TreeDev &t, const uint16_t *leaf_of, const uint8_t *bins, long long rows, double *scores);
+
+}  // namespace mrk

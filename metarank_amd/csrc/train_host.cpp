@@ -1,0 +1,260 @@
+// Host half of the LambdaMART fit: see train_host.hpp.
+#include "train_host.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+
+#include "json.hpp"
+
+namespace mrk {
+
+TrainConfig train_parse_config(const char *text, size_t len) {
+  auto bad = [](const std::string &m) -> void { throw StatusError(MRK_ERR_PARSE, "train config: " + m); };
+  auto range = [](const std::string &m) -> void { throw StatusError(MRK_ERR_INVALID_ARG, "train config: " + m); };
+  json::Value root;
+  try {
+    root = json::parse(text, len);
+  } catch (const std::exception &e) {
+    bad(e.what());
+  }
+  if (!root.is_object()) bad("not an object");
+  TrainConfig c;
+  static const char *known[] = {"iterations", "learningRate", "ndcgCutoff", "maxDepth", "seed", "numLeaves", "sampling", "debias", "max_bin", "truncation",
+                                "sigma", "min_data_in_leaf", "min_sum_hessian", "lambda_l2", "early_stopping"};
+  for (auto &kv : root.obj) {
+    bool ok = false;
+    for (const char *k : known) ok = ok || kv.first == k;
+    if (!ok) bad("unknown key '" + kv.first + "'");
+  }
+  auto integer = [&](const char *key, int &out) {
+    const json::Value *v = root.find(key);
+    if (!v || v->is_null()) return;   // Option[Int]: the default stays
+    if (!v->is_number()) bad(std::string("'") + key + "' is not a number");
+    const double d = v->as_double();
+    if (!(d == std::floor(d)) || d < -2147483648.0 || d > 2147483647.0) bad(std::string("'") + key + "' is not an Int");
+    out = (int)d;
+  };
+  auto real = [&](const char *key, double &out) {
+    const json::Value *v = root.find(key);
+    if (!v || v->is_null()) return;
+    if (!v->is_number()) bad(std::string("'") + key + "' is not a number");
+    out = v->as_double();
+  };
+  integer("iterations", c.iterations);
+  real("learningRate", c.learning_rate);
+  integer("ndcgCutoff", c.ndcg_cutoff);
+  integer("maxDepth", c.max_depth);
+  integer("seed", c.seed);
+  integer("numLeaves", c.num_leaves);
+  real("sampling", c.sampling);
+  if (const json::Value *v = root.find("debias"))
+    if (!v->is_null()) {
+      if (v->type != json::Type::Bool) bad("'debias' is not a Boolean");
+      c.debias = v->b;
+    }
+  integer("max_bin", c.max_bin);
+  integer("truncation", c.truncation);
+  real("sigma", c.sigma);
+  integer("min_data_in_leaf", c.min_data_in_leaf);
+  real("min_sum_hessian", c.min_sum_hessian);
+  real("lambda_l2", c.lambda_l2);
+  integer("early_stopping", c.early_stopping);
+  auto at_least = [&](const char *key, int v, int lo) {
+    if (v < lo) range(std::string(key) + " = " + std::to_string(v) + " (at least " + std::to_string(lo) + ")");
+  };
+  at_least("iterations", c.iterations, 1);
+  at_least("ndcgCutoff", c.ndcg_cutoff, 1);
+  at_least("maxDepth", c.max_depth, 1);
+  at_least("numLeaves", c.num_leaves, 2);
+  at_least("max_bin", c.max_bin, 2);
+  if (c.max_bin > 255) range("max_bin = " + std::to_string(c.max_bin) + " (at most 255: a bin is a byte and 255 is NaN's)");
+  at_least("truncation", c.truncation, 1);
+  at_least("min_data_in_leaf", c.min_data_in_leaf, 1);
+  at_least("early_stopping", c.early_stopping, 1);
+  if (!(c.learning_rate > 0.0) || !std::isfinite(c.learning_rate)) range("learningRate is not a positive number");
+  if (!(c.sampling > 0.0 && c.sampling <= 1.0)) range("sampling is not in (0, 1]");
+  if (!(c.sigma > 0.0) || !std::isfinite(c.sigma)) range("sigma is not a positive number");
+  if (!(c.min_sum_hessian >= 0.0) || !std::isfinite(c.min_sum_hessian)) range("min_sum_hessian is negative");
+  if (!(c.lambda_l2 >= 0.0) || !std::isfinite(c.lambda_l2)) range("lambda_l2 is negative");
+  if (c.debias) throw StatusError(MRK_ERR_UNSUPPORTED, "train config: debias (position-bias correction) is not built");
+  if (c.num_leaves > TRAIN_MAX_LEAVES)
+    throw StatusError(MRK_ERR_UNSUPPORTED, "train config: numLeaves = " + std::to_string(c.num_leaves) + " (limit " + std::to_string(TRAIN_MAX_LEAVES) + ")");
+  return c;
+}
+
+static std::string g17(double x) {
+  char buf[40];
+  snprintf(buf, sizeof buf, "%.17g", x);
+  return buf;
+}
+
+std::vector<double> train_bin_bounds(const double *col, int64_t n, int64_t stride, int max_bin, std::string *info) {
+  std::vector<double> v;
+  v.reserve((size_t)std::max<int64_t>(n, 0));
+  for (int64_t i = 0; i < n; ++i) {
+    double x = col[i * stride];
+    if (x != x) continue;
+    if (std::isinf(x)) throw StatusError(MRK_ERR_INVALID_ARG, "train: cell " + std::to_string(i) + " of a column is infinite");
+    if (x == 0.0) x = 0.0;   // -0.0 and +0.0 are one value
+    v.push_back(x);
+  }
+  std::sort(v.begin(), v.end());
+  const int64_t m = (int64_t)v.size();
+  if (info) *info = m == 0 || v.front() == v.back() ? "none" : "[" + g17(v.front()) + ":" + g17(v.back()) + "]";
+  std::vector<double> out;
+  if (m == 0) return out;
+  std::vector<int64_t> change;   // p: v[p] != v[p - 1]
+  for (int64_t p = 1; p < m; ++p)
+    if (v[(size_t)p] != v[(size_t)p - 1]) change.push_back(p);
+  std::vector<int64_t> cuts;
+  if ((int64_t)change.size() + 1 <= max_bin - 1) cuts = change;
+  else
+    for (int64_t i = 1; i <= max_bin - 2; ++i) {
+      auto it = std::lower_bound(change.begin(), change.end(), i * m / (max_bin - 1));
+      if (it == change.end()) break;
+      if (cuts.empty() || cuts.back() != *it) cuts.push_back(*it);
+    }
+  for (int64_t p : cuts) {
+    const double a = v[(size_t)p - 1], b = v[(size_t)p];
+    double mid = (a + b) / 2.0;
+    if (!(mid < b)) mid = a;   // (also a sum that overflowed)
+    out.push_back(mid);
+  }
+  return out;
+}
+
+static uint64_t splitmix64(uint64_t &state) {
+  state += 0x9E3779B97F4A7C15ull;
+  uint64_t z = state;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
+std::vector<int32_t> train_feature_subset(int cols, double sampling, int seed, int tree) {
+  const int k = std::min(cols, std::max(1, (int)std::floor((double)cols * sampling + 0.5)));
+  uint64_t state = ((uint64_t)(uint32_t)seed << 32) | (uint64_t)(uint32_t)tree;
+  std::vector<int32_t> idx((size_t)cols);
+  for (int i = 0; i < cols; ++i) idx[(size_t)i] = i;
+  for (int j = 0; j < k; ++j) {
+    const int r = j + (int)(splitmix64(state) % (uint64_t)(cols - j));
+    std::swap(idx[(size_t)j], idx[(size_t)r]);
+  }
+  idx.resize((size_t)k);
+  std::sort(idx.begin(), idx.end());
+  return idx;
+}
+
+SigmoidTable train_sigmoid_table(double sigma) {
+  SigmoidTable s;
+  s.lo = -25.0 / sigma;
+  s.f = (double)TRAIN_SIGMOID_BINS / (50.0 / sigma);
+  s.t.resize(TRAIN_SIGMOID_BINS);
+  for (int t = 0; t < TRAIN_SIGMOID_BINS; ++t) {
+    const double x = s.lo + (double)t / s.f;
+    const double z = sigma * x;
+    s.t[(size_t)t] = 1.0 / (1.0 + std::exp(z));
+  }
+  return s;
+}
+
+int train_exponent(double vmax, int64_t rows) {
+  if (vmax == 0.0) return 0;
+  int bitlen = 0;
+  for (uint64_t r = (uint64_t)rows; r; r >>= 1) ++bitlen;
+  int e = 0;
+  std::frexp(vmax, &e);
+  return 61 - bitlen - e;
+}
+
+std::vector<uint8_t> train_check_labels(const double *labels, int64_t rows) {
+  if (!labels) throw StatusError(MRK_ERR_INVALID_ARG, "train: null labels");
+  std::vector<uint8_t> out((size_t)rows);
+  for (int64_t i = 0; i < rows; ++i) {
+    const double y = labels[i];
+    if (!(y >= 0.0 && y <= (double)TRAIN_MAX_LABEL) || y != std::floor(y))
+      throw StatusError(MRK_ERR_INVALID_ARG, "train: label " + std::to_string(i) + " is " + g17(y) + ", not an integer in 0 ... " + std::to_string(TRAIN_MAX_LABEL));
+    out[(size_t)i] = (uint8_t)y;
+  }
+  return out;
+}
+
+int TrainTree::split(int leaf, int col, int b, double thr_, bool nan_left, double gain_) {
+  const int s = (int)feat.size(), fresh = s + 1;
+  feat.push_back(col);
+  bin.push_back(b);
+  gain.push_back(gain_);
+  thr.push_back(thr_);
+  dt.push_back(8 | (nan_left ? 2 : 0));
+  left.push_back(~leaf);
+  right.push_back(~fresh);
+  if (parent_node[(size_t)leaf] >= 0) (parent_side[(size_t)leaf] == 0 ? left : right)[(size_t)parent_node[(size_t)leaf]] = s;
+  parent_node[(size_t)leaf] = s;
+  parent_side[(size_t)leaf] = 0;
+  parent_node.push_back(s);
+  parent_side.push_back(1);
+  depth[(size_t)leaf] += 1;
+  depth.push_back(depth[(size_t)leaf]);
+  return fresh;
+}
+
+double train_leaf_output(const TrainSums &q, int e_g, int e_h, double l2, double lr, double *weight) {
+  const double G = std::ldexp((double)q.g, -e_g), H = std::ldexp((double)q.h, -e_h);
+  if (weight) *weight = H;
+  const double d = H + l2;
+  const double v = -G / d;
+  return v * lr;
+}
+
+std::string train_write_model(const std::vector<TrainTree> &trees, size_t n_trees, int cols, const std::vector<std::string> &infos, double lr) {
+  auto ints = [](std::string &o, const char *key, const auto &a, size_t n) {
+    o += key;
+    for (size_t i = 0; i < n; ++i) o += (i ? " " : "") + std::to_string((long long)a[i]);
+    o += "\n";
+  };
+  auto f64s = [](std::string &o, const char *key, const std::vector<double> &a, size_t n) {
+    o += key;
+    for (size_t i = 0; i < n; ++i) o += (i ? " " : "") + g17(a[i]);
+    o += "\n";
+  };
+  std::vector<std::string> blocks;
+  for (size_t i = 0; i < n_trees; ++i) {
+    const TrainTree &t = trees[i];
+    const size_t nl = (size_t)t.num_leaves(), nn = nl - 1;
+    std::string b = "Tree=" + std::to_string(i) + "\nnum_leaves=" + std::to_string(nl) + "\nnum_cat=0\n";
+    ints(b, "split_feature=", t.feat, nn);
+    b += "split_gain=";
+    for (size_t k = 0; k < nn; ++k) {
+      char buf[40];
+      snprintf(buf, sizeof buf, "%.9g", (double)(float)t.gain[k]);
+      b += (k ? " " : "") + std::string(buf);
+    }
+    b += "\n";
+    f64s(b, "threshold=", t.thr, nn);
+    ints(b, "decision_type=", t.dt, nn);
+    ints(b, "left_child=", t.left, nn);
+    ints(b, "right_child=", t.right, nn);
+    f64s(b, "leaf_value=", t.value, nl);
+    f64s(b, "leaf_weight=", t.weight, nl);
+    ints(b, "leaf_count=", t.count, nl);
+    f64s(b, "internal_value=", t.ivalue, nn);
+    f64s(b, "internal_weight=", t.iweight, nn);
+    ints(b, "internal_count=", t.icount, nn);
+    b += "is_linear=0\nshrinkage=" + g17(lr);
+    blocks.push_back(std::move(b));
+  }
+  std::string o = "tree\nversion=v4\nnum_class=1\nnum_tree_per_iteration=1\nlabel_index=0\nmax_feature_idx=" + std::to_string(cols - 1) + "\nobjective=lambdarank\nfeature_names=";
+  for (int c = 0; c < cols; ++c) o += (c ? " Column_" : "Column_") + std::to_string(c);
+  o += "\nfeature_infos=";
+  for (int c = 0; c < cols; ++c) o += (c ? " " : "") + infos[(size_t)c];
+  o += "\ntree_sizes=";
+  for (size_t i = 0; i < blocks.size(); ++i) o += (i ? " " : "") + std::to_string(blocks[i].size() + 3);
+  o += "\n\n";
+  for (auto &b : blocks) o += b + "\n\n\n";
+  o += "end of trees\n\nfeature_importances:\n\nparameters:\n[boosting: gbdt]\n[objective: lambdarank]\n\nend of parameters\n\npandas_categorical:null\n";
+  return o;
+}
+
+}  // namespace mrk

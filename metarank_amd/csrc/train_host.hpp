@@ -1,0 +1,85 @@
+// Host half of the LambdaMART fit (capi_train.cpp; the algorithm: include/mrk.h): config, bins, feature subsets, the
+// sigmoid table, the quantisation exponents, the tree book-keeping and the model text.  No HIP in here:
+// tests/native/train_host_test.cpp compiles this file with g++ alone.
+// Reference: LambdaMARTPredictor.makeBooster (ml/rank/LambdaMARTRanker.scala:161-190), LightGBMConfig (config/BoosterConfig.scala:19-28).
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "status.hpp"
+
+namespace mrk {
+
+constexpr int TRAIN_SIGMOID_BINS = MRK_TRAIN_SIGMOID_BINS;
+constexpr int TRAIN_NAN_BIN = 255;          // the bin of a NaN cell; a column has at most 254 others
+constexpr int TRAIN_MAX_GROUP = 4096;       // rows of one group (one workgroup orders it: EVAL_GROUP_ITEMS)
+constexpr int TRAIN_MAX_COLS = 65535;
+constexpr int TRAIN_MAX_LEAVES = 4096;
+constexpr int TRAIN_MAX_LABEL = 30;
+
+struct TrainConfig {
+  int iterations = 100;
+  double learning_rate = 0.1;
+  int ndcg_cutoff = 10;
+  int max_depth = 8;
+  int seed = 0;
+  int num_leaves = 16;
+  double sampling = 0.8;
+  bool debias = false;
+  int max_bin = 255;
+  int truncation = 30;
+  double sigma = 1.0;
+  int min_data_in_leaf = 20;
+  double min_sum_hessian = 1e-3;
+  double lambda_l2 = 0.0;
+  int early_stopping = 20;
+};
+// malformed JSON, a value of the wrong type or an unknown key: MRK_ERR_PARSE; a value out of range: MRK_ERR_INVALID_ARG;
+// debias = true or numLeaves > TRAIN_MAX_LEAVES: MRK_ERR_UNSUPPORTED
+TrainConfig train_parse_config(const char *json, size_t len);
+
+// the upper bounds of the bins of one column but the last (bin(x) = the number of bounds < x), from col[i * stride], i < n.
+// An infinite cell: MRK_ERR_INVALID_ARG.  info: LightGBM's feature_infos entry ("none" or "[min:max]").
+std::vector<double> train_bin_bounds(const double *col, int64_t n, int64_t stride, int max_bin, std::string *info = nullptr);
+
+// the columns of tree `tree`, ascending
+std::vector<int32_t> train_feature_subset(int cols, double sampling, int seed, int tree);
+
+struct SigmoidTable {
+  double lo, f;
+  std::vector<double> t;
+};
+SigmoidTable train_sigmoid_table(double sigma);
+
+// 61 - bitlen(rows) - E(vmax), frexp(vmax) = m * 2^E; 0 for vmax == 0
+int train_exponent(double vmax, int64_t rows);
+
+// integers 0 ... TRAIN_MAX_LABEL or MRK_ERR_INVALID_ARG
+std::vector<uint8_t> train_check_labels(const double *labels, int64_t rows);
+
+struct TrainSums {
+  int64_t g = 0, h = 0;
+  int64_t c = 0;
+};
+
+// one tree in LightGBM's numbering: the s-th split makes internal node s, its left child keeps the leaf index, its right child is leaf s + 1
+struct TrainTree {
+  std::vector<int32_t> feat, bin, dt, left, right;
+  std::vector<double> gain, thr, ivalue, iweight;
+  std::vector<int64_t> icount;
+  std::vector<int32_t> parent_node, parent_side, depth;   // per leaf
+  std::vector<double> value, weight;                      // per leaf
+  std::vector<int64_t> count;
+  TrainTree() : parent_node{-1}, parent_side{0}, depth{0} {}
+  int num_leaves() const { return (int)feat.size() + 1; }
+  int split(int leaf, int col, int b, double thr_, bool nan_left, double gain_);   // -> the new leaf
+};
+
+// -G / (H + l2) * lr of quantised sums; *weight: H
+double train_leaf_output(const TrainSums &q, int e_g, int e_h, double l2, double lr, double *weight);
+
+std::string train_write_model(const std::vector<TrainTree> &trees, size_t n_trees, int cols, const std::vector<std::string> &infos, double lr);
+
+}  // namespace mrk

@@ -1,0 +1,101 @@
+"""Micro-benchmark of the LambdaMART fit on the device (mrk_train_*, csrc/train.hip): 100 000 groups of 10 ... 100 rows x 24 columns
+(workloads/synth.py synthetic_ranking_rows: standard normal cells, 5 % NaN in four columns, labels 0 ... 4 that follow three columns
+plus noise), 100 iterations of 16 leaves.
+Deterministic seed.
+
+Reported: the host clock around mrk_train_set (bins on the host, upload in pieces, the binning kernel) and around mrk_train_fit, and
+inside them the HIP-event phases of mrk_profile_get - train_bin, train_grad (LambdaRank, max, quantise), train_hist, train_scan
+(scan + pick), train_apply (leaf_of and score updates), train_eval (with --valid) -; what the fit's host clock holds beyond its
+device phases, per scan (the record read back after every split is a stream synchronisation: this is its price together with the
+host's book-keeping); the restatement (tests/train_reference.py) for ONE iteration on the first --ref-groups groups of the same data on
+this host; and, if sklearn is importable, HistGradientBoostingRegressor's time per tree on the same matrix (a regressor on the labels:
+context only, another objective).  No threshold: nothing was measured before this tool existed.
+  python tools/train_bench.py [--json] [--groups N] [--min-items N] [--max-items N] [--iterations N] [--leaves N] [--ref-groups N] [--valid]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+sys.path.insert(0, os.path.join(REPO, "tests"))
+import metarank_amd as M  # noqa: E402
+from metarank_amd import _native as N  # noqa: E402
+from metarank_amd.train import Trainer  # noqa: E402
+import train_reference as T  # noqa: E402
+from workloads import synth  # noqa: E402
+
+TIMERS = ("train_bin", "train_grad", "train_hist", "train_scan", "train_apply", "train_eval")
+COLS = 24
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--json", action="store_true")
+    ap.add_argument("--groups", type=int, default=100_000)
+    ap.add_argument("--min-items", type=int, default=10)
+    ap.add_argument("--max-items", type=int, default=100)
+    ap.add_argument("--iterations", type=int, default=100)
+    ap.add_argument("--leaves", type=int, default=16)
+    ap.add_argument("--ref-groups", type=int, default=2000, help="groups of the restatement's one iteration (0: skip it)")
+    ap.add_argument("--valid", action="store_true", help="a validation set of a tenth of the groups (early stopping stays out of reach)")
+    a = ap.parse_args()
+    ctx = M.Context(0)
+    X, y, off = synth.synthetic_ranking_rows(a.groups, a.min_items, a.max_items, COLS, seed=0)
+    rows = int(off[-1])
+    cfg = {"iterations": a.iterations, "numLeaves": a.leaves, "early_stopping": a.iterations}
+    out = {"groups": a.groups, "rows": rows, "items_per_group": [a.min_items, a.max_items], "columns": COLS, "iterations": a.iterations, "leaves": a.leaves,
+           "build": N.lib().mrk_build_id().decode()}
+
+    ctx.profile_enable(True)
+    t = Trainer(cfg, ctx)
+    t0 = time.perf_counter()
+    t.set(0, X, y, off)
+    if a.valid:
+        t.set(1, *synth.synthetic_ranking_rows(max(a.groups // 10, 1), a.min_items, a.max_items, COLS, seed=1))
+    out["set_call_ms"] = (time.perf_counter() - t0) * 1e3
+    t0 = time.perf_counter()
+    t.fit()
+    out["fit_call_ms"] = (time.perf_counter() - t0) * 1e3
+    parts = {name: ctx.profile_get(name) for name in TIMERS}
+    ctx.profile_enable(False)
+    hist = t.history()
+    model = t.model()
+    t.close()
+    for name in TIMERS:
+        out[name + "_ms"], out[name + "_launches"] = parts[name]
+    out["trees"] = hist["iterations_run"]
+    out["splits"] = sum(len(b.split("split_feature=")[1].split("\n")[0].split()) for b in model.decode().split("Tree=")[1:])
+    scans = parts["train_scan"][1]                                        # (one timer spans a scan and its pick)
+    device_ms = sum(parts[name][0] for name in TIMERS if name != "train_bin")
+    out["fit_device_phases_ms"] = device_ms
+    out["fit_host_and_sync_ms_per_scan"] = (out["fit_call_ms"] - device_ms) / max(scans, 1)
+    out["fit_ms_per_tree"] = out["fit_call_ms"] / max(hist["iterations_run"], 1)
+
+    if a.ref_groups > 0:
+        g = min(a.ref_groups, a.groups)
+        r = int(off[g])
+        t0 = time.perf_counter()
+        T.fit(X[:r], y[:r], off[:g + 1], cfg={"iterations": 1, "numLeaves": a.leaves})
+        out["restatement_one_iteration_ms"] = (time.perf_counter() - t0) * 1e3
+        out["restatement_rows"] = r
+        out["restatement_us_per_row_iteration"] = out["restatement_one_iteration_ms"] * 1e3 / r
+        out["device_us_per_row_iteration"] = out["fit_call_ms"] * 1e3 / (rows * max(hist["iterations_run"], 1))
+    try:
+        from sklearn.ensemble import HistGradientBoostingRegressor
+    except ImportError:
+        out["sklearn"] = None
+    else:
+        trees = 10
+        t0 = time.perf_counter()
+        HistGradientBoostingRegressor(max_iter=trees, max_leaf_nodes=a.leaves, early_stopping=False).fit(X, y)
+        out["sklearn_hist_gbr_ms_per_tree"] = (time.perf_counter() - t0) * 1e3 / trees
+    ctx.close()
+    print(json.dumps(out) if a.json else json.dumps(out, indent=1))
+
+
+if __name__ == "__main__":
+    main()
