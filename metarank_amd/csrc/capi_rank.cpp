@@ -945,6 +945,34 @@ int mrk_debug_store_info(mrk_ctx *ctx, int scope, int64_t *out) {
   });
 }
 
+/* not part of include/mrk.h: the pre-pass hash tables of a loaded batch as the host sized them - out3 = {fused_entries (the
+ * largest request's table entries: what the fused launch's LDS is sized by), requests, tables per request}; caps (n_caps >=
+ * requests x tables, or NULL) receives every request's per-table capacity in entries, request-major (tests, measurement notes) */
+int mrk_debug_batch_tables(mrk_batch *b, int64_t *out3, uint32_t *caps, int64_t n_caps) {
+  return guard([&] {
+    if (!b || !b->prog || !out3) throw StatusError(MRK_ERR_INVALID_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(b->bmu);
+    const size_t n_prep = b->prog->prep.size(), n = (size_t)b->n_req * n_prep;
+    out3[0] = b->fused_entries; out3[1] = b->n_req; out3[2] = (int64_t)n_prep;
+    if (!caps) return;
+    if (n_caps < (int64_t)n || b->hb.prep_out.size() < n) throw StatusError(MRK_ERR_INVALID_ARG, "caps is too short");
+    for (size_t i = 0; i < n; ++i) caps[i] = b->hb.prep_out[i].tab_cap;
+  });
+}
+
+/* not part of include/mrk.h: the distinct tokens ever stored in one ITEM-scope column (Column::distinct: the bound of
+ * features.cpp table_capacity), -1 = no such column */
+int mrk_debug_column_distinct(mrk_ctx *ctx, const char *column, int64_t *out) {
+  return guard([&] {
+    Store &st = store_of(ctx);
+    if (!column || !out) throw StatusError(MRK_ERR_INVALID_ARG, "null argument");
+    std::shared_lock<std::shared_mutex> lk(ctx->store_mu);
+    const Table &t = st.tables[SC_ITEM];
+    auto it = t.col_of.find(column);
+    *out = it == t.col_of.end() ? -1 : (int64_t)t.cols[(size_t)it->second].distinct;
+  });
+}
+
 int mrk_store_flush(mrk_ctx *ctx) {
   return guard([&] {
     Store &st = store_of(ctx);

@@ -952,8 +952,11 @@ double map_datetime(int mapper, const Civil &c) {
   }
 }
 
-// open-addressing capacity for a table that receives `tokens` insertions (distinct keys <= tokens): load factor
-// <= 0.75 in the worst case, usually far lower (tokens repeat).  The tables of a request live in LDS and their
+// open-addressing capacity for a table that can hold at most `tokens` distinct keys: load factor <= 0.75.  The callers
+// pass min(insertions of this request, twice the distinct tokens the column ever held - store.hpp Column::distinct): a table
+// holds DISTINCT tokens, and a 100-click session that inserts 300 genre tokens from a vocabulary of 20 gets 56 entries, not 402
+// (round 18: the launch's LDS is the largest request's, so that one session cost every workgroup of the batch 3 KB and
+// the CU its eighth workgroup).  The tables of a request live in LDS and their
 // size sets how many requests a CU works on at once; measured on the Ranklens workload (MRK_TABLE_LOAD_PCT
 // sweep): 75 % -> 0.42 ms per 3840 requests, 50 % -> 0.45, 33 % -> 0.52, 25 % -> 0.60: shorter probe chains do
 // not pay for the lost occupancy.  Even => the 8-byte entries of consecutive tables stay 16-byte aligned.
@@ -1140,6 +1143,11 @@ void resolve_requests(const Program &prog, Store &store, const mrk_request *reqs
   }
   const Table &item_table = store.tables[SC_ITEM];
   auto col_max_len = [&](ColRef c) -> uint64_t { return c.tag >= 0 && c.tag < (int)item_table.cols.size() ? item_table.cols[(size_t)c.tag].max_len : 0u; };
+  // TWICE the distinct tokens the column ever held (Column::distinct: what a table keyed by them can hold at most).  Twice: a
+  // table bounded by its vocabulary really fills up, and at load 0.75 its lookups walk further than those of the same table at
+  // the 5 % load it used to have; such tables are tens of entries, and half the load measured +0.6 % on c2 and gave c4 (no LDS
+  // pressure there, only the longer walks) its 0.8 % back (LOG.md round 18)
+  auto vocab_bound = [&](ColRef c) -> uint64_t { return c.tag >= 0 && c.tag < (int)item_table.cols.size() ? 2ull * item_table.cols[(size_t)c.tag].distinct : 0u; };
   struct Worker { std::vector<Override> overrides; int max_items = 0, max_doubles = 0; std::vector<double> enc; };
   std::vector<Worker> workers((size_t)std::max(1, n_workers));
   std::vector<uint64_t> req_entries((size_t)n_req, 0);  // hash-table entries of every request (its tables are contiguous)
@@ -1321,7 +1329,7 @@ void resolve_requests(const Program &prog, Store &store, const mrk_request *reqs
             }
           }
           PrepOut &po = hb.prep_out[(size_t)r * prog.prep.size() + ho.prep_base + fi];
-          const uint32_t cap = table_capacity(count, load_pct);
+          const uint32_t cap = table_capacity(std::min(count, vocab_bound(pe.item_col)), load_pct);
           po.tab_off = (uint32_t)arena;
           po.tab_cap = cap;
           arena += cap;
@@ -1378,7 +1386,7 @@ void resolve_requests(const Program &prog, Store &store, const mrk_request *reqs
           doubles = 0;
         }
         wk.max_doubles = std::max(wk.max_doubles, doubles);
-        const uint32_t cap = table_capacity(tokens, load_pct);
+        const uint32_t cap = table_capacity(std::min(tokens, vocab_bound(pe.item_col)), load_pct);
         po.tab_off = (uint32_t)arena;
         po.tab_cap = cap;
         arena += cap;

@@ -247,6 +247,7 @@ bool Store::put_string(const KeyRef &k, std::string_view v) {
   drop_value(c);
   set_tag(c, TAG_STRING);
   c.c->max_len = std::max<uint32_t>(c.c->max_len, 1u);
+  c.c->note_token(tok);
   uint64_t cell = (uint64_t)tok | ((uint64_t)link << 32);
   set_val(c, 0, cell);
   return true;
@@ -324,6 +325,7 @@ void Store::put_tokens(Cell &c, const uint32_t *toks, uint32_t n) {
   }
   set_tag(c, TAG_STRING_LIST);
   c.c->max_len = std::max<uint32_t>(c.c->max_len, n);
+  for (uint32_t i = 0; i < n; ++i) c.c->note_token(toks[i]);
   const uint64_t cell = (uint64_t)off | ((uint64_t)n << 32);
   set_val(c, 0, cell);
 }

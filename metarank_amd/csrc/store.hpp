@@ -17,6 +17,7 @@
 // item-field-scoped `rate` (item -> "field=<name>:<value>") is resolved at put time into a direct
 // slot reference.
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <climits>
 #include <cstring>
@@ -57,6 +58,21 @@ struct Column {
   // the longest string list ever put into this column (an SString counts 1): upper bound used to size the pre-pass
   // hash tables of a request without reading item records on the host (features.cpp resolve_requests)
   uint32_t max_len = 0;
+  // the number of DISTINCT tokens ever stored in this column (a bitset over the store's interned token ids + a counter; it
+  // never goes down: overwritten and erased values stay counted).  A pre-pass table keyed by this column's tokens can never
+  // hold more keys than this, however many tokens a request inserts (features.cpp table_capacity).  Kept where max_len is
+  // kept - Store::put_string and Store::put_tokens, the only two writers of TAG_STRING / TAG_STRING_LIST cells: the binary
+  // loader (codec.cpp) and the C ABI come through them, append / increment / put_bounded_list write no string cell,
+  // clone_items copies records (tokens already counted) and a request's per-item fields never reach a table.
+  uint32_t distinct = 0;
+  std::vector<uint64_t> seen_tokens;
+  void note_token(uint32_t tok) {
+    const size_t w = tok >> 6;
+    if (w >= seen_tokens.size()) seen_tokens.resize(std::max(w + 1, seen_tokens.size() * 2), 0);
+    const uint64_t bit = 1ull << (tok & 63);
+    distinct += (seen_tokens[w] & bit) ? 0u : 1u;
+    seen_tokens[w] |= bit;
+  }
 };
 
 // device descriptor of a periodic column that owns a bucket ring

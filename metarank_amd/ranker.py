@@ -148,6 +148,17 @@ class Batch:
         N.check(N.lib().mrk_batch_status(self._h, st.ctypes.data_as(C.c_void_p)))
         return st[:self.n_req]
 
+    def tables(self):
+        """(fused_entries, caps): the largest request's pre-pass table entries (what sizes the fused launch's LDS) and every
+        request's per-table capacity, [n_req, tables per request] (mrk_debug_batch_tables)"""
+        fn = N.lib().mrk_debug_batch_tables
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.c_int64]
+        out = (C.c_int64 * 3)()
+        N.check(fn(self._h, out, None, 0))
+        caps = np.zeros((int(out[1]), int(out[2])), dtype=np.uint32)
+        N.check(fn(self._h, out, caps.ctypes.data_as(C.c_void_p), caps.size))
+        return int(out[0]), caps
+
     def close(self):
         if self._h:
             N.lib().mrk_batch_free(self._h)
@@ -238,6 +249,14 @@ class HipRanker:
         out = (C.c_int64 * 6)()
         N.check(fn(self.ctx.handle, scope, out))
         return dict(zip(("slots", "stride", "heap_off", "heap_cap", "tok_pool", "f64_pool"), [int(x) for x in out]))
+
+    def column_distinct(self, column: str) -> int:
+        """distinct tokens ever stored in an item-scope column (mrk_debug_column_distinct), -1 = no such column"""
+        fn = N.lib().mrk_debug_column_distinct
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int64)]
+        n = C.c_int64(0)
+        N.check(fn(self.ctx.handle, column.encode(), C.byref(n)))
+        return n.value
 
     def item_stride(self) -> int:
         return self.store_info(1)["stride"]
