@@ -6,7 +6,7 @@ thin host-side mirror of the reference's interfaces used by tests and benchmarks
 from ._native import MrkError, build, lib, reload_switches  # noqa: F401
 from .booster import LIGHTGBM, XGBOOST, Context, HipBooster, default_context  # noqa: F401
 from .index import HipIndex  # noqa: F401,E402
-from .ranker import Batch, HipRanker, Server  # noqa: F401,E402
+from .ranker import Batch, HipRanker, Server, debug_fused_lds  # noqa: F401,E402
 from .request import Request, RequestSet  # noqa: F401,E402
 from .trending import HipTrending, TrendingBuilder  # noqa: F401,E402
 from .als import AlsBuilder  # noqa: F401,E402

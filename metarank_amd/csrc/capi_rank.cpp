@@ -37,9 +37,10 @@ void launch_score_batch(mrk_ctx *ctx, mrk_model *m, const double *d_x, int rows,
                         int *d_status, const uint32_t *d_row_req);
 void launch_assemble_cells(mrk_ctx *ctx, const StoreDev &st, const ProgramDev &prog, const BatchDev &b, const QsDev &q,
                            uint16_t *cells, bool f64, void *jit_fn, uint32_t max_req_entries, void *jit_rt_fn = nullptr, uint32_t thr_total = 0);
-void launch_rank_fused(mrk_ctx *ctx, const StoreDev &st, const ProgramDev &prog, const BatchDev &b, uint32_t tab_entries,
-                       int vals_cap, int threads, int op_split, int slices, const QsDev *q, uint16_t *cells, bool f64, void *jit_fn, size_t rt_bytes = 0);
-size_t fused_lds_bytes(uint32_t tab_entries, int vals_cap, int threads, uint32_t thr_cap, size_t rt_bytes, bool split);
+size_t launch_rank_fused(mrk_ctx *ctx, const StoreDev &st, const ProgramDev &prog, const BatchDev &b, uint32_t tab_entries,
+                         int vals_cap, int threads, int op_split, int slices, const QsDev *q, uint16_t *cells, bool f64, void *jit_fn, size_t rt_bytes = 0,
+                         int entry_bytes = 8, bool split_kernel = false);
+size_t fused_lds_bytes(uint32_t tab_entries, int vals_cap, int threads, uint32_t thr_cap, size_t rt_bytes, bool split, int entry_bytes = 8);
 size_t fused_rt_max_bytes();
 int fused_max_prep();
 QsDev qs_device_view(const mrk_model *m);
@@ -118,6 +119,11 @@ struct mrk_batch {
   int fused_vals = 1, fused_threads = 64;
   int fused_slices = 1;      // workgroups per request of the fused kernel (rank_device.hpp rank_fused_body)
   int fused_split = 1;       // op split of the fused kernel's workgroups (1 | 2 | 4; rank_device.hpp op_owner)
+  // the last run's fused cells launch (mrk_debug_batch_launch): bytes of a table entry in the kernel that ran (0: no such launch),
+  // which kernel (0 interpreting, 1 mrk_jit_rank_cells, 2 mrk_jit_rank_cells_split), its dynamic LDS and what the LDS was sized from
+  int ran_entry_bytes = 0, ran_kernel = 0;
+  size_t ran_lds = 0, ran_rt_bytes = 0;
+  uint32_t ran_thr_cap = 0;
   // the f64 matrix is materialised only on demand (explain / parity / models without a bit-vector image)
   bool want_matrix = false;
   bool matrix_valid = false;
@@ -469,12 +475,16 @@ static void run_batch(mrk_batch &b, mrk_model *model, int lo, int hi, bool sort,
                            rank_fused_score_lds_bytes(b.fused_entries, b.fused_vals, b.fused_threads, qs_device_view(model).thr_cap, qs_device_view(model).n_views, f64, (size_t)qs_device_view(model).rt_doubles * 8) <= 64 * 1024;
   // (the kernels that write the scorer's tile are keyed by the forest's view signature too: their sinks hold it as constants)
   const QsSignature *sig = cells && sw.thr_stage ? &model->qs_sig : nullptr;
+  // The plain workgroup-per-request kernel keeps its tables in 4-byte entries (table32_device.hpp): a batch with a table they do
+  // not hold (features.hpp compact_table_ok) takes the op-split / sliced kernel at op split 1 and one slice - 8-byte entries,
+  // the same results.  Per launch, not per request; no second copy of the plain kernel, no format switch inside a kernel.
+  const bool plain = b.fused_split == 1 && b.fused_slices == 1, compact = b.hb.compact_tables;
   void *jit_fn = one_walk ? jit_one_walk_function(*b.prog, f64)
                  : !cells ? (b.fused_ok && model && b.fused_split == 1 && b.fused_slices == 1 ? jit_matrix_function(*b.prog) : nullptr)  // a model scored from the f64 matrix: the hot path too
                         : one ? jit_one_function(*b.prog, f64, sig)
                         : fused_score ? jit_fused_score_function(*b.prog, f64, sig)
                         : !b.fused_ok ? jit_items_function(*b.prog, f64, sig)
-                        : b.fused_split > 1 || b.fused_slices > 1 ? jit_split_function(*b.prog, f64, sig) : jit_rank_function(*b.prog, f64, sig);
+                        : !plain || !compact ? jit_split_function(*b.prog, f64, sig) : jit_rank_function(*b.prog, f64, sig);
   void *jit_rt_fn = cells && !one && !fused_score && !b.fused_ok ? jit_items_rt_function(*b.prog, f64, sig) : nullptr;   // the resident-table form of the item-parallel kernel
   void *jit_prep_fn = cells && !one && !fused_score && !b.fused_ok && b.prog->prep.size() && sw.jit_prepass ? jit_prepass_function(*b.prog) : nullptr;   // (before LaunchOn: a first use may compile)
   LaunchOn on(ctx, b.s());
@@ -483,6 +493,8 @@ static void run_batch(mrk_batch &b, mrk_model *model, int lo, int hi, bool sort,
   b.fetch_enqueued = false;
   b.direct_out = false;
   b.values_ran = b.values_direct = false;
+  b.ran_entry_bytes = b.ran_kernel = 0;
+  b.ran_lds = 0;
   if (one || one_walk) {
     b.h_out.reserve(b.out_bytes);
     uint8_t *h = b.h_out.as<uint8_t>();
@@ -519,8 +531,13 @@ static void run_batch(mrk_batch &b, mrk_model *model, int lo, int hi, bool sort,
     if (hi % QS_TILE_ROWS && tile_bytes)  // rows past the last item of the last tile of this range
       MRK_HIP(hipMemsetAsync(b.d_cells.as<uint8_t>() + (size_t)(hi / QS_TILE_ROWS) * tile_bytes, 0, tile_bytes, b.s()));
     if (b.fused_ok) {
-      launch_rank_fused(ctx, st, pd, b.view, b.fused_entries, b.fused_vals, b.fused_threads, b.fused_split, b.fused_slices, &q, b.d_cells.as<uint16_t>(), f64, jit_fn,
-                        sig && sig->ok ? (size_t)sig->rt_total * 8 : 0);
+      // (jit_fn == nullptr: the interpreting kernel, while a background compile is pending - 8-byte entries as before)
+      b.ran_kernel = !jit_fn ? 0 : plain && compact ? 1 : 2;
+      b.ran_entry_bytes = b.ran_kernel == 1 ? 4 : 8;
+      b.ran_rt_bytes = sig && sig->ok ? (size_t)sig->rt_total * 8 : 0;
+      b.ran_thr_cap = q.thr_cap;
+      b.ran_lds = launch_rank_fused(ctx, st, pd, b.view, b.fused_entries, b.fused_vals, b.fused_threads, b.fused_split, b.fused_slices, &q, b.d_cells.as<uint16_t>(), f64, jit_fn,
+                                    b.ran_rt_bytes, b.ran_entry_bytes, b.ran_kernel == 2);
     } else {
       launch_prepass(ctx, st, pd, b.view, b.fused_entries, jit_prep_fn);
       launch_assemble_cells(ctx, st, pd, b.view, q, b.d_cells.as<uint16_t>(), f64, jit_fn, b.fused_entries, jit_rt_fn, jit_rt_fn ? model->qs_sig.rt_total : 0u);
@@ -957,6 +974,33 @@ int mrk_debug_batch_tables(mrk_batch *b, int64_t *out3, uint32_t *caps, int64_t 
     if (!caps) return;
     if (n_caps < (int64_t)n || b->hb.prep_out.size() < n) throw StatusError(MRK_ERR_INVALID_ARG, "caps is too short");
     for (size_t i = 0; i < n; ++i) caps[i] = b->hb.prep_out[i].tab_cap;
+  });
+}
+
+/* not part of include/mrk.h: the fused cells launch of a batch's last run - out10 = {bytes of a table entry in the kernel that ran
+ * (4: the compact form, 8: the wide one, 0: the run had no such launch), the launch's dynamic LDS bytes, the kernel (0 the
+ * interpreting one, 1 mrk_jit_rank_cells, 2 mrk_jit_rank_cells_split), 1 if every table of the batch fits the compact entry,
+ * then what the LDS was sized from: table entries, median values, threads, threshold staging doubles, resident threshold bytes,
+ * 1 if sized for the split kernel} */
+int mrk_debug_batch_launch(mrk_batch *b, int64_t *out10) {
+  return guard([&] {
+    if (!b || !out10) throw StatusError(MRK_ERR_INVALID_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(b->bmu);
+    out10[0] = b->ran_entry_bytes; out10[1] = (int64_t)b->ran_lds; out10[2] = b->ran_kernel; out10[3] = b->hb.compact_tables ? 1 : 0;
+    out10[4] = b->fused_entries; out10[5] = b->fused_vals; out10[6] = b->fused_threads; out10[7] = b->ran_thr_cap; out10[8] = (int64_t)b->ran_rt_bytes;
+    out10[9] = b->fused_split > 1 || b->fused_slices > 1 || b->ran_kernel == 2 ? 1 : 0;
+  });
+}
+
+/* not part of include/mrk.h, host only: the arithmetic of the two rules above - out2 = {1 if a table with `insertions` inserted
+ * tokens over a column whose largest token id is `max_token` fits the compact entry (features.hpp compact_table_ok), the dynamic
+ * LDS bytes of a fused launch (rank.hip fused_lds_bytes)} */
+int mrk_debug_fused_lds(int64_t insertions, int64_t max_token, int64_t tab_entries, int64_t vals_cap, int64_t threads, int64_t thr_cap, int64_t rt_bytes,
+                        int split, int entry_bytes, int64_t *out2) {
+  return guard([&] {
+    if (!out2 || insertions < 0 || max_token < 0 || (entry_bytes != 4 && entry_bytes != 8)) throw StatusError(MRK_ERR_INVALID_ARG, "bad argument");
+    out2[0] = compact_table_ok((uint64_t)insertions, (uint32_t)std::min<int64_t>(max_token, 0xffffffffll)) ? 1 : 0;
+    out2[1] = (int64_t)fused_lds_bytes((uint32_t)tab_entries, (int)vals_cap, (int)threads, (uint32_t)thr_cap, (size_t)rt_bytes, split != 0, entry_bytes);
   });
 }
 

@@ -1031,6 +1031,7 @@ void resolve_requests(const Program &prog, Store &store, const mrk_request *reqs
   hb.irf.clear();
   hb.overrides.clear();
   hb.arena_entries = hb.max_req_entries = 0;
+  hb.compact_tables = true;
   hb.max_doubles = hb.max_items = hb.total_items = 0;
   // first batch item of every request, and where an item's id bytes are
   std::vector<int> begins((size_t)n_req + 1, 0);
@@ -1148,7 +1149,8 @@ void resolve_requests(const Program &prog, Store &store, const mrk_request *reqs
   // the 5 % load it used to have; such tables are tens of entries, and half the load measured +0.6 % on c2 and gave c4 (no LDS
   // pressure there, only the longer walks) its 0.8 % back (LOG.md round 18)
   auto vocab_bound = [&](ColRef c) -> uint64_t { return c.tag >= 0 && c.tag < (int)item_table.cols.size() ? 2ull * item_table.cols[(size_t)c.tag].distinct : 0u; };
-  struct Worker { std::vector<Override> overrides; int max_items = 0, max_doubles = 0; std::vector<double> enc; };
+  auto col_max_token = [&](ColRef c) -> uint32_t { return c.tag >= 0 && c.tag < (int)item_table.cols.size() ? item_table.cols[(size_t)c.tag].max_token : 0u; };
+  struct Worker { std::vector<Override> overrides; int max_items = 0, max_doubles = 0; std::vector<double> enc; bool compact = true; };
   std::vector<Worker> workers((size_t)std::max(1, n_workers));
   std::vector<uint64_t> req_entries((size_t)n_req, 0);  // hash-table entries of every request (its tables are contiguous)
   // one request: everything but the position of its tables in the arena
@@ -1330,6 +1332,7 @@ void resolve_requests(const Program &prog, Store &store, const mrk_request *reqs
           }
           PrepOut &po = hb.prep_out[(size_t)r * prog.prep.size() + ho.prep_base + fi];
           const uint32_t cap = table_capacity(std::min(count, vocab_bound(pe.item_col)), load_pct);
+          wk.compact = wk.compact && compact_table_ok(count, col_max_token(pe.item_col));
           po.tab_off = (uint32_t)arena;
           po.tab_cap = cap;
           arena += cap;
@@ -1387,6 +1390,7 @@ void resolve_requests(const Program &prog, Store &store, const mrk_request *reqs
         }
         wk.max_doubles = std::max(wk.max_doubles, doubles);
         const uint32_t cap = table_capacity(std::min(tokens, vocab_bound(pe.item_col)), load_pct);
+        wk.compact = wk.compact && compact_table_ok(tokens, col_max_token(pe.item_col));
         po.tab_off = (uint32_t)arena;
         po.tab_cap = cap;
         arena += cap;
@@ -1494,6 +1498,7 @@ void resolve_requests(const Program &prog, Store &store, const mrk_request *reqs
     hb.overrides.insert(hb.overrides.end(), wk.overrides.begin(), wk.overrides.end());
     hb.max_items = std::max(hb.max_items, wk.max_items);
     hb.max_doubles = std::max(hb.max_doubles, wk.max_doubles);
+    hb.compact_tables = hb.compact_tables && wk.compact;
   }
   for (const CrossValue &c : cross_values)
     if (c.v == c.v) hb.overrides.push_back({(uint32_t)(hb.reqs[c.req].item_begin + c.item), (uint32_t)c.dst, c.v});

@@ -130,11 +130,19 @@ struct HostBatch {
   std::vector<PrepOut> prep_out;
   uint64_t arena_entries = 0;
   uint64_t max_req_entries = 0;   // largest per-request table total (fused kernel: LDS sizing)
+  bool compact_tables = true;     // every table of every request passes compact_table_ok (no tables at all: true)
   int max_doubles = 0;            // most numeric diversity values of any (request, feature)
   int max_items = 0;              // largest request
   int total_items = 0;
   bool device_ids = false;        // item_slot / item_req are left to the device (resolve.hip): the batch came with flat ids
 };
+
+// The compact 4-byte entry of the pre-pass tables (table32_device.hpp: 20 bits of token id, 11 of count) holds a table when
+// its column never saw a token id >= 2^20 and the request inserts at most 2 047 tokens into it (`insertions`: the count the
+// capacity is computed from, BEFORE the vocabulary bound - no key's count can pass it).  A batch qualifies when all its tables do.
+constexpr uint32_t COMPACT_MAX_TOKEN = (1u << 20) - 1u;
+constexpr uint64_t COMPACT_MAX_COUNT = 2047;
+inline bool compact_table_ok(uint64_t insertions, uint32_t max_token) { return insertions <= COMPACT_MAX_COUNT && max_token <= COMPACT_MAX_TOKEN; }
 
 // ids == nullptr: the ids are reqs[r].item_ids (NUL-terminated strings), looked up on the host, and the pre-pass tables
 // are sized from exact token counts read from the host mirror.  ids != nullptr: reqs[r].item_ids is ignored, the ids of

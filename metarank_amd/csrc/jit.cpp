@@ -115,18 +115,26 @@ std::string jit_source(const Program &prog, bool f64, int kernel, const QsSignat
   // second trip of every op in registers the kernel would take ~200 VGPRs = 2 wavefronts per SIMD; measured on c2
   // (profiles/r02_c): 2 -> 0.436 ms, 3 -> 0.351, 4 -> 0.286 - the kernel hides its trips to memory with resident
   // wavefronts, so 4 is asked for (128 VGPRs).  MRK_JIT_WAVES=n overrides (experiments).
-  std::string attr;
+  // mrk_jit_rank_cells asks for 5 (96 VGPRs): with its tables in 4-byte entries a c2 workgroup is 13 KB of LDS, twelve fit a CU, and
+  // at 5 wavefronts per SIMD the registers allow ten two-wavefront workgroups instead of eight.  Round 19, c2, same box, every
+  // run: 5 against 4 on the compact tables +2.9 % - where the 8-byte tables held the CU at eight either way (round 18: -0.1 %).
+  // It costs 29 spilled VGPRs (80 B of scratch per lane); the other kernels have no LDS room to gain from it and stay at 4.
+  std::string attr, attr_rank;
   {
-    const int w = switches().jit_waves >= 1 && switches().jit_waves <= 8 ? switches().jit_waves : 4;
+    const bool forced = switches().jit_waves >= 1 && switches().jit_waves <= 8;
+    const int w = forced ? switches().jit_waves : 4, wr = forced ? switches().jit_waves : 5;
     attr = " __attribute__((amdgpu_waves_per_eu(" + std::to_string(w) + ", " + std::to_string(w) + ")))";
+    attr_rank = " __attribute__((amdgpu_waves_per_eu(" + std::to_string(wr) + ", " + std::to_string(wr) + ")))";
   }
   // One kernel per translation unit when `kernel` names one (JIT_ALL: all of them - what tools/jit_inspect.py looks at): a
   // specialised kernel is ~150 KB of straight-line code and takes the compiler 10 - 20 s, so a model's first rank compiles
   // the ONE kernel its batch shape runs, not four.
   const std::string b64 = f64 ? "true" : "false";
   if (kernel == JIT_ALL || kernel == JIT_RANK)
-    s += "extern \"C\" __global__ void __launch_bounds__(256)" + attr + "\nmrk_jit_rank_cells"
+    s += "extern \"C\" __global__ void __launch_bounds__(256)" + attr_rank + "\nmrk_jit_rank_cells"
          "(mrk::StoreDev st, mrk::BatchDev b, uint32_t tab_entries, int vals_cap, mrk::QsDev q, uint16_t *cells, int mode) {\n"
+         // (SPLIT = false - this kernel alone - has its tables in table32_device.hpp's 4-byte entries, rank_device.hpp FusedCellsEntry:
+         //  launched for batches that fit them only - capi_rank.cpp run_batch)
          "  mrk::rank_fused_cells_body<" + b64 + ", false, " + qs + ">(st, mrk::JitProg{}, b, tab_entries, vals_cap, q, cells, mode);\n}\n";
   // the same for a handful of requests (mrk_rank) or few large ones: up to 512 lanes per workgroup, the item lanes in
   // op_split copies that share the program's ops between them (rank_device.hpp op_owner), `slices` workgroups per request

@@ -361,9 +361,11 @@ void launch_assemble_cells(mrk_ctx *ctx, const StoreDev &st, const ProgramDev &p
 // thr_cap: doubles per threshold staging buffer (QsDev::thr_cap; QS_LDS_THR = the largest any model needs)
 // rt_bytes: the forest's compact threshold tables when the kernel that runs may keep them resident (rank_device.hpp FUSED_RT_MAX_BYTES;
 // the region then holds whichever the kernel's sink uses - staging buffers or the resident copy - so it is sized for both)
-size_t fused_lds_bytes(uint32_t tab_entries, int vals_cap, int threads, uint32_t thr_cap, size_t rt_bytes, bool split) {
+// entry_bytes: of one hash-table entry in the kernel that runs - 4 in mrk_jit_rank_cells (table32_device.hpp), 8 everywhere else;
+// the tables' region is rounded up to 8 bytes (the median values behind it are doubles)
+size_t fused_lds_bytes(uint32_t tab_entries, int vals_cap, int threads, uint32_t thr_cap, size_t rt_bytes, bool split, int entry_bytes = 8) {
   const size_t staging = (size_t)((threads + 63) / 64) * 2 * thr_cap * 8;  // two buffers per wavefront
-  return (size_t)tab_entries * 8 + (size_t)vals_cap * 8 + FUSED_MAX_PREP * sizeof(PrepOut) + PREP_INTS * sizeof(int) +
+  return (((size_t)tab_entries * (size_t)entry_bytes + 7) & ~(size_t)7) + (size_t)vals_cap * 8 + FUSED_MAX_PREP * sizeof(PrepOut) + PREP_INTS * sizeof(int) +
          16 + std::max(staging, rt_bytes <= (split ? FUSED_RT_MAX_BYTES_SPLIT : FUSED_RT_MAX_BYTES) ? rt_bytes : 0);  // (16-B aligned)
 }
 size_t fused_rt_max_bytes() { return FUSED_RT_MAX_BYTES_SPLIT; }
@@ -372,12 +374,16 @@ int fused_max_prep() { return FUSED_MAX_PREP; }
 // pre-pass + assembly of every request in one launch (one workgroup per request, tables in LDS).
 // cells == nullptr: write the f64 matrix; else write the binned tile.
 // jit_fn: the hipFunction_t of the kernel specialised for this program (jit.cpp), or nullptr = the generic kernel.
-void launch_rank_fused(mrk_ctx *ctx, const StoreDev &st, const ProgramDev &prog, const BatchDev &b, uint32_t tab_entries,
-                       int vals_cap, int threads, int op_split, int slices, const QsDev *q, uint16_t *cells, bool f64, void *jit_fn, size_t rt_bytes) {
-  if (b.n_req <= 0) return;
+// entry_bytes: the table entries of the kernel that jit_fn IS (fused_lds_bytes); split_kernel: jit_fn is the op-split / sliced
+// kernel even at op split 1 and one slice (a batch the plain kernel's compact entries do not hold).  Returns the launch's
+// dynamic LDS bytes.
+size_t launch_rank_fused(mrk_ctx *ctx, const StoreDev &st, const ProgramDev &prog, const BatchDev &b, uint32_t tab_entries,
+                         int vals_cap, int threads, int op_split, int slices, const QsDev *q, uint16_t *cells, bool f64, void *jit_fn, size_t rt_bytes,
+                         int entry_bytes, bool split_kernel) {
+  if (b.n_req <= 0) return 0;
   int mode = (op_split > 1 ? op_split : 1) | ((slices > 1 ? slices : 1) << 8);  // rank_device.hpp rank_fused_body
   const unsigned grid = (unsigned)b.n_req * (unsigned)(slices > 1 ? slices : 1);
-  size_t lds = fused_lds_bytes(tab_entries, vals_cap, threads, q ? q->thr_cap : 0u, q && cells ? rt_bytes : 0, op_split > 1 || slices > 1);
+  size_t lds = fused_lds_bytes(tab_entries, vals_cap, threads, q ? q->thr_cap : 0u, q && cells ? rt_bytes : 0, op_split > 1 || slices > 1 || split_kernel, entry_bytes);
   if (switches().fused_lds_min > 0) lds = std::max(lds, (size_t)switches().fused_lds_min);  // experiments: cap the kernel's residency (co-residency with the scorer)
   {
     ScopedKernelTimer timer(ctx, "assemble");
@@ -409,6 +415,7 @@ void launch_rank_fused(mrk_ctx *ctx, const StoreDev &st, const ProgramDev &prog,
   } else {
     launch_override_cells(ctx, b, *q, cells, f64);
   }
+  return lds;
 }
 
 // LDS of the one-launch values kernel: [status word, 16 B][the regions of rank_fused_body, no threshold staging]

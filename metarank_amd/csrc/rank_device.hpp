@@ -10,6 +10,7 @@
 #include "rank.hpp"
 #include "sort_device.hpp"
 #include "table_device.hpp"
+#include "table32_device.hpp"
 #include "walk_device.hpp"
 #include "wave_device.hpp"
 
@@ -236,9 +237,9 @@ __device__ __forceinline__ bool prepass_waves_ok(const Prog &prog) {
 }
 
 // the interacted_with section of prepass_request, run by lanes `lane_id` of `n_lanes` (nothing in it synchronises)
-template <typename Prog>
+template <typename Prog, typename T>
 __device__ __forceinline__ void prepass_interacted_with(const StoreDev &st, const Prog &prog, const BatchDev &b, int r, const ReqDev &rq,
-                                                        unsigned long long *tab_base, uint32_t tab_sub, PrepOut *po_out, int lane_id, int n_lanes) {
+                                                        T *tab_base, uint32_t tab_sub, PrepOut *po_out, int lane_id, int n_lanes) {
   const int n_prep = prog.n_prep;
   for (int e0 = 0; e0 < n_prep;) {
     const PrepEntry pe0 = prog.prep[e0];
@@ -250,7 +251,7 @@ __device__ __forceinline__ void prepass_interacted_with(const StoreDev &st, cons
       ++n;
     }
     ColRef col[PREP_GROUP];
-    unsigned long long *tab[PREP_GROUP];
+    T *tab[PREP_GROUP];
     uint32_t cap[PREP_GROUP];
 #pragma unroll
     for (int u = 0; u < PREP_GROUP; ++u) {
@@ -288,9 +289,9 @@ __device__ __forceinline__ void prepass_interacted_with(const StoreDev &st, cons
 }
 
 // the diversity section of prepass_request, run by ONE wavefront (all 64 lanes)
-template <typename Prog>
+template <typename Prog, typename T>
 __device__ __forceinline__ void prepass_diversity_wave(const StoreDev &st, const Prog &prog, const BatchDev &b, int r, const ReqDev &rq,
-                                                       unsigned long long *tab_base, uint32_t tab_sub, PrepOut *po_out, const PrepScratch &sc) {
+                                                       T *tab_base, uint32_t tab_sub, PrepOut *po_out, const PrepScratch &sc) {
   const int lane = threadIdx.x & 63;
   const int n_prep = prog.n_prep;
   int *s_first = sc.first();
@@ -309,7 +310,7 @@ __device__ __forceinline__ void prepass_diversity_wave(const StoreDev &st, const
       ++n;
     }
     ColRef col[DIV_GROUP];
-    unsigned long long *tab[DIV_GROUP];
+    T *tab[DIV_GROUP];
     uint32_t cap[DIV_GROUP];
     int top[DIV_GROUP];
 #pragma unroll
@@ -392,7 +393,7 @@ __device__ __forceinline__ void prepass_diversity_wave(const StoreDev &st, const
             const bool take = cand[u] && running[u] + excl < top[u];
             const bool one = take && c[u].tag == TAG_STRING;
             const uint32_t tlen = take && !one ? c[u].hi() : 0u;
-            uint32_t failed = table_add(tab[u], cap[u], c[u].lo(), one) ? 0u : 1u;
+            uint32_t failed = TableOps<T>::add(tab[u], cap[u], c[u].lo(), one) ? 0u : 1u;
             failed += table_add_list(list_tokens(st, irec, c[u].lo()), tab[u], cap[u], tlen);
             if (failed) atomicOr(&b.status[r], ST_TABLE_FULL);
             if (take) atomicAdd(&s_tokens[u], one ? 1 : (int)tlen);
@@ -460,9 +461,9 @@ __device__ __forceinline__ void prepass_diversity_wave(const StoreDev &st, const
 //   * the diversity entries share the pass that finds each one's first candidate with state, the load that
 //     decides string vs number, and - for the string ones - the pass over the first `top` candidates
 //     (one multi-flag prefix scan keeps request order); numeric ones then take their median one by one.
-template <typename Prog>
+template <typename Prog, typename T>
 __device__ __forceinline__ void prepass_request(const StoreDev &st, const Prog &prog, const BatchDev &b, int r, const ReqDev &rq,
-                                unsigned long long *tab_base, uint32_t tab_sub, PrepOut *po_out, const PrepScratch &sc) {
+                                T *tab_base, uint32_t tab_sub, PrepOut *po_out, const PrepScratch &sc) {
   const int tid = threadIdx.x;
   const int nthr = blockDim.x;
   const int n_prep = prog.n_prep;
@@ -478,7 +479,7 @@ __device__ __forceinline__ void prepass_request(const StoreDev &st, const Prog &
       lo = min(lo, o);
       hi = max(hi, o + po_out[e].tab_cap);
     }
-    for (uint32_t i = lo + tid; i < hi; i += nthr) tab_base[i] = 0ull;
+    for (uint32_t i = lo + tid; i < hi; i += nthr) tab_base[i] = (T)0;
     for (int e = tid; e < n_prep; e += nthr) s_first[e] = 0x7fffffff;
   }
   __syncthreads();
@@ -511,7 +512,7 @@ __device__ __forceinline__ void prepass_request(const StoreDev &st, const Prog &
       ++n;
     }
     ColRef col[PREP_GROUP];
-    unsigned long long *tab[PREP_GROUP];
+    T *tab[PREP_GROUP];
     uint32_t cap[PREP_GROUP];
 #pragma unroll
     for (int u = 0; u < PREP_GROUP; ++u) {
@@ -558,7 +559,7 @@ __device__ __forceinline__ void prepass_request(const StoreDev &st, const Prog &
       ++n;
     }
     ColRef col[PREP_GROUP];
-    unsigned long long *tab[PREP_GROUP];
+    T *tab[PREP_GROUP];
     uint32_t cap[PREP_GROUP];
     int top[PREP_GROUP];
 #pragma unroll
@@ -644,7 +645,7 @@ __device__ __forceinline__ void prepass_request(const StoreDev &st, const Prog &
             const bool take = cand[u] && running[u] + excl[u] < top[u];
             const bool one = take && c[u].tag == TAG_STRING;
             const uint32_t tlen = take && !one ? c[u].hi() : 0u;
-            uint32_t failed = table_add(tab[u], cap[u], c[u].lo(), one) ? 0u : 1u;
+            uint32_t failed = TableOps<T>::add(tab[u], cap[u], c[u].lo(), one) ? 0u : 1u;
             failed += table_add_list(list_tokens(st, irec, c[u].lo()), tab[u], cap[u], tlen);
             if (failed) atomicOr(&b.status[r], ST_TABLE_FULL);
             if (take) atomicAdd(&s_tokens[u], one ? 1 : (int)tlen);
@@ -1294,9 +1295,9 @@ __device__ __forceinline__ void run_groups(F &&f) {
 
 // Evaluates the model program for batch item gi of request r.  Hash tables: tab_base + (po.tab_off - tab_sub).
 // (og, G): op split - this wavefront evaluates the ops whose owner & (G - 1) == og; G = 1: all of them
-template <bool SPLIT, typename Prog, typename Sink, typename IR>
+template <bool SPLIT, typename Prog, typename Sink, typename IR, typename T>
 __device__ __forceinline__ void assemble_item_rec(const StoreDev &st, const Prog &prog, const BatchDev &b, int gi, int r,
-                                                  const ReqDev &rq, const unsigned long long *tab_base, uint32_t tab_sub,
+                                                  const ReqDev &rq, const T *tab_base, uint32_t tab_sub,
                                                   const PrepOut *pos, const Sink &sink, int islot, const IR &ir, int og, int G_arg) {
   const int G = SPLIT ? G_arg : 1;  // the hot kernels are instantiated without the split: every guard below folds away
   const uint8_t *irec = ir.p;
@@ -1588,7 +1589,7 @@ __device__ __forceinline__ void assemble_item_rec(const StoreDev &st, const Prog
           for (int u = 0; u < IW_BATCH; ++u) {
             if (f0 + u >= op.dim) break;
             const PrepOut po = pos[op.i1 + f0 + u];
-            const unsigned long long *tab = tab_base + (po.tab_off - tab_sub);
+            const T *tab = tab_base + (po.tab_off - tab_sub);
             const uint32_t len = fc[u].tag == TAG_STRING_LIST ? fc[u].hi() : 0u;
             double cnt = table_sum_tokens<IW_TOK>(tab, po.tab_cap, tk[u], len, 0.0);
             if (wave_any(len > (uint32_t)IW_TOK))  // the rest of longer lists, in list order
@@ -1607,9 +1608,9 @@ __device__ __forceinline__ void assemble_item_rec(const StoreDev &st, const Prog
         } else if (po.mode == DIV_DOUBLE) {
           if (c.tag == TAG_DOUBLE) v = c.f64() - po.scalar;
         } else {
-          const unsigned long long *tab = tab_base + (po.tab_off - tab_sub);
+          const T *tab = tab_base + (po.tab_off - tab_sub);
           const bool one = c.tag == TAG_STRING, list = c.tag == TAG_STRING_LIST;
-          const double w1 = 0.0 + (double)table_get(tab, po.tab_cap, c.lo(), one);
+          const double w1 = 0.0 + (double)TableOps<T>::get(tab, po.tab_cap, c.lo(), one);
           // the list's first TOK_BATCH tokens were fetched ahead; longer lists continue from memory, in list order
           const uint32_t len = list ? c.hi() : 0u;
           uint32_t dtk[TOK_BATCH];
@@ -1766,9 +1767,9 @@ template <typename P> __device__ __forceinline__ constexpr auto prog_item_pieces
 template <typename P> __device__ __forceinline__ constexpr int prog_item_pieces(...) { return 0; }
 constexpr int REC_MAX_PIECES = 24;
 
-template <bool SPLIT = false, typename Prog, typename Sink>
+template <bool SPLIT = false, typename Prog, typename Sink, typename T>
 __device__ __forceinline__ void assemble_item(const StoreDev &st, const Prog &prog, const BatchDev &b, int gi, int r,
-                                              const ReqDev &rq, const unsigned long long *tab_base, uint32_t tab_sub,
+                                              const ReqDev &rq, const T *tab_base, uint32_t tab_sub,
                                               const PrepOut *pos, const Sink &sink, int og = 0, int G = 1) {
   const int islot = sink.active ? b.item_slot[gi] : -1;  // lanes without an item: a missing record
   const uint8_t *irec = record(st, SC_ITEM, islot);
@@ -1784,8 +1785,11 @@ __device__ __forceinline__ void assemble_item(const StoreDev &st, const Prog &pr
 
 
 // Both phases of one request in one workgroup; hash tables, pre-pass results and the median scratch in LDS.
-// Dynamic LDS: [tables: tab_entries x 8 B][median values: vals_cap x 8 B][PrepOut x FUSED_MAX_PREP][PREP_INTS ints]
+// Dynamic LDS: [tables: tab_entries x sizeof(T), rounded up to 8 B][median values: vals_cap x 8 B][PrepOut x FUSED_MAX_PREP][PREP_INTS ints]
 //              [threshold staging: 2 buffers x thr_cap x 8 B per wavefront]
+// T: the tables' element type - unsigned long long (table_device.hpp) everywhere but in mrk_jit_rank_cells, whose tables are the
+// compact uint32_t entries of table32_device.hpp (the host launches that kernel only for batches that fit them: capi_rank.cpp).
+// Table e of the request lies at entry po.tab_off - arena_begin of the region in either form.
 // `mode` = op_split | slices << 8.
 //   op_split (1 | 2 | 4; SPLIT kernels only): the workgroup's lanes are op_split copies of the item lanes (see op_owner).
 //   slices (>= 1; SPLIT kernels only): a request is covered by `slices` workgroups; each runs the request's pre-pass (its tables are private,
@@ -1798,7 +1802,7 @@ __device__ __forceinline__ void assemble_item(const StoreDev &st, const Prog &pr
 // lds_skip: bytes at the start of the dynamic LDS that belong to the caller (the one-launch kernel keeps the scorer's slab there).
 // rt_src / rt_doubles: compact threshold tables the workgroup copies into the threshold region before its pre-pass (0: none - the
 // region is per-wavefront staging buffers); make_sink gets both views of the region.
-template <bool SPLIT, typename Prog, typename SinkMaker>
+template <bool SPLIT, typename T = unsigned long long, typename Prog, typename SinkMaker>
 __device__ __forceinline__ void rank_fused_body(const StoreDev &st, const Prog &prog, const BatchDev &b, uint32_t tab_entries,
                                                 int vals_cap, uint32_t thr_cap, int mode, const SinkMaker &make_sink, uint32_t lds_skip = 0,
                                                 const double *rt_src = nullptr, uint32_t rt_doubles = 0, int blk = -1) {
@@ -1806,9 +1810,10 @@ __device__ __forceinline__ void rank_fused_body(const StoreDev &st, const Prog &
   const int slices = SPLIT ? (((mode >> 8) & 255) > 1 ? ((mode >> 8) & 255) : 1) : 1;   // (the plain kernel keeps its registers for the ops)
   extern __shared__ __align__(16) uint8_t smem_base[];
   uint8_t *smem = smem_base + lds_skip;
-  unsigned long long *s_tab = (unsigned long long *)smem;
-  double *s_vals = (double *)(smem + (size_t)tab_entries * 8);
-  PrepOut *s_po = (PrepOut *)(smem + (size_t)tab_entries * 8 + (size_t)vals_cap * 8);
+  T *s_tab = (T *)smem;
+  const size_t tab_bytes = sizeof(T) == 8 ? (size_t)tab_entries * 8 : ((size_t)tab_entries * sizeof(T) + 7) & ~(size_t)7;
+  double *s_vals = (double *)(smem + tab_bytes);
+  PrepOut *s_po = (PrepOut *)(smem + tab_bytes + (size_t)vals_cap * 8);
   int *s_int = (int *)(s_po + FUSED_MAX_PREP);
   const size_t thr_at = ((size_t)((uint8_t *)(s_int + PREP_INTS) - smem) + 15) & ~(size_t)15;  // LDS-DMA writes 16 B per lane
   qs_lds_double *s_thr_all = (qs_lds_double *)(smem + thr_at);
@@ -2012,15 +2017,19 @@ __device__ __forceinline__ void rank_values_body(const StoreDev &st, const Prog 
 }
 
 // the hot-path instance of rank_fused_body: straight into the scorer's binned tile
-template <bool F64, bool SPLIT = false, typename QS = QsDyn, typename Prog>
+// (the tables' element type: compact 4-byte entries in the plain kernel - SPLIT = false is instantiated by mrk_jit_rank_cells alone -
+//  and the 8-byte ones in the op-split / sliced kernel and its interpreting twin)
+template <bool SPLIT> struct FusedCellsEntry { typedef unsigned long long type; };
+template <> struct FusedCellsEntry<false> { typedef uint32_t type; };
+template <bool F64, bool SPLIT = false, typename QS = QsDyn, typename T = typename FusedCellsEntry<SPLIT>::type, typename Prog>
 __device__ __forceinline__ void rank_fused_cells_body(const StoreDev &st, const Prog &prog, const BatchDev &b, uint32_t tab_entries,
                                                       int vals_cap, const QsDev &q, uint16_t *cells, int mode = 1) {
   if constexpr (qs_fused_rt<QS, SPLIT>()) {   // the forest's compact tables fit: resident, searched four columns at a time (CellSinkRT)
-    rank_fused_body<SPLIT>(st, prog, b, tab_entries, vals_cap, qs_thr_cap<QS>(q), mode, [&](int gi, int r, bool active, qs_lds_double *, qs_lds_double *s_all) {
+    rank_fused_body<SPLIT, T>(st, prog, b, tab_entries, vals_cap, qs_thr_cap<QS>(q), mode, [&](int gi, int r, bool active, qs_lds_double *, qs_lds_double *s_all) {
       return CellSinkRT<F64, QS, !SPLIT>{q, cells + (size_t)(gi / QS_TILE_ROWS) * QS::n_views * QS_TILE_ROWS + (gi % QS_TILE_ROWS), &b.status[r], s_all, active};
     }, 0u, q.thr_rt, QS::rt_total);
   } else {
-    rank_fused_body<SPLIT>(st, prog, b, tab_entries, vals_cap, qs_thr_cap<QS>(q), mode, [&](int gi, int r, bool active, qs_lds_double *s_thr, qs_lds_double *) {
+    rank_fused_body<SPLIT, T>(st, prog, b, tab_entries, vals_cap, qs_thr_cap<QS>(q), mode, [&](int gi, int r, bool active, qs_lds_double *s_thr, qs_lds_double *) {
       return CellSink<F64, QS>{q, cells + (size_t)(gi / QS_TILE_ROWS) * qs_n_views<QS>(q) * QS_TILE_ROWS + (gi % QS_TILE_ROWS), &b.status[r], s_thr, active};
     });
   }

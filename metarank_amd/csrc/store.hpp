@@ -65,8 +65,11 @@ struct Column {
   // loader (codec.cpp) and the C ABI come through them, append / increment / put_bounded_list write no string cell,
   // clone_items copies records (tokens already counted) and a request's per-item fields never reach a table.
   uint32_t distinct = 0;
+  // ... and the largest of them: the compact 4-byte table entries hold token ids below 2^20 (features.hpp compact_table_ok)
+  uint32_t max_token = 0;
   std::vector<uint64_t> seen_tokens;
   void note_token(uint32_t tok) {
+    max_token = std::max(max_token, tok);
     const size_t w = tok >> 6;
     if (w >= seen_tokens.size()) seen_tokens.resize(std::max(w + 1, seen_tokens.size() * 2), 0);
     const uint64_t bit = 1ull << (tok & 63);

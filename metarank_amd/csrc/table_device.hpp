@@ -122,6 +122,14 @@ __device__ __forceinline__ uint32_t table_get(const unsigned long long *tab, uin
   return table_get_from(tab, nb, tok, want, tok_home(tok, nb), 0u, 0u);
 }
 
+// The list forms below and the kernels (rank_device.hpp) take the table's element type as a template parameter and reach the two
+// primitives through TableOps<T>: unsigned long long = the entries above; uint32_t = the compact entries of table32_device.hpp.
+template <typename T> struct TableOps;
+template <> struct TableOps<unsigned long long> {
+  static __device__ __forceinline__ bool add(unsigned long long *tab, uint32_t cap, uint32_t tok, bool want) { return table_add(tab, cap, tok, want); }
+  static __device__ __forceinline__ uint32_t get(const unsigned long long *tab, uint32_t cap, uint32_t tok, bool want) { return table_get(tab, cap, tok, want); }
+};
+
 // (Measured and removed, round 6 - profiles/r06_l_get_k_ab.txt: K lookups of one table sharing their trips - the K buckets of a trip read
 // together, one loop for all K.  K = 2 / 4 against one at a time, same box: c2 assembly 0.212 / 0.221 vs 0.206 ms, c4x 0.828 / 0.907 vs
 // 0.775 ms - K buckets in registers spill (6 -> 17 -> 53 VGPRs spilled in the c2 kernel), and with the walked-past mark a lookup
@@ -135,7 +143,8 @@ constexpr int TOK_BATCH = MRK_TOK_BATCH;
 
 // every token of toks[0, len) -> table (pre-pass); len = 0 for lanes without a list.  Returns the
 // number of tokens this lane could not insert (table full).
-__device__ __forceinline__ uint32_t table_add_list(const uint32_t *toks, unsigned long long *tab, uint32_t cap, uint32_t len) {
+template <typename T>
+__device__ __forceinline__ uint32_t table_add_list(const uint32_t *toks, T *tab, uint32_t cap, uint32_t len) {
   uint32_t failed = 0;
   for (uint32_t j0 = 0; wave_any(j0 < len); j0 += TOK_BATCH) {
     uint32_t tk[TOK_BATCH];
@@ -144,26 +153,27 @@ __device__ __forceinline__ uint32_t table_add_list(const uint32_t *toks, unsigne
 #pragma unroll
     for (int t = 0; t < TOK_BATCH; ++t) {
       if (!wave_any(j0 + t < len)) break;
-      failed += table_add(tab, cap, tk[t], j0 + t < len) ? 0u : 1u;
+      failed += TableOps<T>::add(tab, cap, tk[t], j0 + t < len) ? 0u : 1u;
     }
   }
   return failed;
 }
 
 // cnt + the table counts of tk[0, min(len, N)), added as doubles in token order (lanes past their list add 0.0)
-template <int N>
-__device__ __forceinline__ double table_sum_tokens(const unsigned long long *tab, uint32_t cap, const uint32_t (&tk)[N], uint32_t len, double cnt) {
+template <int N, typename T>
+__device__ __forceinline__ double table_sum_tokens(const T *tab, uint32_t cap, const uint32_t (&tk)[N], uint32_t len, double cnt) {
 #pragma unroll
   for (int t = 0; t < N; ++t) {
     if (!wave_any((uint32_t)t < len)) break;
-    cnt = cnt + (double)table_get(tab, cap, tk[t], (uint32_t)t < len);
+    cnt = cnt + (double)TableOps<T>::get(tab, cap, tk[t], (uint32_t)t < len);
   }
   return cnt;
 }
 
 // sum over the tokens toks[0, len) of their table counts, added as doubles in list order
 // (InteractedWithFeature.scala:150-160 / DiversityFeature.scala:112-122: integers, exact)
-__device__ __forceinline__ double table_sum_list(const uint32_t *toks, const unsigned long long *tab, uint32_t cap, uint32_t len,
+template <typename T>
+__device__ __forceinline__ double table_sum_list(const uint32_t *toks, const T *tab, uint32_t cap, uint32_t len,
                                                  double cnt = 0.0) {
   for (uint32_t j0 = 0; wave_any(j0 < len); j0 += TOK_BATCH) {
     uint32_t tk[TOK_BATCH];

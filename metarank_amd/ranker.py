@@ -159,6 +159,16 @@ class Batch:
         N.check(fn(self._h, out, caps.ctypes.data_as(C.c_void_p), caps.size))
         return int(out[0]), caps
 
+    def launch_info(self) -> dict:
+        """the fused cells launch of the batch's last run (mrk_debug_batch_launch): entry_bytes 4 = the compact table entries, 8 =
+        the wide ones, 0 = no such launch; its dynamic LDS bytes; kernel 0 interpreting / 1 mrk_jit_rank_cells / 2 the split one;
+        whether the batch's tables fit the compact entry; and what the LDS was sized from"""
+        fn = N.lib().mrk_debug_batch_launch
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]
+        out = (C.c_int64 * 10)()
+        N.check(fn(self._h, out))
+        return dict(zip(("entry_bytes", "lds", "kernel", "qualifies", "tab_entries", "vals_cap", "threads", "thr_cap", "rt_bytes", "split"), [int(x) for x in out]))
+
     def close(self):
         if self._h:
             N.lib().mrk_batch_free(self._h)
@@ -169,6 +179,17 @@ class Batch:
             self.close()
         except Exception:
             pass
+
+
+def debug_fused_lds(insertions: int, max_token: int, tab_entries: int = 0, vals_cap: int = 1, threads: int = 64, thr_cap: int = 0, rt_bytes: int = 0,
+                    split: bool = False, entry_bytes: int = 8):
+    """host only (mrk_debug_fused_lds): (a table of `insertions` tokens over a column whose largest token id is `max_token` fits the
+    compact entry, the dynamic LDS bytes of a fused launch of that shape)"""
+    fn = N.lib().mrk_debug_fused_lds
+    fn.restype, fn.argtypes = C.c_int, [C.c_int64] * 7 + [C.c_int, C.c_int, C.POINTER(C.c_int64)]
+    out = (C.c_int64 * 2)()
+    N.check(fn(insertions, max_token, tab_entries, vals_cap, threads, thr_cap, rt_bytes, int(split), entry_bytes, out))
+    return bool(out[0]), int(out[1])
 
 
 class HipRanker:
