@@ -31,7 +31,6 @@ static Switches read_switches() {
   s.rank_one = flag("MRK_RANK_ONE", true);
   s.values_one = flag("MRK_VALUES_ONE", true);
   if (const char *e = getenv("MRK_RANK_ONE_WALK")) s.rank_one_walk = !strcmp(e, "0") ? 0 : !strcmp(e, "1") ? 1 : -1;
-  s.rank_fused_score = flag("MRK_RANK_FUSED_SCORE", false);
   s.rank_serve = flag("MRK_RANK_SERVE", true);
   s.serve_idle_us = std::max(1, num("MRK_SERVE_IDLE_US", 2000));
   s.serve_spin_callers = std::max(0, num("MRK_SERVE_SPIN_CALLERS", 8));

@@ -16,10 +16,9 @@
 #include <cstdlib>
 
 #include "features.hpp"
-#include "jit.hpp"
-#include "launch_shape.hpp"
 #include "qs_device.hpp"
 #include "rank.hpp"
+#include "rank_plan.hpp"
 #include "runtime.hpp"
 
 namespace mrk {
@@ -40,15 +39,8 @@ void launch_assemble_cells(mrk_ctx *ctx, const StoreDev &st, const ProgramDev &p
 size_t launch_rank_fused(mrk_ctx *ctx, const StoreDev &st, const ProgramDev &prog, const BatchDev &b, uint32_t tab_entries,
                          int vals_cap, int threads, int op_split, int slices, const QsDev *q, uint16_t *cells, bool f64, void *jit_fn, size_t rt_bytes = 0,
                          int entry_bytes = 8, bool split_kernel = false);
-size_t fused_lds_bytes(uint32_t tab_entries, int vals_cap, int threads, uint32_t thr_cap, size_t rt_bytes, bool split, int entry_bytes = 8);
-size_t fused_rt_max_bytes();
-int fused_max_prep();
 QsDev qs_device_view(const mrk_model *m);
 QsForestDev qs_forest_view(const mrk_model *m);  // score_qs.hip
-size_t rank_one_lds_bytes(uint32_t tab_entries, int vals_cap, int threads, uint32_t thr_cap, int n_views, bool f64, size_t rt_bytes);
-size_t rank_fused_score_lds_bytes(uint32_t tab_entries, int vals_cap, int threads, uint32_t thr_cap, int n_views, bool f64, size_t rt_bytes);
-void launch_rank_fused_score(mrk_ctx *ctx, const StoreDev &st, const ProgramDev &prog, const BatchDev &b, uint32_t tab_entries, int vals_cap,
-                             int threads, const QsDev &q, const QsForestDev &f, uint16_t *cells, bool f64, void *jit_fn);
 void launch_rank_serve(mrk_ctx *ctx, hipStream_t stream, const StoreDev &st, const ProgramDev &prog, const QsDev &q, const QsForestDev &f, const ServeGangDev &gang,
                        int n_slots, int threads, size_t lds, bool f64, void *jit_fn);
 void launch_rank_one(mrk_ctx *ctx, const StoreDev &st, const ProgramDev &prog, const BatchDev &b, uint32_t tab_entries, int vals_cap,
@@ -97,7 +89,6 @@ struct mrk_batch {
   size_t out_order_off = 0, out_status_off = 0, out_bytes = 0;
   PinBuf h_out;
   bool fetch_enqueued = false;          // the download of d_out into h_out is on the stream behind the last run
-  bool direct_out = false;              // the last run was the one-launch kernel: scores / order / status were written into h_out by the device
   DevBuf d_cells;            // the scorer's binned tile (bit-vector models), grow-only
   DevBuf d_sort;                        // scratch of the multi-workgroup sort (bigsort.hip)
   DevBuf d_norm_order;                  // norm: position over a request of more than SORT_MAX_ITEMS candidates: its column's order
@@ -112,27 +103,26 @@ struct mrk_batch {
   BatchDev view{};
   std::vector<int32_t> h_status;
   std::vector<int32_t> codes;           // mrk_status per request (mrk_batch_host_outputs)
-  bool ran = false;
-  // one-workgroup-per-request path (tables in LDS)
-  bool fused_ok = false;
-  uint32_t fused_entries = 0;
-  int fused_vals = 1, fused_threads = 64;
-  int fused_slices = 1;      // workgroups per request of the fused kernel (rank_device.hpp rank_fused_body)
-  int fused_split = 1;       // op split of the fused kernel's workgroups (1 | 2 | 4; rank_device.hpp op_owner)
-  // the last run's fused cells launch (mrk_debug_batch_launch): bytes of a table entry in the kernel that ran (0: no such launch),
-  // which kernel (0 interpreting, 1 mrk_jit_rank_cells, 2 mrk_jit_rank_cells_split), its dynamic LDS and what the LDS was sized from
-  int ran_entry_bytes = 0, ran_kernel = 0;
-  size_t ran_lds = 0, ran_rt_bytes = 0;
-  uint32_t ran_thr_cap = 0;
+  BatchShape sh;             // what the plans read of the load (rank_plan.hpp; want_matrix is filled in per run)
   // the f64 matrix is materialised only on demand (explain / parity / models without a bit-vector image)
   bool want_matrix = false;
-  bool matrix_valid = false;
   // training rows (mrk_values, mrk_batch_load_values): mrk_batch_run(batch, NULL) assembles the rows of the loaded values program
   bool values = false;
-  bool values_ran = false;              // the last run was such a run: scores are 0.0 and the order is the request's own (NoopRanker.scala:22-26), filled by the host
-  bool values_direct = false;           // ... by the one-launch values kernel: the device wrote rows and status words into h_vals itself
   PinBuf h_vals;                        // [rows: T x dim f64][status: n_req i32][load status: n_req i32]
   size_t vals_status_off = 0;
+  // what the last run left behind (reset by every run and every load)
+  struct Ran {
+    bool direct_out = false;            // the one-launch kernel: scores / order / status were written into h_out by the device
+    bool matrix_valid = false;
+    bool values = false;                // a values run: scores are 0.0 and the order is the request's own (NoopRanker.scala:22-26), filled by the host
+    bool values_direct = false;         // ... by the one-launch values kernel: the device wrote rows and status words into h_vals itself
+    // the fused cells launch (mrk_debug_batch_launch): bytes of a table entry in the kernel that ran (0: no such launch), which kernel
+    // (0 interpreting, 1 mrk_jit_rank_cells, 2 mrk_jit_rank_cells_split), its dynamic LDS and what the LDS was sized from
+    int entry_bytes = 0, kernel = 0;
+    bool split_sized = false;
+    size_t lds = 0, rt_bytes = 0;
+    uint32_t thr_cap = 0;
+  } ran;
 };
 
 namespace mrk {
@@ -224,6 +214,40 @@ static bool is_pinned_host(const void *p) {
   return a.type == hipMemoryTypeHost;
 }
 
+// One block for a load's inputs - the arrays BatchDev points into, each at a multiple of `align`: 256 for a batch's device block,
+// 16 for a serving slot's, whose offsets travel in ServeCtl.  An array without elements (no overrides) takes no room.
+struct InputLayout {
+  size_t o_reqs, o_consts, o_irf, o_ov, o_prep, o_slot, o_ireq;
+  size_t host_bytes;   // everything the host always fills; the per-item arrays follow
+  size_t bytes;
+  InputLayout(const HostBatch &hb, size_t align) {
+    size_t off = 0;
+    auto place = [&](size_t n) { size_t o = off; off = align_up(off + n, align); return o; };
+    o_reqs = place(hb.reqs.size() * sizeof(ReqDev));
+    o_consts = place(hb.consts.size() * 8);
+    o_irf = place(hb.irf.size() * 4);
+    o_ov = place(hb.overrides.size() * sizeof(Override));
+    o_prep = place(hb.prep_out.size() * sizeof(PrepOut));
+    host_bytes = std::max(off, align);
+    o_slot = place((size_t)hb.total_items * 4);
+    o_ireq = place((size_t)hb.total_items * 4);
+    bytes = std::max(off, align);
+  }
+  // device-resolved ids: item_slot / item_req are written by a kernel
+  size_t filled(const HostBatch &hb) const { return hb.device_ids ? host_bytes : bytes; }
+  void fill(uint8_t *h, const HostBatch &hb) const {
+    auto put = [&](size_t o, const void *src, size_t n) { if (n) memcpy(h + o, src, n); };
+    put(o_reqs, hb.reqs.data(), hb.reqs.size() * sizeof(ReqDev));
+    put(o_consts, hb.consts.data(), hb.consts.size() * 8);
+    put(o_irf, hb.irf.data(), hb.irf.size() * 4);
+    put(o_ov, hb.overrides.data(), hb.overrides.size() * sizeof(Override));
+    put(o_prep, hb.prep_out.data(), hb.prep_out.size() * sizeof(PrepOut));
+    if (hb.device_ids) return;
+    put(o_slot, hb.item_slot.data(), (size_t)hb.total_items * 4);
+    put(o_ireq, hb.item_req.data(), (size_t)hb.total_items * 4);
+  }
+};
+
 // (re)builds the device-resident batch (inputs uploaded, outputs allocated, id resolution enqueued); the caller holds
 // the store (StoreAccess) and the batch
 static void build_batch(mrk_ctx *ctx, const Program &prog, const mrk_request *reqs, int n_req, const mrk_item_ids *ids, mrk_batch &b) {
@@ -236,33 +260,12 @@ static void build_batch(mrk_ctx *ctx, const Program &prog, const mrk_request *re
   b.n_req = n_req;
   b.total_items = hb.total_items;
   const int T = hb.total_items;
-  // one staging blob for all inputs
-  size_t off = 0;
-  auto place = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
-  const size_t o_reqs = place(hb.reqs.size() * sizeof(ReqDev));
-  const size_t o_consts = place(hb.consts.size() * 8);
-  const size_t o_irf = place(hb.irf.size() * 4);
-  const size_t o_ov = place(hb.overrides.size() * sizeof(Override));
-  const size_t o_prep = place(hb.prep_out.size() * sizeof(PrepOut));
-  const size_t host_bytes = std::max<size_t>(off, 256);  // everything the host fills; the per-item arrays follow
-  const size_t o_slot = place((size_t)T * 4);
-  const size_t o_ireq = place((size_t)T * 4);
-  const size_t total_bytes = std::max<size_t>(off, 256);
-  const size_t up_bytes = hb.device_ids ? host_bytes : total_bytes;  // device-resolved ids: item_slot / item_req are written by a kernel
+  const InputLayout in(hb, 256);
+  const size_t up_bytes = in.filled(hb);
   b.h_in.reserve(up_bytes);
-  b.d_in.reserve(total_bytes);
-  uint8_t *h = b.h_in.as<uint8_t>();
-  auto put = [&](size_t o, const void *src, size_t bytes) { if (bytes) memcpy(h + o, src, bytes); };
-  put(o_reqs, hb.reqs.data(), hb.reqs.size() * sizeof(ReqDev));
-  put(o_consts, hb.consts.data(), hb.consts.size() * 8);
-  put(o_irf, hb.irf.data(), hb.irf.size() * 4);
-  put(o_ov, hb.overrides.data(), hb.overrides.size() * sizeof(Override));
-  put(o_prep, hb.prep_out.data(), hb.prep_out.size() * sizeof(PrepOut));
-  if (!hb.device_ids) {
-    put(o_slot, hb.item_slot.data(), (size_t)T * 4);
-    put(o_ireq, hb.item_req.data(), (size_t)T * 4);
-  }
-  MRK_HIP(hipMemcpyAsync(b.d_in.p, h, up_bytes, hipMemcpyHostToDevice, b.s()));
+  b.d_in.reserve(in.bytes);
+  in.fill(b.h_in.as<uint8_t>(), hb);
+  MRK_HIP(hipMemcpyAsync(b.d_in.p, b.h_in.p, up_bytes, hipMemcpyHostToDevice, b.s()));
   uint8_t *d = b.d_in.as<uint8_t>();
   // outputs in one allocation: one device-to-host copy per fetch (single-request latency)
   const size_t score_slots = (size_t)T + 256 * QS_TILE_ROWS;  // room for the padded chunks of an item-sharded all-gather
@@ -293,33 +296,31 @@ static void build_batch(mrk_ctx *ctx, const Program &prog, const mrk_request *re
     MRK_HIP(hipMemcpyAsync(b.d_ids.p, src_off, off_bytes, hipMemcpyHostToDevice, b.s()));
     if (id_bytes) MRK_HIP(hipMemcpyAsync(b.d_ids.as<uint8_t>() + o_bytes, src_bytes, id_bytes, hipMemcpyHostToDevice, b.s()));
     launch_resolve_ids(b.s(), store.tables[SC_ITEM].id_table_view(), b.d_ids.as<uint8_t>() + o_bytes, b.d_ids.as<uint32_t>(), (uint32_t)id_bytes,
-                       (const ReqDev *)(d + o_reqs), n_req, T, (int32_t *)(d + o_slot), (uint32_t *)(d + o_ireq), d_load_status);
+                       (const ReqDev *)(d + in.o_reqs), n_req, T, (int32_t *)(d + in.o_slot), (uint32_t *)(d + in.o_ireq), d_load_status);
   }
   b.d_arena.reserve(std::max<size_t>(hb.arena_entries, 1) * 8);
   b.d_matrix.reserve(std::max<size_t>((size_t)T * prog.dim, 1) * 8);
   BatchDev &v = b.view;
-  v.reqs = (const ReqDev *)(d + o_reqs);
+  v.reqs = (const ReqDev *)(d + in.o_reqs);
   v.n_req = n_req;
   v.total_items = T;
   v.item_lo = 0;
   v.item_hi = T;
-  v.item_slot = (const int32_t *)(d + o_slot);
-  v.item_req = (const uint32_t *)(d + o_ireq);
-  v.consts = (const double *)(d + o_consts);
-  v.irf = (const int32_t *)(d + o_irf);
-  v.overrides = (const Override *)(d + o_ov);
+  v.item_slot = (const int32_t *)(d + in.o_slot);
+  v.item_req = (const uint32_t *)(d + in.o_ireq);
+  v.consts = (const double *)(d + in.o_consts);
+  v.irf = (const int32_t *)(d + in.o_irf);
+  v.overrides = (const Override *)(d + in.o_ov);
   v.n_overrides = (int)hb.overrides.size();
-  v.prep_out = (PrepOut *)(d + o_prep);
+  v.prep_out = (PrepOut *)(d + in.o_prep);
   v.arena = (unsigned long long *)b.d_arena.p;
   v.status = (int32_t *)(b.d_out.as<uint8_t>() + b.out_status_off);
   v.matrix = (double *)b.d_matrix.p;
   v.scores = (double *)b.d_out.p;
   v.order = (int32_t *)(b.d_out.as<uint8_t>() + b.out_order_off);
   b.h_status.assign(n_req, 0);
-  b.ran = false;
-  b.matrix_valid = false;
+  b.ran = {};
   b.fetch_enqueued = false;
-  b.values_ran = b.values_direct = false;
   b.big.clear();
   size_t big_bytes = 0;
   for (int r = 0; r < n_req; ++r)
@@ -328,18 +329,39 @@ static void build_batch(mrk_ctx *ctx, const Program &prog, const mrk_request *re
       big_bytes = std::max(big_bytes, big_sort_scratch_bytes(hb.reqs[r].n_items));
     }
   if (big_bytes) b.d_sort.reserve(big_bytes);  // one scratch: the big requests of a batch are sorted one after the other on its stream
-  // small requests: both phases in one workgroup, tables in LDS (<= 64 KB keeps two workgroups per CU)
-  uint32_t vals = 1;
-  while ((int)vals < hb.max_doubles) vals <<= 1;
-  b.fused_entries = (uint32_t)std::max<uint64_t>(hb.max_req_entries, 1);
-  b.fused_vals = (int)vals;
-  const Switches &sw = switches();
-  const FusedShape shape = fused_launch_shape(n_req, hb.max_items, sw.fused_threads, sw.fused_split, sw.fused_slices, sw.split_max_req);  // launch_shape.hpp
-  b.fused_split = shape.split;
-  b.fused_slices = shape.slices;
-  b.fused_threads = shape.threads();
-  b.fused_ok = sw.rank_fused && (int)prog.prep.size() <= fused_max_prep() && hb.max_items <= 1024 &&
-               hb.max_req_entries <= (1u << 20) && fused_lds_bytes(b.fused_entries, b.fused_vals, b.fused_threads, QS_LDS_THR, fused_rt_max_bytes(), true) <= 64 * 1024;
+  b.sh = BatchShape{};
+  b.sh.n_req = n_req;
+  b.sh.total_items = T;
+  b.sh.max_items = hb.max_items;
+  b.sh.compact_tables = hb.compact_tables;
+  b.sh.overrides = !hb.overrides.empty();
+  b.sh.normalises = prog.normalises();
+  b.sh.n_prep = (int)prog.prep.size();
+  b.sh.dim = prog.dim;
+  fused_batch_shape(b.sh, hb.max_req_entries, hb.max_doubles, switches());
+}
+
+static BatchShape shape_of(const mrk_batch &b) {
+  BatchShape sh = b.sh;
+  sh.want_matrix = b.want_matrix;
+  return sh;
+}
+
+static ModelShape shape_of(const mrk_model *m) {
+  ModelShape s;
+  if (!m) return s;
+  s.present = true;
+  s.qs_ok = m->qs.ok;
+  s.f64 = m->forest.backend == Backend::LightGBM;
+  if (s.qs_ok) {
+    const QsDev q = qs_device_view(m);
+    s.thr_cap = q.thr_cap;
+    s.rt_doubles = q.rt_doubles;
+    s.n_views = q.n_views;
+  }
+  s.max_chunk_bytes = m->packed.max_chunk_bytes;
+  s.max_chunk_trees = (int)m->packed.max_chunk_trees;
+  return s;
 }
 
 static void check_model_fits(mrk_model *model, const Program &prog) {
@@ -356,10 +378,10 @@ static void check_model_fits(mrk_model *model, const Program &prog) {
 // pre-pass + assembly into the row-major f64 matrix (ClickthroughQuery's layout); inside a LaunchOn
 static void assemble_matrix(mrk_batch &b, const StoreDev &st, const ProgramDev &pd, void *jit_matrix_fn = nullptr) {
   mrk_ctx *ctx = b.ctx;
-  if (b.fused_ok) {
-    launch_rank_fused(ctx, st, pd, b.view, b.fused_entries, b.fused_vals, b.fused_threads, b.fused_split, jit_matrix_fn ? 1 : b.fused_slices, nullptr, nullptr, true, jit_matrix_fn);
+  if (b.sh.fused_ok) {
+    launch_rank_fused(ctx, st, pd, b.view, b.sh.fused_entries, b.sh.fused_vals, b.sh.fused_threads, b.sh.fused_split, jit_matrix_fn ? 1 : b.sh.fused_slices, nullptr, nullptr, true, jit_matrix_fn);
   } else {
-    launch_prepass(ctx, st, pd, b.view, b.fused_entries, nullptr);
+    launch_prepass(ctx, st, pd, b.view, b.sh.fused_entries, nullptr);
     launch_assemble(ctx, st, pd, b.view);
   }
   for (const Program::NormCol &nc : b.prog->norm_cols)  // schema.norm.scale over the request's column (Normalize.scala:13-45)
@@ -371,7 +393,7 @@ static void assemble_matrix(mrk_batch &b, const StoreDev &st, const ProgramDev &
           launch_normalize_big(ctx, b.view, pd.dim, nc.col, br.item_begin, br.n_items, b.d_norm_order.as<int>(), b.d_sort.p);
         }
     }
-  b.matrix_valid = true;
+  b.ran.matrix_valid = true;
 }
 
 // items per shard of an item-sharded run: ceil(total / count) rounded up to whole scorer tiles
@@ -397,16 +419,6 @@ struct LaunchOn {
   ~LaunchOn() { ctx->launch = ctx->stream; }
 };
 
-// A handful of small requests (mrk_rank and its batching front): everything in ONE launch, results straight into the
-// batch's pinned buffer (rank_device.hpp rank_one_body).  Only for callers that read the results through h_out.
-static bool rank_one_applies(const mrk_batch &b, const mrk_model *model, bool cells) {
-  const Switches &sw = switches();
-  if (!sw.rank_one || !cells || !b.fused_ok || b.n_req < 1 || b.n_req > sw.rank_one_max || b.hb.max_items > QS_TILE_ROWS || b.view.n_overrides > 0) return false;
-  if (b.fused_slices != 1 || b.fused_threads > 512) return false;
-  const QsDev q = qs_device_view(model);
-  return rank_one_lds_bytes(b.fused_entries, b.fused_vals, b.fused_threads, q.thr_cap, q.n_views, model->forest.backend == Backend::LightGBM, (size_t)q.rt_doubles * 8) <= 96 * 1024;
-}
-
 // ---- forests the bit-vector scorer does not take (trees of more than 16 leaves), and any forest under MRK_SCORER=walk: the
 // one-request kernels that walk the trees in the request's workgroup (rank_device.hpp rank_one_walk_body)
 static WalkDev walk_device_view(const mrk_model *m, int cols) {
@@ -426,181 +438,121 @@ static WalkDev walk_device_view(const mrk_model *m, int cols) {
 }
 static_assert(sizeof(TreeRef) == 12 && WALK_TILE_ROWS == QS_TILE_ROWS, "launch_shape.hpp sizes the TreeRef rows and the matrix of rank_one_walk_body");
 
-static size_t walk_one_lds_bytes(const mrk_model *m, int cols, uint32_t tab_entries, int vals_cap, int threads) {
-  return rank_one_walk_lds_bytes(cols, m->forest.backend == Backend::LightGBM, m->packed.max_chunk_bytes, (int)m->packed.max_chunk_trees,
-                                 walk_leaf_trees((int)m->packed.max_chunk_trees), fused_lds_bytes(tab_entries, vals_cap, threads, 0u, 0, true));
-}
-
-// the model is one the walking one-request kernels are for (the serving queue: unless MRK_RANK_ONE_WALK=0)
-static bool walk_one_model(const mrk_model *model) {
-  const Switches &sw = switches();
-  return model && sw.rank_one_walk != 0 && (!model->qs.ok || sw.scorer_walk);
-}
-
-// mrk_rank's one-launch path for such a model: rank_one_applies' conditions, the walk kernel's LDS
-static bool rank_one_walk_applies(const mrk_batch &b, const mrk_model *model) {
-  const Switches &sw = switches();
-  if (!sw.rank_one || sw.rank_one_walk != 1 || !walk_one_model(model) || b.want_matrix || b.prog->normalises() || !b.fused_ok || b.n_req < 1 || b.n_req > sw.rank_one_max ||
-      b.hb.max_items > QS_TILE_ROWS || b.view.n_overrides > 0)
-    return false;
-  if (b.fused_slices != 1 || b.fused_threads > 512 || b.fused_threads < b.hb.max_items) return false;   // (every candidate has a lane that owns its row)
-  return walk_one_lds_bytes(model, b.prog->dim, b.fused_entries, b.fused_vals, b.fused_threads) <= RANK_ONE_LDS_CAP;
-}
-
-// enqueue the pipeline on the batch's stream for batch items [lo, hi); the caller holds the store (StoreAccess)
+// enqueue the pipeline on the batch's stream for batch items [lo, hi); the caller holds the store (StoreAccess).  Which pipeline:
+// rank_plan.hpp plan_rank, asked once.
 static void run_batch(mrk_batch &b, mrk_model *model, int lo, int hi, bool sort, bool direct = false) {
   mrk_ctx *ctx = b.ctx;
   MRK_HIP(hipSetDevice(ctx->device));
   check_model_fits(model, *b.prog);
-  const Switches &sw = switches();
+  const BatchShape &sh = b.sh;
+  const ModelShape ms = shape_of(model);
+  const RankPlan plan = plan_rank(shape_of(b), ms, switches(), lo, hi, sort, direct);
   const int rows = hi - lo;
-  // MRK_RANK_CELLS=0 / MRK_SCORER=walk keep the f64 matrix between assembly and scoring (A/B measurements)
-  // a column normalised across the request (bi- / cross-encoder `norm`) needs every raw value of the request before
-  // any of them can be binned: such models go through the f64 matrix
-  // A SHARD of such a model assembles and normalises the whole batch - every rank holds the whole store, and the
-  // normalised column (one cosine per candidate) is the cheap part of that model - and scores its own slice: the forest
-  // is what the ranks share out.  (Exchanging the raw column instead would put a collective between assembly and scoring.)
-  const bool normalises = b.prog->normalises();
-  const bool whole_matrix = normalises && (lo != 0 || hi != b.total_items);
-  const bool cells = sw.rank_cells && !sw.scorer_walk && model && model->qs.ok && !b.want_matrix && rows > 0 && !normalises;
-  const bool f64 = model && model->forest.backend == Backend::LightGBM;
-  // the kernel specialised for this model (hiprtc, ~7 s the first time): compiled before the launch lock is taken
-  // (the specialised matrix kernel has no op-split form: a split batch of a matrix-scored model runs the interpreting kernel)
-  const bool one = direct && sort && lo == 0 && hi == b.total_items && rank_one_applies(b, model, cells);
-  const bool one_walk = !one && !cells && direct && sort && rows > 0 && lo == 0 && hi == b.total_items && rank_one_walk_applies(b, model);
-  // full batches of small requests: assembly + forest + ordering in the request's workgroup (one launch, phases of different
-  // kinds side by side on every CU)
-  const bool fused_score = !one && sort && lo == 0 && hi == b.total_items && cells && sw.rank_fused_score && b.fused_ok && b.fused_split == 1 &&
-                           b.fused_slices == 1 && b.hb.max_items <= QS_TILE_ROWS && b.view.n_overrides == 0 && b.big.empty() && b.fused_threads <= 256 &&
-                           rank_fused_score_lds_bytes(b.fused_entries, b.fused_vals, b.fused_threads, qs_device_view(model).thr_cap, qs_device_view(model).n_views, f64, (size_t)qs_device_view(model).rt_doubles * 8) <= 64 * 1024;
-  // (the kernels that write the scorer's tile are keyed by the forest's view signature too: their sinks hold it as constants)
-  const QsSignature *sig = cells && sw.thr_stage ? &model->qs_sig : nullptr;
-  // The plain workgroup-per-request kernel keeps its tables in 4-byte entries (table32_device.hpp): a batch with a table they do
-  // not hold (features.hpp compact_table_ok) takes the op-split / sliced kernel at op split 1 and one slice - 8-byte entries,
-  // the same results.  Per launch, not per request; no second copy of the plain kernel, no format switch inside a kernel.
-  const bool plain = b.fused_split == 1 && b.fused_slices == 1, compact = b.hb.compact_tables;
-  void *jit_fn = one_walk ? jit_one_walk_function(*b.prog, f64)
-                 : !cells ? (b.fused_ok && model && b.fused_split == 1 && b.fused_slices == 1 ? jit_matrix_function(*b.prog) : nullptr)  // a model scored from the f64 matrix: the hot path too
-                        : one ? jit_one_function(*b.prog, f64, sig)
-                        : fused_score ? jit_fused_score_function(*b.prog, f64, sig)
-                        : !b.fused_ok ? jit_items_function(*b.prog, f64, sig)
-                        : !plain || !compact ? jit_split_function(*b.prog, f64, sig) : jit_rank_function(*b.prog, f64, sig);
-  void *jit_rt_fn = cells && !one && !fused_score && !b.fused_ok ? jit_items_rt_function(*b.prog, f64, sig) : nullptr;   // the resident-table form of the item-parallel kernel
-  void *jit_prep_fn = cells && !one && !fused_score && !b.fused_ok && b.prog->prep.size() && sw.jit_prepass ? jit_prepass_function(*b.prog) : nullptr;   // (before LaunchOn: a first use may compile)
+  const bool f64 = ms.present && ms.f64;
+  // the kernels specialised for this model (hiprtc, ~7 s the first time): compiled before the launch lock is taken.  nullptr (specialisation
+  // off, a background compile pending): the interpreting kernel of the same path
+  const QsSignature *sig = plan.keyed ? &model->qs_sig : nullptr;
+  void *jit_fn = jit_function(*b.prog, plan.kernel, f64, sig);
+  void *jit_rt_fn = jit_function(*b.prog, plan.items_rt ? JIT_ITEMS_RT : JIT_NONE, f64, sig);
+  void *jit_prep_fn = jit_function(*b.prog, plan.prepass ? JIT_PREPASS : JIT_NONE, f64, sig);
   LaunchOn on(ctx, b.s());
   const StoreDev st = ctx->store->device_view();
   const ProgramDev pd = b.prog->device_view();
   b.fetch_enqueued = false;
-  b.direct_out = false;
-  b.values_ran = b.values_direct = false;
-  b.ran_entry_bytes = b.ran_kernel = 0;
-  b.ran_lds = 0;
-  if (one || one_walk) {
-    b.h_out.reserve(b.out_bytes);
-    uint8_t *h = b.h_out.as<uint8_t>();
-    const OneOut out{(double *)h, (int32_t *)(h + b.out_order_off), (int32_t *)(h + b.out_status_off),
-                     (const int32_t *)(b.d_out.as<uint8_t>() + b.out_status_off) + std::max(b.n_req, 1), std::max(b.n_req, 1)};
-    b.view.item_lo = 0;
-    b.view.item_hi = b.total_items;
-    if (one_walk)
-      launch_rank_one_walk(ctx, st, pd, b.view, b.fused_entries, b.fused_vals, b.fused_threads, b.fused_split, walk_device_view(model, pd.dim), out, f64,
-                           walk_one_lds_bytes(model, pd.dim, b.fused_entries, b.fused_vals, b.fused_threads), jit_fn);
-    else launch_rank_one(ctx, st, pd, b.view, b.fused_entries, b.fused_vals, b.fused_threads, b.fused_split, qs_device_view(model), qs_forest_view(model), out, f64, jit_fn);
-    b.matrix_valid = false;
-    b.direct_out = true;
-    b.ran = true;
-    return;
-  }
-  MRK_HIP(hipMemsetAsync(b.view.status, 0, std::max<size_t>(b.n_req, 1) * 4, b.s()));
-  b.view.item_lo = whole_matrix ? 0 : lo;
-  b.view.item_hi = whole_matrix ? b.total_items : hi;
-  if (fused_score) {
-    const QsDev q = qs_device_view(model);
-    b.d_cells.reserve(std::max<size_t>((size_t)b.n_req * q.n_views * QS_TILE_ROWS * 2, 16));   // one tile per request
-    launch_rank_fused_score(ctx, st, pd, b.view, b.fused_entries, b.fused_vals, b.fused_threads, q, qs_forest_view(model), b.d_cells.as<uint16_t>(), f64, jit_fn);
-    b.matrix_valid = false;
-    b.ran = true;
-    return;
-  }
-  if (cells) {
-    // hot path: the assembled values go straight into the scorer's binned tile; no f64 matrix
-    const QsDev q = qs_device_view(model);
-    const size_t tile_bytes = (size_t)q.n_views * QS_TILE_ROWS * 2;
-    const size_t n_tiles = ((size_t)b.total_items + QS_TILE_ROWS - 1) / QS_TILE_ROWS;
-    b.d_cells.reserve(std::max<size_t>(n_tiles * tile_bytes, 16));
-    if (hi % QS_TILE_ROWS && tile_bytes)  // rows past the last item of the last tile of this range
-      MRK_HIP(hipMemsetAsync(b.d_cells.as<uint8_t>() + (size_t)(hi / QS_TILE_ROWS) * tile_bytes, 0, tile_bytes, b.s()));
-    if (b.fused_ok) {
-      // (jit_fn == nullptr: the interpreting kernel, while a background compile is pending - 8-byte entries as before)
-      b.ran_kernel = !jit_fn ? 0 : plain && compact ? 1 : 2;
-      b.ran_entry_bytes = b.ran_kernel == 1 ? 4 : 8;
-      b.ran_rt_bytes = sig && sig->ok ? (size_t)sig->rt_total * 8 : 0;
-      b.ran_thr_cap = q.thr_cap;
-      b.ran_lds = launch_rank_fused(ctx, st, pd, b.view, b.fused_entries, b.fused_vals, b.fused_threads, b.fused_split, b.fused_slices, &q, b.d_cells.as<uint16_t>(), f64, jit_fn,
-                                    b.ran_rt_bytes, b.ran_entry_bytes, b.ran_kernel == 2);
-    } else {
-      launch_prepass(ctx, st, pd, b.view, b.fused_entries, jit_prep_fn);
-      launch_assemble_cells(ctx, st, pd, b.view, q, b.d_cells.as<uint16_t>(), f64, jit_fn, b.fused_entries, jit_rt_fn, jit_rt_fn ? model->qs_sig.rt_total : 0u);
+  b.ran = {};
+  b.view.item_lo = plan.whole_matrix ? 0 : lo;
+  b.view.item_hi = plan.whole_matrix ? b.total_items : hi;
+  switch (plan.path) {
+    case RankPath::One:
+    case RankPath::OneWalk: {   // (the whole batch; the kernel writes the status words itself, and orders)
+      b.h_out.reserve(b.out_bytes);
+      uint8_t *h = b.h_out.as<uint8_t>();
+      const OneOut out{(double *)h, (int32_t *)(h + b.out_order_off), (int32_t *)(h + b.out_status_off),
+                       (const int32_t *)(b.d_out.as<uint8_t>() + b.out_status_off) + std::max(b.n_req, 1), std::max(b.n_req, 1)};
+      if (plan.path == RankPath::OneWalk)
+        launch_rank_one_walk(ctx, st, pd, b.view, sh.fused_entries, sh.fused_vals, sh.fused_threads, sh.fused_split, walk_device_view(model, pd.dim), out, f64,
+                             one_request_lds_bytes(ms, true, pd.dim, sh.fused_entries, sh.fused_vals, sh.fused_threads), jit_fn);
+      else launch_rank_one(ctx, st, pd, b.view, sh.fused_entries, sh.fused_vals, sh.fused_threads, sh.fused_split, qs_device_view(model), qs_forest_view(model), out, f64, jit_fn);
+      b.ran.direct_out = true;
+      return;
     }
-    b.matrix_valid = false;
-    // lo is a multiple of the tile size: the scorer sees rows [lo, hi) as its rows [0, hi - lo)
-    launch_score_qs_cells(ctx, model, b.d_cells.as<uint16_t>() + (size_t)(lo / QS_TILE_ROWS) * (tile_bytes / 2), rows, b.view.scores + lo);
-  } else {
-    assemble_matrix(b, st, pd, jit_fn);
-    b.matrix_valid = whole_matrix || (lo == 0 && hi == b.total_items);
-    if (model && rows > 0) {
-      launch_score_batch(ctx, model, b.view.matrix + (size_t)lo * pd.dim, rows, pd.dim, b.view.scores + lo, b.view.status, b.view.item_req + lo);
-    } else if (rows > 0) {
-      // NoopModel (ml/rank/NoopRanker.scala:22-26): every score is 0.0
-      MRK_HIP(hipMemsetAsync(b.view.scores + lo, 0, (size_t)rows * 8, b.s()));
+    case RankPath::FusedCells:
+    case RankPath::ItemCells: {
+      // hot path: the assembled values go straight into the scorer's binned tile; no f64 matrix
+      MRK_HIP(hipMemsetAsync(b.view.status, 0, std::max<size_t>(b.n_req, 1) * 4, b.s()));
+      const QsDev q = qs_device_view(model);
+      const size_t tile_bytes = (size_t)q.n_views * QS_TILE_ROWS * 2;
+      const size_t n_tiles = ((size_t)b.total_items + QS_TILE_ROWS - 1) / QS_TILE_ROWS;
+      b.d_cells.reserve(std::max<size_t>(n_tiles * tile_bytes, 16));
+      if (hi % QS_TILE_ROWS && tile_bytes)  // rows past the last item of the last tile of this range
+        MRK_HIP(hipMemsetAsync(b.d_cells.as<uint8_t>() + (size_t)(hi / QS_TILE_ROWS) * tile_bytes, 0, tile_bytes, b.s()));
+      if (plan.path == RankPath::FusedCells) {
+        // (jit_fn == nullptr: the interpreting kernel - 8-byte entries, sized as a split kernel only when it splits)
+        const bool split_kernel = jit_fn && plan.split_kernel;
+        b.ran.kernel = !jit_fn ? 0 : split_kernel ? 2 : 1;
+        b.ran.entry_bytes = jit_fn ? plan.entry_bytes : 8;
+        b.ran.split_sized = sh.fused_split > 1 || sh.fused_slices > 1 || split_kernel;
+        b.ran.rt_bytes = sig && sig->ok ? (size_t)sig->rt_total * 8 : 0;
+        b.ran.thr_cap = q.thr_cap;
+        b.ran.lds = launch_rank_fused(ctx, st, pd, b.view, sh.fused_entries, sh.fused_vals, sh.fused_threads, sh.fused_split, sh.fused_slices, &q, b.d_cells.as<uint16_t>(), f64, jit_fn,
+                                      b.ran.rt_bytes, b.ran.entry_bytes, split_kernel);
+      } else {
+        launch_prepass(ctx, st, pd, b.view, sh.fused_entries, jit_prep_fn);
+        launch_assemble_cells(ctx, st, pd, b.view, q, b.d_cells.as<uint16_t>(), f64, jit_fn, sh.fused_entries, jit_rt_fn, jit_rt_fn ? model->qs_sig.rt_total : 0u);
+      }
+      // lo is a multiple of the tile size: the scorer sees rows [lo, hi) as its rows [0, hi - lo)
+      launch_score_qs_cells(ctx, model, b.d_cells.as<uint16_t>() + (size_t)(lo / QS_TILE_ROWS) * (tile_bytes / 2), rows, b.view.scores + lo);
+      break;
     }
+    case RankPath::Matrix:
+      MRK_HIP(hipMemsetAsync(b.view.status, 0, std::max<size_t>(b.n_req, 1) * 4, b.s()));
+      assemble_matrix(b, st, pd, jit_fn);
+      b.ran.matrix_valid = plan.whole_matrix || (lo == 0 && hi == b.total_items);
+      if (model && rows > 0) {
+        launch_score_batch(ctx, model, b.view.matrix + (size_t)lo * pd.dim, rows, pd.dim, b.view.scores + lo, b.view.status, b.view.item_req + lo);
+      } else if (rows > 0) {
+        // NoopModel (ml/rank/NoopRanker.scala:22-26): every score is 0.0
+        MRK_HIP(hipMemsetAsync(b.view.scores + lo, 0, (size_t)rows * 8, b.s()));
+      }
+      break;
   }
   b.view.item_lo = 0;
   b.view.item_hi = b.total_items;
   if (sort) sort_batch(b);
-  b.ran = true;
 }
 
 static void run_batch(mrk_batch &b, mrk_model *model) { run_batch(b, model, 0, b.total_items, true); }
 
 // The training rows of a batch (TrainBuffer.handleRanking: ItemValue.fromState over the loaded values program) on the batch's
-// stream; the caller holds the store (StoreAccess).  Small requests: ONE launch that writes rows and status words straight
-// into the batch's pinned block (rank_device.hpp rank_values_body) - no forest, no ordering, no copy command.  Anything else
-// (requests sliced over several workgroups or too large for one, per-item overrides, a request-normalised column, a caller
-// that asked for the device matrix, MRK_VALUES_ONE=0): today's assembly launch(es) into the device matrix, fetched by a copy.
-// The specialised kernel is used with or without a model.
+// stream; the caller holds the store (StoreAccess).  One launch into the batch's pinned block - no forest, no ordering, no copy
+// command - or the matrix path's assembly, fetched by a copy: rank_plan.hpp plan_values.  The specialised kernel is used with or
+// without a model.
 static void run_values(mrk_batch &b) {
   mrk_ctx *ctx = b.ctx;
   MRK_HIP(hipSetDevice(ctx->device));
-  const Switches &sw = switches();
+  const BatchShape &sh = b.sh;
+  const ValuesPlan plan = plan_values(shape_of(b), switches());
   const size_t T = (size_t)b.total_items, R = (size_t)std::max(b.n_req, 1);
-  const bool one = sw.values_one && b.fused_ok && b.n_req >= 1 && T > 0 && b.prog->dim > 0 && b.fused_slices == 1 && b.fused_threads <= 512 &&
-                   b.view.n_overrides == 0 && !b.prog->normalises() && !b.want_matrix;
-  // (before LaunchOn: a first use may compile)
-  void *jit_fn = one ? jit_values_function(*b.prog) : b.fused_ok && b.fused_split == 1 && b.fused_slices == 1 ? jit_matrix_function(*b.prog) : nullptr;
+  void *jit_fn = jit_function(*b.prog, plan.kernel, true, nullptr);   // (before LaunchOn: a first use may compile)
   LaunchOn on(ctx, b.s());
   const StoreDev st = ctx->store->device_view();
   const ProgramDev pd = b.prog->device_view();
   b.fetch_enqueued = false;
-  b.direct_out = false;
-  b.values_ran = true;
-  b.values_direct = false;
+  b.ran = {};
+  b.ran.values = true;
   b.view.item_lo = 0;
   b.view.item_hi = b.total_items;
-  if (one) {
+  if (plan.one) {
     b.vals_status_off = align_up(T * (size_t)pd.dim * 8, 256);
     b.h_vals.reserve(b.vals_status_off + 2 * R * 4);
     uint8_t *h = b.h_vals.as<uint8_t>();
     const ValuesOut out{(double *)h, (int32_t *)(h + b.vals_status_off), (const int32_t *)(b.d_out.as<uint8_t>() + b.out_status_off) + R, (int32_t)R};
-    launch_rank_values(ctx, st, pd, b.view, b.fused_entries, b.fused_vals, b.fused_threads, b.fused_split, out, jit_fn);
-    b.matrix_valid = false;
-    b.values_direct = true;
-    b.ran = true;
+    launch_rank_values(ctx, st, pd, b.view, sh.fused_entries, sh.fused_vals, sh.fused_threads, sh.fused_split, out, jit_fn);
+    b.ran.values_direct = true;
     return;
   }
   MRK_HIP(hipMemsetAsync(b.view.status, 0, R * 4, b.s()));
   assemble_matrix(b, st, pd, jit_fn);
-  b.ran = true;
 }
 
 // NoopRanker's answer (ml/rank/NoopRanker.scala:22-26) for a values run: every score 0.0, every request in its own order
@@ -614,7 +566,7 @@ static void fill_noop_outputs(const mrk_batch &b, double *scores, int32_t *order
 // scores + order + status -> the batch's pinned result buffer, one copy (a copy into pageable caller memory is staged by
 // the runtime anyway, and three small copies cost three round trips); asynchronous
 static void enqueue_fetch(mrk_batch &b, bool scores, bool order) {
-  if (b.direct_out || b.values_direct) return;  // the device wrote h_out / h_vals itself
+  if (b.ran.direct_out || b.ran.values_direct) return;  // the device wrote h_out / h_vals itself
   const size_t T = (size_t)b.total_items;
   b.h_out.reserve(b.out_bytes);
   uint8_t *h = b.h_out.as<uint8_t>();
@@ -633,35 +585,31 @@ static void fetch_batch(mrk_batch &b, double *scores, int32_t *order, double *ma
   mrk_ctx *ctx = b.ctx;
   MRK_HIP(hipSetDevice(ctx->device));
   const size_t T = (size_t)b.total_items;
-  if (b.values_direct) {   // the one-launch values kernel: rows and status words are in the batch's pinned block once the stream is idle
+  const int32_t *hs;   // [status of the run: max(n_req, 1)][load status], in pinned memory
+  if (b.ran.values_direct) {   // the one-launch values kernel: rows and status words are in the batch's pinned block once the stream is idle
     MRK_HIP(hipStreamSynchronize(b.s()));
     const uint8_t *h = b.h_vals.as<uint8_t>();
     if (matrix && T && b.prog->dim) memcpy(matrix, h, T * b.prog->dim * 8);
-    const int32_t *hs = (const int32_t *)(h + b.vals_status_off), *hl = hs + std::max(b.n_req, 1);
-    for (int r = 0; r < b.n_req; ++r) b.h_status[(size_t)r] = hs[r] | hl[r];
-    fill_noop_outputs(b, scores, order);
-    if (ctx->profile) {
-      std::lock_guard<std::mutex> lk(ctx->mu);
-      drain_profile_events(ctx);
+    hs = (const int32_t *)(h + b.vals_status_off);
+  } else {
+    if (matrix && T && b.prog->dim && !b.ran.matrix_valid) {
+      // the last run assembled straight into the scorer's tile: materialise the f64 matrix now
+      LaunchOn on(ctx, b.s());
+      assemble_matrix(b, ctx->store->device_view(), b.prog->device_view());
     }
-    return;
+    if (!b.fetch_enqueued) enqueue_fetch(b, scores != nullptr, order != nullptr);
+    b.fetch_enqueued = false;
+    if (matrix && T && b.prog->dim) MRK_HIP(hipMemcpyAsync(matrix, b.d_matrix.p, T * b.prog->dim * 8, hipMemcpyDeviceToHost, b.s()));
+    // (Measured and removed, round 6: a leader of mrk_rank's front sleeping on a hipEventBlockingSync event instead of this polling
+    // wait when several lanes are in flight - 183 k vs 183 k requests/s at 64 callers, 289 k vs 301 k at 128, profiles/r06_e_callers.txt.)
+    MRK_HIP(hipStreamSynchronize(b.s()));
+    const uint8_t *h = b.h_out.as<uint8_t>();
+    if (scores && T) memcpy(scores, h, T * 8);
+    if (order && T) memcpy(order, h + b.out_order_off, T * 4);
+    hs = (const int32_t *)(h + b.out_status_off);
   }
-  if (matrix && T && b.prog->dim && !b.matrix_valid) {
-    // the last run assembled straight into the scorer's tile: materialise the f64 matrix now
-    LaunchOn on(ctx, b.s());
-    assemble_matrix(b, ctx->store->device_view(), b.prog->device_view());
-  }
-  if (!b.fetch_enqueued) enqueue_fetch(b, scores != nullptr, order != nullptr);
-  b.fetch_enqueued = false;
-  if (matrix && T && b.prog->dim) MRK_HIP(hipMemcpyAsync(matrix, b.d_matrix.p, T * b.prog->dim * 8, hipMemcpyDeviceToHost, b.s()));
-  // (Measured and removed, round 6: a leader of mrk_rank's front sleeping on a hipEventBlockingSync event instead of this polling
-  // wait when several lanes are in flight - 183 k vs 183 k requests/s at 64 callers, 289 k vs 301 k at 128, profiles/r06_e_callers.txt.)
-  MRK_HIP(hipStreamSynchronize(b.s()));
-  const uint8_t *h = b.h_out.as<uint8_t>();
-  if (scores && T) memcpy(scores, h, T * 8);
-  if (order && T) memcpy(order, h + b.out_order_off, T * 4);
-  if (b.values_ran) fill_noop_outputs(b, scores, order);   // (a values run launches neither scorer nor sort)
-  const int32_t *hs = (const int32_t *)(h + b.out_status_off), *hl = hs + std::max(b.n_req, 1);
+  if (b.ran.values) fill_noop_outputs(b, scores, order);   // (a values run launches neither scorer nor sort)
+  const int32_t *hl = hs + std::max(b.n_req, 1);
   for (int r = 0; r < b.n_req; ++r) b.h_status[(size_t)r] = hs[r] | hl[r];
   if (ctx->profile) {
     std::lock_guard<std::mutex> lk(ctx->mu);
@@ -691,7 +639,7 @@ int mrk_config_specialize(const char *json, size_t len, const char *model_name, 
   return guard([&] {
     const int kernel = (what >> 8) - 1;  // what = (1 + kernel) << 8 | form: one kernel's translation unit; high byte 0: all kernels
     what &= 0xff;
-    if (!json || !model_name || !needed || (what != 0 && what != 1) || kernel < JIT_ALL || kernel > JIT_ITEMS_RT)  // (the two kernels of forests scored by the tree walk: JIT_ALL shows them, mrk_config_precompile builds them)
+    if (!json || !model_name || !needed || (what != 0 && what != 1) || kernel < JIT_ALL || kernel > JIT_ITEMS_RT || kernel == JIT_UNUSED)  // (the two kernels of forests scored by the tree walk: JIT_ALL shows them, mrk_config_precompile builds them)
       throw StatusError(MRK_ERR_INVALID_ARG, "null argument / unknown `what`");
     Store st;
     std::unique_ptr<Registry> reg = load_config(json, len, st, /*upload=*/false);
@@ -717,7 +665,7 @@ int mrk_config_specialize_values(const char *json, size_t len, const char *model
   return guard([&] {
     const int kernel = (what >> 8) - 1;  // as mrk_config_specialize; the values kernel (1 + JIT_VALUES) included
     what &= 0xff;
-    if (!json || !needed || (what != 0 && what != 1) || kernel < JIT_ALL || kernel > JIT_VALUES) throw StatusError(MRK_ERR_INVALID_ARG, "null argument / unknown `what`");
+    if (!json || !needed || (what != 0 && what != 1) || kernel < JIT_ALL || kernel > JIT_VALUES || kernel == JIT_UNUSED) throw StatusError(MRK_ERR_INVALID_ARG, "null argument / unknown `what`");
     if (mode != MODE_ONLINE && mode != MODE_OFFLINE) throw StatusError(MRK_ERR_INVALID_ARG, "mode must be 0 (online) or 1 (offline)");
     Store st;
     std::unique_ptr<Registry> reg = load_config(json, len, st, /*upload=*/false);
@@ -751,7 +699,7 @@ int mrk_config_specialize_for_model(const char *json, size_t len, const char *mo
   return guard([&] {
     const int kernel = (what >> 8) - 1;
     what &= 0xff;
-    if (!json || !model_name || !needed || (what != 0 && what != 1) || kernel < JIT_ALL || kernel > JIT_ITEMS_RT)  // (the two kernels of forests scored by the tree walk: JIT_ALL shows them, mrk_config_precompile builds them)
+    if (!json || !model_name || !needed || (what != 0 && what != 1) || kernel < JIT_ALL || kernel > JIT_ITEMS_RT || kernel == JIT_UNUSED)  // (the two kernels of forests scored by the tree walk: JIT_ALL shows them, mrk_config_precompile builds them)
       throw StatusError(MRK_ERR_INVALID_ARG, "null argument / unknown `what`");
     bool f64 = true;
     const QsSignature sig = signature_of_bytes(backend, model_bytes, model_len, f64);
@@ -929,6 +877,36 @@ int mrk_debug_fused_shape(int n_req, int max_items, int *out3) {
   out3[2] = s.slices;
   return MRK_OK;
 }
+// rank_plan.hpp through the C ABI, for tests without a device, under the DEFAULT switches but for the three the table varies.
+// in[24] = {n_req, candidates per request, the largest request's table entries, its median values, compact_tables, overrides,
+// want_matrix, normalises, n_prep, dim | model: present, bit-vector image, f64, thr_cap, n_views, rt_doubles, max_chunk_bytes,
+// max_chunk_trees | lo, hi (-1: every item), sort, direct | MRK_RANK_ONE_WALK (-1 unset), MRK_SCORER=walk};
+// out8 = {path (RankPath), kernel (JIT_*, -2 none), items_rt, prepass, keyed, whole_matrix, entry_bytes, split_kernel};
+// values != 0: plan_values instead - out8 = {one launch, kernel}
+int mrk_debug_rank_plan(const int64_t *in, int values, int64_t *out8) {
+  mrk::Switches sw;
+  sw.rank_one_walk = (int)in[22];
+  sw.scorer_walk = in[23] != 0;
+  mrk::BatchShape b;
+  b.n_req = (int)in[0]; b.max_items = (int)in[1]; b.total_items = b.n_req * b.max_items;
+  b.compact_tables = in[4] != 0; b.overrides = in[5] != 0; b.want_matrix = in[6] != 0; b.normalises = in[7] != 0;
+  b.n_prep = (int)in[8]; b.dim = (int)in[9];
+  mrk::fused_batch_shape(b, (uint64_t)in[2], (int)in[3], sw);
+  mrk::ModelShape m;
+  m.present = in[10] != 0; m.qs_ok = in[11] != 0; m.f64 = in[12] != 0;
+  m.thr_cap = (uint32_t)in[13]; m.n_views = (int)in[14]; m.rt_doubles = (uint32_t)in[15];
+  m.max_chunk_bytes = (size_t)in[16]; m.max_chunk_trees = (int)in[17];
+  for (int i = 0; i < 8; ++i) out8[i] = 0;
+  if (values) {
+    const mrk::ValuesPlan v = mrk::plan_values(b, sw);
+    out8[0] = v.one; out8[1] = v.kernel;
+    return MRK_OK;
+  }
+  const mrk::RankPlan p = mrk::plan_rank(b, m, sw, (int)in[18], in[19] < 0 ? b.total_items : (int)in[19], in[20] != 0, in[21] != 0);
+  out8[0] = (int64_t)p.path; out8[1] = p.kernel; out8[2] = p.items_rt; out8[3] = p.prepass; out8[4] = p.keyed; out8[5] = p.whole_matrix;
+  out8[6] = p.entry_bytes; out8[7] = p.split_kernel;
+  return MRK_OK;
+}
 int mrk_debug_scorer_split(int rows, int views, int f64, int n_cus) {
   return mrk::scorer_waves_per_tile(((long long)rows + mrk::QS_TILE_ROWS - 1) / mrk::QS_TILE_ROWS, views, f64 != 0, n_cus, mrk::QS_LEAVES, mrk::QS_TILE_ROWS);
 }
@@ -970,7 +948,7 @@ int mrk_debug_batch_tables(mrk_batch *b, int64_t *out3, uint32_t *caps, int64_t 
     if (!b || !b->prog || !out3) throw StatusError(MRK_ERR_INVALID_ARG, "null argument");
     std::lock_guard<std::mutex> lk(b->bmu);
     const size_t n_prep = b->prog->prep.size(), n = (size_t)b->n_req * n_prep;
-    out3[0] = b->fused_entries; out3[1] = b->n_req; out3[2] = (int64_t)n_prep;
+    out3[0] = b->sh.fused_entries; out3[1] = b->n_req; out3[2] = (int64_t)n_prep;
     if (!caps) return;
     if (n_caps < (int64_t)n || b->hb.prep_out.size() < n) throw StatusError(MRK_ERR_INVALID_ARG, "caps is too short");
     for (size_t i = 0; i < n; ++i) caps[i] = b->hb.prep_out[i].tab_cap;
@@ -981,20 +959,21 @@ int mrk_debug_batch_tables(mrk_batch *b, int64_t *out3, uint32_t *caps, int64_t 
  * (4: the compact form, 8: the wide one, 0: the run had no such launch), the launch's dynamic LDS bytes, the kernel (0 the
  * interpreting one, 1 mrk_jit_rank_cells, 2 mrk_jit_rank_cells_split), 1 if every table of the batch fits the compact entry,
  * then what the LDS was sized from: table entries, median values, threads, threshold staging doubles, resident threshold bytes,
- * 1 if sized for the split kernel} */
+ * 1 if sized for the split kernel}.  The launch's own figures ([0] - [2], [7] - [9]) are what that launch recorded: all 0 after a run
+ * without a fused cells launch (one launch, item-parallel, matrix) - [7] - [9] used to keep an earlier launch's values or, for [9], the batch's shape */
 int mrk_debug_batch_launch(mrk_batch *b, int64_t *out10) {
   return guard([&] {
     if (!b || !out10) throw StatusError(MRK_ERR_INVALID_ARG, "null argument");
     std::lock_guard<std::mutex> lk(b->bmu);
-    out10[0] = b->ran_entry_bytes; out10[1] = (int64_t)b->ran_lds; out10[2] = b->ran_kernel; out10[3] = b->hb.compact_tables ? 1 : 0;
-    out10[4] = b->fused_entries; out10[5] = b->fused_vals; out10[6] = b->fused_threads; out10[7] = b->ran_thr_cap; out10[8] = (int64_t)b->ran_rt_bytes;
-    out10[9] = b->fused_split > 1 || b->fused_slices > 1 || b->ran_kernel == 2 ? 1 : 0;
+    out10[0] = b->ran.entry_bytes; out10[1] = (int64_t)b->ran.lds; out10[2] = b->ran.kernel; out10[3] = b->sh.compact_tables ? 1 : 0;
+    out10[4] = b->sh.fused_entries; out10[5] = b->sh.fused_vals; out10[6] = b->sh.fused_threads; out10[7] = b->ran.thr_cap; out10[8] = (int64_t)b->ran.rt_bytes;
+    out10[9] = b->ran.split_sized ? 1 : 0;
   });
 }
 
 /* not part of include/mrk.h, host only: the arithmetic of the two rules above - out2 = {1 if a table with `insertions` inserted
  * tokens over a column whose largest token id is `max_token` fits the compact entry (features.hpp compact_table_ok), the dynamic
- * LDS bytes of a fused launch (rank.hip fused_lds_bytes)} */
+ * LDS bytes of a fused launch (launch_shape.hpp fused_lds_bytes)} */
 int mrk_debug_fused_lds(int64_t insertions, int64_t max_token, int64_t tab_entries, int64_t vals_cap, int64_t threads, int64_t thr_cap, int64_t rt_bytes,
                         int split, int entry_bytes, int64_t *out2) {
   return guard([&] {
@@ -1374,7 +1353,7 @@ int mrk_values(mrk_ctx *ctx, const char *model_name, int mode, const mrk_request
     b.values = true;
     b.want_matrix = false;
     run_values(b);
-    if (!b.values_direct) {
+    if (!b.ran.values_direct) {
       enqueue_fetch(b, false, false);
       b.fetch_enqueued = true;
     }
@@ -1660,7 +1639,7 @@ int mrk_batch_host_outputs(mrk_batch *batch, const double **scores, const int32_
       batch->fetch_enqueued = true;
     }
     fetch_batch(*batch, nullptr, nullptr, nullptr);  // waits for the batch; status words -> h_status
-    if (batch->values_ran) {   // (a values run launches neither scorer nor sort)
+    if (batch->ran.values) {   // (a values run launches neither scorer nor sort)
       batch->h_out.reserve(batch->out_bytes);
       fill_noop_outputs(*batch, batch->h_out.as<double>(), (int32_t *)(batch->h_out.as<uint8_t>() + batch->out_order_off));
     }
@@ -1918,32 +1897,19 @@ bool serve_fast(mrk_server &srv, const mrk_request *req, double *out_scores, int
   HostBatch &hb = sl.hb;
   resolve_requests(prog, *ctx->store, req, 1, nullptr, hb);
   const int T = hb.total_items;
-  uint32_t vals = 1;
-  while ((int)vals < hb.max_doubles) vals <<= 1;
-  const uint32_t entries = (uint32_t)std::max<uint64_t>(hb.max_req_entries, 1);
-  const QsDev q = qs_device_view(srv.model);
-  if (!hb.overrides.empty() || (int)prog.prep.size() > fused_max_prep() || hb.max_req_entries > (1u << 20) ||
-      (srv.walk ? walk_one_lds_bytes(srv.model, prog.dim, entries, (int)vals, SERVE_THREADS)
-                : rank_one_lds_bytes(entries, (int)vals, SERVE_THREADS, q.thr_cap, q.n_views, srv.f64, (size_t)q.rt_doubles * 8)) > SERVE_LDS)
+  const int vals = median_vals_cap(hb.max_doubles);
+  if (!one_workgroup_takes(shape_of(srv.model), srv.walk, prog.dim, (int)prog.prep.size(), hb.max_items, !hb.overrides.empty(), hb.max_req_entries, vals,
+                           SERVE_THREADS, SERVE_LDS))
     return false;
   // the request's input block: build_batch's arrays, 16-byte aligned
-  size_t off = 0;
-  auto place = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 16); return o; };
-  const size_t o_reqs = place(hb.reqs.size() * sizeof(ReqDev)), o_consts = place(hb.consts.size() * 8), o_irf = place(hb.irf.size() * 4);
-  const size_t o_prep = place(hb.prep_out.size() * sizeof(PrepOut)), o_slot = place((size_t)T * 4), o_ireq = place((size_t)T * 4);
-  if (off > SERVE_IN_CAP) return false;
-  auto put = [&](size_t o, const void *src, size_t bytes) { if (bytes) memcpy(sl.h_in + o, src, bytes); };
-  put(o_reqs, hb.reqs.data(), hb.reqs.size() * sizeof(ReqDev));
-  put(o_consts, hb.consts.data(), hb.consts.size() * 8);
-  put(o_irf, hb.irf.data(), hb.irf.size() * 4);
-  put(o_prep, hb.prep_out.data(), hb.prep_out.size() * sizeof(PrepOut));
-  put(o_slot, hb.item_slot.data(), (size_t)T * 4);
-  put(o_ireq, hb.item_req.data(), (size_t)T * 4);
+  const InputLayout in(hb, 16);
+  if (in.bytes > SERVE_IN_CAP) return false;
+  in.fill(sl.h_in, hb);
   ServeCtl &ctl = *sl.ctl;
-  ctl.in_bytes = (uint32_t)std::max<size_t>(off, 16);
-  ctl.o_reqs = (uint32_t)o_reqs; ctl.o_consts = (uint32_t)o_consts; ctl.o_irf = (uint32_t)o_irf;
-  ctl.o_prep = (uint32_t)o_prep; ctl.o_slot = (uint32_t)o_slot; ctl.o_ireq = (uint32_t)o_ireq;
-  ctl.total_items = (uint32_t)T; ctl.tab_entries = entries; ctl.vals_cap = vals; ctl.mode = 4;
+  ctl.in_bytes = (uint32_t)in.bytes;
+  ctl.o_reqs = (uint32_t)in.o_reqs; ctl.o_consts = (uint32_t)in.o_consts; ctl.o_irf = (uint32_t)in.o_irf;
+  ctl.o_prep = (uint32_t)in.o_prep; ctl.o_slot = (uint32_t)in.o_slot; ctl.o_ireq = (uint32_t)in.o_ireq;
+  ctl.total_items = (uint32_t)T; ctl.tab_entries = table_entries(hb.max_req_entries); ctl.vals_cap = (uint32_t)vals; ctl.mode = 4;
   const uint32_t seq = ++sl.seq;
   if (seq == 0xffffffffu) sl.seq = 0;  // (never: 4 G requests through one slot)
   const auto h1 = std::chrono::steady_clock::now();
@@ -2073,13 +2039,14 @@ int mrk_serve_start(mrk_ctx *ctx, mrk_model *model, const char *model_name, int 
     const Program &prog = locked_program(ctx, model_name);
     // a forest of larger trees is walked in the request's workgroup (rank_serve_walk_body) when its matrix, its largest chunk and
     // the chunk's leaf values fit the workgroup's LDS next to each other; MRK_RANK_ONE_WALK=0: refused, as before that kernel
-    const bool walk = walk_one_model(model);
+    const ModelShape ms = shape_of(model);
+    const bool walk = walk_one_model(ms, switches());
     if (!model->qs.ok && !walk) throw StatusError(MRK_ERR_UNSUPPORTED, "the serving queue scores with the bit-vector scorer (trees of <= 16 leaves); use mrk_rank for this model");
     check_model_fits(model, prog);
     if (walk) {
-      const bool wf64 = model->forest.backend == Backend::LightGBM;
-      const int lt = walk_leaf_trees((int)model->packed.max_chunk_trees);
-      const size_t need = rank_one_walk_lds_bytes(prog.dim, wf64, model->packed.max_chunk_bytes, (int)model->packed.max_chunk_trees, lt, 0);
+      const bool wf64 = ms.f64;
+      const int lt = walk_leaf_trees(ms.max_chunk_trees);
+      const size_t need = rank_one_walk_lds_bytes(prog.dim, wf64, ms.max_chunk_bytes, ms.max_chunk_trees, lt, 0);   // (the forest alone: a request's tables come on top)
       if (need > SERVE_LDS) {
         if (model->qs.ok) throw StatusError(MRK_ERR_UNSUPPORTED, "MRK_SCORER=walk: this model's matrix and chunk do not fit the serving workgroup's LDS");
         throw StatusError(MRK_ERR_UNSUPPORTED, "the serving queue walks this forest in one workgroup's LDS (" + std::to_string(SERVE_LDS) + " bytes) and it does not fit: matrix " +
@@ -2096,12 +2063,12 @@ int mrk_serve_start(mrk_ctx *ctx, mrk_model *model, const char *model_name, int 
     srv->model = model;
     srv->model_name = model_name;
     srv->prog = &prog;
-    srv->f64 = model->forest.backend == Backend::LightGBM;
+    srv->f64 = ms.f64;
     srv->idle_ticks = (uint64_t)std::max(1, switches().serve_idle_us) * 100ull;  // wall_clock64: 100 MHz
     srv->life_ticks = (uint64_t)std::max(1, switches().serve_life_us) * 100ull;
     srv->walk = walk;
-    srv->jit_fn = walk ? jit_serve_walk_function(prog, srv->f64)
-                       : jit_serve_function(prog, srv->f64, switches().thr_stage ? &model->qs_sig : nullptr);  // warm-up: the compile happens here, not under the first request
+    // warm-up: the compile happens here, not under the first request
+    srv->jit_fn = jit_function(prog, walk ? JIT_SERVE_WALK : JIT_SERVE, srv->f64, !walk && switches().thr_stage ? &model->qs_sig : nullptr);
     srv->front_ns = (int64_t)switches().serve_overload_ms * 1000000;
     // A resident kernel holds its stream's hardware queue for as long as it stays, and streams that share a hardware queue wait
     // for each other: round 5's "collapse at 32 callers" (p99 76 ms) was a slot whose stream had landed behind another slot's

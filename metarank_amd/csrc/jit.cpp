@@ -171,11 +171,6 @@ std::string jit_source(const Program &prog, bool f64, int kernel, const QsSignat
     s += "extern \"C\" __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2)))\nmrk_jit_rank_one"
          "(mrk::StoreDev st, mrk::BatchDev b, uint32_t tab_entries, int vals_cap, mrk::QsDev q, mrk::QsForestDev f, int mode, mrk::OneOut out) {\n"
          "  mrk::rank_one_body<" + b64 + ", " + qs + ">(st, mrk::JitProg{}, b, tab_entries, vals_cap, q, f, mode, out);\n}\n";
-  // full batches of small requests: assembly + forest + ordering in the request's workgroup (rank_fused_score_body)
-  if (kernel == JIT_ALL || kernel == JIT_FUSED_SCORE)
-    s += "extern \"C\" __global__ void __launch_bounds__(256)" + attr + "\nmrk_jit_rank_fused_score"
-         "(mrk::StoreDev st, mrk::BatchDev b, uint32_t tab_entries, int vals_cap, mrk::QsDev q, mrk::QsForestDev f, uint16_t *cells) {\n"
-         "  mrk::rank_fused_score_body<" + b64 + ", " + qs + ">(st, mrk::JitProg{}, b, tab_entries, vals_cap, q, f, cells);\n}\n";
   // the pre-pass of requests too large for one workgroup's assembly (config 4: ONE workgroup per request builds the tables the
   // item-parallel kernel reads; on the critical path of the request, so no register cap)
   if ((kernel == JIT_ALL && f64) || kernel == JIT_PREPASS)
@@ -251,7 +246,9 @@ struct JitKernels {
   std::map<std::string, std::unique_ptr<JitSlotSet>> by_sig;
 };
 
-const char *const JIT_KERNEL_NAME[JIT_KERNELS] = {"mrk_jit_rank_cells", "mrk_jit_rank_cells_split", "mrk_jit_rank_matrix", "mrk_jit_assemble_cells", "mrk_jit_rank_one", "mrk_jit_rank_serve", "mrk_jit_rank_fused_score", "mrk_jit_prepass", "mrk_jit_assemble_cells_rt", "mrk_jit_rank_one_walk", "mrk_jit_rank_serve_walk", "mrk_jit_rank_values"};
+const char *const JIT_KERNEL_NAME[JIT_KERNELS] = {"mrk_jit_rank_cells", "mrk_jit_rank_cells_split", "mrk_jit_rank_matrix", "mrk_jit_assemble_cells", "mrk_jit_rank_one", "mrk_jit_rank_serve", nullptr, "mrk_jit_prepass", "mrk_jit_assemble_cells_rt", "mrk_jit_rank_one_walk", "mrk_jit_rank_serve_walk", "mrk_jit_rank_values"};
+// (index 6, JIT_UNUSED, has no kernel: the number stays taken so that cache slots and mrk_config_precompile's mask bits keep their meaning)
+static inline bool jit_unused(int kernel) { return !JIT_KERNEL_NAME[kernel]; }
 // a kernel that exists only with a forest signature: no program-only stand-in (the caller falls back to another KERNEL meanwhile)
 static inline bool jit_needs_sig(int kernel) { return kernel == JIT_ITEMS_RT; }
 // the resident-table kernel: every table in LDS (<= 64 KB of thresholds leaves room for a request's hash tables and a second workgroup)
@@ -397,7 +394,7 @@ static void *jit_function_locked(const Program &prog, int kernel, bool f64, bool
         void *fallback = nullptr;
         if (keyed && !no_compile) {
           for (int kn = 0; kn < JIT_KERNELS; ++kn) {
-            if (jit_needs_sig(kn) || jit_walk_kind(kn)) continue;
+            if (jit_unused(kn) || jit_needs_sig(kn) || jit_walk_kind(kn)) continue;
             void *f = jit_function_locked(prog, kn, jit_program_only(kn) ? true : f64, false, nullptr, true);
             if (kn == kernel) fallback = f;
           }
@@ -446,8 +443,9 @@ static void *jit_function_locked(const Program &prog, int kernel, bool f64, bool
   return (void *)sl.fn;
 }
 
-static void *jit_function(const Program &prog, int kernel, bool f64, const QsSignature *sig, bool wait = false) {
-  if (jit_mode() == 0) return nullptr;
+void *jit_function(const Program &prog, int kernel, bool f64, const QsSignature *sig) {
+  if (jit_mode() == 0 || kernel < 0 || kernel >= JIT_KERNELS || jit_unused(kernel)) return nullptr;   // (JIT_NONE: no kernel asked for)
+  const bool wait = kernel == JIT_SERVE || kernel == JIT_SERVE_WALK;   // mrk_serve_start IS the warm-up
   std::lock_guard<std::mutex> lk(prog.jit_mu);
   return jit_function_locked(prog, kernel, f64, wait, sig, false);
 }
@@ -457,7 +455,7 @@ static void *jit_function(const Program &prog, int kernel, bool f64, const QsSig
 int jit_precompile(const Program &prog, bool f64, unsigned kernel_mask, const std::string &dir, const QsSignature *sig) {
   int compiled = 0;
   for (int k = 0; k < JIT_KERNELS; ++k) {
-    if (!(kernel_mask & (1u << k))) continue;
+    if (!(kernel_mask & (1u << k)) || jit_unused(k)) continue;
     const bool kf64 = jit_program_only(k) ? true : f64;
     if (jit_needs_sig(k) && !jit_items_rt_applies(sig)) continue;
     const std::string src = jit_source(prog, kf64, k, switches().jit_sig ? sig : nullptr);
@@ -476,23 +474,6 @@ int jit_precompile(const Program &prog, bool f64, unsigned kernel_mask, const st
   }
   return compiled;
 }
-
-void *jit_rank_function(const Program &prog, bool f64, const QsSignature *sig) { return jit_function(prog, JIT_RANK, f64, sig); }
-// the item-parallel kernel (nullptr under the same conditions)
-void *jit_items_function(const Program &prog, bool f64, const QsSignature *sig) { return jit_function(prog, JIT_ITEMS, f64, sig); }
-void *jit_items_rt_function(const Program &prog, bool f64, const QsSignature *sig) { return jit_function(prog, JIT_ITEMS_RT, f64, sig); }
-// the op-split / sliced form of the fused kernel (small batches, few large requests)
-void *jit_split_function(const Program &prog, bool f64, const QsSignature *sig) { return jit_function(prog, JIT_SPLIT, f64, sig); }
-// the f64-matrix form of the fused kernel
-void *jit_matrix_function(const Program &prog) { return jit_function(prog, JIT_MATRIX, true, nullptr); }
-void *jit_prepass_function(const Program &prog) { return jit_function(prog, JIT_PREPASS, true, nullptr); }
-void *jit_values_function(const Program &prog) { return jit_function(prog, JIT_VALUES, true, nullptr); }
-// the one-launch kernel of small requests
-void *jit_one_function(const Program &prog, bool f64, const QsSignature *sig) { return jit_function(prog, JIT_ONE, f64, sig); }
-void *jit_one_walk_function(const Program &prog, bool f64) { return jit_function(prog, JIT_ONE_WALK, f64, nullptr); }
-void *jit_serve_walk_function(const Program &prog, bool f64) { return jit_function(prog, JIT_SERVE_WALK, f64, nullptr, /*wait=*/true); }  // mrk_serve_start IS the warm-up
-void *jit_fused_score_function(const Program &prog, bool f64, const QsSignature *sig) { return jit_function(prog, JIT_FUSED_SCORE, f64, sig); }
-void *jit_serve_function(const Program &prog, bool f64, const QsSignature *sig) { return jit_function(prog, JIT_SERVE, f64, sig, /*wait=*/true); }  // mrk_serve_start IS the warm-up
 
 // "<kernel name> <key>\n" for every specialised kernel of `prog` that is loaded (measurement provenance: which code ran)
 std::string jit_loaded_keys(const Program &prog) {

@@ -3,6 +3,7 @@
 #pragma once
 #include <algorithm>
 #include <cstddef>
+#include <cstdint>
 
 namespace mrk {
 
@@ -72,13 +73,38 @@ inline int scorer_waves_per_tile(long long n_tiles, int V, bool f64, int n_cus, 
   return std::max(nw, fill);
 }
 
+// Dynamic LDS of the workgroup-per-request kernels (rank_device.hpp rank_fused_body):
+//   [tables][median values: vals_cap x 8 B][PrepOut x 32][96 ints][16 B][max(threshold staging, resident thresholds)]
+// (the device code's constants as plain numbers; rank.hip asserts that they are the same)
+// thr_cap: doubles per threshold staging buffer (QsDev::thr_cap; HOST_QS_LDS_THR = the largest any model needs)
+// rt_bytes: the forest's compact threshold tables when the kernel that runs may keep them resident (the region then holds whichever
+// the kernel's sink uses - staging buffers or the resident copy - so it is sized for both)
+// entry_bytes: of one hash-table entry in the kernel that runs - 4 in mrk_jit_rank_cells (table32_device.hpp), 8 everywhere else;
+// the tables' region is rounded up to 8 bytes (the median values behind it are doubles)
+constexpr int HOST_FUSED_MAX_PREP = 32, HOST_QS_LEAVES = 16;
+constexpr uint32_t HOST_QS_LDS_THR = 256;
+constexpr size_t HOST_FUSED_LDS_FIXED = HOST_FUSED_MAX_PREP * 24 + 96 * 4 + 16, HOST_FUSED_RT_MAX = 8192, HOST_FUSED_RT_MAX_SPLIT = 20480;
+constexpr int WALK_TILE_ROWS = 128;   // = QS_TILE_ROWS
+inline size_t fused_lds_bytes(uint32_t tab_entries, int vals_cap, int threads, uint32_t thr_cap, size_t rt_bytes, bool split, int entry_bytes = 8) {
+  const size_t staging = (size_t)((threads + 63) / 64) * 2 * thr_cap * 8;  // two buffers per wavefront
+  return (((size_t)tab_entries * (size_t)entry_bytes + 7) & ~(size_t)7) + (size_t)vals_cap * 8 + HOST_FUSED_LDS_FIXED +
+         std::max(staging, rt_bytes <= (split ? HOST_FUSED_RT_MAX_SPLIT : HOST_FUSED_RT_MAX) ? rt_bytes : 0);
+}
+// ... of the one-launch values kernel: [status word, 16 B][the regions above, no threshold staging]
+inline size_t rank_values_lds_bytes(uint32_t tab_entries, int vals_cap, int threads) { return 16 + fused_lds_bytes(tab_entries, vals_cap, threads, 0u, 0, true); }
+// ... of the one-launch kernel: [slab][status word][max(assembly regions, scoring regions)]
+inline size_t rank_one_lds_bytes(uint32_t tab_entries, int vals_cap, int threads, uint32_t thr_cap, int n_views, bool f64, size_t rt_bytes) {
+  const size_t nw = (size_t)threads / 64;
+  const size_t scoring = 8 * nw * (HOST_QS_LEAVES * (f64 ? 8 : 4) + WALK_TILE_ROWS) + WALK_TILE_ROWS * 8;
+  return (size_t)n_views * WALK_TILE_ROWS * 2 + 16 + std::max(fused_lds_bytes(tab_entries, vals_cap, threads, thr_cap, rt_bytes, true), scoring);
+}
+
 // LDS of the one-request kernel of forests the bit-vector scorer does not take (rank_device.hpp rank_one_walk_body):
 //   [matrix: cols x 128 rows x (8 | 4) B][status word, 16 B][max(assembly regions, scoring regions)]
 // scoring regions = the largest chunk of the tree-walk image (rounded up to 16 B) + its TreeRef rows (12 B a tree, rounded up) +
 // the leaf values of `leaf_trees` trees x 128 rows x (8 | 4) B (at least the 1 KB the 128 sort keys take there afterwards).
 // A chunk's trees are walked walk_leaf_trees() at a time: 24 KB of 16-leaf LightGBM trees are 65 trees, whose leaf values alone
 // (65 KB) would push a 24-column model past the 96 KB the one-launch kernels keep to; 32 trees are 4 rounds of 8 wavefronts x WALK_U.
-constexpr int WALK_TILE_ROWS = 128;
 constexpr int WALK_LEAF_TREES_MAX = 32;
 inline int walk_leaf_trees(int chunk_trees) { return std::max(1, std::min(chunk_trees, WALK_LEAF_TREES_MAX)); }
 inline size_t rank_one_walk_matrix_bytes(int cols, bool f64) { return (size_t)std::max(cols, 0) * WALK_TILE_ROWS * (f64 ? 8 : 4); }
@@ -89,6 +115,6 @@ inline size_t rank_one_walk_scoring_bytes(bool f64, size_t chunk_bytes, int chun
 inline size_t rank_one_walk_lds_bytes(int cols, bool f64, size_t chunk_bytes, int chunk_trees, int leaf_trees, size_t assembly_bytes) {
   return rank_one_walk_matrix_bytes(cols, f64) + 16 + std::max(assembly_bytes, rank_one_walk_scoring_bytes(f64, chunk_bytes, chunk_trees, leaf_trees));
 }
-constexpr size_t RANK_ONE_LDS_CAP = 96 * 1024;   // what mrk_rank's one-launch kernels keep to (capi_rank.cpp rank_one_applies)
+constexpr size_t RANK_ONE_LDS_CAP = 96 * 1024;   // what mrk_rank's one-launch kernels keep to (rank_plan.hpp plan_rank)
 
 }  // namespace mrk

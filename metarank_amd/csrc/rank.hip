@@ -25,6 +25,7 @@
 #include <mutex>
 #include <utility>
 
+#include "launch_shape.hpp"
 #include "rank_device.hpp"
 #include "sort_device.hpp"
 #include "runtime.hpp"
@@ -78,13 +79,6 @@ template <bool F64>
 __global__ void __launch_bounds__(512)
 rank_one_kernel(StoreDev st, ProgramDev prog, BatchDev b, uint32_t tab_entries, int vals_cap, QsDev q, QsForestDev f, int mode, OneOut out) {
   rank_one_body<F64>(st, prog, b, tab_entries, vals_cap, q, f, mode, out);
-}
-
-// full batches of small requests: assembly, forest and ordering in the request's workgroup (rank_device.hpp rank_fused_score_body)
-template <bool F64>
-__global__ void __launch_bounds__(256)
-rank_fused_score_kernel(StoreDev st, ProgramDev prog, BatchDev b, uint32_t tab_entries, int vals_cap, QsDev q, QsForestDev f, uint16_t *cells) {
-  rank_fused_score_body<F64>(st, prog, b, tab_entries, vals_cap, q, f, cells);
 }
 
 // the persistent form: one workgroup serves the requests published in its slot (rank_device.hpp rank_serve_body)
@@ -264,6 +258,23 @@ normalize_kernel(BatchDev b, int dim, int col, int mode) {
 
 void launch_big_sort(mrk_ctx *ctx, hipStream_t stream, const SortSrc &src, int n, int *out_order, void *scratch);  // bigsort.hip
 
+// A specialised kernel (a hipFunction_t of jit.cpp) with its arguments, by value, in the kernel's parameter order.
+template <typename... Args>
+static void launch_jit(void *jit_fn, unsigned grid, unsigned threads, size_t lds, hipStream_t stream, Args... a) {
+  void *args[] = {(void *)&a...};
+  MRK_HIP(hipModuleLaunchKernel((hipFunction_t)jit_fn, grid, 1, 1, threads, 1, 1, (unsigned)lds, stream, args, nullptr));
+}
+
+// The interpreting kernel of the scorer's precision: `k64` for f64 leaves, `k32` for f32.  optin: the launch may ask for more than
+// 64 KB of dynamic LDS.
+template <typename K, typename... Args>
+static void launch_f64_or_f32(mrk_ctx *ctx, bool f64, K k64, K k32, bool optin, unsigned grid, unsigned threads, size_t lds, hipStream_t stream, Args... a) {
+  const K k = f64 ? k64 : k32;
+  if (optin) lds_optin(ctx, (const void *)k);
+  hipLaunchKernelGGL(k, dim3(grid), dim3(threads), lds, stream, a...);
+  MRK_HIP(hipGetLastError());
+}
+
 // jit_fn: mrk_jit_prepass of this program (jit.cpp), or nullptr = the kernel that interprets the program
 void launch_prepass(mrk_ctx *ctx, const StoreDev &st, const ProgramDev &prog, const BatchDev &b, uint32_t max_req_entries, void *jit_fn) {
   if (b.n_req <= 0 || prog.n_prep <= 0) return;
@@ -274,10 +285,7 @@ void launch_prepass(mrk_ctx *ctx, const StoreDev &st, const ProgramDev &prog, co
   ScopedKernelTimer timer(ctx, "prepass");
   // (a module function keeps the default 64 KB limit on static + dynamic LDS: 33 KB are static here)
   if (jit_fn && (size_t)lds_entries * 8 <= 30 * 1024) {
-    StoreDev a_st = st;
-    BatchDev a_b = b;
-    void *args[] = {&a_st, &a_b, &lds_entries};
-    MRK_HIP(hipModuleLaunchKernel((hipFunction_t)jit_fn, (unsigned)b.n_req, 1, 1, PREP_THREADS, 1, 1, (unsigned)((size_t)lds_entries * 8), ctx->launch, args, nullptr));
+    launch_jit(jit_fn, (unsigned)b.n_req, PREP_THREADS, (size_t)lds_entries * 8, ctx->launch, st, b, lds_entries);
   } else {
     hipLaunchKernelGGL(prepass_kernel, dim3(b.n_req), dim3(PREP_THREADS), (size_t)lds_entries * 8, ctx->launch, st, prog, b, lds_entries);
   }
@@ -302,10 +310,7 @@ void launch_assemble(mrk_ctx *ctx, const StoreDev &st, const ProgramDev &prog, c
 static void launch_override_cells(mrk_ctx *ctx, const BatchDev &b, const QsDev &q, uint16_t *cells, bool f64) {
   if (b.n_overrides <= 0) return;
   ScopedKernelTimer timer(ctx, "override");
-  const dim3 grid((b.n_overrides + 255) / 256);
-  if (f64) hipLaunchKernelGGL(override_cells_kernel<true>, grid, dim3(256), 0, ctx->launch, b, q, cells);
-  else hipLaunchKernelGGL(override_cells_kernel<false>, grid, dim3(256), 0, ctx->launch, b, q, cells);
-  MRK_HIP(hipGetLastError());
+  launch_f64_or_f32(ctx, f64, override_cells_kernel<true>, override_cells_kernel<false>, false, (unsigned)(b.n_overrides + 255) / 256, 256, 0, ctx->launch, b, q, cells);
 }
 
 // assembly straight into the scorer's binned tile (tables from a previous launch_prepass); jit_fn: the specialised
@@ -330,46 +335,28 @@ void launch_assemble_cells(mrk_ctx *ctx, const StoreDev &st, const ProgramDev &p
     // resident workgroups per CU: by LDS (160 KB) and by wavefronts (16 at 128 VGPRs)
     const int per_cu = std::max(1, std::min((int)((160 * 1024) / std::max<size_t>(lds, 1)), 16 / (threads / 64)));
     const unsigned grid = (unsigned)std::min(n_blocks, per_cu * ctx->n_cus);
-    StoreDev a_st = st;
-    BatchDev a_b = b;
-    QsDev a_q = q;
-    void *args[] = {&a_st, &a_b, &a_q, &cells, &lds_entries};
-    MRK_HIP(hipModuleLaunchKernel((hipFunction_t)jit_rt_fn, grid, 1, 1, (unsigned)threads, 1, 1, (unsigned)lds, ctx->launch, args, nullptr));
+    launch_jit(jit_rt_fn, grid, (unsigned)threads, lds, ctx->launch, st, b, q, cells, lds_entries);
     launch_override_cells(ctx, b, q, cells, f64);
     return;
   }
   {
     ScopedKernelTimer timer(ctx, "assemble");
-    const dim3 grid((b.item_hi - b.item_lo + ASM_THREADS - 1) / ASM_THREADS);
+    const unsigned grid = (unsigned)(b.item_hi - b.item_lo + ASM_THREADS - 1) / ASM_THREADS;
     // 16 KB of static threshold staging + <= 24 KB of tables: four workgroups per CU, what 128 VGPRs allow anyway
     constexpr uint32_t ITEMS_LDS_TABLE_BYTES = 24 * 1024;
     uint32_t lds_entries = switches().items_lds && prog.n_prep > 0 && (uint64_t)max_req_entries * 8 <= ITEMS_LDS_TABLE_BYTES ? max_req_entries : 0u;
     const size_t lds = (size_t)lds_entries * 8;
-    if (jit_fn) {  // the kernel specialised for this model's program (jit.cpp)
-      StoreDev a_st = st;
-      BatchDev a_b = b;
-      QsDev a_q = q;
-      void *args[] = {&a_st, &a_b, &a_q, &cells, &lds_entries};
-      MRK_HIP(hipModuleLaunchKernel((hipFunction_t)jit_fn, grid.x, 1, 1, ASM_THREADS, 1, 1, (unsigned)lds, ctx->launch, args, nullptr));
-    } else if (f64) hipLaunchKernelGGL(assemble_cells_kernel<true>, grid, dim3(ASM_THREADS), lds, ctx->launch, st, prog, b, q, cells, lds_entries);
-    else hipLaunchKernelGGL(assemble_cells_kernel<false>, grid, dim3(ASM_THREADS), lds, ctx->launch, st, prog, b, q, cells, lds_entries);
-    MRK_HIP(hipGetLastError());
+    if (jit_fn) launch_jit(jit_fn, grid, ASM_THREADS, lds, ctx->launch, st, b, q, cells, lds_entries);   // the kernel specialised for this model's program (jit.cpp)
+    else launch_f64_or_f32(ctx, f64, assemble_cells_kernel<true>, assemble_cells_kernel<false>, false, grid, ASM_THREADS, lds, ctx->launch, st, prog, b, q, cells, lds_entries);
   }
   launch_override_cells(ctx, b, q, cells, f64);
 }
 
-// thr_cap: doubles per threshold staging buffer (QsDev::thr_cap; QS_LDS_THR = the largest any model needs)
-// rt_bytes: the forest's compact threshold tables when the kernel that runs may keep them resident (rank_device.hpp FUSED_RT_MAX_BYTES;
-// the region then holds whichever the kernel's sink uses - staging buffers or the resident copy - so it is sized for both)
-// entry_bytes: of one hash-table entry in the kernel that runs - 4 in mrk_jit_rank_cells (table32_device.hpp), 8 everywhere else;
-// the tables' region is rounded up to 8 bytes (the median values behind it are doubles)
-size_t fused_lds_bytes(uint32_t tab_entries, int vals_cap, int threads, uint32_t thr_cap, size_t rt_bytes, bool split, int entry_bytes = 8) {
-  const size_t staging = (size_t)((threads + 63) / 64) * 2 * thr_cap * 8;  // two buffers per wavefront
-  return (((size_t)tab_entries * (size_t)entry_bytes + 7) & ~(size_t)7) + (size_t)vals_cap * 8 + FUSED_MAX_PREP * sizeof(PrepOut) + PREP_INTS * sizeof(int) +
-         16 + std::max(staging, rt_bytes <= (split ? FUSED_RT_MAX_BYTES_SPLIT : FUSED_RT_MAX_BYTES) ? rt_bytes : 0);  // (16-B aligned)
-}
-size_t fused_rt_max_bytes() { return FUSED_RT_MAX_BYTES_SPLIT; }
-int fused_max_prep() { return FUSED_MAX_PREP; }
+// launch_shape.hpp sizes these kernels' dynamic LDS (fused_lds_bytes, rank_one_lds_bytes) with the device code's constants as plain numbers
+static_assert(HOST_FUSED_MAX_PREP == FUSED_MAX_PREP && HOST_FUSED_LDS_FIXED == FUSED_MAX_PREP * sizeof(PrepOut) + PREP_INTS * sizeof(int) + 16 &&
+                  HOST_FUSED_RT_MAX == FUSED_RT_MAX_BYTES && HOST_FUSED_RT_MAX_SPLIT == FUSED_RT_MAX_BYTES_SPLIT && HOST_QS_LDS_THR == QS_LDS_THR &&
+                  HOST_QS_LEAVES == QS_LEAVES && WALK_TILE_ROWS == QS_TILE_ROWS,
+              "launch_shape.hpp and rank_device.hpp disagree about the layout of a request workgroup's LDS");
 
 // pre-pass + assembly of every request in one launch (one workgroup per request, tables in LDS).
 // cells == nullptr: write the f64 matrix; else write the binned tile.
@@ -387,24 +374,14 @@ size_t launch_rank_fused(mrk_ctx *ctx, const StoreDev &st, const ProgramDev &pro
   if (switches().fused_lds_min > 0) lds = std::max(lds, (size_t)switches().fused_lds_min);  // experiments: cap the kernel's residency (co-residency with the scorer)
   {
     ScopedKernelTimer timer(ctx, "assemble");
-    if (!jit_fn) lds_optin(ctx, !cells ? (const void *)rank_fused_matrix_kernel : f64 ? (const void *)rank_fused_cells_kernel<true> : (const void *)rank_fused_cells_kernel<false>);
-    if (!cells && jit_fn) {  // mrk_jit_rank_matrix
-      StoreDev a_st = st;
-      BatchDev a_b = b;
-      int a_vals = vals_cap;
-      void *args[] = {&a_st, &a_b, &tab_entries, &a_vals, &mode};   // mrk_jit_rank_matrix (no op-split form: the caller asked for none)
-      MRK_HIP(hipModuleLaunchKernel((hipFunction_t)jit_fn, grid, 1, 1, (unsigned)threads, 1, 1, (unsigned)lds, ctx->launch, args, nullptr));
-    } else if (cells && jit_fn) {
-      StoreDev a_st = st;
-      BatchDev a_b = b;
-      QsDev a_q = *q;
-      int a_vals = vals_cap;
-      void *args[] = {&a_st, &a_b, &tab_entries, &a_vals, &a_q, &cells, &mode};
-      MRK_HIP(hipModuleLaunchKernel((hipFunction_t)jit_fn, grid, 1, 1, (unsigned)threads, 1, 1, (unsigned)lds, ctx->launch, args, nullptr));
-    } else if (!cells) hipLaunchKernelGGL(rank_fused_matrix_kernel, dim3(grid), dim3(threads), lds, ctx->launch, st, prog, b, tab_entries, vals_cap, mode);
-    else if (f64) hipLaunchKernelGGL(rank_fused_cells_kernel<true>, dim3(grid), dim3(threads), lds, ctx->launch, st, prog, b, tab_entries, vals_cap, *q, cells, mode);
-    else hipLaunchKernelGGL(rank_fused_cells_kernel<false>, dim3(grid), dim3(threads), lds, ctx->launch, st, prog, b, tab_entries, vals_cap, *q, cells, mode);
-    MRK_HIP(hipGetLastError());
+    if (!cells && jit_fn) launch_jit(jit_fn, grid, (unsigned)threads, lds, ctx->launch, st, b, tab_entries, vals_cap, mode);   // mrk_jit_rank_matrix (no op-split form: the caller asked for none)
+    else if (jit_fn) launch_jit(jit_fn, grid, (unsigned)threads, lds, ctx->launch, st, b, tab_entries, vals_cap, *q, cells, mode);
+    else if (cells) launch_f64_or_f32(ctx, f64, rank_fused_cells_kernel<true>, rank_fused_cells_kernel<false>, true, grid, (unsigned)threads, lds, ctx->launch, st, prog, b, tab_entries, vals_cap, *q, cells, mode);
+    else {
+      lds_optin(ctx, (const void *)rank_fused_matrix_kernel);
+      hipLaunchKernelGGL(rank_fused_matrix_kernel, dim3(grid), dim3(threads), lds, ctx->launch, st, prog, b, tab_entries, vals_cap, mode);
+      MRK_HIP(hipGetLastError());
+    }
   }
   if (!cells) {
     if (b.n_overrides > 0) {
@@ -418,9 +395,6 @@ size_t launch_rank_fused(mrk_ctx *ctx, const StoreDev &st, const ProgramDev &pro
   return lds;
 }
 
-// LDS of the one-launch values kernel: [status word, 16 B][the regions of rank_fused_body, no threshold staging]
-size_t rank_values_lds_bytes(uint32_t tab_entries, int vals_cap, int threads) { return 16 + fused_lds_bytes(tab_entries, vals_cap, threads, 0u, 0, true); }
-
 // One workgroup per request, no slices (`threads` = item lanes x op split, <= 512); jit_fn: the specialised mrk_jit_rank_values of
 // this program, or nullptr = the interpreting kernel.
 void launch_rank_values(mrk_ctx *ctx, const StoreDev &st, const ProgramDev &prog, const BatchDev &b, uint32_t tab_entries, int vals_cap,
@@ -429,14 +403,8 @@ void launch_rank_values(mrk_ctx *ctx, const StoreDev &st, const ProgramDev &prog
   int mode = op_split > 1 ? op_split : 1;
   const size_t lds = rank_values_lds_bytes(tab_entries, vals_cap, threads);
   ScopedKernelTimer timer(ctx, "rank_values");
-  if (jit_fn) {
-    StoreDev a_st = st;
-    BatchDev a_b = b;
-    ValuesOut a_out = out;
-    int a_vals = vals_cap;
-    void *args[] = {&a_st, &a_b, &tab_entries, &a_vals, &mode, &a_out};
-    MRK_HIP(hipModuleLaunchKernel((hipFunction_t)jit_fn, (unsigned)b.n_req, 1, 1, (unsigned)threads, 1, 1, (unsigned)lds, ctx->launch, args, nullptr));
-  } else {
+  if (jit_fn) launch_jit(jit_fn, (unsigned)b.n_req, (unsigned)threads, lds, ctx->launch, st, b, tab_entries, vals_cap, mode, out);
+  else {
     lds_optin(ctx, (const void *)rank_values_kernel);
     hipLaunchKernelGGL(rank_values_kernel, dim3(b.n_req), dim3(threads), lds, ctx->launch, st, prog, b, tab_entries, vals_cap, mode, out);
     MRK_HIP(hipGetLastError());
@@ -463,13 +431,6 @@ void launch_normalize_big(mrk_ctx *ctx, const BatchDev &b, int dim, int col, int
   MRK_HIP(hipGetLastError());
 }
 
-// LDS of the one-launch kernel: [slab][status word][max(assembly regions, scoring regions)]
-size_t rank_one_lds_bytes(uint32_t tab_entries, int vals_cap, int threads, uint32_t thr_cap, int n_views, bool f64, size_t rt_bytes) {
-  const size_t nw = (size_t)threads / 64;
-  const size_t scoring = 8 * nw * (QS_LEAVES * (f64 ? 8 : 4) + QS_TILE_ROWS) + QS_TILE_ROWS * 8;
-  return (size_t)n_views * QS_TILE_ROWS * 2 + 16 + std::max(fused_lds_bytes(tab_entries, vals_cap, threads, thr_cap, rt_bytes, true), scoring);
-}
-
 // One workgroup per request (requests of <= QS_TILE_ROWS candidates, `threads` = item lanes x op split, <= 512);
 // jit_fn: the specialised mrk_jit_rank_one of this program, or nullptr = the interpreting kernel.
 void launch_rank_one(mrk_ctx *ctx, const StoreDev &st, const ProgramDev &prog, const BatchDev &b, uint32_t tab_entries, int vals_cap,
@@ -478,21 +439,8 @@ void launch_rank_one(mrk_ctx *ctx, const StoreDev &st, const ProgramDev &prog, c
   int mode = op_split > 1 ? op_split : 1;
   const size_t lds = rank_one_lds_bytes(tab_entries, vals_cap, threads, q.thr_cap, f.n_views, f64, (size_t)q.rt_doubles * 8);
   ScopedKernelTimer timer(ctx, "rank_one");
-  if (jit_fn) {
-    StoreDev a_st = st;
-    BatchDev a_b = b;
-    QsDev a_q = q;
-    QsForestDev a_f = f;
-    OneOut a_out = out;
-    int a_vals = vals_cap;
-    void *args[] = {&a_st, &a_b, &tab_entries, &a_vals, &a_q, &a_f, &mode, &a_out};
-    MRK_HIP(hipModuleLaunchKernel((hipFunction_t)jit_fn, (unsigned)b.n_req, 1, 1, (unsigned)threads, 1, 1, (unsigned)lds, ctx->launch, args, nullptr));
-  } else {
-    lds_optin(ctx, f64 ? (const void *)rank_one_kernel<true> : (const void *)rank_one_kernel<false>);
-    if (f64) hipLaunchKernelGGL(rank_one_kernel<true>, dim3(b.n_req), dim3(threads), lds, ctx->launch, st, prog, b, tab_entries, vals_cap, q, f, mode, out);
-    else hipLaunchKernelGGL(rank_one_kernel<false>, dim3(b.n_req), dim3(threads), lds, ctx->launch, st, prog, b, tab_entries, vals_cap, q, f, mode, out);
-    MRK_HIP(hipGetLastError());
-  }
+  if (jit_fn) launch_jit(jit_fn, (unsigned)b.n_req, (unsigned)threads, lds, ctx->launch, st, b, tab_entries, vals_cap, q, f, mode, out);
+  else launch_f64_or_f32(ctx, f64, rank_one_kernel<true>, rank_one_kernel<false>, true, (unsigned)b.n_req, (unsigned)threads, lds, ctx->launch, st, prog, b, tab_entries, vals_cap, q, f, mode, out);
 }
 
 // the same for a forest scored by the tree walk (rank_one_walk_body); `lds`: launch_shape.hpp rank_one_walk_lds_bytes;
@@ -502,84 +450,23 @@ void launch_rank_one_walk(mrk_ctx *ctx, const StoreDev &st, const ProgramDev &pr
   if (b.n_req <= 0) return;
   int mode = op_split > 1 ? op_split : 1;
   ScopedKernelTimer timer(ctx, "rank_one_walk");
-  if (jit_fn) {
-    StoreDev a_st = st;
-    BatchDev a_b = b;
-    WalkDev a_w = w;
-    OneOut a_out = out;
-    int a_vals = vals_cap;
-    void *args[] = {&a_st, &a_b, &tab_entries, &a_vals, &a_w, &mode, &a_out};
-    MRK_HIP(hipModuleLaunchKernel((hipFunction_t)jit_fn, (unsigned)b.n_req, 1, 1, (unsigned)threads, 1, 1, (unsigned)lds, ctx->launch, args, nullptr));
-  } else {
-    lds_optin(ctx, f64 ? (const void *)rank_one_walk_kernel<true> : (const void *)rank_one_walk_kernel<false>);
-    if (f64) hipLaunchKernelGGL(rank_one_walk_kernel<true>, dim3(b.n_req), dim3(threads), lds, ctx->launch, st, prog, b, tab_entries, vals_cap, w, mode, out);
-    else hipLaunchKernelGGL(rank_one_walk_kernel<false>, dim3(b.n_req), dim3(threads), lds, ctx->launch, st, prog, b, tab_entries, vals_cap, w, mode, out);
-    MRK_HIP(hipGetLastError());
-  }
-}
-
-size_t rank_fused_score_lds_bytes(uint32_t tab_entries, int vals_cap, int threads, uint32_t thr_cap, int n_views, bool f64, size_t rt_bytes) {
-  const size_t nw = (size_t)threads / 64;
-  const size_t scoring = (size_t)n_views * QS_TILE_ROWS * 2 + 16 + 8 * nw * (QS_LEAVES * (f64 ? 8 : 4) + QS_TILE_ROWS) + QS_TILE_ROWS * 8;
-  return std::max(fused_lds_bytes(tab_entries, vals_cap, threads, thr_cap, rt_bytes, false), scoring);
-}
-
-// One workgroup per request of a full batch (requests of <= QS_TILE_ROWS candidates, 128 or 64 lanes); `cells`: one tile per request.
-void launch_rank_fused_score(mrk_ctx *ctx, const StoreDev &st, const ProgramDev &prog, const BatchDev &b, uint32_t tab_entries, int vals_cap,
-                             int threads, const QsDev &q, const QsForestDev &f, uint16_t *cells, bool f64, void *jit_fn) {
-  if (b.n_req <= 0) return;
-  const size_t lds = rank_fused_score_lds_bytes(tab_entries, vals_cap, threads, q.thr_cap, f.n_views, f64, (size_t)q.rt_doubles * 8);
-  ScopedKernelTimer timer(ctx, "rank_fused");
-  if (jit_fn) {
-    StoreDev a_st = st;
-    BatchDev a_b = b;
-    QsDev a_q = q;
-    QsForestDev a_f = f;
-    int a_vals = vals_cap;
-    void *args[] = {&a_st, &a_b, &tab_entries, &a_vals, &a_q, &a_f, &cells};
-    MRK_HIP(hipModuleLaunchKernel((hipFunction_t)jit_fn, (unsigned)b.n_req, 1, 1, (unsigned)threads, 1, 1, (unsigned)lds, ctx->launch, args, nullptr));
-    return;
-  }
-  lds_optin(ctx, f64 ? (const void *)rank_fused_score_kernel<true> : (const void *)rank_fused_score_kernel<false>);
-  if (f64) hipLaunchKernelGGL(rank_fused_score_kernel<true>, dim3(b.n_req), dim3(threads), lds, ctx->launch, st, prog, b, tab_entries, vals_cap, q, f, cells);
-  else hipLaunchKernelGGL(rank_fused_score_kernel<false>, dim3(b.n_req), dim3(threads), lds, ctx->launch, st, prog, b, tab_entries, vals_cap, q, f, cells);
-  MRK_HIP(hipGetLastError());
+  if (jit_fn) launch_jit(jit_fn, (unsigned)b.n_req, (unsigned)threads, lds, ctx->launch, st, b, tab_entries, vals_cap, w, mode, out);
+  else launch_f64_or_f32(ctx, f64, rank_one_walk_kernel<true>, rank_one_walk_kernel<false>, true, (unsigned)b.n_req, (unsigned)threads, lds, ctx->launch, st, prog, b, tab_entries, vals_cap, w, mode, out);
 }
 
 // a gang of `n_slots` persistent workgroups of `threads` lanes with `lds` bytes of dynamic LDS each, one kernel on `stream`
 // (capi_rank.cpp mrk_serve_*)
 void launch_rank_serve(mrk_ctx *ctx, hipStream_t stream, const StoreDev &st, const ProgramDev &prog, const QsDev &q, const QsForestDev &f, const ServeGangDev &gang,
                        int n_slots, int threads, size_t lds, bool f64, void *jit_fn) {
-  if (jit_fn) {
-    StoreDev a_st = st;
-    QsDev a_q = q;
-    QsForestDev a_f = f;
-    ServeGangDev a_s = gang;
-    void *args[] = {&a_st, &a_q, &a_f, &a_s};
-    MRK_HIP(hipModuleLaunchKernel((hipFunction_t)jit_fn, (unsigned)n_slots, 1, 1, (unsigned)threads, 1, 1, (unsigned)lds, stream, args, nullptr));
-    return;
-  }
-  lds_optin(ctx, f64 ? (const void *)rank_serve_kernel<true> : (const void *)rank_serve_kernel<false>);
-  if (f64) hipLaunchKernelGGL(rank_serve_kernel<true>, dim3(n_slots), dim3(threads), lds, stream, st, prog, q, f, gang);
-  else hipLaunchKernelGGL(rank_serve_kernel<false>, dim3(n_slots), dim3(threads), lds, stream, st, prog, q, f, gang);
-  MRK_HIP(hipGetLastError());
+  if (jit_fn) launch_jit(jit_fn, (unsigned)n_slots, (unsigned)threads, lds, stream, st, q, f, gang);
+  else launch_f64_or_f32(ctx, f64, rank_serve_kernel<true>, rank_serve_kernel<false>, true, (unsigned)n_slots, (unsigned)threads, lds, stream, st, prog, q, f, gang);
 }
 
 // ... of a forest scored by the tree walk (rank_serve_walk_body)
 void launch_rank_serve_walk(mrk_ctx *ctx, hipStream_t stream, const StoreDev &st, const ProgramDev &prog, const WalkDev &w, const ServeGangDev &gang,
                             int n_slots, int threads, size_t lds, bool f64, void *jit_fn) {
-  if (jit_fn) {
-    StoreDev a_st = st;
-    WalkDev a_w = w;
-    ServeGangDev a_s = gang;
-    void *args[] = {&a_st, &a_w, &a_s};
-    MRK_HIP(hipModuleLaunchKernel((hipFunction_t)jit_fn, (unsigned)n_slots, 1, 1, (unsigned)threads, 1, 1, (unsigned)lds, stream, args, nullptr));
-    return;
-  }
-  lds_optin(ctx, f64 ? (const void *)rank_serve_walk_kernel<true> : (const void *)rank_serve_walk_kernel<false>);
-  if (f64) hipLaunchKernelGGL(rank_serve_walk_kernel<true>, dim3(n_slots), dim3(threads), lds, stream, st, prog, w, gang);
-  else hipLaunchKernelGGL(rank_serve_walk_kernel<false>, dim3(n_slots), dim3(threads), lds, stream, st, prog, w, gang);
-  MRK_HIP(hipGetLastError());
+  if (jit_fn) launch_jit(jit_fn, (unsigned)n_slots, (unsigned)threads, lds, stream, st, w, gang);
+  else launch_f64_or_f32(ctx, f64, rank_serve_walk_kernel<true>, rank_serve_walk_kernel<false>, true, (unsigned)n_slots, (unsigned)threads, lds, stream, st, prog, w, gang);
 }
 
 // Normalize.scale over matrix column `col` of every request of the batch (after assembly and overrides)

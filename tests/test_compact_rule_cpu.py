@@ -1,5 +1,5 @@
 """CPU: which pre-pass tables fit the compact 4-byte entry (features.hpp compact_table_ok: at most 2 047 insertions, token ids
-below 2^20) and how much dynamic LDS a fused launch asks for at 4 and 8 bytes per entry (rank.hip fused_lds_bytes), through the
+below 2^20) and how much dynamic LDS a fused launch asks for at 4 and 8 bytes per entry (launch_shape.hpp fused_lds_bytes), through the
 host-only debug export mrk_debug_fused_lds - against the arithmetic written out here."""
 import pytest
 

@@ -38,9 +38,12 @@ def test_source_carries_the_program_as_constants():
     # what the library compiles by itself is ONE kernel per translation unit (the kernel a batch shape needs, 10 - 20 s of
     # compiler time each instead of 50 s for all four): what = form | (1 + kernel) << 8
     names = ["mrk_jit_rank_cells(", "mrk_jit_rank_cells_split(", "mrk_jit_rank_matrix(", "mrk_jit_assemble_cells(", "mrk_jit_rank_one(",
-             "mrk_jit_rank_serve(", "mrk_jit_rank_fused_score("]
+             "mrk_jit_rank_serve("]
     flat = text.replace("\n", "")
     assert all(n in flat for n in names)
+    # kernel 6 (once the one-launch kernel of full batches) is gone; its number stays taken
+    assert "mrk_jit_rank_fused_score" not in text
+    assert specialize(cfg, 7 << 8)[0] == _native.ERR_INVALID_ARG
     for k, name in enumerate(names):
         rc, one = specialize(cfg, 0 | ((k + 1) << 8))
         one = one.decode().replace("\n", "")
@@ -193,5 +196,8 @@ def test_precompile_writes_the_code_objects_a_deployment_ships(tmp_path):
         blob = open(os.path.join(tmp_path, f), "rb").read()
         assert blob[:4] == b"\x7fELF" and (b"mrk_jit_rank_cells" in blob or b"mrk_jit_rank_one" in blob)
     assert lib.mrk_config_precompile(js, len(js), model, 1, mask, str(tmp_path).encode(), C.byref(n)) == 0 and n.value == 0
+    # bit 6 names no kernel any more: accepted (masks written for earlier versions keep working), nothing compiled, nothing written
+    assert lib.mrk_config_precompile(js, len(js), model, 1, 1 << 6, str(tmp_path).encode(), C.byref(n)) == 0 and n.value == 0
+    assert sorted(os.listdir(tmp_path)) == files
     assert lib.mrk_config_precompile(js, len(js), b"nope", 1, mask, str(tmp_path).encode(), C.byref(n)) == _native.ERR_NOT_FOUND
     assert lib.mrk_config_precompile(None, 0, model, 1, mask, str(tmp_path).encode(), None) == _native.ERR_INVALID_ARG

@@ -65,3 +65,77 @@ def test_slices_never_exceed_the_rounds_or_one_residency(lib):
 ])
 def test_scorer_wavefronts_per_tile(lib, rows, views, f64, want, why):
     assert lib.mrk_debug_scorer_split(rows, views, f64, 256) == want, why
+
+
+# ---- which pipeline a batch runs (metarank_amd/csrc/rank_plan.hpp), under the default switches
+ONE, ONE_WALK, FUSED_CELLS, ITEM_CELLS, MATRIX = range(5)                       # RankPath
+JIT_RANK, JIT_SPLIT, JIT_MATRIX, JIT_ITEMS, JIT_ONE, JIT_ONE_WALK, JIT_VALUES, JIT_NONE = 0, 1, 2, 3, 4, 9, 11, -2
+PLAN_INPUTS = ["n_req", "items", "entries", "doubles", "compact", "overrides", "want_matrix", "normalises", "n_prep", "dim",
+               "model", "bitvector", "f64", "thr_cap", "n_views", "rt_doubles", "chunk_bytes", "chunk_trees",
+               "lo", "hi", "sort", "direct", "rank_one_walk", "scorer_walk"]
+# a bit-vector LightGBM model over the stock Ranklens program (24 columns, 9 pre-pass reductions, 41 views, 740 resident thresholds),
+# tables that fit a workgroup's LDS and the compact entry, no overrides, no matrix asked for, the whole range, sort on
+PLAN_DEFAULTS = dict(n_req=1, items=100, entries=1024, doubles=100, compact=1, overrides=0, want_matrix=0, normalises=0, n_prep=9, dim=24,
+                     model=1, bitvector=1, f64=1, thr_cap=128, n_views=41, rt_doubles=740, chunk_bytes=0, chunk_trees=0,
+                     lo=0, hi=-1, sort=1, direct=0, rank_one_walk=-1, scorer_walk=0)
+# a forest of 64-leaf trees: no bit-vector image; the tree-walk image's largest chunk is 24 KB of 65 trees
+DEEP = dict(bitvector=0, thr_cap=0, n_views=0, rt_doubles=0, chunk_bytes=24 * 1024, chunk_trees=65)
+
+
+def plan(values=0, **kw):
+    L = _native.lib()
+    L.mrk_debug_rank_plan.restype = C.c_int
+    L.mrk_debug_rank_plan.argtypes = [C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_int64)]
+    assert not set(kw) - set(PLAN_INPUTS), kw
+    args = dict(PLAN_DEFAULTS, **kw)
+    inp = (C.c_int64 * len(PLAN_INPUTS))(*[args[k] for k in PLAN_INPUTS])
+    out = (C.c_int64 * 8)()
+    assert L.mrk_debug_rank_plan(inp, values, out) == 0
+    if values:
+        return dict(one=int(out[0]), kernel=int(out[1]))
+    return dict(zip(("path", "kernel", "items_rt", "prepass", "keyed", "whole_matrix", "entry_bytes", "split_kernel"), (int(x) for x in out)))
+
+
+@pytest.mark.parametrize("shape,want,why", [
+    (dict(n_req=3840, items=100), dict(path=FUSED_CELLS, kernel=JIT_RANK, entry_bytes=4, split_kernel=0, keyed=1), "c2: the plain kernel, compact tables, keyed by the forest"),
+    (dict(n_req=3840, items=100, compact=0), dict(path=FUSED_CELLS, kernel=JIT_SPLIT, entry_bytes=8, split_kernel=1, keyed=1), "a table the 4-byte entries do not hold: the split kernel at op split 1"),
+    (dict(n_req=384, items=1000), dict(path=FUSED_CELLS, kernel=JIT_SPLIT, entry_bytes=8, split_kernel=1), "c3: two slices"),
+    (dict(n_req=1, items=100_000), dict(path=ITEM_CELLS, kernel=JIT_ITEMS, items_rt=1, prepass=1, keyed=1), "c4: pre-pass + item-parallel assembly"),
+    (dict(n_req=1, items=100_000, n_prep=0), dict(path=ITEM_CELLS, kernel=JIT_ITEMS, items_rt=1, prepass=0), "... no pre-pass kernel for a program without reductions"),
+    (dict(direct=1), dict(path=ONE, kernel=JIT_ONE, keyed=1), "mrk_rank, one request of 100 candidates: one launch"),
+    (dict(direct=1, items=128), dict(path=ONE, kernel=JIT_ONE), "... up to a scorer tile of candidates"),
+    (dict(direct=1, items=129), dict(path=FUSED_CELLS, kernel=JIT_SPLIT), "... and not one more"),
+    (dict(direct=1, n_req=128), dict(path=ONE, kernel=JIT_ONE), "the front's combined batches: up to MRK_RANK_ONE_MAX = 128 requests"),
+    (dict(direct=1, n_req=129), dict(path=FUSED_CELLS, kernel=JIT_RANK, entry_bytes=4), "... and not one more"),
+    (dict(direct=1, n_req=2, lo=128), dict(path=FUSED_CELLS, kernel=JIT_SPLIT), "a slice of the batch is never one launch"),
+    (dict(direct=1, sort=0), dict(path=FUSED_CELLS, kernel=JIT_SPLIT), "... nor a run that does not order"),
+    (dict(direct=1, overrides=1), dict(path=FUSED_CELLS, kernel=JIT_SPLIT), "... nor a request with per-item overrides"),
+    (dict(direct=0), dict(path=FUSED_CELLS, kernel=JIT_SPLIT, split_kernel=1), "a prepared batch of one request: its caller reads device memory"),
+    (dict(want_matrix=1), dict(path=MATRIX, kernel=JIT_NONE), "explain: the matrix kernel has no op-split form (op split 4 here)"),
+    (dict(want_matrix=1, direct=1), dict(path=MATRIX, kernel=JIT_NONE), "... through mrk_rank too"),
+    (dict(want_matrix=1, n_req=3840), dict(path=MATRIX, kernel=JIT_MATRIX, keyed=0), "... a full batch takes the specialised matrix kernel"),
+    (dict(normalises=1, n_req=3840, hi=3840 * 50), dict(path=MATRIX, kernel=JIT_MATRIX, whole_matrix=1), "a shard of a normalising program assembles the whole batch"),
+    (dict(normalises=1, n_req=3840), dict(path=MATRIX, kernel=JIT_MATRIX, whole_matrix=0), "... the whole range is not a shard"),
+    (dict(model=0, n_req=3840), dict(path=MATRIX, kernel=JIT_NONE), "no model (NoopRanker): the interpreting matrix kernel"),
+    (dict(direct=1, **DEEP), dict(path=MATRIX, kernel=JIT_NONE), "a forest without a bit-vector image: mrk_rank keeps its three launches"),
+    (dict(direct=1, rank_one_walk=1, **DEEP), dict(path=ONE_WALK, kernel=JIT_ONE_WALK, keyed=0), "... unless MRK_RANK_ONE_WALK=1"),
+    (dict(direct=1, rank_one_walk=1, want_matrix=1, **DEEP), dict(path=MATRIX, kernel=JIT_NONE), "... and not with the matrix asked for"),
+    (dict(direct=1, rank_one_walk=1, dim=64, **DEEP), dict(path=MATRIX, kernel=JIT_NONE), "... nor when matrix and chunk pass 96 KB of LDS"),
+    (dict(n_req=3840, scorer_walk=1), dict(path=MATRIX, kernel=JIT_MATRIX), "MRK_SCORER=walk on a bit-vector model"),
+    (dict(direct=1, scorer_walk=1), dict(path=MATRIX, kernel=JIT_NONE), "... for mrk_rank too (MRK_RANK_ONE_WALK unset)"),
+    (dict(items=0), dict(path=MATRIX), "a request without candidates"),
+    (dict(n_req=0, items=0), dict(path=MATRIX, kernel=JIT_NONE), "an empty batch"),
+])
+def test_rank_plan(shape, want, why):
+    got = plan(**shape)
+    assert {k: got[k] for k in want} == want, (why, got)
+
+
+@pytest.mark.parametrize("shape,want,why", [
+    (dict(), dict(one=1, kernel=JIT_VALUES), "mrk_values: one launch into pinned memory"),
+    (dict(n_req=384, items=1000), dict(one=0, kernel=JIT_NONE), "sliced requests: the matrix path, interpreting"),
+    (dict(n_req=3840, want_matrix=1), dict(one=0, kernel=JIT_MATRIX), "the device matrix asked for: the matrix path, its specialised kernel on a plain shape"),
+    (dict(overrides=1), dict(one=0, kernel=JIT_NONE), "per-item overrides"),
+])
+def test_values_plan(shape, want, why):
+    assert plan(values=1, **shape) == want, why

@@ -3,7 +3,7 @@ and the rule that decides which batches get them (features.hpp compact_table_ok;
 oracle and against the interpreting kernel (MRK_RANK_JIT=0: 8-byte entries), on the small state of test_table_bounds_gpu.py's
 shape: vocabularies of 1 / 3 / ~40 tokens, sessions of 0 / 1 / 37 / 100 clicks, lists past MRK_IW_TOK = 5 and TOK_BATCH = 8, plus
 one session whose 100 clicks insert exactly 2 047 tokens - all the same one - into one table.  Every case asks the debug export
-which form ran and checks the launch's dynamic LDS bytes against the formula of rank.hip fused_lds_bytes.
+which form ran and checks the launch's dynamic LDS bytes against the formula of launch_shape.hpp fused_lds_bytes.
 One config: the specialised kernels compile once per module (MRK_RANK_JIT=1 waits for them)."""
 import os
 
@@ -27,7 +27,7 @@ def same(a, b):
 
 
 def lds_formula(i):
-    """rank.hip fused_lds_bytes: tables (rounded up to 8 B) | median values | 32 PrepOut of 24 B | 96 ints | 16 | the larger of the
+    """launch_shape.hpp fused_lds_bytes: tables (rounded up to 8 B) | median values | 32 PrepOut of 24 B | 96 ints | 16 | the larger of the
     threshold staging buffers and the resident threshold tables (when they fit the kernel's limit: 8 KB plain, 20 KB split)"""
     staging = (i["threads"] + 63) // 64 * 2 * i["thr_cap"] * 8
     rt = i["rt_bytes"] if i["rt_bytes"] <= (20480 if i["split"] else 8192) else 0

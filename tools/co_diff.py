@@ -1,6 +1,8 @@
 """Compare the machine code of two sets of specialised-kernel code objects kernel by kernel (llvm-objdump -d, addresses
-stripped): `python tools/co_diff.py DIR_A DIR_B` - which kernels exist on both sides and whether their instruction streams
-are identical.  Used to show that a refactoring or an `#ifdef`-gated experiment leaves the default kernels untouched.
+stripped - the pc-relative displacements of references to other symbols of the code object among them): `python tools/co_diff.py
+DIR_A DIR_B` - which kernels exist on both sides and whether their instruction streams are identical.  (Stripping those displacements has a price: a call whose TARGET changed to another out-of-line function of the same code
+object is not seen - the displacement is not resolved to a symbol name.  Where that matters, compare `llvm-objdump -t`'s
+function symbols and their instruction counts too: the report lists both per symbol.)  Used to show that a refactoring or an `#ifdef`-gated experiment leaves the default kernels untouched.
 With several code objects of one kernel in a directory (older builds), the NEWEST file wins."""
 import os
 import re
@@ -22,7 +24,17 @@ def kernels(d):
                     out[name] = (f, body)
                 name, body = m.group(1), []
             elif name and line.strip():
-                body.append(re.sub(r"//.*$", "", line).strip())
+                ins = re.sub(r"//.*$", "", line).strip()
+                # `s_getpc_b64 s[a:b]; s_add_u32 sa, sa, <lit>; s_addc_u32 sb, sb, <lit>` forms the address of another symbol of the code
+                # object (a function that was not inlined): the displacement is an address too - it moves when a kernel between the
+                # two is added or removed, with no change to either
+                pc = re.match(r"s_getpc_b64 s\[(\d+):(\d+)\]", body[-1]) if body else None
+                pc2 = re.match(r"s_getpc_b64 s\[(\d+):(\d+)\]", body[-2]) if len(body) > 1 else None
+                if pc and re.match(rf"s_add_u32 s{pc.group(1)}, s{pc.group(1)}, (0x[0-9a-f]+|-?\d+)$", ins):
+                    ins = f"s_add_u32 s{pc.group(1)}, s{pc.group(1)}, <pc-relative>"
+                elif pc2 and body[-1].endswith("<pc-relative>") and re.match(rf"s_addc_u32 s{pc2.group(2)}, s{pc2.group(2)}, (0x[0-9a-f]+|-?\d+)$", ins):
+                    ins = f"s_addc_u32 s{pc2.group(2)}, s{pc2.group(2)}, <pc-relative>"
+                body.append(ins)
         if name:
             out[name] = (f, body)
     return out
