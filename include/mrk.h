@@ -872,7 +872,10 @@ int mrk_model_eval(mrk_model *model, const int *metrics, const int *cutoffs, int
  * tests/train_reference.py restates it and the device agrees with that to the bit and the byte.  Config keys and [defaults]:
  * LightGBMConfig's iterations [100], learningRate [0.1], ndcgCutoff [10], maxDepth [8], seed [0], numLeaves [16], sampling [0.8],
  * debias [false; true is MRK_ERR_UNSUPPORTED], and max_bin [255], truncation [30], sigma [1.0], min_data_in_leaf [20],
- * min_sum_hessian [1e-3], lambda_l2 [0], early_stopping [20].  An unknown key is MRK_ERR_PARSE.
+ * min_sum_hessian [1e-3], lambda_l2 [0], early_stopping [20]; for categorical columns (steps 2c, 5c) categorical [[]: an array of
+ * distinct column indices >= 0; one >= cols is MRK_ERR_INVALID_ARG at mrk_train_set], max_cat_to_onehot [4], max_cat_threshold
+ * [32], cat_smooth [10.0, > 0], cat_l2 [10.0, >= 0], min_data_per_group [100].  An unknown key is MRK_ERR_PARSE.  Without
+ * `categorical` a fit gives the bytes it gave before these keys existed.
  *  1 input     f64 row-major rows x cols; labels integers 0 ... 30; groups under mrk_model_eval's rules, at most 4096 rows each; an
  *              infinite cell is MRK_ERR_INVALID_ARG; the initial score is 0.
  *  2 bins      per column, on the host: v = the sorted non-NaN cells (-0.0 is +0.0), m of them.  At most max_bin - 1 distinct
@@ -880,6 +883,16 @@ int mrk_model_eval(mrk_model *model, const int *metrics, const int *cutoffs, int
  *              floor(i * m / (max_bin - 1)) with v[p] != v[p - 1], duplicates dropped.  The bound between a < b is (a + b) / 2 in
  *              f64, or a when that is not below b.  bin(x) = the number of bounds < x (so x <= bound goes left, as the scorers
  *              decide); NaN is bin 255.  A column with one bin never splits.  The validation set uses the same bounds.
+ *  2c bins of a categorical column (string features with encode: index and the one-dimensional referer, FeatureMapping.scala:91,
+ *              RefererFeature.scala:109: mrk_values_columns' `category`), on the host: the category of a cell is c = (int64) trunc(x);
+ *              NaN and c < 0 have none; an infinite cell is MRK_ERR_INVALID_ARG; c > 32764 (the largest id the scorers' categorical
+ *              cell holds exactly) is MRK_ERR_UNSUPPORTED, naming column, row and value.  Counted over the TRAINING set, the
+ *              min(distinct, max_bin - 1) most frequent categories are kept, ties to the lower id; the bin of a kept category is
+ *              its position among the kept ones in ascending id, K of them (the column's nbins).  Everything else is bin 255: NaN,
+ *              a negative value, a category not kept (rare, or seen only in the validation set).  Bin 255 of a categorical column
+ *              ALWAYS goes right - what CategoricalDecision does with NaN, a negative value and an id outside the bitset - so the
+ *              trainer's routing and the model's prediction agree for every possible cell.  Rows are binned on the device through
+ *              a dense id -> bin byte table per column (at most 32765 bytes).  The validation set uses the training set's table.
  *  3 gradients per group of n rows: pi = the order of mrk_eval_scores; gain(y) = 2^y - 1; k = min(truncation, n); inv = 1 /
  *              (sum over i < k of sorted-descending gain_i / lg[i], added in order from 0.0), 0 when that sum is 0; lg[i] =
  *              log2(i + 2).  A pair of ranks (r, q) counts when the labels differ and min(r, q) < k; with hi / lo the item of the
@@ -899,6 +912,25 @@ int mrk_model_eval(mrk_model *model, const int *metrics, const int *cutoffs, int
  *              numLeaves leaves or no candidate.  LightGBM's numbering: split s makes node s, the left child keeps the leaf index,
  *              the right is leaf s + 1.  threshold = the bound of b; decision_type = 8 | (NaN left ? 2 : 0); leaf_value =
  *              (-G / (H + l2)) * learningRate.  A tree that cannot split ends training and is not emitted.
+ *  5c categorical column: from the same (sum q_g, sum q_h, count) histogram, every operation f64, correctly rounded, never fused.  A
+ *              candidate is a set L of bins < K that goes left; everything else goes right, bin 255 included.
+ *              K <= max_cat_to_onehot, one-vs-rest: L = {b} for b < K; gain is step 5's with lambda_l2; admitted as in step 5;
+ *              best: the highest gain, then the lowest b.
+ *              Else, sorted: a bin is eligible when count >= cat_smooth; its key is G_b / (H_b + cat_smooth); the m eligible bins
+ *              ascending by (key, bin) (keys are finite and never -0.0: a total order); max_num = min(max_cat_threshold, (m + 1) /
+ *              2); candidates are the first i bins of that order (direction 0) and the last i (direction 1), i = 1 ... max_num;
+ *              gain = (GL * GL / (HL + l2c) + GR * GR / (HR + l2c)) - G * G / (H + lambda_l2), l2c = lambda_l2 + cat_l2 (the sides
+ *              are regularised by cat_l2, the parent's term is not: LightGBM's rule); admitted when both counts >=
+ *              max(min_data_in_leaf, min_data_per_group), both hessian sums >= min_sum_hessian and gain > 0; best: the highest
+ *              gain, then direction 0, then the smaller i.
+ *              Departures from LightGBM: every prefix is judged on its own (LightGBM's running cnt_cur_group makes a candidate
+ *              depend on which earlier ones were skipped; judged alone, 256 lanes take all prefixes at once); leaf values keep
+ *              step 5's -G / (H + lambda_l2) * learningRate: cat_l2 does not enter outputs.
+ *              Across columns and leaves nothing changes: the highest gain, then the lowest column, a numeric and a categorical
+ *              column each with its own gain.  In the text a categorical node has decision_type = 9 (categorical, missing type
+ *              NaN), threshold = its ordinal among the tree's categorical nodes; the tree carries num_cat, cat_boundaries and
+ *              cat_threshold (u32 words over category IDS, max member id / 32 + 1 words per node); feature_infos of the column is
+ *              the kept ids joined by ':' or `none`.  A tree without such a node is written as before.
  *  6 scores    score[row] += leaf_value, in tree order; validation rows walk the tree by their bins.
  *  7 subset    per tree min(cols, max(1, floor(cols * sampling + 0.5))) columns: a partial Fisher-Yates shuffle of 0 ... cols - 1
  *              (position j swaps with j + z % (cols - j), z the next splitmix64 output; state = (uint32) seed << 32 | tree index),
@@ -935,6 +967,9 @@ int mrk_train_gradients(mrk_ctx *ctx, const char *config_json, const double *sco
                         int64_t n_groups, double *out_g, double *out_h);
 /* Step 2 for one column of n cells (host only, no context): *n_bounds bounds, copied when cap >= *n_bounds. */
 int mrk_train_bins(const char *config_json, const double *column, int64_t n, double *out_bounds, int cap, int *n_bounds);
+/* Step 2c for one column of n cells (host only, no context): *n_ids kept category ids in ascending order (the bin of an id is its
+ * position), copied when cap >= *n_ids.  Uses max_bin of the config. */
+int mrk_train_categories(const char *config_json, const double *column, int64_t n, int32_t *out_ids, int cap, int *n_ids);
 
 #ifdef __cplusplus
 }

@@ -290,6 +290,7 @@ SIGNATURES = {
     "mrk_train_free": (None, [_V]),
     "mrk_train_gradients": (_I, [_V, _S, _P, _P, _P, C.c_int64, _P, _P]),
     "mrk_train_bins": (_I, [_S, _P, C.c_int64, _P, _I, C.POINTER(_I)]),
+    "mrk_train_categories": (_I, [_S, _P, C.c_int64, _P, _I, C.POINTER(_I)]),
 }
 
 _lib = None

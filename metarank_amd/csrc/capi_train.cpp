@@ -41,7 +41,10 @@ struct mrk_trainer {
   int cols = 0;
   std::vector<std::vector<double>> bounds;
   std::vector<std::string> infos;
-  DevBuf d_bounds, d_bound_off, d_nbins;
+  std::vector<std::vector<int32_t>> kept;   // step 2c: per categorical column its kept ids (a numeric column: empty)
+  std::vector<int32_t> is_cat;              // per column
+  bool any_cat = false;
+  DevBuf d_bounds, d_bound_off, d_nbins, d_is_cat, d_cat_idx, d_cat_tables;
   TrainSet set[2];
   bool fitted = false;
   std::vector<TrainTree> trees;
@@ -100,6 +103,8 @@ void set_locked(mrk_trainer *t, int which, const double *x, int64_t rows, int co
   need(rows >= 1 && cols >= 1, "train: rows / cols < 1");
   if (cols > TRAIN_MAX_COLS) throw StatusError(MRK_ERR_UNSUPPORTED, "train: " + std::to_string(cols) + " columns (limit " + std::to_string(TRAIN_MAX_COLS) + ")");
   if (rows >= (int64_t(1) << 31)) throw StatusError(MRK_ERR_UNSUPPORTED, "train: " + std::to_string(rows) + " rows (limit 2^31 - 1)");
+  for (int32_t c : t->cfg.categorical)
+    if (c >= cols) throw StatusError(MRK_ERR_INVALID_ARG, "train: categorical holds the index " + std::to_string(c) + ", the matrix has " + std::to_string(cols) + " columns");
   const EvalShape sh = eval_check_groups(off, n_groups);
   need(sh.rows == rows, "train: the group offsets do not end at `rows`");
   if (sh.max_len > TRAIN_MAX_GROUP)
@@ -115,12 +120,20 @@ void set_locked(mrk_trainer *t, int which, const double *x, int64_t rows, int co
     eval_pack_labels(labels, rows, true, s.gains.data(), s.rel.data());
     for (int64_t i = 0; i < rows * cols; ++i)
       if (std::isinf(x[i])) throw StatusError(MRK_ERR_INVALID_ARG, "train: cell " + std::to_string(i) + " of the validation matrix is infinite");
+    for (int32_t c : t->cfg.categorical) train_check_categories(x + c, rows, cols, c);
   } else {
     t->set[1] = TrainSet();
     t->cols = cols;
     t->bounds.assign((size_t)cols, {});
     t->infos.assign((size_t)cols, "");
-    for_columns(cols, [&](int c) { t->bounds[(size_t)c] = train_bin_bounds(x + c, rows, cols, t->cfg.max_bin, &t->infos[(size_t)c]); });
+    t->kept.assign((size_t)cols, {});
+    t->is_cat.assign((size_t)cols, 0);
+    for (int32_t c : t->cfg.categorical) t->is_cat[(size_t)c] = 1;
+    t->any_cat = !t->cfg.categorical.empty();
+    for_columns(cols, [&](int c) {
+      if (t->is_cat[(size_t)c]) t->kept[(size_t)c] = train_kept_categories(x + c, rows, cols, t->cfg.max_bin, c, &t->infos[(size_t)c]);
+      else t->bounds[(size_t)c] = train_bin_bounds(x + c, rows, cols, t->cfg.max_bin, &t->infos[(size_t)c]);
+    });
   }
   s.rows = rows, s.n_groups = n_groups, s.max_len = sh.max_len;
   s.offsets.assign(off, off + n_groups + 1);
@@ -143,11 +156,23 @@ void set_locked(mrk_trainer *t, int which, const double *x, int64_t rows, int co
     for (int c = 0; c < cols; ++c) {
       flat.insert(flat.end(), t->bounds[(size_t)c].begin(), t->bounds[(size_t)c].end());
       boff[(size_t)c + 1] = (int)flat.size();
-      nbins[(size_t)c] = (int)t->bounds[(size_t)c].size() + 1;
+      nbins[(size_t)c] = t->is_cat[(size_t)c] ? (int)t->kept[(size_t)c].size() : (int)t->bounds[(size_t)c].size() + 1;
     }
     upload(t->d_bounds, flat, st);
     upload(t->d_bound_off, boff, st);
     upload(t->d_nbins, nbins, st);
+    upload(t->d_is_cat, t->is_cat, st);
+    std::vector<int> cat_idx((size_t)cols * 2, -1);   // per column (offset, length) of its id -> bin table
+    std::vector<uint8_t> tables;
+    for (int32_t c : t->cfg.categorical) {
+      const std::vector<uint8_t> table = train_category_table(t->kept[(size_t)c]);
+      cat_idx[(size_t)c * 2] = (int)tables.size(), cat_idx[(size_t)c * 2 + 1] = (int)table.size();
+      tables.insert(tables.end(), table.begin(), table.end());
+    }
+    if (t->any_cat) {
+      upload(t->d_cat_idx, cat_idx, st);
+      upload(t->d_cat_tables, tables, st);
+    }
     MRK_HIP(hipStreamSynchronize(st));   // the vectors are locals
   }
   s.d_bins.reserve((size_t)rows * (size_t)cols);
@@ -155,7 +180,8 @@ void set_locked(mrk_trainer *t, int which, const double *x, int64_t rows, int co
   d_x.reserve(piece_bytes);
   for (const EvalPiece &pc : pieces) {
     MRK_HIP(hipMemcpyAsync(d_x.p, x + (size_t)pc.row0 * (size_t)cols, (size_t)pc.rows * (size_t)cols * 8, hipMemcpyHostToDevice, st));
-    train_launch_bin(ctx, st, d_x.as<double>(), pc.rows, cols, t->d_bounds.as<double>(), t->d_bound_off.as<int>(), s.d_bins.as<uint8_t>(), rows, pc.row0);
+    train_launch_bin(ctx, st, d_x.as<double>(), pc.rows, cols, t->d_bounds.as<double>(), t->d_bound_off.as<int>(), t->any_cat ? t->d_cat_idx.as<int>() : nullptr,
+                     t->any_cat ? t->d_cat_tables.as<uint8_t>() : nullptr, s.d_bins.as<uint8_t>(), rows, pc.row0);
   }
   upload(s.d_labels, s.labels, st);
   upload(s.d_off, s.offsets, st);
@@ -220,7 +246,7 @@ void fit_locked(mrk_trainer *t) {
   tab.make(cfg, std::max(tr.max_len, va.given ? va.max_len : 0), st);
   const int n_sub_max = (int)train_feature_subset(cols, cfg.sampling, 0, 0).size();
   DevBuf d_g, d_h, d_qg, d_qh, d_leaf_of, d_maxes, d_G, d_H, d_C, d_feat_best, d_recs, d_subset;
-  DevBuf d_tcol, d_tbin, d_tnan, d_tleft, d_tright, d_tvalue;
+  DevBuf d_tcol, d_tbin, d_tnan, d_tleft, d_tright, d_tvalue, d_tis_cat, d_tmask;
   d_g.reserve((size_t)rows * 8), d_h.reserve((size_t)rows * 8), d_qg.reserve((size_t)rows * 8), d_qh.reserve((size_t)rows * 8);
   d_leaf_of.reserve((size_t)rows * 2);
   d_maxes.reserve(16);
@@ -231,6 +257,7 @@ void fit_locked(mrk_trainer *t) {
   d_subset.reserve((size_t)n_sub_max * 4);
   for (DevBuf *b : {&d_tcol, &d_tbin, &d_tnan, &d_tleft, &d_tright}) b->reserve((size_t)cfg.num_leaves * 4);
   d_tvalue.reserve((size_t)cfg.num_leaves * 8);
+  if (t->any_cat) d_tis_cat.reserve((size_t)cfg.num_leaves * 4), d_tmask.reserve((size_t)cfg.num_leaves * 32);
   PinBuf h_back;   // what the host reads per iteration / split: two maxima, two records
   h_back.reserve(16 + 2 * sizeof(LeafRec));
   unsigned long long *h_maxes = h_back.as<unsigned long long>();
@@ -275,14 +302,16 @@ void fit_locked(mrk_trainer *t) {
     double gmax, hmax;
     memcpy(&gmax, &h_maxes[0], 8), memcpy(&hmax, &h_maxes[1], 8);
     if (gmax == 0.0) break;
-    ScanParams sp{train_exponent(gmax, rows), train_exponent(hmax, rows), cfg.min_data_in_leaf, cfg.min_sum_hessian, cfg.lambda_l2};
+    ScanParams sp{train_exponent(gmax, rows), train_exponent(hmax, rows), cfg.min_data_in_leaf, cfg.min_sum_hessian, cfg.lambda_l2,
+                  cfg.max_cat_to_onehot, cfg.max_cat_threshold, std::max(cfg.min_data_in_leaf, cfg.min_data_per_group), cfg.cat_smooth, cfg.lambda_l2 + cfg.cat_l2};
     train_launch_quantise(ctx, st, gd.g, gd.h, rows, sp.e_g, sp.e_h, d_qg.as<long long>(), d_qh.as<long long>(), leaf_of);
     const std::vector<int32_t> subset = train_feature_subset(cols, cfg.sampling, cfg.seed, it);
     MRK_HIP(hipMemcpyAsync(d_subset.p, subset.data(), subset.size() * 4, hipMemcpyHostToDevice, st));   // (waited for with the root's record)
     HistDev hd{d_G.as<long long>(), d_H.as<long long>(), d_C.as<unsigned>(), (int)subset.size()};
 
     auto scan = [&](int leaf_a, int leaf_b, bool small_is_left) {
-      train_launch_scan(ctx, st, hd, d_subset.as<int>(), t->d_nbins.as<int>(), leaf_a, leaf_b, small_is_left, sp, d_feat_best.as<LeafRec>(), d_recs.as<LeafRec>());
+      train_launch_scan(ctx, st, hd, d_subset.as<int>(), t->d_nbins.as<int>(), t->d_is_cat.as<int>(), leaf_a, leaf_b, small_is_left, sp, d_feat_best.as<LeafRec>(),
+                        d_recs.as<LeafRec>());
       MRK_HIP(hipMemcpyAsync(h_recs, d_recs.p, 2 * sizeof(LeafRec), hipMemcpyDeviceToHost, st));
       MRK_HIP(hipStreamSynchronize(st));
     };
@@ -302,8 +331,16 @@ void fit_locked(mrk_trainer *t) {
       tree.ivalue.push_back(train_leaf_output(whole, sp.e_g, sp.e_h, cfg.lambda_l2, cfg.learning_rate, &weight));
       tree.iweight.push_back(weight);
       tree.icount.push_back(whole.c);
-      const int fresh = tree.split(leaf, c.col, c.bin, t->bounds[(size_t)c.col][(size_t)c.bin], c.nan_left != 0, c.gain);
-      train_launch_split(ctx, st, bins + (size_t)c.col * (size_t)rows, rows, leaf_of, leaf, fresh, c.bin, c.nan_left);
+      int fresh;
+      if (c.is_cat) {
+        fresh = tree.split_cat(leaf, c.col, c.cat_mask, c.gain);
+        CatMask mask;
+        memcpy(mask.w, c.cat_mask, sizeof mask.w);
+        train_launch_split_cat(ctx, st, bins + (size_t)c.col * (size_t)rows, rows, leaf_of, leaf, fresh, mask);
+      } else {
+        fresh = tree.split(leaf, c.col, c.bin, t->bounds[(size_t)c.col][(size_t)c.bin], c.nan_left != 0, c.gain);
+        train_launch_split(ctx, st, bins + (size_t)c.col * (size_t)rows, rows, leaf_of, leaf, fresh, c.bin, c.nan_left);
+      }
       const TrainSums left{c.gl, c.hl, c.cl}, right{whole.g - c.gl, whole.h - c.hl, whole.c - c.cl};
       totals[(size_t)leaf] = left;
       totals.push_back(right);
@@ -333,7 +370,13 @@ void fit_locked(mrk_trainer *t) {
     MRK_HIP(hipMemcpyAsync(d_tleft.p, tree.left.data(), (size_t)(nl - 1) * 4, hipMemcpyHostToDevice, st));
     MRK_HIP(hipMemcpyAsync(d_tright.p, tree.right.data(), (size_t)(nl - 1) * 4, hipMemcpyHostToDevice, st));
     MRK_HIP(hipMemcpyAsync(d_tvalue.p, tree.value.data(), (size_t)nl * 8, hipMemcpyHostToDevice, st));
-    const TreeDev td{d_tcol.as<int>(), d_tbin.as<int>(), d_tnan.as<int>(), d_tleft.as<int>(), d_tright.as<int>(), d_tvalue.as<double>()};
+    const bool cat_tree = tree.num_cat() > 0;   // (the validation walk takes its categorical form only for such a tree)
+    if (cat_tree) {
+      MRK_HIP(hipMemcpyAsync(d_tis_cat.p, tree.is_cat.data(), (size_t)(nl - 1) * 4, hipMemcpyHostToDevice, st));
+      MRK_HIP(hipMemcpyAsync(d_tmask.p, tree.cat_mask.data(), (size_t)(nl - 1) * 32, hipMemcpyHostToDevice, st));
+    }
+    const TreeDev td{d_tcol.as<int>(), d_tbin.as<int>(), d_tnan.as<int>(), d_tleft.as<int>(), d_tright.as<int>(), d_tvalue.as<double>(),
+                     cat_tree ? d_tis_cat.as<int>() : nullptr, cat_tree ? d_tmask.as<unsigned>() : nullptr};
     train_launch_apply(ctx, st, td, leaf_of, nullptr, rows, tr.d_score.as<double>());
     if (va.given) {
       train_launch_apply(ctx, st, td, nullptr, va.d_bins.as<uint8_t>(), va.rows, va.d_score.as<double>());
@@ -366,7 +409,7 @@ void fit_locked(mrk_trainer *t) {
   }
   MRK_HIP(hipStreamSynchronize(st));
   drain_profile_events(ctx);
-  t->model = train_write_model(t->trees, (size_t)t->best_iteration, cols, t->infos, cfg.learning_rate);
+  t->model = train_write_model(t->trees, (size_t)t->best_iteration, cols, t->infos, cfg.learning_rate, &t->kept);
   t->fitted = true;
 }
 
@@ -500,6 +543,18 @@ int mrk_train_bins(const char *config_json, const double *column, int64_t n, dou
     const std::vector<double> b = train_bin_bounds(column, n, 1, cfg.max_bin);
     *n_bounds = (int)b.size();
     if (out_bounds && cap >= (int)b.size() && !b.empty()) memcpy(out_bounds, b.data(), b.size() * 8);
+  });
+}
+
+int mrk_train_categories(const char *config_json, const double *column, int64_t n, int32_t *out_ids, int cap, int *n_ids) {
+  return guard([&] {
+    need(config_json != nullptr, "null config");
+    const TrainConfig cfg = train_parse_config(config_json, strlen(config_json));
+    need(n_ids != nullptr, "n_ids is null");
+    need(n >= 0 && (column != nullptr || n == 0), "train: null column");
+    const std::vector<int32_t> ids = train_kept_categories(column, n, 1, cfg.max_bin, 0);
+    *n_ids = (int)ids.size();
+    if (out_ids && cap >= (int)ids.size() && !ids.empty()) memcpy(out_ids, ids.data(), ids.size() * 4);
   });
 }
 

@@ -13,10 +13,11 @@
 //   train_hist                           per (TRAIN_HIST_ROWS rows, TRAIN_HIST_FEATS columns): LDS histograms of the rows of one
 //                                        leaf, non-empty bins flushed with global integer atomics
 //   train_scan, train_pick               sibling = parent - small; per (leaf, column) a prefix scan over the bins and the best
-//                                        admitted candidate; per leaf the best column
-//   train_split                          rows of the split leaf that go right get the new leaf
+//                                        admitted candidate - a categorical column (step 5c): a sort-and-scan over its bins,
+//                                        scan_cat_column -; per leaf the best column
+//   train_split, train_split_cat         rows of the split leaf that go right get the new leaf (by bin <= b; by a mask over bins)
 //   train_apply                          score += leaf value (training rows by leaf_of, validation rows by walking the tree)
-// train_bin (once per fit) turns the f64 matrix into column-major bytes.
+// train_bin (once per fit) turns the f64 matrix into column-major bytes (a categorical column through its id -> bin table, step 2c).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -159,12 +160,16 @@ train_grad_group_kernel(GradDev d, const int *__restrict__ groups) {
 
 __global__ void __launch_bounds__(TRAIN_BIN_ROWS)
 train_bin_kernel(const double *__restrict__ x, int piece_rows, int cols, const double *__restrict__ bounds, const int *__restrict__ bound_off,
-                 uint8_t *__restrict__ bins, long long rows, long long row0) {
+                 const int *__restrict__ cat_idx, const uint8_t *__restrict__ cat_tables, uint8_t *__restrict__ bins, long long rows, long long row0) {
   const int i = blockIdx.x * TRAIN_BIN_ROWS + threadIdx.x;
   if (i >= piece_rows) return;
   const double *row = x + (long long)i * cols;
   for (int c = 0; c < cols; ++c) {
     const double v = row[c];
+    if (cat_idx && cat_idx[2 * c] >= 0) {   // (the same for every lane: a categorical column, step 2c)
+      bins[(long long)c * rows + row0 + i] = (uint8_t)train_category_bin(v, cat_tables + cat_idx[2 * c], cat_idx[2 * c + 1]);
+      continue;
+    }
     int a = bound_off[c], b = bound_off[c + 1];
     const int first = a;
     while (a < b) {   // the number of bounds < v
@@ -263,9 +268,32 @@ __device__ void block_scan(long long &g, long long &h, long long &c, long long (
 
 __device__ __forceinline__ double real_of(long long q, int e) { return ldexp((double)q, -e); }   // (the conversion rounds to nearest even)
 
-__device__ __forceinline__ double side_term(long long qg, long long qh, const ScanParams &p) {
+__device__ __forceinline__ double side_term_l2(long long qg, long long qh, const ScanParams &p, double l2) {
   const double G = real_of(qg, p.e_g), H = real_of(qh, p.e_h);
-  return __ddiv_rn(__dmul_rn(G, G), __dadd_rn(H, p.l2));
+  return __ddiv_rn(__dmul_rn(G, G), __dadd_rn(H, l2));
+}
+
+__device__ __forceinline__ double side_term(long long qg, long long qh, const ScanParams &p) { return side_term_l2(qg, qh, p, p.l2); }
+
+// every lane brings its best candidate (code < 0: none): the code of the workgroup's best - the highest gain, then the lowest code -
+// or -1; its gain is left in s_gain[0]
+__device__ int block_best(double best, int code, double *s_gain, int *s_code) {
+  const int tid = threadIdx.x;
+  s_gain[tid] = best;
+  s_code[tid] = code;
+  __syncthreads();
+  for (int d = 128; d > 0; d >>= 1) {
+    if (tid < d) {
+      const double ga = s_gain[tid], gb = s_gain[tid + d];
+      const int ca = s_code[tid], cb = s_code[tid + d];
+      if (cb >= 0 && (ca < 0 || gb > ga || (gb == ga && cb < ca))) {
+        s_gain[tid] = gb;
+        s_code[tid] = cb;
+      }
+    }
+    __syncthreads();
+  }
+  return s_code[0];
 }
 
 // lane b holds bin b of one (leaf, column); the best admitted candidate of the column into *out
@@ -300,21 +328,7 @@ __device__ void scan_column(long long g, long long h, long long c, int nb, int c
       }
     }
   }
-  s_gain[tid] = best;
-  s_code[tid] = code;
-  __syncthreads();
-  for (int d = 128; d > 0; d >>= 1) {
-    if (tid < d) {
-      const double ga = s_gain[tid], gb = s_gain[tid + d];
-      const int ca = s_code[tid], cb = s_code[tid + d];
-      if (cb >= 0 && (ca < 0 || gb > ga || (gb == ga && cb < ca))) {
-        s_gain[tid] = gb;
-        s_code[tid] = cb;
-      }
-    }
-    __syncthreads();
-  }
-  const int win = s_code[0];
+  const int win = block_best(best, code, s_gain, s_code);
   if (win < 0 ? tid == 0 : tid == (win >> 1)) {
     LeafRec r;
     r.gain = win < 0 ? 0.0 : best;
@@ -324,21 +338,125 @@ __device__ void scan_column(long long g, long long h, long long c, int nb, int c
     r.nan_left = win < 0 ? 0 : (win & 1);
     r.gl = bl_g, r.hl = bl_h, r.cl = bl_c;
     r.g = Tg, r.h = Th, r.c = Tc;
+    r.is_cat = 0;
+    for (int w = 0; w < 8; ++w) r.cat_mask[w] = 0;
     *out = r;
   }
   __syncthreads();   // (s_gain, s_code, s_nan are written again by the next call)
 }
 
+// Step 5c: lane b holds bin b of one (leaf, CATEGORICAL column) - b < nb a kept category, 255 everything without one, which always goes
+// right.  A candidate is a set of bins < nb that goes left.  nb <= max_onehot: one bin against the rest, lane b judges {b}.  Else the
+// bins with count >= cat_smooth, ordered ascending by (G / (H + cat_smooth), bin): lane i judges the first i + 1 of them and the last
+// i + 1, i < min(max_cat_threshold, (m + 1) / 2), each on its own.  The order is a counting rank: every lane compares its key with
+// all nb keys, read as LDS broadcasts (one address per instruction: no bank conflict) behind ONE barrier; a bitonic network would
+// take 36 barrier-separated stages for 256 keys and padding keys for the bins that are not eligible.  The bins that are not
+// eligible are put behind the eligible ones, so one block_scan gives the prefix sums, the eligible total (position m - 1) and the
+// leaf's total (position 255).
+__device__ void scan_cat_column(long long g, long long h, long long c, int nb, int col, const ScanParams &p, LeafRec *out, long long (*s_buf)[3][256],
+                                double *s_gain, int *s_code, long long *s_nan, u64 *s_mask) {
+  const int tid = threadIdx.x;
+  const bool onehot = nb <= p.max_onehot;
+  bool elig = false;
+  int pos = tid, m = 0;   // pos: where this lane's bin stands in the order; m: eligible bins
+  if (!onehot) {
+    elig = tid < nb && (double)c >= p.cat_smooth;
+    const double key = elig ? __ddiv_rn(real_of(g, p.e_g), __dadd_rn(real_of(h, p.e_h), p.cat_smooth)) : 0.0;   // finite, never -0.0
+    s_gain[tid] = key;
+    s_code[tid] = elig ? 1 : 0;
+    __syncthreads();
+    int below = 0, before = 0;   // eligible bins that stand before this one in the order; eligible bins of a lower index
+    for (int j = 0; j < nb; ++j) {
+      const double kj = s_gain[j];
+      const int ej = s_code[j];
+      m += ej;
+      before += (ej && j < tid) ? 1 : 0;
+      below += (ej && (kj < key || (kj == key && j < tid))) ? 1 : 0;
+    }
+    pos = elig ? below : m + (tid - before);   // (a permutation of 0 ... 255)
+    s_buf[0][0][pos] = g;
+    s_buf[0][1][pos] = h;
+    s_buf[0][2][pos] = c;
+    __syncthreads();
+    g = s_buf[0][0][tid];
+    h = s_buf[0][1][tid];
+    c = s_buf[0][2][tid];
+  }
+  long long pg = g, ph = h, pc = c;
+  block_scan(pg, ph, pc, s_buf);   // (its first barrier: every lane has read its position)
+  s_buf[0][0][tid] = pg;
+  s_buf[0][1][tid] = ph;
+  s_buf[0][2][tid] = pc;
+  __syncthreads();
+  const long long Tg = s_buf[0][0][255], Th = s_buf[0][1][255], Tc = s_buf[0][2][255];
+  const double l2s = onehot ? p.l2 : p.l2_cat;
+  const long long min_count = onehot ? p.min_data : p.min_data_cat;
+  const int n_cand = onehot ? nb : min(p.max_cat_threshold, (m + 1) / 2);
+  double best = 0.0;
+  int code = -1;
+  long long bl_g = 0, bl_h = 0, bl_c = 0;
+  if (tid < n_cand) {
+    const double parent = side_term(Tg, Th, p);   // (the parent's term keeps lambda_l2 alone)
+    for (int dir = 0; dir <= (onehot ? 0 : 1); ++dir) {
+      long long lg_, lh, lc;
+      if (onehot) lg_ = g, lh = h, lc = c;
+      else if (dir == 0) lg_ = pg, lh = ph, lc = pc;
+      else {   // the last tid + 1 of the m eligible bins: their total minus the first m - 1 - tid
+        const int k = m - 2 - tid;
+        lg_ = s_buf[0][0][m - 1] - (k >= 0 ? s_buf[0][0][k] : 0);
+        lh = s_buf[0][1][m - 1] - (k >= 0 ? s_buf[0][1][k] : 0);
+        lc = s_buf[0][2][m - 1] - (k >= 0 ? s_buf[0][2][k] : 0);
+      }
+      const long long rg = Tg - lg_, rh = Th - lh, rc = Tc - lc;
+      const double HL = real_of(lh, p.e_h), HR = real_of(rh, p.e_h);
+      const double gain = __dsub_rn(__dadd_rn(side_term_l2(lg_, lh, p, l2s), side_term_l2(rg, rh, p, l2s)), parent);
+      const bool ok = lc >= min_count && rc >= min_count && HL >= p.min_hess && HR >= p.min_hess && gain > 0.0;
+      if (ok && (code < 0 || gain > best)) {   // (direction 0 wins a tie)
+        best = gain;
+        code = dir * 256 + tid;
+        bl_g = lg_, bl_h = lh, bl_c = lc;
+      }
+    }
+  }
+  const int win = block_best(best, code, s_gain, s_code);
+  const int wdir = win >> 8, wi = win & 255;
+  if (win >= 0 && tid == wi) s_nan[0] = bl_g, s_nan[1] = bl_h, s_nan[2] = bl_c;
+  // the winner's left set as a mask over BINS: lane b knows where bin b stands
+  const bool member = win >= 0 && (onehot ? tid == wi : (elig && (wdir == 0 ? pos <= wi : pos >= m - 1 - wi)));
+  const u64 wave_mask = __ballot(member);
+  if ((tid & 63) == 0) s_mask[tid >> 6] = wave_mask;
+  __syncthreads();
+  if (tid == 0) {
+    LeafRec r;
+    r.gain = win < 0 ? 0.0 : s_gain[0];
+    r.valid = win < 0 ? 0 : 1;
+    r.col = col;
+    r.bin = 0;
+    r.nan_left = 0;
+    r.gl = win < 0 ? 0 : s_nan[0], r.hl = win < 0 ? 0 : s_nan[1], r.cl = win < 0 ? 0 : s_nan[2];
+    r.g = Tg, r.h = Th, r.c = Tc;
+    r.is_cat = 1;
+    for (int w = 0; w < 4; ++w) {
+      r.cat_mask[2 * w] = (unsigned)s_mask[w];
+      r.cat_mask[2 * w + 1] = (unsigned)(s_mask[w] >> 32);
+    }
+    *out = r;
+  }
+  __syncthreads();   // (everything in LDS is written again by the next call)
+}
+
 // one workgroup per subset column j, lane b = bin b
 __global__ void __launch_bounds__(256)
-train_scan_kernel(HistDev hd, const int *__restrict__ subset, const int *__restrict__ nbins, int leaf_a, int leaf_b, int small_is_left, ScanParams p,
-                  LeafRec *__restrict__ feat_best) {
+train_scan_kernel(HistDev hd, const int *__restrict__ subset, const int *__restrict__ nbins, const int *__restrict__ is_cat, int leaf_a, int leaf_b,
+                  int small_is_left, ScanParams p, LeafRec *__restrict__ feat_best) {
   __shared__ long long s_buf[2][3][256];
   __shared__ double s_gain[256];
   __shared__ int s_code[256];
   __shared__ long long s_nan[6];   // the NaN bin's sums, the leaf's totals
+  __shared__ u64 s_mask[4];        // a categorical winner's left bins: one ballot per wavefront
   const int tid = threadIdx.x, j = blockIdx.x;
   const int col = subset[j], nb = nbins[col];
+  const bool cat = is_cat[col] != 0;   // (the same for the whole workgroup)
   const size_t ia = ((size_t)leaf_a * hd.n_sub + j) * 256 + tid;
   long long ag = hd.G[ia], ah = hd.H[ia], ac = hd.C[ia];
   long long bg = 0, bh = 0, bc = 0;
@@ -355,6 +473,11 @@ train_scan_kernel(HistDev hd, const int *__restrict__ subset, const int *__restr
     }
     hd.G[ia] = ag, hd.H[ia] = ah, hd.C[ia] = (unsigned)ac;
     hd.G[ib] = bg, hd.H[ib] = bh, hd.C[ib] = (unsigned)bc;
+  }
+  if (cat) {
+    scan_cat_column(ag, ah, ac, nb, col, p, &feat_best[j], s_buf, s_gain, s_code, s_nan, s_mask);
+    if (leaf_b >= 0) scan_cat_column(bg, bh, bc, nb, col, p, &feat_best[hd.n_sub + j], s_buf, s_gain, s_code, s_nan, s_mask);
+    return;
   }
   scan_column(ag, ah, ac, nb, col, p, &feat_best[j], s_buf, s_gain, s_code, s_nan);
   if (leaf_b >= 0) scan_column(bg, bh, bc, nb, col, p, &feat_best[hd.n_sub + j], s_buf, s_gain, s_code, s_nan);
@@ -396,6 +519,21 @@ train_split_kernel(const uint8_t *__restrict__ col_bins, long long rows, uint16_
   if (!left) leaf_of[i] = (uint16_t)fresh;
 }
 
+// the categorical form: the mask comes as kernel arguments; its word is picked by selects (a lane-indexed argument would go to scratch)
+__global__ void __launch_bounds__(TRAIN_ROW_THREADS)
+train_split_cat_kernel(const uint8_t *__restrict__ col_bins, long long rows, uint16_t *__restrict__ leaf_of, int leaf, int fresh, CatMask mask) {
+  const long long i = (long long)blockIdx.x * TRAIN_ROW_THREADS + threadIdx.x;
+  if (i >= rows || leaf_of[i] != leaf) return;
+  const int b = col_bins[i];
+  unsigned word = 0;
+#pragma unroll
+  for (int w = 0; w < 8; ++w) word = (b >> 5) == w ? mask.w[w] : word;
+  const bool left = b != TRAIN_NAN_BIN && ((word >> (b & 31)) & 1u);
+  if (!left) leaf_of[i] = (uint16_t)fresh;
+}
+
+// CAT: the tree has a categorical node (the host picks the form; the numeric one reads neither is_cat nor cat_mask)
+template <bool CAT>
 __global__ void __launch_bounds__(TRAIN_ROW_THREADS)
 train_apply_kernel(TreeDev t, const uint16_t *__restrict__ leaf_of, const uint8_t *__restrict__ bins, long long rows, double *__restrict__ scores) {
   const long long i = (long long)blockIdx.x * TRAIN_ROW_THREADS + threadIdx.x;
@@ -406,7 +544,10 @@ train_apply_kernel(TreeDev t, const uint16_t *__restrict__ leaf_of, const uint8_
     int n = 0;
     while (n >= 0) {
       const int b = bins[(long long)t.col[n] * rows + i];
-      n = (b <= t.bin[n] || (b == TRAIN_NAN_BIN && t.nan_left[n])) ? t.left[n] : t.right[n];
+      bool left;
+      if (CAT && t.is_cat[n]) left = b != TRAIN_NAN_BIN && ((t.cat_mask[n * 8 + (b >> 5)] >> (b & 31)) & 1u);
+      else left = b <= t.bin[n] || (b == TRAIN_NAN_BIN && t.nan_left[n]);
+      n = left ? t.left[n] : t.right[n];
     }
     leaf = ~n;
   }
@@ -432,12 +573,12 @@ void train_launch_grad_group(mrk_ctx *ctx, hipStream_t s, const GradDev &d, cons
   MRK_HIP(hipGetLastError());
 }
 
-void train_launch_bin(mrk_ctx *ctx, hipStream_t s, const double *x, int piece_rows, int cols, const double *bounds, const int *bound_off, uint8_t *bins,
-                      long long rows, long long row0) {
+void train_launch_bin(mrk_ctx *ctx, hipStream_t s, const double *x, int piece_rows, int cols, const double *bounds, const int *bound_off, const int *cat_idx,
+                      const uint8_t *cat_tables, uint8_t *bins, long long rows, long long row0) {
   if (piece_rows <= 0 || cols <= 0) return;
   ScopedKernelTimer timer(ctx, "train_bin");
   hipLaunchKernelGGL(train_bin_kernel, dim3((unsigned)((piece_rows + TRAIN_BIN_ROWS - 1) / TRAIN_BIN_ROWS)), dim3(TRAIN_BIN_ROWS), 0, s, x, piece_rows, cols, bounds,
-                     bound_off, bins, rows, row0);
+                     bound_off, cat_idx, cat_tables, bins, rows, row0);
   MRK_HIP(hipGetLastError());
 }
 
@@ -466,10 +607,10 @@ void train_launch_hist(mrk_ctx *ctx, hipStream_t s, const uint8_t *bins, long lo
   MRK_HIP(hipGetLastError());
 }
 
-void train_launch_scan(mrk_ctx *ctx, hipStream_t s, const HistDev &hd, const int *subset, const int *nbins, int leaf_a, int leaf_b, bool small_is_left,
-                       const ScanParams &p, LeafRec *feat_best, LeafRec *out) {
+void train_launch_scan(mrk_ctx *ctx, hipStream_t s, const HistDev &hd, const int *subset, const int *nbins, const int *is_cat, int leaf_a, int leaf_b,
+                       bool small_is_left, const ScanParams &p, LeafRec *feat_best, LeafRec *out) {
   ScopedKernelTimer timer(ctx, "train_scan");
-  hipLaunchKernelGGL(train_scan_kernel, dim3((unsigned)hd.n_sub), dim3(256), 0, s, hd, subset, nbins, leaf_a, leaf_b, small_is_left ? 1 : 0, p, feat_best);
+  hipLaunchKernelGGL(train_scan_kernel, dim3((unsigned)hd.n_sub), dim3(256), 0, s, hd, subset, nbins, is_cat, leaf_a, leaf_b, small_is_left ? 1 : 0, p, feat_best);
   MRK_HIP(hipGetLastError());
   hipLaunchKernelGGL(train_pick_kernel, dim3(leaf_b >= 0 ? 2u : 1u), dim3(64), 0, s, (const LeafRec *)feat_best, hd.n_sub, out);
   MRK_HIP(hipGetLastError());
@@ -481,10 +622,17 @@ void train_launch_split(mrk_ctx *ctx, hipStream_t s, const uint8_t *col_bins, lo
   MRK_HIP(hipGetLastError());
 }
 
+void train_launch_split_cat(mrk_ctx *ctx, hipStream_t s, const uint8_t *col_bins, long long rows, uint16_t *leaf_of, int leaf, int fresh, const CatMask &mask) {
+  ScopedKernelTimer timer(ctx, "train_apply");
+  hipLaunchKernelGGL(train_split_cat_kernel, dim3(row_grid(rows)), dim3(TRAIN_ROW_THREADS), 0, s, col_bins, rows, leaf_of, leaf, fresh, mask);
+  MRK_HIP(hipGetLastError());
+}
+
 void train_launch_apply(mrk_ctx *ctx, hipStream_t s, const TreeDev &t, const uint16_t *leaf_of, const uint8_t *bins, long long rows, double *scores) {
   if (rows <= 0) return;
   ScopedKernelTimer timer(ctx, "train_apply");
-  hipLaunchKernelGGL(train_apply_kernel, dim3(row_grid(rows)), dim3(TRAIN_ROW_THREADS), 0, s, t, leaf_of, bins, rows, scores);
+  if (t.is_cat) hipLaunchKernelGGL(train_apply_kernel<true>, dim3(row_grid(rows)), dim3(TRAIN_ROW_THREADS), 0, s, t, leaf_of, bins, rows, scores);
+  else hipLaunchKernelGGL(train_apply_kernel<false>, dim3(row_grid(rows)), dim3(TRAIN_ROW_THREADS), 0, s, t, leaf_of, bins, rows, scores);
   MRK_HIP(hipGetLastError());
 }
 

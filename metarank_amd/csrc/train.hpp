@@ -32,9 +32,11 @@ void train_launch_grad_wave(mrk_ctx *ctx, hipStream_t s, const GradDev &d, const
 void train_launch_grad_group(mrk_ctx *ctx, hipStream_t s, const GradDev &d, const int *groups, int count, int max_len);
 
 // a piece of the row-major matrix into the column-major byte matrix: bins[c * rows + row0 + i] = the number of bounds of column c
-// below x[i * cols + c], or 255 for NaN.  bounds of column c: bounds[bound_off[c] ... bound_off[c + 1])
-void train_launch_bin(mrk_ctx *ctx, hipStream_t s, const double *x, int piece_rows, int cols, const double *bounds, const int *bound_off, uint8_t *bins,
-                      long long rows, long long row0);
+// below x[i * cols + c], or 255 for NaN.  bounds of column c: bounds[bound_off[c] ... bound_off[c + 1]).
+// cat_idx (null: no categorical column): per column (offset, length) of its id -> bin table in cat_tables, offset < 0 for a numeric
+// column; a cell of a categorical column gets train_category_bin under that table
+void train_launch_bin(mrk_ctx *ctx, hipStream_t s, const double *x, int piece_rows, int cols, const double *bounds, const int *bound_off, const int *cat_idx,
+                      const uint8_t *cat_tables, uint8_t *bins, long long rows, long long row0);
 
 // maxes[0] = max |g| and maxes[1] = max h as bit patterns (both >= 0: the integer order is the order of the values); the caller zeroes them
 void train_launch_max(mrk_ctx *ctx, hipStream_t s, const double *g, const double *h, long long rows, unsigned long long *maxes);
@@ -58,25 +60,39 @@ struct LeafRec {
   int valid, col, bin, nan_left;
   long long gl, hl, cl;        // the left side's sums
   long long g, h, c;           // the leaf's
+  int is_cat;                  // a categorical candidate: cat_mask bit b <=> bin b goes left (bin, nan_left unused)
+  unsigned cat_mask[8];
 };
 struct ScanParams {
   int e_g, e_h;
   int min_data;
   double min_hess, l2;
+  // step 5c
+  int max_onehot, max_cat_threshold, min_data_cat;   // min_data_cat = max(min_data_in_leaf, min_data_per_group)
+  double cat_smooth, l2_cat;                         // l2_cat = lambda_l2 + cat_l2
 };
 // leaf_b < 0: scans leaf_a alone (the root).  Else slot leaf_b holds the histogram of the smaller child of a split and slot leaf_a its
 // parent's: first leaves both slots with their own leaf's (sibling = parent - small; leaf_a is the left child), then scans both.
-// feat_best: scratch of 2 * n_sub records; out: 2 records (leaf_a, leaf_b)
-void train_launch_scan(mrk_ctx *ctx, hipStream_t s, const HistDev &hd, const int *subset, const int *nbins, int leaf_a, int leaf_b, bool small_is_left,
-                       const ScanParams &p, LeafRec *feat_best, LeafRec *out);
+// feat_best: scratch of 2 * n_sub records; out: 2 records (leaf_a, leaf_b).  nbins / is_cat: per column; a categorical column is
+// searched by step 5c
+void train_launch_scan(mrk_ctx *ctx, hipStream_t s, const HistDev &hd, const int *subset, const int *nbins, const int *is_cat, int leaf_a, int leaf_b,
+                       bool small_is_left, const ScanParams &p, LeafRec *feat_best, LeafRec *out);
 
 // rows of `leaf` whose bin of column `col` goes right move to leaf `fresh`
 void train_launch_split(mrk_ctx *ctx, hipStream_t s, const uint8_t *col_bins, long long rows, uint16_t *leaf_of, int leaf, int fresh, int bin, int nan_left);
+// the same for a categorical node: a bin goes left when it is not 255 and its bit of the mask is set
+struct CatMask {
+  unsigned w[8];
+};
+void train_launch_split_cat(mrk_ctx *ctx, hipStream_t s, const uint8_t *col_bins, long long rows, uint16_t *leaf_of, int leaf, int fresh, const CatMask &mask);
 
-// a finished tree on the device: per internal node (column, bin, nan_left, left, right), children as in the model text (~leaf)
+// a finished tree on the device: per internal node (column, bin, nan_left, left, right), children as in the model text (~leaf).
+// is_cat (null: a tree without a categorical node): per node, and cat_mask 8 words per node
 struct TreeDev {
   const int *col, *bin, *nan_left, *left, *right;
   const double *leaf_value;
+  const int *is_cat;
+  const unsigned *cat_mask;
 };
 // scores[row] += leaf_value[leaf]: leaf_of given (the training rows) or found by walking the tree over the rows' bins (validation)
 void train_launch_apply(mrk_ctx *ctx, hipStream_t s, const TreeDev &t, const uint16_t *leaf_of, const uint8_t *bins, long long rows, double *scores);

@@ -22,7 +22,8 @@ TrainConfig train_parse_config(const char *text, size_t len) {
   if (!root.is_object()) bad("not an object");
   TrainConfig c;
   static const char *known[] = {"iterations", "learningRate", "ndcgCutoff", "maxDepth", "seed", "numLeaves", "sampling", "debias", "max_bin", "truncation",
-                                "sigma", "min_data_in_leaf", "min_sum_hessian", "lambda_l2", "early_stopping"};
+                                "sigma", "min_data_in_leaf", "min_sum_hessian", "lambda_l2", "early_stopping", "categorical", "max_cat_to_onehot",
+                                "max_cat_threshold", "cat_smooth", "cat_l2", "min_data_per_group"};
   for (auto &kv : root.obj) {
     bool ok = false;
     for (const char *k : known) ok = ok || kv.first == k;
@@ -61,6 +62,24 @@ TrainConfig train_parse_config(const char *text, size_t len) {
   real("min_sum_hessian", c.min_sum_hessian);
   real("lambda_l2", c.lambda_l2);
   integer("early_stopping", c.early_stopping);
+  integer("max_cat_to_onehot", c.max_cat_to_onehot);
+  integer("max_cat_threshold", c.max_cat_threshold);
+  real("cat_smooth", c.cat_smooth);
+  real("cat_l2", c.cat_l2);
+  integer("min_data_per_group", c.min_data_per_group);
+  if (const json::Value *v = root.find("categorical"))
+    if (!v->is_null()) {
+      if (!v->is_array()) bad("'categorical' is not an array");
+      for (const json::Value &e : v->arr) {
+        if (!e.is_number()) bad("'categorical' holds something that is not a number");
+        const double d = e.as_double();
+        if (!(d == std::floor(d)) || d < -2147483648.0 || d > 2147483647.0) bad("'categorical' holds something that is not an Int");
+        if (d < 0.0) range("categorical holds the negative index " + std::to_string((int)d));
+        for (int32_t seen : c.categorical)
+          if (seen == (int32_t)d) range("categorical holds the index " + std::to_string((int)d) + " twice");
+        c.categorical.push_back((int32_t)d);
+      }
+    }
   auto at_least = [&](const char *key, int v, int lo) {
     if (v < lo) range(std::string(key) + " = " + std::to_string(v) + " (at least " + std::to_string(lo) + ")");
   };
@@ -73,6 +92,11 @@ TrainConfig train_parse_config(const char *text, size_t len) {
   at_least("truncation", c.truncation, 1);
   at_least("min_data_in_leaf", c.min_data_in_leaf, 1);
   at_least("early_stopping", c.early_stopping, 1);
+  at_least("max_cat_to_onehot", c.max_cat_to_onehot, 1);
+  at_least("max_cat_threshold", c.max_cat_threshold, 1);
+  at_least("min_data_per_group", c.min_data_per_group, 1);
+  if (!(c.cat_smooth > 0.0) || !std::isfinite(c.cat_smooth)) range("cat_smooth is not a positive number");
+  if (!(c.cat_l2 >= 0.0) || !std::isfinite(c.cat_l2)) range("cat_l2 is negative");
   if (!(c.learning_rate > 0.0) || !std::isfinite(c.learning_rate)) range("learningRate is not a positive number");
   if (!(c.sampling > 0.0 && c.sampling <= 1.0)) range("sampling is not in (0, 1]");
   if (!(c.sigma > 0.0) || !std::isfinite(c.sigma)) range("sigma is not a positive number");
@@ -123,6 +147,47 @@ std::vector<double> train_bin_bounds(const double *col, int64_t n, int64_t strid
     out.push_back(mid);
   }
   return out;
+}
+
+// the category of a cell or -1; the refusals of step 2c
+static int32_t category_of(double x, int64_t row, int column) {
+  if (x != x) return -1;
+  if (std::isinf(x)) throw StatusError(MRK_ERR_INVALID_ARG, "train: cell " + std::to_string(row) + " of a column is infinite");
+  if (x >= (double)(TRAIN_MAX_CATEGORY + 1))
+    throw StatusError(MRK_ERR_UNSUPPORTED, "train: categorical column " + std::to_string(column) + ", row " + std::to_string(row) + " holds " + g17(x) +
+                                               " (the largest category is " + std::to_string(TRAIN_MAX_CATEGORY) + ")");
+  return x <= -1.0 ? -1 : (int32_t)x;   // (the conversion truncates: -0.5 is category 0)
+}
+
+std::vector<int32_t> train_kept_categories(const double *col, int64_t n, int64_t stride, int max_bin, int column, std::string *info) {
+  std::vector<int64_t> count((size_t)TRAIN_MAX_CATEGORY + 1, 0);
+  for (int64_t i = 0; i < n; ++i) {
+    const int32_t c = category_of(col[i * stride], i, column);
+    if (c >= 0) count[(size_t)c] += 1;
+  }
+  std::vector<int32_t> ids;
+  for (int32_t c = 0; c <= TRAIN_MAX_CATEGORY; ++c)
+    if (count[(size_t)c] > 0) ids.push_back(c);
+  if ((int64_t)ids.size() > max_bin - 1) {
+    std::sort(ids.begin(), ids.end(), [&](int32_t a, int32_t b) { return count[(size_t)a] != count[(size_t)b] ? count[(size_t)a] > count[(size_t)b] : a < b; });
+    ids.resize((size_t)(max_bin - 1));
+    std::sort(ids.begin(), ids.end());
+  }
+  if (info) {
+    *info = ids.empty() ? "none" : "";
+    for (size_t k = 0; k < ids.size(); ++k) *info += (k ? ":" : "") + std::to_string(ids[k]);
+  }
+  return ids;
+}
+
+void train_check_categories(const double *col, int64_t n, int64_t stride, int column) {
+  for (int64_t i = 0; i < n; ++i) (void)category_of(col[i * stride], i, column);
+}
+
+std::vector<uint8_t> train_category_table(const std::vector<int32_t> &kept) {
+  std::vector<uint8_t> table(kept.empty() ? 0 : (size_t)kept.back() + 1, (uint8_t)TRAIN_NAN_BIN);
+  for (size_t k = 0; k < kept.size(); ++k) table[(size_t)kept[k]] = (uint8_t)k;
+  return table;
 }
 
 static uint64_t splitmix64(uint64_t &state) {
@@ -188,6 +253,8 @@ int TrainTree::split(int leaf, int col, int b, double thr_, bool nan_left, doubl
   gain.push_back(gain_);
   thr.push_back(thr_);
   dt.push_back(8 | (nan_left ? 2 : 0));
+  is_cat.push_back(0);
+  cat_mask.resize(cat_mask.size() + 8, 0u);
   left.push_back(~leaf);
   right.push_back(~fresh);
   if (parent_node[(size_t)leaf] >= 0) (parent_side[(size_t)leaf] == 0 ? left : right)[(size_t)parent_node[(size_t)leaf]] = s;
@@ -200,6 +267,21 @@ int TrainTree::split(int leaf, int col, int b, double thr_, bool nan_left, doubl
   return fresh;
 }
 
+int TrainTree::num_cat() const {
+  int n = 0;
+  for (int32_t c : is_cat) n += c;
+  return n;
+}
+
+int TrainTree::split_cat(int leaf, int col, const uint32_t *mask8, double gain_) {
+  const int ordinal = num_cat();
+  const int fresh = split(leaf, col, 0, (double)ordinal, false, gain_);
+  dt.back() = 9;
+  is_cat.back() = 1;
+  std::copy(mask8, mask8 + 8, cat_mask.end() - 8);
+  return fresh;
+}
+
 double train_leaf_output(const TrainSums &q, int e_g, int e_h, double l2, double lr, double *weight) {
   const double G = std::ldexp((double)q.g, -e_g), H = std::ldexp((double)q.h, -e_h);
   if (weight) *weight = H;
@@ -208,7 +290,8 @@ double train_leaf_output(const TrainSums &q, int e_g, int e_h, double l2, double
   return v * lr;
 }
 
-std::string train_write_model(const std::vector<TrainTree> &trees, size_t n_trees, int cols, const std::vector<std::string> &infos, double lr) {
+std::string train_write_model(const std::vector<TrainTree> &trees, size_t n_trees, int cols, const std::vector<std::string> &infos, double lr,
+                              const std::vector<std::vector<int32_t>> *kept) {
   auto ints = [](std::string &o, const char *key, const auto &a, size_t n) {
     o += key;
     for (size_t i = 0; i < n; ++i) o += (i ? " " : "") + std::to_string((long long)a[i]);
@@ -223,7 +306,8 @@ std::string train_write_model(const std::vector<TrainTree> &trees, size_t n_tree
   for (size_t i = 0; i < n_trees; ++i) {
     const TrainTree &t = trees[i];
     const size_t nl = (size_t)t.num_leaves(), nn = nl - 1;
-    std::string b = "Tree=" + std::to_string(i) + "\nnum_leaves=" + std::to_string(nl) + "\nnum_cat=0\n";
+    const int n_cat = t.num_cat();
+    std::string b = "Tree=" + std::to_string(i) + "\nnum_leaves=" + std::to_string(nl) + "\nnum_cat=" + std::to_string(n_cat) + "\n";
     ints(b, "split_feature=", t.feat, nn);
     b += "split_gain=";
     for (size_t k = 0; k < nn; ++k) {
@@ -242,6 +326,25 @@ std::string train_write_model(const std::vector<TrainTree> &trees, size_t n_tree
     f64s(b, "internal_value=", t.ivalue, nn);
     f64s(b, "internal_weight=", t.iweight, nn);
     ints(b, "internal_count=", t.icount, nn);
+    if (n_cat > 0) {   // per categorical node, in node order, a bitset over category IDS
+      if (!kept) throw StatusError(MRK_ERR_INVALID_ARG,"train: a categorical node without the tables of kept ids");
+      std::vector<int64_t> boundaries{0};
+      std::vector<uint32_t> words;
+      for (size_t k = 0; k < nn; ++k) {
+        if (!t.is_cat[k]) continue;
+        const std::vector<int32_t> &ids = (*kept)[(size_t)t.feat[k]];
+        const size_t first = words.size();
+        for (size_t bin = 0; bin < ids.size(); ++bin) {   // ascending ids: the last member sizes the bitset
+          if (!(t.cat_mask[k * 8 + bin / 32] >> (bin % 32) & 1u)) continue;
+          const size_t id = (size_t)ids[bin];
+          if (words.size() < first + id / 32 + 1) words.resize(first + id / 32 + 1, 0u);
+          words[first + id / 32] |= 1u << (id % 32);
+        }
+        boundaries.push_back((int64_t)words.size());
+      }
+      ints(b, "cat_boundaries=", boundaries, boundaries.size());
+      ints(b, "cat_threshold=", words, words.size());
+    }
     b += "is_linear=0\nshrinkage=" + g17(lr);
     blocks.push_back(std::move(b));
   }

@@ -18,6 +18,13 @@ constexpr int TRAIN_MAX_GROUP = 4096;       // rows of one group (one workgroup 
 constexpr int TRAIN_MAX_COLS = 65535;
 constexpr int TRAIN_MAX_LEAVES = 4096;
 constexpr int TRAIN_MAX_LABEL = 30;
+constexpr int TRAIN_MAX_CATEGORY = 32764;   // 0x7FFC: the largest id the scorers' categorical cell holds exactly (forest.hpp, QV_CAT)
+
+#ifdef __HIPCC__
+#define MRK_TRAIN_HD __host__ __device__
+#else
+#define MRK_TRAIN_HD
+#endif
 
 struct TrainConfig {
   int iterations = 100;
@@ -35,6 +42,12 @@ struct TrainConfig {
   double min_sum_hessian = 1e-3;
   double lambda_l2 = 0.0;
   int early_stopping = 20;
+  std::vector<int32_t> categorical;   // column indices, distinct, >= 0 (below `cols`: judged by mrk_train_set)
+  int max_cat_to_onehot = 4;
+  int max_cat_threshold = 32;
+  double cat_smooth = 10.0;
+  double cat_l2 = 10.0;
+  int min_data_per_group = 100;
 };
 // malformed JSON, a value of the wrong type or an unknown key: MRK_ERR_PARSE; a value out of range: MRK_ERR_INVALID_ARG;
 // debias = true or numLeaves > TRAIN_MAX_LEAVES: MRK_ERR_UNSUPPORTED
@@ -43,6 +56,22 @@ TrainConfig train_parse_config(const char *json, size_t len);
 // the upper bounds of the bins of one column but the last (bin(x) = the number of bounds < x), from col[i * stride], i < n.
 // An infinite cell: MRK_ERR_INVALID_ARG.  info: LightGBM's feature_infos entry ("none" or "[min:max]").
 std::vector<double> train_bin_bounds(const double *col, int64_t n, int64_t stride, int max_bin, std::string *info = nullptr);
+
+// step 2c: the category ids of a categorical column that get a bin, ascending (the bin of an id is its position): the
+// min(distinct, max_bin - 1) most frequent of col[i * stride], i < n, ties to the lower id.  The category of a cell is trunc(x); NaN and
+// negative ones have none.  An infinite cell: MRK_ERR_INVALID_ARG; a category beyond TRAIN_MAX_CATEGORY: MRK_ERR_UNSUPPORTED, naming
+// `column`, the row and the value.  info: LightGBM's feature_infos entry (the ids joined by ':', or "none").
+std::vector<int32_t> train_kept_categories(const double *col, int64_t n, int64_t stride, int max_bin, int column, std::string *info = nullptr);
+// the cells of a categorical column of another set than the one the ids were kept from: the same two refusals
+void train_check_categories(const double *col, int64_t n, int64_t stride, int column);
+// id -> bin for ids 0 ... kept.back(), TRAIN_NAN_BIN where the id has none; empty without a kept id
+std::vector<uint8_t> train_category_table(const std::vector<int32_t> &kept);
+// the bin of a cell of a categorical column under a table of `len` bytes: NaN, a negative category and an id without a bin are
+// TRAIN_NAN_BIN (which always goes right: what CategoricalDecision does with them).  The binning kernel calls this too.
+MRK_TRAIN_HD inline int train_category_bin(double x, const uint8_t *table, int len) {
+  if (!(x > -1.0) || !(x < (double)len)) return TRAIN_NAN_BIN;   // (NaN fails both; -1 < x < 0 truncates to category 0)
+  return table[(int)x];
+}
 
 // the columns of tree `tree`, ascending
 std::vector<int32_t> train_feature_subset(int cols, double sampling, int seed, int tree);
@@ -72,14 +101,22 @@ struct TrainTree {
   std::vector<int32_t> parent_node, parent_side, depth;   // per leaf
   std::vector<double> value, weight;                      // per leaf
   std::vector<int64_t> count;
+  std::vector<int32_t> is_cat;                            // per node
+  std::vector<uint32_t> cat_mask;                         // per node 8 words: bit b <=> bin b goes left (zeros for a numeric node)
   TrainTree() : parent_node{-1}, parent_side{0}, depth{0} {}
   int num_leaves() const { return (int)feat.size() + 1; }
+  int num_cat() const;
   int split(int leaf, int col, int b, double thr_, bool nan_left, double gain_);   // -> the new leaf
+  // a categorical node: threshold = its ordinal among the tree's categorical nodes, decision_type = 9 (categorical, missing type NaN)
+  int split_cat(int leaf, int col, const uint32_t *mask8, double gain_);
 };
 
 // -G / (H + l2) * lr of quantised sums; *weight: H
 double train_leaf_output(const TrainSums &q, int e_g, int e_h, double l2, double lr, double *weight);
 
-std::string train_write_model(const std::vector<TrainTree> &trees, size_t n_trees, int cols, const std::vector<std::string> &infos, double lr);
+// kept: per column the kept ids of step 2c (empty for a numeric column), needed when a tree has a categorical node: its bins go back
+// to ids, a node's bitset has max member id / 32 + 1 words.  A tree without one is written as before (num_cat=0, no cat_* lines).
+std::string train_write_model(const std::vector<TrainTree> &trees, size_t n_trees, int cols, const std::vector<std::string> &infos, double lr,
+                              const std::vector<std::vector<int32_t>> *kept = nullptr);
 
 }  // namespace mrk

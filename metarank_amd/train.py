@@ -41,6 +41,23 @@ def bin_bounds(column, **config) -> np.ndarray:
     return out
 
 
+def kept_categories(column, **config) -> np.ndarray:
+    """mrk_train_categories: the category ids of a categorical column that get a bin of their own, ascending (host only)"""
+    col = _f64(column)
+    n = C.c_int(0)
+    cfg = _config(config)
+    N.check(N.lib().mrk_train_categories(cfg, col.ctypes.data, col.size, None, 0, C.byref(n)))
+    out = np.zeros(n.value, dtype=np.int32)
+    N.check(N.lib().mrk_train_categories(cfg, col.ctypes.data, col.size, out.ctypes.data, n.value, C.byref(n)))
+    return out
+
+
+def categorical_columns(columns) -> list:
+    """the `categorical` key of a fit on mrk_values' rows: the first column of every `category` feature of
+    HipRanker.values_columns() (string features with encode: index, the one-dimensional referer)"""
+    return [int(first) for _, first, _, kind in columns if kind == "category"]
+
+
 def lambdarank_gradients(scores, labels, group_offsets, ctx: Context | None = None, **config):
     """mrk_train_gradients: (g, h) of the lambdarank objective, one f64 per row"""
     s, y, off = _f64(scores), _f64(labels), _offsets(group_offsets)
@@ -111,7 +128,9 @@ class Trainer:
 def fit_lambdamart(X, labels, group_offsets, valid=None, ctx: Context | None = None, **config):
     """-> (HipBooster, history).  valid: (X, labels, group_offsets), which turns early stopping on.  history: iterations_run,
     best_iteration, metric (the validation ndcg after every iteration), model (the text), scores / valid_scores (the trainer's own, at
-    the best iteration).  A fit that ends without a tree has no forest to load: the booster is None."""
+    the best iteration).  A fit that ends without a tree has no forest to load: the booster is None.
+    Categorical columns (set-membership splits, include/mrk.h steps 2c and 5c) are named by the config:
+    fit_lambdamart(X, y, off, categorical=categorical_columns(ranker.values_columns()))."""
     ctx = ctx or default_context()
     t = Trainer(config, ctx)
     try:

@@ -10,14 +10,19 @@ device phases, per scan (the record read back after every split is a stream sync
 host's book-keeping); the restatement (tests/train_reference.py) for ONE iteration on the first --ref-groups groups of the same data on
 this host; and, if sklearn is importable, HistGradientBoostingRegressor's time per tree on the same matrix (a regressor on the labels:
 context only, another objective).  No threshold: nothing was measured before this tool existed.
+--categorical N declares the last N columns categorical (their cells rounded to ids 0 ... 49): the split search of those columns is
+include/mrk.h's step 5c, the restatement and sklearn then see the rounded columns as numbers.
   python tools/train_bench.py [--json] [--groups N] [--min-items N] [--max-items N] [--iterations N] [--leaves N] [--ref-groups N] [--valid]
+                              [--categorical N]
 """
 import argparse
+import hashlib
 import json
 import os
 import sys
 import time
 
+import numpy as np
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
@@ -42,13 +47,18 @@ def main():
     ap.add_argument("--leaves", type=int, default=16)
     ap.add_argument("--ref-groups", type=int, default=2000, help="groups of the restatement's one iteration (0: skip it)")
     ap.add_argument("--valid", action="store_true", help="a validation set of a tenth of the groups (early stopping stays out of reach)")
+    ap.add_argument("--categorical", type=int, default=0, help="declare the last N columns categorical; their cells are rounded to ids 0 ... 49 (NaN stays)")
     a = ap.parse_args()
     ctx = M.Context(0)
     X, y, off = synth.synthetic_ranking_rows(a.groups, a.min_items, a.max_items, COLS, seed=0)
     rows = int(off[-1])
     cfg = {"iterations": a.iterations, "numLeaves": a.leaves, "early_stopping": a.iterations}
+    cats = list(range(COLS - a.categorical, COLS))
+    if cats:                                                              # (without the option the config has no `categorical` key)
+        X[:, cats] = np.clip(np.rint((X[:, cats] + 3.0) * (49.0 / 6.0)), 0.0, 49.0)
+        cfg["categorical"] = cats
     out = {"groups": a.groups, "rows": rows, "items_per_group": [a.min_items, a.max_items], "columns": COLS, "iterations": a.iterations, "leaves": a.leaves,
-           "build": N.lib().mrk_build_id().decode()}
+           "categorical": cats, "build": N.lib().mrk_build_id().decode()}
 
     ctx.profile_enable(True)
     t = Trainer(cfg, ctx)
@@ -68,6 +78,8 @@ def main():
     for name in TIMERS:
         out[name + "_ms"], out[name + "_launches"] = parts[name]
     out["trees"] = hist["iterations_run"]
+    out["model_sha256"] = hashlib.sha256(model).hexdigest()               # (two builds that fit the same forest print the same digest)
+    out["categorical_nodes"] = sum(int(b.split("num_cat=")[1].split("\n")[0]) for b in model.decode().split("Tree=")[1:])
     out["splits"] = sum(len(b.split("split_feature=")[1].split("\n")[0].split()) for b in model.decode().split("Tree=")[1:])
     scans = parts["train_scan"][1]                                        # (one timer spans a scan and its pick)
     device_ms = sum(parts[name][0] for name in TIMERS if name != "train_bin")
