@@ -49,6 +49,8 @@
  * Still ABI 9, new symbols only: mrk_trending_* (the trending recommender of /recommend).
  * Still ABI 9, new symbols only: mrk_index_build_texts (the semantic recommender's fit), mrk_index_vectors.
  * Still ABI 9, new symbols only: mrk_als_* (the similar-items recommender's fit: eALS factors on the device).
+ * Still ABI 9, no new symbol and no struct change: mrk_train_* takes the config key "backend" ("xgboost": the level-wise fit that
+ * returns XGBoost JSON) and its keys lambda, gamma, min_child_weight; without the key a fit gives the bytes it gave before.
  */
 #ifndef MRK_H
 #define MRK_H
@@ -937,7 +939,48 @@ int mrk_model_eval(mrk_model *model, const int *metrics, const int *cutoffs, int
  *              the first ones taken, ascending.  Made on the host.
  *  8 stopping  with a validation set: ndcg@ndcgCutoff (relpow, nolabels = 1.0: mrk_eval_scores' number) after every iteration; the
  *              best iteration is replaced only by a strictly greater value; stops after early_stopping iterations without one;
- *              the model holds the trees up to the best iteration.  Without one: `iterations` trees. */
+ *              the model holds the trees up to the best iteration.  Without one: `iterations` trees.
+ *
+ * backend: "xgboost" - the XGBoostConfig arm of makeBooster (the default backend of a Metarank model, LambdaMARTRanker.scala:461), through
+ * the same symbols.  The key "backend" is "lightgbm" [the default: every rule above, byte for byte] or "xgboost"; another string is
+ * MRK_ERR_INVALID_ARG, another type MRK_ERR_PARSE.  ASSUMPTIONS (unpinned, as above): neither libxgboost nor its sources are on hand, so its
+ * bits are not claimed; treeMethod "exact" enumerates every distinct value, this is a histogram learner over at most 255 bins.  Both
+ * reproducibility rules hold unchanged (int64 sums of quantised values; exp and log2 from the host's tables).
+ * tests/train_xgb_reference.py restates it and the device agrees to the bit and the byte.  Keys and [defaults]: XGBoostConfig's iterations
+ * [100], learningRate [0.1], ndcgCutoff [10], maxDepth [8; 1 ... 15], seed [0], sampling [0.8: the ROW subsample, 0 < s <= 1], debias
+ * [false; true is MRK_ERR_UNSUPPORTED], and max_bin [255], truncation [30], sigma [1.0], early_stopping [20], lambda [1.0, >= 0], gamma
+ * [0.0, >= 0], min_child_weight [1.0, >= 0].  numLeaves, min_data_in_leaf, min_sum_hessian, lambda_l2, max_cat_to_onehot,
+ * max_cat_threshold, cat_smooth, cat_l2 and min_data_per_group are MRK_ERR_INVALID_ARG naming the key (a setting that would do
+ * nothing); so are lambda, gamma and min_child_weight under the default backend.  A non-empty `categorical` is MRK_ERR_UNSUPPORTED
+ * (set-membership splits in XGBoost JSON are not built; an undeclared category column splits as a number).  Steps 1, 3, 4 and 8 are the
+ * ones above; step 3 and step 8's metric read the widened f32 scores of 6x.
+ *  2x bins     per column, on the host: the cells are narrowed to f32 (round to nearest even; -0.0f counts as +0.0f); a finite f64 that
+ *              narrows to +-inf is MRK_ERR_INVALID_ARG naming column and row (predictMat refuses such a cell), in either set.  v = the
+ *              sorted non-NaN narrowed cells; the positions are step 2's.  The bound between neighbours a < b is b ITSELF, an f32:
+ *              XGBoost's cut convention is x < cut.  bin(x) = the number of bounds <= (float) x; NaN is bin 255.  Candidate c sends left
+ *              exactly the cells with (float) x < bound[c] - the emitted model's own test - so every possible cell, seen in training or
+ *              not, is routed the same way by the trainer and by the model.  mrk_train_bins returns these bounds widened to f64.
+ *  7x rows     row r is in tree t's sample when sampling >= 1 or (z >> 11) * 2^-53 < sampling, z = the first splitmix64 output from
+ *              the state ((uint64) (uint32) seed << 32 | t) ^ (r * 0xD6E8FEB86659FD93).  Computed where it is used; no list exists.  A
+ *              row outside the sample adds nothing to any histogram (neither its count nor q_g, q_h); it is still routed and scored.
+ *              Every tree sees all columns.
+ *  5x tree     level-wise.  The root is node 0.  The open nodes of depth d are taken in ascending id; a node that splits gives its left
+ *              child the next free id and its right child the one after: XGBoost's breadth-first numbering.  Per open node and column a
+ *              histogram (sum q_g, sum q_h, count) per bin over the SAMPLED rows.  Candidates and the NaN rule are step 5's.  Admitted
+ *              when both sides have >= 1 sampled row, HL >= min_child_weight and HR >= min_child_weight, d < maxDepth and gain =
+ *              (GL * GL / (HL + lambda) + GR * GR / (HR + lambda)) - G * G / (H + lambda) > gamma; every operation f64, correctly
+ *              rounded, never fused, from ldexp((double) Q, -e).  Best per node: the highest gain, then the lowest column, the lowest
+ *              bin, NaN right.  EVERY open node with an admitted candidate splits - nodes do not compete -, the others are leaves.
+ *              weight = -G / (H + lambda) (H + lambda == 0: MRK_ERR_INVALID_ARG at mrk_train_fit); a leaf's value is (float) (weight *
+ *              learningRate).  A tree whose root cannot split ends training and is not emitted.
+ *  6x scores   f32, as the model predicts them: s = 0.5f (the base_score), then s = s + leaf in f32, in tree order.  Training rows -
+ *              the unsampled ones too - and validation rows take the leaf their bins route them to.  mrk_train_scores returns the
+ *              widened value, equal to mrk_model_predict_f64 of the emitted model bit for bit; without a tree every score is 0.5.
+ *  model text  XGBoost's JSON as libxgboost 2.1 writes it (version [2,1,0], objective rank:ndcg, base_score "5E-1", num_feature = cols,
+ *              empty categorical arrays), no whitespace.  Per tree split_conditions = the bound or the leaf value, base_weights =
+ *              (float) weight, loss_changes = (float) gain (0 for a leaf: Booster.weights() works), sum_hessian = (float) H, parents
+ *              2147483647 for the root, default_left = NaN goes left, split_type all 0.  Every f32 is printed as %.9g of its widened
+ *              value.  mrk_model_load(MRK_BACKEND_XGBOOST) reads it. */
 #define MRK_TRAIN_SIGMOID_BINS 65536
 typedef struct mrk_trainer mrk_trainer;
 
@@ -948,12 +991,13 @@ int mrk_train_begin(mrk_ctx *ctx, const char *config_json, mrk_trainer **out);
  * the device, and nothing of the caller's is kept.  MRK_ERR_INVALID_ARG: null pointers, a bad `which`, rows / cols < 1, offsets
  * that do not start at 0 or do not strictly increase, a label that is no integer in 0 ... 30, an infinite cell.
  * MRK_ERR_UNSUPPORTED, with the sizes in mrk_last_error: cols > 65535, rows >= 2^31, a group of more than 4096 rows, working
- * memory (bins, gradients, numLeaves x subset x 256 histogram cells) beyond what the device has free. */
+ * memory (bins, gradients, numLeaves x subset x 256 histogram cells; backend "xgboost": 2 levels x min(2^(maxDepth - 1), rows) nodes x
+ * cols x 256 cells of 20 B) beyond what the device has free. */
 int mrk_train_set(mrk_trainer *t, int which, const double *rowmajor, int64_t rows, int cols, const double *labels, const int64_t *group_offsets,
                   int64_t n_groups);
 /* Runs the fit (steps 3 - 8). */
 int mrk_train_fit(mrk_trainer *t);
-/* The model text.  *needed: its length in bytes; copies it when cap >= *needed (out may be NULL to ask for the length). */
+/* The model text (LightGBM's text format, or XGBoost's JSON with backend "xgboost").  *needed: its length in bytes; copies it when cap >= *needed (out may be NULL to ask for the length). */
 int mrk_train_model(mrk_trainer *t, void *out, size_t cap, size_t *needed);
 /* iterations_run: trees grown; best_iteration: trees in the model; out_metric (nullable): the validation metric after each iteration,
  * min(cap, iterations_run) values (none without a validation set). */
@@ -965,7 +1009,8 @@ void mrk_train_free(mrk_trainer *t);
  * host that keeps lib_lightgbm.  A non-finite score is MRK_ERR_INVALID_ARG. */
 int mrk_train_gradients(mrk_ctx *ctx, const char *config_json, const double *scores, const double *labels, const int64_t *group_offsets,
                         int64_t n_groups, double *out_g, double *out_h);
-/* Step 2 for one column of n cells (host only, no context): *n_bounds bounds, copied when cap >= *n_bounds. */
+/* Step 2 (step 2x when the config says backend "xgboost") for one column of n cells (host only, no context): *n_bounds bounds, copied
+ * when cap >= *n_bounds. */
 int mrk_train_bins(const char *config_json, const double *column, int64_t n, double *out_bounds, int cap, int *n_bounds);
 /* Step 2c for one column of n cells (host only, no context): *n_ids kept category ids in ascending order (the bin of an id is its
  * position), copied when cap >= *n_ids.  Uses max_bin of the config. */

@@ -2,6 +2,8 @@
 // LightGBM backend.  Gradients, histograms, split scans and score updates are train.hip; config, bins, feature subsets, tables, the
 // tree book-keeping and the model text are train_host.cpp; the validation metric is eval.hip's (the number mrk_eval_scores gives).
 // The loop over splits is driven from here: per split one histogram launch, one scan, two records read back.
+// backend "xgboost" (steps 2x, 5x, 6x, 7x): the loop is over LEVELS - per level one histogram launch, one scan, the level's records
+// read back once - and the model text is XGBoost's JSON.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -48,6 +50,8 @@ struct mrk_trainer {
   TrainSet set[2];
   bool fitted = false;
   std::vector<TrainTree> trees;
+  std::vector<TrainXgbTree> xtrees;         // backend "xgboost"
+  int iterations_run = 0;
   std::vector<double> history;
   int best_iteration = 0;
   std::string model;
@@ -89,6 +93,9 @@ void for_columns(int cols, F f) {
   if (err) std::rethrow_exception(err);
 }
 
+// backend "xgboost": the most nodes of one level that is scanned (depth < maxDepth; every node holds a sampled row)
+int64_t level_cap(const TrainConfig &cfg, int64_t rows) { return std::max<int64_t>(1, std::min<int64_t>(int64_t(1) << (cfg.max_depth - 1), rows)); }
+
 void check_free(double want, const std::string &what) {
   size_t free_b = 0, total_b = 0;
   MRK_HIP(hipMemGetInfo(&free_b, &total_b));
@@ -121,6 +128,7 @@ void set_locked(mrk_trainer *t, int which, const double *x, int64_t rows, int co
     for (int64_t i = 0; i < rows * cols; ++i)
       if (std::isinf(x[i])) throw StatusError(MRK_ERR_INVALID_ARG, "train: cell " + std::to_string(i) + " of the validation matrix is infinite");
     for (int32_t c : t->cfg.categorical) train_check_categories(x + c, rows, cols, c);
+    if (t->cfg.backend == TRAIN_BACKEND_XGBOOST) for_columns(cols, [&](int c) { train_check_f32_cells(x + c, rows, cols, c); });
   } else {
     t->set[1] = TrainSet();
     t->cols = cols;
@@ -131,7 +139,8 @@ void set_locked(mrk_trainer *t, int which, const double *x, int64_t rows, int co
     for (int32_t c : t->cfg.categorical) t->is_cat[(size_t)c] = 1;
     t->any_cat = !t->cfg.categorical.empty();
     for_columns(cols, [&](int c) {
-      if (t->is_cat[(size_t)c]) t->kept[(size_t)c] = train_kept_categories(x + c, rows, cols, t->cfg.max_bin, c, &t->infos[(size_t)c]);
+      if (t->cfg.backend == TRAIN_BACKEND_XGBOOST) t->bounds[(size_t)c] = train_bin_bounds_f32(x + c, rows, cols, t->cfg.max_bin, c);
+      else if (t->is_cat[(size_t)c]) t->kept[(size_t)c] = train_kept_categories(x + c, rows, cols, t->cfg.max_bin, c, &t->infos[(size_t)c]);
       else t->bounds[(size_t)c] = train_bin_bounds(x + c, rows, cols, t->cfg.max_bin, &t->infos[(size_t)c]);
     });
   }
@@ -144,12 +153,17 @@ void set_locked(mrk_trainer *t, int which, const double *x, int64_t rows, int co
   hipStream_t st = lk.stream;
   const std::vector<EvalPiece> pieces = eval_pieces(rows, cols, env_int("MRK_TRAIN_PIECE_ROWS", 0));
   const size_t piece_bytes = (size_t)pieces[0].rows * (size_t)cols * 8;
-  const int n_sub = (int)train_feature_subset(cols, t->cfg.sampling, 0, 0).size();
+  const bool xgb = t->cfg.backend == TRAIN_BACKEND_XGBOOST;
+  const int n_sub = xgb ? cols : (int)train_feature_subset(cols, t->cfg.sampling, 0, 0).size();
+  // the histograms: numLeaves slots, or (xgboost) two levels of level_cap slots; per slot and column 256 cells of 20 B and a record
+  const double hist_slots = xgb ? 2.0 * (double)level_cap(t->cfg, rows) : (double)t->cfg.num_leaves;
   // resident for the fit: the bins, per row g, h, q_g, q_h, score, best score, leaf and label, the lists of groups, the histograms
   const double fit_bytes = (double)rows * cols + 51.0 * (double)rows + 12.0 * (double)n_groups +
-                           (which == 0 ? 20.0 * 256.0 * (double)n_sub * (double)t->cfg.num_leaves + 2.0 * sizeof(LeafRec) * (double)n_sub : 9.0 * (double)rows + 8.0 * (double)n_groups);
+                           (which == 0 ? (20.0 * 256.0 + (xgb ? sizeof(LeafRec) : 0)) * (double)n_sub * hist_slots + 2.0 * sizeof(LeafRec) * (double)n_sub + (xgb ? 2.0 * (double)rows : 0.0)
+                                       : 9.0 * (double)rows + 8.0 * (double)n_groups + (xgb ? 2.0 * (double)rows : 0.0));
   check_free(fit_bytes + (double)piece_bytes + 1048576.0, std::to_string(rows) + " rows x " + std::to_string(cols) + " columns in " + std::to_string(n_groups) + " groups, " +
-                                                              std::to_string(t->cfg.num_leaves) + " leaves x " + std::to_string(n_sub) + " columns of histograms");
+                                                              (xgb ? "2 levels x " + std::to_string(level_cap(t->cfg, rows)) + " nodes x " : std::to_string(t->cfg.num_leaves) + " leaves x ") + std::to_string(n_sub) +
+                                                              " columns of histograms");
   if (which == 0) {
     std::vector<double> flat;
     std::vector<int> boff((size_t)cols + 1, 0), nbins((size_t)cols);
@@ -180,8 +194,10 @@ void set_locked(mrk_trainer *t, int which, const double *x, int64_t rows, int co
   d_x.reserve(piece_bytes);
   for (const EvalPiece &pc : pieces) {
     MRK_HIP(hipMemcpyAsync(d_x.p, x + (size_t)pc.row0 * (size_t)cols, (size_t)pc.rows * (size_t)cols * 8, hipMemcpyHostToDevice, st));
-    train_launch_bin(ctx, st, d_x.as<double>(), pc.rows, cols, t->d_bounds.as<double>(), t->d_bound_off.as<int>(), t->any_cat ? t->d_cat_idx.as<int>() : nullptr,
-                     t->any_cat ? t->d_cat_tables.as<uint8_t>() : nullptr, s.d_bins.as<uint8_t>(), rows, pc.row0);
+    if (xgb) train_launch_bin_f32(ctx, st, d_x.as<double>(), pc.rows, cols, t->d_bounds.as<double>(), t->d_bound_off.as<int>(), s.d_bins.as<uint8_t>(), rows, pc.row0);
+    else
+      train_launch_bin(ctx, st, d_x.as<double>(), pc.rows, cols, t->d_bounds.as<double>(), t->d_bound_off.as<int>(), t->any_cat ? t->d_cat_idx.as<int>() : nullptr,
+                       t->any_cat ? t->d_cat_tables.as<uint8_t>() : nullptr, s.d_bins.as<uint8_t>(), rows, pc.row0);
   }
   upload(s.d_labels, s.labels, st);
   upload(s.d_off, s.offsets, st);
@@ -223,6 +239,121 @@ void launch_gradients(mrk_ctx *ctx, hipStream_t st, const GradDev &d, const Eval
   train_launch_grad_group(ctx, st, d, d_group.as<int>(), (int)by_size.group.size(), (int)by_size.group_max_len);
 }
 
+// backend "xgboost": the buffers of the level-wise grower and one tree's growth (step 5x).  Two levels of histograms are resident -
+// the level being built and its parents' (sibling = parent - built child) - in slots [buf * cap, buf * cap + cap) of one HistDev.
+struct LevelGrower {
+  int64_t cap = 0;   // level_cap
+  int cols = 0;
+  DevBuf d_G, d_H, d_C, d_feat_best, d_recs, d_tables, d_value, d_hist_slot, d_vnode_of;
+  PinBuf h_recs, h_tables, h_value;
+  // one block per level, host -> device in one copy: the level's split records, the next level's built slots and scan nodes
+  size_t off_build = 0, off_nodes = 0, table_bytes = 0;
+
+  void reserve(const TrainConfig &cfg, int64_t rows, int64_t valid_rows, int cols_) {
+    cap = level_cap(cfg, rows), cols = cols_;
+    const size_t cells = 2 * (size_t)cap * (size_t)cols * 256;
+    d_G.reserve(cells * 8), d_H.reserve(cells * 8), d_C.reserve(cells * 4);
+    d_feat_best.reserve((size_t)cap * (size_t)cols * sizeof(LeafRec));
+    d_recs.reserve((size_t)cap * sizeof(LeafRec)), h_recs.reserve((size_t)cap * sizeof(LeafRec));
+    off_build = (size_t)cap * sizeof(LevelRec), off_nodes = off_build + (size_t)cap * 4, table_bytes = off_nodes + (size_t)cap * sizeof(LevelNode);
+    d_tables.reserve(table_bytes), h_tables.reserve(table_bytes);
+    const size_t max_nodes = std::min<size_t>((size_t(2) << cfg.max_depth), 4 * (size_t)cap + 1);   // (a level has at most twice the nodes of the one above)
+    d_value.reserve(max_nodes * 4), h_value.reserve(max_nodes * 4);
+    d_hist_slot.reserve((size_t)rows * 2);
+    if (valid_rows > 0) d_vnode_of.reserve((size_t)valid_rows * 2);
+  }
+
+  // -> false when the root cannot split.  node_of: per training row, 0 on entry (train_launch_quantise); on return every row's node.
+  // The stream is waited for once per level that is scanned (the level's records), never per node.
+  bool grow(mrk_trainer *t, hipStream_t st, int tree_index, const ScanParams &sp, const long long *qg, const long long *qh, uint16_t *node_of, TrainXgbTree &tree,
+            std::vector<TrainSums> &totals) {
+    mrk_ctx *ctx = t->ctx;
+    const TrainConfig &cfg = t->cfg;
+    TrainSet &tr = t->set[0], &va = t->set[1];
+    const HistDev hd{d_G.as<long long>(), d_H.as<long long>(), d_C.as<unsigned>(), cols};
+    uint16_t *hist_slot = d_hist_slot.as<uint16_t>();
+    LevelRec *h_lrec = (LevelRec *)h_tables.as<uint8_t>();
+    int *h_build = (int *)(h_tables.as<uint8_t>() + off_build);
+    LevelNode *h_nodes = (LevelNode *)(h_tables.as<uint8_t>() + off_nodes);
+    const LevelRec *d_lrec = (const LevelRec *)d_tables.as<uint8_t>();
+    const int *d_build = (const int *)(d_tables.as<uint8_t>() + off_build);
+    const LevelNode *d_nodes = (const LevelNode *)(d_tables.as<uint8_t>() + off_nodes);
+    const LeafRec *recs = h_recs.as<LeafRec>();
+    auto zero_level = [&](int buf, size_t n) {
+      const size_t at = (size_t)buf * (size_t)cap * (size_t)cols * 256, cells = n * (size_t)cols * 256;
+      MRK_HIP(hipMemsetAsync(hd.G + at, 0, cells * 8, st));
+      MRK_HIP(hipMemsetAsync(hd.H + at, 0, cells * 8, st));
+      MRK_HIP(hipMemsetAsync(hd.C + at, 0, cells * 4, st));
+    };
+
+    train_launch_level_begin(ctx, st, tr.rows, cfg.sampling, cfg.seed, tree_index, node_of, hist_slot);
+    if (va.given) MRK_HIP(hipMemsetAsync(d_vnode_of.p, 0, (size_t)va.rows * 2, st));
+    tree = TrainXgbTree();
+    tree.add(2147483647);
+    totals.assign(1, TrainSums());
+    std::vector<int> ids{0};   // the nodes of the level, ascending
+    h_build[0] = 0;
+    h_nodes[0] = LevelNode{0, -1, -1};
+    MRK_HIP(hipMemcpyAsync(d_tables.p, h_tables.p, table_bytes, hipMemcpyHostToDevice, st));
+    zero_level(0, 1);
+    train_launch_level_hist(ctx, st, tr.d_bins.as<uint8_t>(), tr.rows, hist_slot, qg, qh, d_build, 1, hd);
+    for (int d = 0, buf = 0; d < cfg.max_depth; ++d, buf ^= 1) {
+      const int n = (int)ids.size();
+      train_launch_level_scan(ctx, st, hd, t->d_nbins.as<int>(), d_nodes, n, sp, d_feat_best.as<LeafRec>(), d_recs.as<LeafRec>());
+      {
+        ScopedKernelTimer timer(ctx, "train_level_readback");
+        MRK_HIP(hipMemcpyAsync(h_recs.p, d_recs.p, (size_t)n * sizeof(LeafRec), hipMemcpyDeviceToHost, st));
+      }
+      MRK_HIP(hipStreamSynchronize(st));   // (h_tables is free again too)
+      if (d == 0) totals[0] = TrainSums{recs[0].g, recs[0].h, recs[0].c};
+      const bool build_next = d + 1 < cfg.max_depth;
+      std::vector<int> next;
+      int n_build = 0;
+      for (int k = 0; k < n; ++k) {
+        const LeafRec &c = recs[k];
+        LevelRec &lr = h_lrec[k];
+        lr = LevelRec{-1, 0, (uint16_t)TRAIN_NO_SLOT, (uint16_t)TRAIN_NO_SLOT, 0, 0};
+        if (!c.valid) continue;
+        const int node = ids[(size_t)k];
+        const TrainSums whole = totals[(size_t)node];
+        tree.split(node, c.col, c.bin, (float)t->bounds[(size_t)c.col][(size_t)c.bin], c.nan_left != 0, (float)c.gain);
+        const int l = tree.num_nodes() - 2;
+        const TrainSums left{c.gl, c.hl, c.cl}, right{whole.g - c.gl, whole.h - c.hl, whole.c - c.cl};
+        totals.push_back(left), totals.push_back(right);
+        lr.col = c.col, lr.left = (uint16_t)l, lr.bin = (uint8_t)c.bin, lr.nan_left = (uint8_t)(c.nan_left != 0);
+        if (build_next) {   // the child with fewer sampled rows is built (ties: the left), its sibling is parent - built
+          const int kl = (int)next.size(), parent_slot = buf * (int)cap + k, slot_l = (buf ^ 1) * (int)cap + kl;
+          const bool left_built = left.c <= right.c;
+          (left_built ? lr.slot_l : lr.slot_r) = (uint16_t)n_build;
+          h_build[n_build++] = left_built ? slot_l : slot_l + 1;
+          h_nodes[kl] = left_built ? LevelNode{slot_l, -1, -1} : LevelNode{slot_l, parent_slot, slot_l + 1};
+          h_nodes[kl + 1] = left_built ? LevelNode{slot_l + 1, parent_slot, slot_l} : LevelNode{slot_l + 1, -1, -1};
+        }
+        next.push_back(l), next.push_back(l + 1);
+      }
+      if (next.empty()) break;
+      MRK_HIP(hipMemcpyAsync(d_tables.p, h_tables.p, table_bytes, hipMemcpyHostToDevice, st));
+      train_launch_level_split(ctx, st, tr.d_bins.as<uint8_t>(), tr.rows, node_of, hist_slot, d_lrec, ids[0], n, cfg.sampling, cfg.seed, tree_index);
+      if (va.given) train_launch_level_split(ctx, st, va.d_bins.as<uint8_t>(), va.rows, d_vnode_of.as<uint16_t>(), nullptr, d_lrec, ids[0], n, cfg.sampling, cfg.seed, tree_index);
+      if (build_next) {
+        zero_level(buf ^ 1, next.size());
+        train_launch_level_hist(ctx, st, tr.d_bins.as<uint8_t>(), tr.rows, hist_slot, qg, qh, d_build, n_build, hd);
+      }
+      ids.swap(next);
+    }
+    if (tree.num_nodes() == 1) return false;
+    float *value = h_value.as<float>();
+    for (int node = 0; node < tree.num_nodes(); ++node) {
+      tree.weigh(node, totals[(size_t)node], sp.e_g, sp.e_h, cfg.lambda, cfg.learning_rate);
+      value[node] = tree.cond[(size_t)node];   // (read for leaves alone)
+    }
+    MRK_HIP(hipMemcpyAsync(d_value.p, h_value.p, (size_t)tree.num_nodes() * 4, hipMemcpyHostToDevice, st));
+    train_launch_level_apply(ctx, st, d_value.as<float>(), node_of, tr.rows, tr.d_score.as<double>());
+    if (va.given) train_launch_level_apply(ctx, st, d_value.as<float>(), d_vnode_of.as<uint16_t>(), va.rows, va.d_score.as<double>());
+    return true;
+  }
+};
+
 void fit_locked(mrk_trainer *t) {
   need(t->set[0].given, "train: no training set");
   need(!t->fitted, "train: the trainer has been fitted");
@@ -236,15 +367,23 @@ void fit_locked(mrk_trainer *t) {
   std::unique_ptr<DeviceLock> lk(new DeviceLock(ctx));
   hipStream_t st = lk->stream;
   // a fit starts from score 0, also after one that a device error ended half-way
+  const bool xgb = cfg.backend == TRAIN_BACKEND_XGBOOST;
   for (TrainSet *s : {&tr, &va})
     if (s->given) {
+      if (xgb) {   // step 6x: the model's base_score
+        train_launch_level_base(ctx, st, s->rows, s->d_score.as<double>());
+        train_launch_level_base(ctx, st, s->rows, s->d_best.as<double>());
+        continue;
+      }
       MRK_HIP(hipMemsetAsync(s->d_score.p, 0, (size_t)s->rows * 8, st));
       MRK_HIP(hipMemsetAsync(s->d_best.p, 0, (size_t)s->rows * 8, st));
     }
 
   GradTables tab;
   tab.make(cfg, std::max(tr.max_len, va.given ? va.max_len : 0), st);
-  const int n_sub_max = (int)train_feature_subset(cols, cfg.sampling, 0, 0).size();
+  const int n_sub_max = xgb ? 0 : (int)train_feature_subset(cols, cfg.sampling, 0, 0).size();   // (the xgboost backend's histograms are the grower's)
+  LevelGrower grower;
+  if (xgb) grower.reserve(cfg, rows, va.given ? va.rows : 0, cols);
   DevBuf d_g, d_h, d_qg, d_qh, d_leaf_of, d_maxes, d_G, d_H, d_C, d_feat_best, d_recs, d_subset;
   DevBuf d_tcol, d_tbin, d_tnan, d_tleft, d_tright, d_tvalue, d_tis_cat, d_tmask;
   d_g.reserve((size_t)rows * 8), d_h.reserve((size_t)rows * 8), d_qg.reserve((size_t)rows * 8), d_qh.reserve((size_t)rows * 8);
@@ -286,7 +425,7 @@ void fit_locked(mrk_trainer *t) {
   const uint8_t *bins = tr.d_bins.as<uint8_t>();
   uint16_t *leaf_of = d_leaf_of.as<uint16_t>();
   double best_metric = 0.0;
-  t->trees.clear(), t->history.clear(), t->best_iteration = 0;
+  t->trees.clear(), t->xtrees.clear(), t->history.clear(), t->best_iteration = 0, t->iterations_run = 0;
 
   for (int it = 0; it < cfg.iterations; ++it) {
     if (it > 0) {
@@ -303,8 +442,14 @@ void fit_locked(mrk_trainer *t) {
     memcpy(&gmax, &h_maxes[0], 8), memcpy(&hmax, &h_maxes[1], 8);
     if (gmax == 0.0) break;
     ScanParams sp{train_exponent(gmax, rows), train_exponent(hmax, rows), cfg.min_data_in_leaf, cfg.min_sum_hessian, cfg.lambda_l2,
-                  cfg.max_cat_to_onehot, cfg.max_cat_threshold, std::max(cfg.min_data_in_leaf, cfg.min_data_per_group), cfg.cat_smooth, cfg.lambda_l2 + cfg.cat_l2};
+                  cfg.max_cat_to_onehot, cfg.max_cat_threshold, std::max(cfg.min_data_in_leaf, cfg.min_data_per_group), cfg.cat_smooth, cfg.lambda_l2 + cfg.cat_l2, 0.0};
+    if (xgb) sp.min_data = 1, sp.min_hess = cfg.min_child_weight, sp.l2 = cfg.lambda, sp.min_gain = cfg.gamma;   // step 5x's admission rule
     train_launch_quantise(ctx, st, gd.g, gd.h, rows, sp.e_g, sp.e_h, d_qg.as<long long>(), d_qh.as<long long>(), leaf_of);
+    TrainXgbTree xtree;
+    std::vector<TrainSums> xtotals;
+    if (xgb && !grower.grow(t, st, it, sp, d_qg.as<long long>(), d_qh.as<long long>(), leaf_of, xtree, xtotals)) break;
+    TrainTree tree;
+    if (!xgb) {
     const std::vector<int32_t> subset = train_feature_subset(cols, cfg.sampling, cfg.seed, it);
     MRK_HIP(hipMemcpyAsync(d_subset.p, subset.data(), subset.size() * 4, hipMemcpyHostToDevice, st));   // (waited for with the root's record)
     HistDev hd{d_G.as<long long>(), d_H.as<long long>(), d_C.as<unsigned>(), (int)subset.size()};
@@ -315,7 +460,6 @@ void fit_locked(mrk_trainer *t) {
       MRK_HIP(hipMemcpyAsync(h_recs, d_recs.p, 2 * sizeof(LeafRec), hipMemcpyDeviceToHost, st));
       MRK_HIP(hipStreamSynchronize(st));
     };
-    TrainTree tree;
     train_launch_hist(ctx, st, bins, rows, leaf_of, 0, 0, d_qg.as<long long>(), d_qh.as<long long>(), d_subset.as<int>(), hd);
     scan(0, -1, false);
     std::vector<LeafRec> cand{h_recs[0]};
@@ -378,8 +522,9 @@ void fit_locked(mrk_trainer *t) {
     const TreeDev td{d_tcol.as<int>(), d_tbin.as<int>(), d_tnan.as<int>(), d_tleft.as<int>(), d_tright.as<int>(), d_tvalue.as<double>(),
                      cat_tree ? d_tis_cat.as<int>() : nullptr, cat_tree ? d_tmask.as<unsigned>() : nullptr};
     train_launch_apply(ctx, st, td, leaf_of, nullptr, rows, tr.d_score.as<double>());
+    if (va.given) train_launch_apply(ctx, st, td, nullptr, va.d_bins.as<uint8_t>(), va.rows, va.d_score.as<double>());
+    }
     if (va.given) {
-      train_launch_apply(ctx, st, td, nullptr, va.d_bins.as<uint8_t>(), va.rows, va.d_score.as<double>());
       {
         ScopedKernelTimer timer(ctx, "train_eval");
         eval_launch_wave(ctx, st, ev, va.d_wave.as<int>(), (int)va.by_size.wave.size());
@@ -388,8 +533,9 @@ void fit_locked(mrk_trainer *t) {
       MRK_HIP(hipMemcpyAsync(per_group.data(), d_metric.p, per_group.size() * 8, hipMemcpyDeviceToHost, st));
     }
     MRK_HIP(hipStreamSynchronize(st));   // the tree's arrays have left the host; the metric has arrived
-    t->trees.push_back(std::move(tree));
-    const int n_trees = (int)t->trees.size();
+    if (xgb) t->xtrees.push_back(std::move(xtree));
+    else t->trees.push_back(std::move(tree));
+    const int n_trees = t->iterations_run = (int)(xgb ? t->xtrees.size() : t->trees.size());
     if (!va.given) {
       t->best_iteration = n_trees;
       continue;
@@ -409,7 +555,8 @@ void fit_locked(mrk_trainer *t) {
   }
   MRK_HIP(hipStreamSynchronize(st));
   drain_profile_events(ctx);
-  t->model = train_write_model(t->trees, (size_t)t->best_iteration, cols, t->infos, cfg.learning_rate, &t->kept);
+  t->model = xgb ? train_write_xgb_model(t->xtrees, (size_t)t->best_iteration, cols)
+                 : train_write_model(t->trees, (size_t)t->best_iteration, cols, t->infos, cfg.learning_rate, &t->kept);
   t->fitted = true;
 }
 
@@ -466,7 +613,7 @@ int mrk_train_history(mrk_trainer *t, int *iterations_run, int *best_iteration, 
     check_trainer(t);
     std::lock_guard<std::mutex> lk(t->mu);
     if (!t->fitted) throw StatusError(MRK_ERR_NOT_FOUND, "train: not fitted yet");
-    if (iterations_run) *iterations_run = (int)t->trees.size();
+    if (iterations_run) *iterations_run = t->iterations_run;
     if (best_iteration) *best_iteration = t->best_iteration;
     if (out_metric)
       for (int i = 0; i < cap && i < (int)t->history.size(); ++i) out_metric[i] = t->history[(size_t)i];
@@ -540,7 +687,7 @@ int mrk_train_bins(const char *config_json, const double *column, int64_t n, dou
     const TrainConfig cfg = train_parse_config(config_json, strlen(config_json));
     need(n_bounds != nullptr, "n_bounds is null");
     need(n >= 0 && (column != nullptr || n == 0), "train: null column");
-    const std::vector<double> b = train_bin_bounds(column, n, 1, cfg.max_bin);
+    const std::vector<double> b = cfg.backend == TRAIN_BACKEND_XGBOOST ? train_bin_bounds_f32(column, n, 1, cfg.max_bin, 0) : train_bin_bounds(column, n, 1, cfg.max_bin);
     *n_bounds = (int)b.size();
     if (out_bounds && cap >= (int)b.size() && !b.empty()) memcpy(out_bounds, b.data(), b.size() * 8);
   });

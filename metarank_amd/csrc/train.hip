@@ -18,6 +18,16 @@
 //   train_split, train_split_cat         rows of the split leaf that go right get the new leaf (by bin <= b; by a mask over bins)
 //   train_apply                          score += leaf value (training rows by leaf_of, validation rows by walking the tree)
 // train_bin (once per fit) turns the f64 matrix into column-major bytes (a categorical column through its id -> bin table, step 2c).
+// backend "xgboost" (steps 2x, 5x, 6x, 7x) grows LEVEL-wise with the same gradients, quantisation and scan body:
+//   train_bin_f32                        the cell narrowed to f32, bin = the number of f32 bounds <= it
+//   train_level_begin                    per tree: node_of = 0, hist_slot = 0 for a sampled row, 0xFFFF for the others
+//   train_level_hist                     one launch per level, per (row tile, column, chunk of built nodes): LDS histograms of the rows
+//                                        whose hist_slot lies in the chunk, non-empty bins flushed with global integer atomics
+//   train_level_scan (+ train_pick)      per (node of the level, column): sibling = parent - built child, then scan_column under step
+//                                        5x's admission rule; per node the best column; the level's records are read back once
+//   train_level_split                    one row pass per level: the level's records in LDS, a row moves to its child and gets the
+//                                        child's built slot (0xFFFF when the child is not built or the row is outside the sample)
+//   train_level_apply, train_level_base  score = (double) ((float) score + leaf[node_of]); score = 0.5, the base_score
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -32,7 +42,7 @@
 namespace mrk {
 
 static_assert(TRAIN_MAX_GROUP <= 65536, "the group kernel keeps indices as u16");
-static_assert(TRAIN_HIST_ROWS % TRAIN_ROW_THREADS == 0, "a histogram workgroup takes whole rounds of rows");
+static_assert(TRAIN_HIST_ROWS % TRAIN_ROW_THREADS == 0 && TRAIN_LEVEL_ROWS % TRAIN_ROW_THREADS == 0, "a histogram workgroup takes whole rounds of rows");
 
 namespace {
 
@@ -320,7 +330,7 @@ __device__ void scan_column(long long g, long long h, long long c, int nb, int c
       const long long rg = Tg - lg_, rh = Th - lh, rc = Tc - lc;
       const double HL = real_of(lh, p.e_h), HR = real_of(rh, p.e_h);
       const double gain = __dsub_rn(__dadd_rn(side_term(lg_, lh, p), side_term(rg, rh, p)), parent);
-      const bool ok = lc >= p.min_data && rc >= p.min_data && HL >= p.min_hess && HR >= p.min_hess && gain > 0.0;
+      const bool ok = lc >= p.min_data && rc >= p.min_data && HL >= p.min_hess && HR >= p.min_hess && gain > p.min_gain;
       if (ok && (code < 0 || gain > best)) {   // (NaN to the right wins a tie)
         best = gain;
         code = tid * 2 + nl;
@@ -554,6 +564,139 @@ train_apply_kernel(TreeDev t, const uint16_t *__restrict__ leaf_of, const uint8_
   scores[i] = __dadd_rn(scores[i], t.leaf_value[leaf]);
 }
 
+// ---- the xgboost backend (train.hpp: the level-wise grower) ----
+
+// step 2x: the cell narrowed to f32 (round to nearest even), its bin the number of bounds <= it
+__global__ void __launch_bounds__(TRAIN_BIN_ROWS)
+train_bin_f32_kernel(const double *__restrict__ x, int piece_rows, int cols, const double *__restrict__ bounds, const int *__restrict__ bound_off,
+                     uint8_t *__restrict__ bins, long long rows, long long row0) {
+  const int i = blockIdx.x * TRAIN_BIN_ROWS + threadIdx.x;
+  if (i >= piece_rows) return;
+  const double *row = x + (long long)i * cols;
+  for (int c = 0; c < cols; ++c) {
+    const float v = __double2float_rn(row[c]);
+    int a = bound_off[c], b = bound_off[c + 1];
+    const int first = a;
+    while (a < b) {   // the number of bounds <= v (a bound is an f32 value: the conversion is exact)
+      const int m = (a + b) >> 1;
+      if ((float)bounds[m] <= v) a = m + 1;
+      else b = m;
+    }
+    bins[(long long)c * rows + row0 + i] = v != v ? (uint8_t)TRAIN_NAN_BIN : (uint8_t)(a - first);
+  }
+}
+
+__global__ void __launch_bounds__(TRAIN_ROW_THREADS)
+train_level_begin_kernel(long long rows, double sampling, int seed, int tree, uint16_t *__restrict__ node_of, uint16_t *__restrict__ hist_slot) {
+  const long long i = (long long)blockIdx.x * TRAIN_ROW_THREADS + threadIdx.x;
+  if (i >= rows) return;
+  node_of[i] = 0;
+  hist_slot[i] = train_row_sampled(sampling, seed, tree, (u64)i) ? (uint16_t)0 : (uint16_t)TRAIN_NO_SLOT;
+}
+
+// blockIdx: (row tile, column, chunk of built nodes).  A row whose hist_slot lies in the chunk adds (q_g, q_h, 1) to its node's LDS
+// histogram of this column; non-empty bins go to memory with integer atomics: every arrangement of tiles gives the same sums
+__global__ void __launch_bounds__(TRAIN_ROW_THREADS)
+train_level_hist_kernel(const uint8_t *__restrict__ bins, long long rows, const uint16_t *__restrict__ hist_slot, const long long *__restrict__ qg,
+                        const long long *__restrict__ qh, const int *__restrict__ build_slot, int n_build, HistDev hd) {
+  __shared__ u64 s_g[TRAIN_LEVEL_CHUNK][256], s_h[TRAIN_LEVEL_CHUNK][256];
+  __shared__ unsigned s_c[TRAIN_LEVEL_CHUNK][256];
+  const int tid = threadIdx.x;
+  const int j = blockIdx.y;
+  const unsigned chunk = blockIdx.z;
+  const int nn = min(TRAIN_LEVEL_CHUNK, n_build - (int)chunk * TRAIN_LEVEL_CHUNK);
+  for (int f = 0; f < nn; ++f) {
+    s_g[f][tid] = 0;
+    s_h[f][tid] = 0;
+    s_c[f][tid] = 0;
+  }
+  const uint8_t *col = bins + (long long)j * rows;
+  __syncthreads();
+  const long long tile0 = (long long)blockIdx.x * TRAIN_LEVEL_ROWS;
+  for (int step = 0; step < TRAIN_LEVEL_ROWS / TRAIN_ROW_THREADS; ++step) {
+    const long long row = tile0 + step * TRAIN_ROW_THREADS + tid;
+    if (row >= rows) continue;
+    const unsigned bs = hist_slot[row];
+    if (bs / TRAIN_LEVEL_CHUNK != chunk) continue;   // (TRAIN_NO_SLOT lies in no chunk: n_build <= 32768)
+    const int f = (int)(bs % TRAIN_LEVEL_CHUNK);     // (< nn: a slot is below n_build)
+    const int b = col[row];
+    atomicAdd(&s_g[f][b], (u64)qg[row]);             // (two's complement: the unsigned sum is the signed one)
+    atomicAdd(&s_h[f][b], (u64)qh[row]);
+    atomicAdd(&s_c[f][b], 1u);
+  }
+  __syncthreads();
+  for (int f = 0; f < nn; ++f) {
+    const unsigned c = s_c[f][tid];
+    if (c == 0) continue;
+    const size_t at = ((size_t)build_slot[chunk * TRAIN_LEVEL_CHUNK + f] * hd.n_sub + (size_t)j) * 256 + tid;
+    atomicAdd((u64 *)&hd.G[at], s_g[f][tid]);
+    atomicAdd((u64 *)&hd.H[at], s_h[f][tid]);
+    atomicAdd(&hd.C[at], c);
+  }
+}
+
+// blockIdx: (node of the level, column); lane b = bin b.  A node that was not built gets parent - sibling first (its sibling's
+// workgroups only read the sibling's slot), then step 5's candidate loop under the caller's admission rule
+__global__ void __launch_bounds__(256)
+train_level_scan_kernel(HistDev hd, const int *__restrict__ nbins, const LevelNode *__restrict__ nodes, ScanParams p, LeafRec *__restrict__ feat_best) {
+  __shared__ long long s_buf[2][3][256];
+  __shared__ double s_gain[256];
+  __shared__ int s_code[256];
+  __shared__ long long s_nan[6];
+  const int tid = threadIdx.x, j = blockIdx.y;
+  const LevelNode nd = nodes[blockIdx.x];
+  const size_t at = ((size_t)nd.slot * hd.n_sub + j) * 256 + tid;
+  long long g, h, c;
+  if (nd.parent_slot >= 0) {
+    const size_t ip = ((size_t)nd.parent_slot * hd.n_sub + j) * 256 + tid, is = ((size_t)nd.sibling_slot * hd.n_sub + j) * 256 + tid;
+    g = hd.G[ip] - hd.G[is], h = hd.H[ip] - hd.H[is], c = (long long)hd.C[ip] - (long long)hd.C[is];
+    hd.G[at] = g, hd.H[at] = h, hd.C[at] = (unsigned)c;
+  } else {
+    g = hd.G[at], h = hd.H[at], c = hd.C[at];
+  }
+  scan_column(g, h, c, nbins[j], j, p, &feat_best[(size_t)blockIdx.x * hd.n_sub + j], s_buf, s_gain, s_code, s_nan);
+}
+
+__global__ void __launch_bounds__(TRAIN_ROW_THREADS)
+train_level_split_kernel(const uint8_t *__restrict__ bins, long long rows, uint16_t *__restrict__ node_of, uint16_t *__restrict__ hist_slot,
+                         const LevelRec *__restrict__ recs, int first, int n, double sampling, int seed, int tree) {
+  __shared__ LevelRec s_recs[TRAIN_LEVEL_LDS_RECS];
+  const bool in_lds = n <= TRAIN_LEVEL_LDS_RECS;   // (the same for every lane)
+  if (in_lds) {
+    for (int k = threadIdx.x; k < n; k += TRAIN_ROW_THREADS) s_recs[k] = recs[k];
+    __syncthreads();
+  }
+  const long long i = (long long)blockIdx.x * TRAIN_ROW_THREADS + threadIdx.x;
+  if (i >= rows) return;
+  const unsigned s = (unsigned)node_of[i] - (unsigned)first;
+  if (s >= (unsigned)n) return;                    // a row of a finished leaf: its hist_slot is TRAIN_NO_SLOT already
+  const LevelRec r = in_lds ? s_recs[s] : recs[s];
+  if (r.col < 0) {
+    if (hist_slot) hist_slot[i] = (uint16_t)TRAIN_NO_SLOT;
+    return;
+  }
+  const int b = bins[(long long)r.col * rows + i];
+  const bool left = b <= r.bin || (b == TRAIN_NAN_BIN && r.nan_left);
+  node_of[i] = (uint16_t)(r.left + (left ? 0 : 1));
+  if (hist_slot) {
+    const unsigned to = left ? r.slot_l : r.slot_r;
+    hist_slot[i] = to != TRAIN_NO_SLOT && train_row_sampled(sampling, seed, tree, (u64)i) ? (uint16_t)to : (uint16_t)TRAIN_NO_SLOT;
+  }
+}
+
+__global__ void __launch_bounds__(TRAIN_ROW_THREADS)
+train_level_apply_kernel(const float *__restrict__ value, const uint16_t *__restrict__ node_of, long long rows, double *__restrict__ scores) {
+  const long long i = (long long)blockIdx.x * TRAIN_ROW_THREADS + threadIdx.x;
+  if (i >= rows) return;
+  scores[i] = (double)__fadd_rn(__double2float_rn(scores[i]), value[node_of[i]]);   // (the score is an f32 value: the narrowing is exact)
+}
+
+__global__ void __launch_bounds__(TRAIN_ROW_THREADS)
+train_level_base_kernel(long long rows, double *__restrict__ scores) {
+  const long long i = (long long)blockIdx.x * TRAIN_ROW_THREADS + threadIdx.x;
+  if (i < rows) scores[i] = 0.5;
+}
+
 unsigned row_grid(long long rows) { return (unsigned)((rows + TRAIN_ROW_THREADS - 1) / TRAIN_ROW_THREADS); }
 
 }  // namespace
@@ -633,6 +776,61 @@ void train_launch_apply(mrk_ctx *ctx, hipStream_t s, const TreeDev &t, const uin
   ScopedKernelTimer timer(ctx, "train_apply");
   if (t.is_cat) hipLaunchKernelGGL(train_apply_kernel<true>, dim3(row_grid(rows)), dim3(TRAIN_ROW_THREADS), 0, s, t, leaf_of, bins, rows, scores);
   else hipLaunchKernelGGL(train_apply_kernel<false>, dim3(row_grid(rows)), dim3(TRAIN_ROW_THREADS), 0, s, t, leaf_of, bins, rows, scores);
+  MRK_HIP(hipGetLastError());
+}
+
+void train_launch_bin_f32(mrk_ctx *ctx, hipStream_t s, const double *x, int piece_rows, int cols, const double *bounds, const int *bound_off, uint8_t *bins,
+                          long long rows, long long row0) {
+  if (piece_rows <= 0 || cols <= 0) return;
+  ScopedKernelTimer timer(ctx, "train_bin");
+  hipLaunchKernelGGL(train_bin_f32_kernel, dim3((unsigned)((piece_rows + TRAIN_BIN_ROWS - 1) / TRAIN_BIN_ROWS)), dim3(TRAIN_BIN_ROWS), 0, s, x, piece_rows, cols, bounds,
+                     bound_off, bins, rows, row0);
+  MRK_HIP(hipGetLastError());
+}
+
+void train_launch_level_begin(mrk_ctx *ctx, hipStream_t s, long long rows, double sampling, int seed, int tree, uint16_t *node_of, uint16_t *hist_slot) {
+  ScopedKernelTimer timer(ctx, "train_level_split");
+  hipLaunchKernelGGL(train_level_begin_kernel, dim3(row_grid(rows)), dim3(TRAIN_ROW_THREADS), 0, s, rows, sampling, seed, tree, node_of, hist_slot);
+  MRK_HIP(hipGetLastError());
+}
+
+void train_launch_level_hist(mrk_ctx *ctx, hipStream_t s, const uint8_t *bins, long long rows, const uint16_t *hist_slot, const long long *qg, const long long *qh,
+                             const int *build_slot, int n_build, const HistDev &hd) {
+  if (n_build <= 0) return;
+  ScopedKernelTimer timer(ctx, "train_level_hist");
+  const dim3 grid((unsigned)((rows + TRAIN_LEVEL_ROWS - 1) / TRAIN_LEVEL_ROWS), (unsigned)hd.n_sub, (unsigned)((n_build + TRAIN_LEVEL_CHUNK - 1) / TRAIN_LEVEL_CHUNK));
+  hipLaunchKernelGGL(train_level_hist_kernel, grid, dim3(TRAIN_ROW_THREADS), 0, s, bins, rows, hist_slot, qg, qh, build_slot, n_build, hd);
+  MRK_HIP(hipGetLastError());
+}
+
+void train_launch_level_scan(mrk_ctx *ctx, hipStream_t s, const HistDev &hd, const int *nbins, const LevelNode *nodes, int n_nodes, const ScanParams &p,
+                             LeafRec *feat_best, LeafRec *out) {
+  ScopedKernelTimer timer(ctx, "train_level_scan");
+  hipLaunchKernelGGL(train_level_scan_kernel, dim3((unsigned)n_nodes, (unsigned)hd.n_sub), dim3(256), 0, s, hd, nbins, nodes, p, feat_best);
+  MRK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(train_pick_kernel, dim3((unsigned)n_nodes), dim3(64), 0, s, (const LeafRec *)feat_best, hd.n_sub, out);
+  MRK_HIP(hipGetLastError());
+}
+
+void train_launch_level_split(mrk_ctx *ctx, hipStream_t s, const uint8_t *bins, long long rows, uint16_t *node_of, uint16_t *hist_slot, const LevelRec *recs, int first,
+                              int n, double sampling, int seed, int tree) {
+  if (rows <= 0) return;
+  ScopedKernelTimer timer(ctx, "train_level_split");
+  hipLaunchKernelGGL(train_level_split_kernel, dim3(row_grid(rows)), dim3(TRAIN_ROW_THREADS), 0, s, bins, rows, node_of, hist_slot, recs, first, n, sampling, seed, tree);
+  MRK_HIP(hipGetLastError());
+}
+
+void train_launch_level_apply(mrk_ctx *ctx, hipStream_t s, const float *value, const uint16_t *node_of, long long rows, double *scores) {
+  if (rows <= 0) return;
+  ScopedKernelTimer timer(ctx, "train_apply");
+  hipLaunchKernelGGL(train_level_apply_kernel, dim3(row_grid(rows)), dim3(TRAIN_ROW_THREADS), 0, s, value, node_of, rows, scores);
+  MRK_HIP(hipGetLastError());
+}
+
+void train_launch_level_base(mrk_ctx *ctx, hipStream_t s, long long rows, double *scores) {
+  if (rows <= 0) return;
+  ScopedKernelTimer timer(ctx, "train_apply");
+  hipLaunchKernelGGL(train_level_base_kernel, dim3(row_grid(rows)), dim3(TRAIN_ROW_THREADS), 0, s, rows, scores);
   MRK_HIP(hipGetLastError());
 }
 

@@ -70,6 +70,7 @@ struct ScanParams {
   // step 5c
   int max_onehot, max_cat_threshold, min_data_cat;   // min_data_cat = max(min_data_in_leaf, min_data_per_group)
   double cat_smooth, l2_cat;                         // l2_cat = lambda_l2 + cat_l2
+  double min_gain;                                   // a numeric candidate is admitted when gain > min_gain: 0 (step 5), gamma (step 5x)
 };
 // leaf_b < 0: scans leaf_a alone (the root).  Else slot leaf_b holds the histogram of the smaller child of a split and slot leaf_a its
 // parent's: first leaves both slots with their own leaf's (sibling = parent - small; leaf_a is the left child), then scans both.
@@ -96,5 +97,53 @@ struct TreeDev {
 };
 // scores[row] += leaf_value[leaf]: leaf_of given (the training rows) or found by walking the tree over the rows' bins (validation)
 void train_launch_apply(mrk_ctx *ctx, hipStream_t s, const TreeDev &t, const uint16_t *leaf_of, const uint8_t *bins, long long rows, double *scores);
+
+// ---- the xgboost backend: a LEVEL-wise grower (include/mrk.h steps 2x, 5x, 6x, 7x) ---------------------------------------------------
+// Per level one histogram launch for every node of the level that is built, one scan launch for every node of the level, one routing
+// pass.  Per row two u16: node_of, the row's node in XGBoost's breadth-first numbering (the nodes of one depth have consecutive ids, so
+// the slot of a node within its level is id - first id of the level), and hist_slot, the index of the row's node among the level's
+// BUILT nodes - TRAIN_NO_SLOT when the node is not built (a leaf, the sibling that comes from parent - built child, a node at maxDepth)
+// or the row is outside the tree's sample (step 7x): such a row adds nothing to a histogram and is routed all the same.
+constexpr int TRAIN_LEVEL_ROWS = 8192;        // rows per workgroup of the level histogram kernel (256 lanes x 32 rows): zeroing and flushing 40 KiB of LDS is paid per tile
+constexpr int TRAIN_LEVEL_CHUNK = 8;          // built nodes per workgroup of the level histogram kernel: 8 x 256 x 20 B = 40 KiB of LDS
+constexpr int TRAIN_LEVEL_LDS_RECS = 1024;    // split records of a level the routing kernel holds in LDS (12 KiB); more are read from memory
+constexpr unsigned TRAIN_NO_SLOT = 0xFFFFu;
+
+// as train_launch_bin for step 2x: the cell is narrowed to f32, its bin is the number of bounds (f32 values widened) <= it
+void train_launch_bin_f32(mrk_ctx *ctx, hipStream_t s, const double *x, int piece_rows, int cols, const double *bounds, const int *bound_off, uint8_t *bins,
+                          long long rows, long long row0);
+
+// node_of = 0; hist_slot = 0 for a row of tree `tree`'s sample, TRAIN_NO_SLOT for the others
+void train_launch_level_begin(mrk_ctx *ctx, hipStream_t s, long long rows, double sampling, int seed, int tree, uint16_t *node_of, uint16_t *hist_slot);
+
+// zeroes nothing: the caller has zeroed the level's slots.  Adds every row with hist_slot = b < n_build to histogram slot build_slot[b]
+// of all `hd.n_sub` (= all) columns.  Grid: (row tiles of TRAIN_LEVEL_ROWS, columns, chunks of TRAIN_LEVEL_CHUNK built nodes)
+void train_launch_level_hist(mrk_ctx *ctx, hipStream_t s, const uint8_t *bins, long long rows, const uint16_t *hist_slot, const long long *qg, const long long *qh,
+                             const int *build_slot, int n_build, const HistDev &hd);
+
+// a node of the level for the scan: its histogram slot; parent_slot >= 0: the slot is first filled with parent - sibling
+struct LevelNode {
+  int slot, parent_slot, sibling_slot;
+};
+// per (node, column) scan_column under ScanParams (step 5x: min_data 1, min_hess min_child_weight, l2 lambda, min_gain gamma), then per
+// node the best column.  feat_best: scratch of n_nodes * hd.n_sub records; out: n_nodes records
+void train_launch_level_scan(mrk_ctx *ctx, hipStream_t s, const HistDev &hd, const int *nbins, const LevelNode *nodes, int n_nodes, const ScanParams &p,
+                             LeafRec *feat_best, LeafRec *out);
+
+// what a row needs to leave a node of the level: col < 0 a leaf (the row stays); else bin <= `bin` (NaN when nan_left) goes to node
+// `left`, the others to left + 1; slot_l / slot_r: the children's index among the next level's built nodes or TRAIN_NO_SLOT
+struct LevelRec {
+  int col;
+  uint16_t left, slot_l, slot_r;
+  uint8_t bin, nan_left;
+};
+// rows whose node_of is first ... first + n - 1 move to their child.  hist_slot null: routing alone (the validation rows)
+void train_launch_level_split(mrk_ctx *ctx, hipStream_t s, const uint8_t *bins, long long rows, uint16_t *node_of, uint16_t *hist_slot, const LevelRec *recs, int first,
+                              int n, double sampling, int seed, int tree);
+
+// step 6x: scores[row] = (double) ((float) scores[row] + value[node_of[row]])
+void train_launch_level_apply(mrk_ctx *ctx, hipStream_t s, const float *value, const uint16_t *node_of, long long rows, double *scores);
+// scores[row] = 0.5 (the base_score)
+void train_launch_level_base(mrk_ctx *ctx, hipStream_t s, long long rows, double *scores);
 
 }  // namespace mrk

@@ -23,11 +23,31 @@ TrainConfig train_parse_config(const char *text, size_t len) {
   TrainConfig c;
   static const char *known[] = {"iterations", "learningRate", "ndcgCutoff", "maxDepth", "seed", "numLeaves", "sampling", "debias", "max_bin", "truncation",
                                 "sigma", "min_data_in_leaf", "min_sum_hessian", "lambda_l2", "early_stopping", "categorical", "max_cat_to_onehot",
-                                "max_cat_threshold", "cat_smooth", "cat_l2", "min_data_per_group"};
+                                "max_cat_threshold", "cat_smooth", "cat_l2", "min_data_per_group", "backend", "lambda", "gamma", "min_child_weight"};
   for (auto &kv : root.obj) {
     bool ok = false;
     for (const char *k : known) ok = ok || kv.first == k;
     if (!ok) bad("unknown key '" + kv.first + "'");
+  }
+  if (const json::Value *v = root.find("backend"))
+    if (!v->is_null()) {
+      if (v->type != json::Type::String) bad("'backend' is not a string");
+      if (v->str == "lightgbm") c.backend = TRAIN_BACKEND_LIGHTGBM;
+      else if (v->str == "xgboost") c.backend = TRAIN_BACKEND_XGBOOST;
+      else range("backend = '" + v->str + "' (lightgbm or xgboost)");
+    }
+  {  // a key of the other backend is refused, not ignored: it would be a setting that silently does nothing
+    static const char *lgb_only[] = {"numLeaves", "min_data_in_leaf", "min_sum_hessian", "lambda_l2", "max_cat_to_onehot", "max_cat_threshold", "cat_smooth", "cat_l2",
+                                     "min_data_per_group"};
+    static const char *xgb_only[] = {"lambda", "gamma", "min_child_weight"};
+    auto refuse = [&](const char *key, const char *backend) {
+      const json::Value *v = root.find(key);
+      if (v && !v->is_null()) range(std::string(key) + " is not a key of the " + backend + " backend");
+    };
+    if (c.backend == TRAIN_BACKEND_XGBOOST)
+      for (const char *k : lgb_only) refuse(k, "xgboost");
+    else
+      for (const char *k : xgb_only) refuse(k, "lightgbm");
   }
   auto integer = [&](const char *key, int &out) {
     const json::Value *v = root.find(key);
@@ -67,6 +87,9 @@ TrainConfig train_parse_config(const char *text, size_t len) {
   real("cat_smooth", c.cat_smooth);
   real("cat_l2", c.cat_l2);
   integer("min_data_per_group", c.min_data_per_group);
+  real("lambda", c.lambda);
+  real("gamma", c.gamma);
+  real("min_child_weight", c.min_child_weight);
   if (const json::Value *v = root.find("categorical"))
     if (!v->is_null()) {
       if (!v->is_array()) bad("'categorical' is not an array");
@@ -102,6 +125,13 @@ TrainConfig train_parse_config(const char *text, size_t len) {
   if (!(c.sigma > 0.0) || !std::isfinite(c.sigma)) range("sigma is not a positive number");
   if (!(c.min_sum_hessian >= 0.0) || !std::isfinite(c.min_sum_hessian)) range("min_sum_hessian is negative");
   if (!(c.lambda_l2 >= 0.0) || !std::isfinite(c.lambda_l2)) range("lambda_l2 is negative");
+  if (!(c.lambda >= 0.0) || !std::isfinite(c.lambda)) range("lambda is negative");
+  if (!(c.gamma >= 0.0) || !std::isfinite(c.gamma)) range("gamma is negative");
+  if (!(c.min_child_weight >= 0.0) || !std::isfinite(c.min_child_weight)) range("min_child_weight is negative");
+  if (c.backend == TRAIN_BACKEND_XGBOOST && c.max_depth > TRAIN_XGB_MAX_DEPTH)
+    range("maxDepth = " + std::to_string(c.max_depth) + " (at most " + std::to_string(TRAIN_XGB_MAX_DEPTH) + " with the xgboost backend)");
+  if (c.backend == TRAIN_BACKEND_XGBOOST && !c.categorical.empty())
+    throw StatusError(MRK_ERR_UNSUPPORTED, "train config: categorical columns are not built for the xgboost backend (set-membership splits in XGBoost JSON)");
   if (c.debias) throw StatusError(MRK_ERR_UNSUPPORTED, "train config: debias (position-bias correction) is not built");
   if (c.num_leaves > TRAIN_MAX_LEAVES)
     throw StatusError(MRK_ERR_UNSUPPORTED, "train config: numLeaves = " + std::to_string(c.num_leaves) + " (limit " + std::to_string(TRAIN_MAX_LEAVES) + ")");
@@ -112,6 +142,23 @@ static std::string g17(double x) {
   char buf[40];
   snprintf(buf, sizeof buf, "%.17g", x);
   return buf;
+}
+
+// step 2's choice of positions over the sorted values v: the p with a bound between v[p - 1] and v[p]
+template <typename T>
+static std::vector<int64_t> bin_cuts(const std::vector<T> &v, int max_bin) {
+  const int64_t m = (int64_t)v.size();
+  std::vector<int64_t> change;   // p: v[p] != v[p - 1]
+  for (int64_t p = 1; p < m; ++p)
+    if (v[(size_t)p] != v[(size_t)p - 1]) change.push_back(p);
+  if ((int64_t)change.size() + 1 <= max_bin - 1) return change;
+  std::vector<int64_t> cuts;
+  for (int64_t i = 1; i <= max_bin - 2; ++i) {
+    auto it = std::lower_bound(change.begin(), change.end(), i * m / (max_bin - 1));
+    if (it == change.end()) break;
+    if (cuts.empty() || cuts.back() != *it) cuts.push_back(*it);
+  }
+  return cuts;
 }
 
 std::vector<double> train_bin_bounds(const double *col, int64_t n, int64_t stride, int max_bin, std::string *info) {
@@ -128,25 +175,48 @@ std::vector<double> train_bin_bounds(const double *col, int64_t n, int64_t strid
   const int64_t m = (int64_t)v.size();
   if (info) *info = m == 0 || v.front() == v.back() ? "none" : "[" + g17(v.front()) + ":" + g17(v.back()) + "]";
   std::vector<double> out;
-  if (m == 0) return out;
-  std::vector<int64_t> change;   // p: v[p] != v[p - 1]
-  for (int64_t p = 1; p < m; ++p)
-    if (v[(size_t)p] != v[(size_t)p - 1]) change.push_back(p);
-  std::vector<int64_t> cuts;
-  if ((int64_t)change.size() + 1 <= max_bin - 1) cuts = change;
-  else
-    for (int64_t i = 1; i <= max_bin - 2; ++i) {
-      auto it = std::lower_bound(change.begin(), change.end(), i * m / (max_bin - 1));
-      if (it == change.end()) break;
-      if (cuts.empty() || cuts.back() != *it) cuts.push_back(*it);
-    }
-  for (int64_t p : cuts) {
+  for (int64_t p : bin_cuts(v, max_bin)) {
     const double a = v[(size_t)p - 1], b = v[(size_t)p];
     double mid = (a + b) / 2.0;
     if (!(mid < b)) mid = a;   // (also a sum that overflowed)
     out.push_back(mid);
   }
   return out;
+}
+
+// (float) x, or the refusal of step 2x
+static float narrowed(double x, int64_t row, int column) {
+  const float f = (float)x;   // round to nearest even
+  if (std::isinf(f))
+    throw StatusError(MRK_ERR_INVALID_ARG, "train: column " + std::to_string(column) + ", row " + std::to_string(row) + " holds " + g17(x) + ", which is not finite as an f32");
+  return f;
+}
+
+std::vector<double> train_bin_bounds_f32(const double *col, int64_t n, int64_t stride, int max_bin, int column) {
+  std::vector<float> v;
+  v.reserve((size_t)std::max<int64_t>(n, 0));
+  for (int64_t i = 0; i < n; ++i) {
+    const double x = col[i * stride];
+    if (x != x) continue;
+    float f = narrowed(x, i, column);
+    if (f == 0.0f) f = 0.0f;   // -0.0f and +0.0f are one value
+    v.push_back(f);
+  }
+  std::sort(v.begin(), v.end());
+  std::vector<double> out;
+  for (int64_t p : bin_cuts(v, max_bin)) out.push_back((double)v[(size_t)p]);
+  return out;
+}
+
+void train_check_f32_cells(const double *col, int64_t n, int64_t stride, int column) {
+  for (int64_t i = 0; i < n; ++i)
+    if (col[i * stride] == col[i * stride]) (void)narrowed(col[i * stride], i, column);
+}
+
+int train_bin_f32(double x, const double *bounds, int n_bounds) {
+  if (x != x) return TRAIN_NAN_BIN;
+  const double v = (double)(float)x;
+  return (int)(std::upper_bound(bounds, bounds + n_bounds, v) - bounds);   // the number of bounds <= v
 }
 
 // the category of a cell or -1; the refusals of step 2c
@@ -357,6 +427,76 @@ std::string train_write_model(const std::vector<TrainTree> &trees, size_t n_tree
   o += "\n\n";
   for (auto &b : blocks) o += b + "\n\n\n";
   o += "end of trees\n\nfeature_importances:\n\nparameters:\n[boosting: gbdt]\n[objective: lambdarank]\n\nend of parameters\n\npandas_categorical:null\n";
+  return o;
+}
+
+int TrainXgbTree::add(int parent_) {
+  left.push_back(-1), right.push_back(-1), parent.push_back(parent_), col.push_back(0), bin.push_back(0), default_left.push_back(0);
+  cond.push_back(0.0f), base_weight.push_back(0.0f), loss_change.push_back(0.0f), sum_hessian.push_back(0.0f);
+  return num_nodes() - 1;
+}
+
+void TrainXgbTree::split(int node, int col_, int bin_, float bound, bool nan_left, float gain) {
+  const size_t n = (size_t)node;
+  col[n] = col_, bin[n] = bin_, default_left[n] = nan_left ? 1 : 0, cond[n] = bound, loss_change[n] = gain;
+  const int l = add(node), r = add(node);
+  left[n] = l, right[n] = r;
+}
+
+void TrainXgbTree::weigh(int node, const TrainSums &q, int e_g, int e_h, double lambda, double lr) {
+  const double G = std::ldexp((double)q.g, -e_g), H = std::ldexp((double)q.h, -e_h);
+  const double d = H + lambda;
+  if (d == 0.0) throw StatusError(MRK_ERR_INVALID_ARG, "train: node " + std::to_string(node) + " has a hessian sum of 0 and lambda is 0: its weight is not finite");
+  const double w = -G / d;
+  base_weight[(size_t)node] = (float)w;
+  sum_hessian[(size_t)node] = (float)H;
+  if (left[(size_t)node] < 0) {
+    const double v = w * lr;
+    cond[(size_t)node] = (float)v;
+  }
+}
+
+std::string train_write_xgb_model(const std::vector<TrainXgbTree> &trees, size_t n_trees, int cols) {
+  auto ints = [](std::string &o, const char *key, const std::vector<int32_t> &a) {
+    o += std::string("\"") + key + "\":[";
+    for (size_t i = 0; i < a.size(); ++i) o += (i ? "," : "") + std::to_string(a[i]);
+    o += "],";
+  };
+  auto f32s = [](std::string &o, const char *key, const std::vector<float> &a) {
+    o += std::string("\"") + key + "\":[";
+    for (size_t i = 0; i < a.size(); ++i) {
+      char buf[40];
+      snprintf(buf, sizeof buf, "%.9g", (double)a[i]);
+      o += (i ? "," : "") + std::string(buf);
+    }
+    o += "],";
+  };
+  const std::string n = std::to_string(n_trees), nf = std::to_string(cols);
+  std::string o = "{\"learner\":{\"attributes\":{},\"feature_names\":[],\"feature_types\":[],\"gradient_booster\":{\"model\":{\"gbtree_model_param\":{\"num_parallel_tree\":\"1\",\"num_trees\":\"" + n + "\"},\"iteration_indptr\":[";
+  for (size_t i = 0; i <= n_trees; ++i) o += (i ? "," : "") + std::to_string(i);
+  o += "],\"tree_info\":[";
+  for (size_t i = 0; i < n_trees; ++i) o += i ? ",0" : "0";
+  o += "],\"trees\":[";
+  for (size_t i = 0; i < n_trees; ++i) {
+    const TrainXgbTree &t = trees[i];
+    const std::vector<int32_t> zeros((size_t)t.num_nodes(), 0);
+    o += i ? ",{" : "{";
+    f32s(o, "base_weights", t.base_weight);
+    o += "\"categories\":[],\"categories_nodes\":[],\"categories_segments\":[],\"categories_sizes\":[],";
+    ints(o, "default_left", t.default_left);
+    o += "\"id\":" + std::to_string(i) + ",";
+    ints(o, "left_children", t.left);
+    f32s(o, "loss_changes", t.loss_change);
+    ints(o, "parents", t.parent);
+    ints(o, "right_children", t.right);
+    f32s(o, "split_conditions", t.cond);
+    ints(o, "split_indices", t.col);
+    ints(o, "split_type", zeros);
+    f32s(o, "sum_hessian", t.sum_hessian);
+    o += "\"tree_param\":{\"num_deleted\":\"0\",\"num_feature\":\"" + nf + "\",\"num_nodes\":\"" + std::to_string(t.num_nodes()) + "\",\"size_leaf_vector\":\"1\"}}";
+  }
+  o += "]},\"name\":\"gbtree\"},\"learner_model_param\":{\"base_score\":\"5E-1\",\"boost_from_average\":\"1\",\"num_class\":\"0\",\"num_feature\":\"" + nf +
+       "\",\"num_target\":\"1\"},\"objective\":{\"name\":\"rank:ndcg\",\"lambdarank_param\":{}}},\"version\":[2,1,0]}";
   return o;
 }
 

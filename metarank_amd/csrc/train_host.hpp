@@ -48,14 +48,31 @@ struct TrainConfig {
   double cat_smooth = 10.0;
   double cat_l2 = 10.0;
   int min_data_per_group = 100;
+  int backend = 0;                    // "backend": 0 "lightgbm" (steps 2, 5, 6, 7), 1 "xgboost" (steps 2x, 5x, 6x, 7x)
+  double lambda = 1.0;                // the three keys of the xgboost backend alone
+  double gamma = 0.0;
+  double min_child_weight = 1.0;
 };
+constexpr int TRAIN_BACKEND_LIGHTGBM = 0, TRAIN_BACKEND_XGBOOST = 1;
+constexpr int TRAIN_XGB_MAX_DEPTH = 15;     // a node id is a u16: a complete tree of depth 15 has 65535 nodes
 // malformed JSON, a value of the wrong type or an unknown key: MRK_ERR_PARSE; a value out of range: MRK_ERR_INVALID_ARG;
-// debias = true or numLeaves > TRAIN_MAX_LEAVES: MRK_ERR_UNSUPPORTED
+// debias = true or numLeaves > TRAIN_MAX_LEAVES: MRK_ERR_UNSUPPORTED.  backend "xgboost": numLeaves, min_data_in_leaf,
+// min_sum_hessian, lambda_l2 and the categorical keys but `categorical` are MRK_ERR_INVALID_ARG naming the key, a non-empty
+// `categorical` is MRK_ERR_UNSUPPORTED; backend "lightgbm": lambda, gamma and min_child_weight are MRK_ERR_INVALID_ARG
 TrainConfig train_parse_config(const char *json, size_t len);
 
 // the upper bounds of the bins of one column but the last (bin(x) = the number of bounds < x), from col[i * stride], i < n.
 // An infinite cell: MRK_ERR_INVALID_ARG.  info: LightGBM's feature_infos entry ("none" or "[min:max]").
 std::vector<double> train_bin_bounds(const double *col, int64_t n, int64_t stride, int max_bin, std::string *info = nullptr);
+
+// step 2x: the bounds of one column for the xgboost backend, f32 values widened to f64: the cells are narrowed to f32 first, the bound
+// between neighbours a < b is b (bin(x) = the number of bounds <= (float) x, so x < bound goes left: the model's own test).  A finite
+// cell that narrows to +-inf, or an infinite one: MRK_ERR_INVALID_ARG naming `column` and the row.
+std::vector<double> train_bin_bounds_f32(const double *col, int64_t n, int64_t stride, int max_bin, int column);
+// the cells of another set than the one the bounds came from: the same refusal
+void train_check_f32_cells(const double *col, int64_t n, int64_t stride, int column);
+// bin(x) of step 2x on the host (the device's is train.hip's): NaN is TRAIN_NAN_BIN
+int train_bin_f32(double x, const double *bounds, int n_bounds);
 
 // step 2c: the category ids of a categorical column that get a bin, ascending (the bin of an id is its position): the
 // min(distinct, max_bin - 1) most frequent of col[i * stride], i < n, ties to the lower id.  The category of a cell is trunc(x); NaN and
@@ -71,6 +88,16 @@ std::vector<uint8_t> train_category_table(const std::vector<int32_t> &kept);
 MRK_TRAIN_HD inline int train_category_bin(double x, const uint8_t *table, int len) {
   if (!(x > -1.0) || !(x < (double)len)) return TRAIN_NAN_BIN;   // (NaN fails both; -1 < x < 0 truncates to category 0)
   return table[(int)x];
+}
+
+// step 7x: is row `row` in the sample of tree `tree`?  The histogram kernels call this too.
+MRK_TRAIN_HD inline bool train_row_sampled(double sampling, int seed, int tree, uint64_t row) {
+  if (sampling >= 1.0) return true;
+  uint64_t z = ((((uint64_t)(uint32_t)seed << 32) | (uint64_t)(uint32_t)tree) ^ (row * 0xD6E8FEB86659FD93ull)) + 0x9E3779B97F4A7C15ull;   // splitmix64's first output
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  z ^= z >> 31;
+  return (double)(z >> 11) * 0x1.0p-53 < sampling;   // (53 bits: the conversion and the product are exact)
 }
 
 // the columns of tree `tree`, ascending
@@ -118,5 +145,20 @@ double train_leaf_output(const TrainSums &q, int e_g, int e_h, double l2, double
 // to ids, a node's bitset has max member id / 32 + 1 words.  A tree without one is written as before (num_cat=0, no cat_* lines).
 std::string train_write_model(const std::vector<TrainTree> &trees, size_t n_trees, int cols, const std::vector<std::string> &infos, double lr,
                               const std::vector<std::vector<int32_t>> *kept = nullptr);
+
+// one tree of the xgboost backend in XGBoost's breadth-first numbering (step 5x): node 0 is the root, a node that splits gives its
+// children the next two free ids.  cond: the bound of a split node, (float)(weight * learningRate) of a leaf.
+struct TrainXgbTree {
+  std::vector<int32_t> left, right, parent, col, bin, default_left;   // left / right -1 for a leaf; parent 2147483647 for the root
+  std::vector<float> cond, base_weight, loss_change, sum_hessian;
+  int num_nodes() const { return (int)left.size(); }
+  int add(int parent_);                                             // a new leaf -> its id
+  void split(int node, int col_, int bin_, float bound, bool nan_left, float gain);   // -> children num_nodes() - 2, num_nodes() - 1
+  // weight = -G / (H + lambda) of a node's quantised sums into base_weight / sum_hessian; a leaf's cond = (float)(weight * lr).
+  // H + lambda == 0 (no finite weight): MRK_ERR_INVALID_ARG
+  void weigh(int node, const TrainSums &q, int e_g, int e_h, double lambda, double lr);
+};
+// XGBoost's JSON (version [2,1,0], objective rank:ndcg, base_score 5E-1), no whitespace; every f32 as %.9g of its widened value
+std::string train_write_xgb_model(const std::vector<TrainXgbTree> &trees, size_t n_trees, int cols);
 
 }  // namespace mrk

@@ -1,4 +1,4 @@
-"""Host-side mirror of the reference's LambdaMART fit for the LightGBM backend.
+"""Host-side mirror of the reference's LambdaMART fit, for both of its backends.
 
 Reference interfaces (ml/rank/LambdaMARTRanker.scala:161-190, config/BoosterConfig.scala:19-28):
     LambdaMARTPredictor.makeBooster(LightGBMConfig(iterations, learningRate, ndcgCutoff, maxDepth, seed, numLeaves, sampling, debias),
@@ -6,6 +6,9 @@ Reference interfaces (ml/rank/LambdaMARTRanker.scala:161-190, config/BoosterConf
 `fit_lambdamart(X, labels, group_offsets, valid=(X, labels, group_offsets), **config)` is that call: the gradients, histograms,
 split scans and score updates happen in libmrk_hip.so (csrc/train.hip); there is no CPU path.  The algorithm is include/mrk.h's
 (DESIGN.md 19): this project's, not LightGBM's bit stream.  The forest comes back as LightGBM's text format in a HipBooster.
+`backend="xgboost"` is the XGBoostConfig arm of the same call (config/BoosterConfig.scala: iterations, learningRate, ndcgCutoff, maxDepth,
+seed, sampling - the ROW subsample -, debias; plus lambda, gamma, min_child_weight): a level-wise grower that bins in f32 (include/mrk.h
+steps 2x, 5x, 6x, 7x) and returns XGBoost's JSON, loaded with the XGBoost backend constant.
 """
 from __future__ import annotations
 
@@ -15,7 +18,7 @@ import json
 import numpy as np
 
 from . import _native as N
-from .booster import LIGHTGBM, Context, HipBooster, default_context
+from .booster import LIGHTGBM, XGBOOST, Context, HipBooster, default_context
 
 
 def _config(config) -> bytes:
@@ -31,7 +34,8 @@ def _offsets(group_offsets):
 
 
 def bin_bounds(column, **config) -> np.ndarray:
-    """mrk_train_bins: the upper bounds of a column's bins but the last (host only)"""
+    """mrk_train_bins: the upper bounds of a column's bins but the last (host only).  backend="xgboost": step 2x's bounds - f32 values,
+    widened; a cell goes left of a bound when (float) x < bound"""
     col = _f64(column)
     n = C.c_int(0)
     cfg = _config(config)
@@ -130,7 +134,9 @@ def fit_lambdamart(X, labels, group_offsets, valid=None, ctx: Context | None = N
     best_iteration, metric (the validation ndcg after every iteration), model (the text), scores / valid_scores (the trainer's own, at
     the best iteration).  A fit that ends without a tree has no forest to load: the booster is None.
     Categorical columns (set-membership splits, include/mrk.h steps 2c and 5c) are named by the config:
-    fit_lambdamart(X, y, off, categorical=categorical_columns(ranker.values_columns()))."""
+    fit_lambdamart(X, y, off, categorical=categorical_columns(ranker.values_columns())).
+    backend="xgboost": the level-wise fit; the model is XGBoost's JSON and the booster is loaded as an XGBoost one; scores are the f32
+    sums the model predicts (from its base_score 0.5), widened."""
     ctx = ctx or default_context()
     t = Trainer(config, ctx)
     try:
@@ -144,5 +150,5 @@ def fit_lambdamart(X, labels, group_offsets, valid=None, ctx: Context | None = N
         hist["valid_scores"] = t.scores(1) if valid is not None else None
     finally:
         t.close()
-    booster = HipBooster(hist["model"], LIGHTGBM, ctx) if hist["best_iteration"] > 0 else None
+    booster = HipBooster(hist["model"], XGBOOST if config.get("backend") == "xgboost" else LIGHTGBM, ctx) if hist["best_iteration"] > 0 else None
     return booster, hist

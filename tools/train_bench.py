@@ -12,7 +12,12 @@ this host; and, if sklearn is importable, HistGradientBoostingRegressor's time p
 context only, another objective).  No threshold: nothing was measured before this tool existed.
 --categorical N declares the last N columns categorical (their cells rounded to ids 0 ... 49): the split search of those columns is
 include/mrk.h's step 5c, the restatement and sklearn then see the rounded columns as numbers.
-  python tools/train_bench.py [--json] [--groups N] [--min-items N] [--max-items N] [--iterations N] [--leaves N] [--ref-groups N] [--valid]
+--backend xgboost [--depth D] fits the same matrix with the level-wise grower (include/mrk.h steps 2x, 5x, 6x, 7x; --leaves is unused):
+the phases are then train_level_hist, train_level_scan (scan + pick), train_level_split (the per-tree start and one routing pass per
+level), train_level_readback (the level's records copied back: one stream synchronisation each) and train_apply; `launches` holds the
+launch count of every phase and the bounds they must keep - for T trees of depth D at most T x D histogram launches, scan launches and
+read-backs - and the tool exits 1 when a count is above its bound.  The restatement is then tests/train_xgb_reference.py.
+  python tools/train_bench.py [--json] [--backend lightgbm|xgboost] [--depth D] [--groups N] [--min-items N] [--max-items N] [--iterations N] [--leaves N] [--ref-groups N] [--valid]
                               [--categorical N]
 """
 import argparse
@@ -31,9 +36,11 @@ import metarank_amd as M  # noqa: E402
 from metarank_amd import _native as N  # noqa: E402
 from metarank_amd.train import Trainer  # noqa: E402
 import train_reference as T  # noqa: E402
+import train_xgb_reference as TX  # noqa: E402
 from workloads import synth  # noqa: E402
 
 TIMERS = ("train_bin", "train_grad", "train_hist", "train_scan", "train_apply", "train_eval")
+LEVEL_TIMERS = ("train_bin", "train_grad", "train_level_hist", "train_level_scan", "train_level_split", "train_level_readback", "train_apply", "train_eval")
 COLS = 24
 
 
@@ -48,17 +55,23 @@ def main():
     ap.add_argument("--ref-groups", type=int, default=2000, help="groups of the restatement's one iteration (0: skip it)")
     ap.add_argument("--valid", action="store_true", help="a validation set of a tenth of the groups (early stopping stays out of reach)")
     ap.add_argument("--categorical", type=int, default=0, help="declare the last N columns categorical; their cells are rounded to ids 0 ... 49 (NaN stays)")
+    ap.add_argument("--backend", choices=("lightgbm", "xgboost"), default="lightgbm")
+    ap.add_argument("--depth", type=int, default=8, help="maxDepth of the xgboost backend")
     a = ap.parse_args()
+    xgb = a.backend == "xgboost"
+    timers = LEVEL_TIMERS if xgb else TIMERS
     ctx = M.Context(0)
     X, y, off = synth.synthetic_ranking_rows(a.groups, a.min_items, a.max_items, COLS, seed=0)
     rows = int(off[-1])
     cfg = {"iterations": a.iterations, "numLeaves": a.leaves, "early_stopping": a.iterations}
+    if xgb:
+        cfg = {"backend": "xgboost", "iterations": a.iterations, "maxDepth": a.depth, "early_stopping": a.iterations}
     cats = list(range(COLS - a.categorical, COLS))
     if cats:                                                              # (without the option the config has no `categorical` key)
         X[:, cats] = np.clip(np.rint((X[:, cats] + 3.0) * (49.0 / 6.0)), 0.0, 49.0)
         cfg["categorical"] = cats
     out = {"groups": a.groups, "rows": rows, "items_per_group": [a.min_items, a.max_items], "columns": COLS, "iterations": a.iterations, "leaves": a.leaves,
-           "categorical": cats, "build": N.lib().mrk_build_id().decode()}
+           "backend": a.backend, "depth": a.depth if xgb else None, "categorical": cats, "build": N.lib().mrk_build_id().decode()}
 
     ctx.profile_enable(True)
     t = Trainer(cfg, ctx)
@@ -70,15 +83,17 @@ def main():
     t0 = time.perf_counter()
     t.fit()
     out["fit_call_ms"] = (time.perf_counter() - t0) * 1e3
-    parts = {name: ctx.profile_get(name) for name in TIMERS}
+    parts = {name: ctx.profile_get(name) for name in timers}
     ctx.profile_enable(False)
     hist = t.history()
     model = t.model()
     t.close()
-    for name in TIMERS:
+    for name in timers:
         out[name + "_ms"], out[name + "_launches"] = parts[name]
     out["trees"] = hist["iterations_run"]
     out["model_sha256"] = hashlib.sha256(model).hexdigest()               # (two builds that fit the same forest print the same digest)
+    if xgb:
+        return finish_xgboost(a, ctx, out, parts, hist, model, X, y, off, rows)
     out["categorical_nodes"] = sum(int(b.split("num_cat=")[1].split("\n")[0]) for b in model.decode().split("Tree=")[1:])
     out["splits"] = sum(len(b.split("split_feature=")[1].split("\n")[0].split()) for b in model.decode().split("Tree=")[1:])
     scans = parts["train_scan"][1]                                        # (one timer spans a scan and its pick)
@@ -107,6 +122,34 @@ def main():
         out["sklearn_hist_gbr_ms_per_tree"] = (time.perf_counter() - t0) * 1e3 / trees
     ctx.close()
     print(json.dumps(out) if a.json else json.dumps(out, indent=1))
+
+
+def finish_xgboost(a, ctx, out, parts, hist, model, X, y, off, rows):
+    trees = json.loads(model)["learner"]["gradient_booster"]["model"]["trees"]
+    out["nodes"] = sum(int(t["tree_param"]["num_nodes"]) for t in trees)
+    out["splits"] = sum(sum(1 for l in t["left_children"] if l >= 0) for t in trees)
+    bound = hist["iterations_run"] * a.depth                             # derived: one launch / read-back per level that can still split
+    counts = {name: int(parts[name][1]) for name in LEVEL_TIMERS}
+    out["launches"] = {"per_phase": counts, "bound_trees_x_depth": bound, "histogram": counts["train_level_hist"], "scan": counts["train_level_scan"],
+                       "record_readbacks": counts["train_level_readback"]}
+    out["launches"]["within_bound"] = all(out["launches"][k] <= bound for k in ("histogram", "scan", "record_readbacks"))
+    device_ms = sum(parts[name][0] for name in LEVEL_TIMERS if name != "train_bin")
+    out["fit_device_phases_ms"] = device_ms
+    out["fit_host_and_sync_ms_per_readback"] = (out["fit_call_ms"] - device_ms) / max(counts["train_level_readback"], 1)
+    out["fit_ms_per_tree"] = out["fit_call_ms"] / max(hist["iterations_run"], 1)
+    if a.ref_groups > 0:
+        g = min(a.ref_groups, a.groups)
+        r = int(off[g])
+        t0 = time.perf_counter()
+        TX.fit(X[:r], y[:r], off[:g + 1], cfg={"iterations": 1, "maxDepth": a.depth})
+        out["restatement_one_iteration_ms"] = (time.perf_counter() - t0) * 1e3
+        out["restatement_rows"] = r
+        out["restatement_us_per_row_iteration"] = out["restatement_one_iteration_ms"] * 1e3 / r
+        out["device_us_per_row_iteration"] = out["fit_call_ms"] * 1e3 / (rows * max(hist["iterations_run"], 1))
+    ctx.close()
+    print(json.dumps(out) if a.json else json.dumps(out, indent=1))
+    if not out["launches"]["within_bound"]:
+        sys.exit(1)
 
 
 if __name__ == "__main__":
