@@ -1,4 +1,4 @@
-// Device half of the LambdaMART fit (train.hip), driven by capi_train.cpp.
+// Device half of the LambdaMART fit (train.hip), driven by train_fit.cpp (the fit) and capi_train.cpp (binning, mrk_train_gradients).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -304,6 +304,25 @@ int train_exponent(double vmax, int64_t rows) {
   return 61 - bitlen - e;
 }
 
+int64_t train_level_cap(const TrainConfig &cfg, int64_t rows) { return std::max<int64_t>(1, std::min<int64_t>(int64_t(1) << (cfg.max_depth - 1), rows)); }
+
+double train_fit_bytes(const TrainConfig &cfg, int which, int64_t rows_, int cols, int64_t n_groups_) {
+  const bool xgb = cfg.backend == TRAIN_BACKEND_XGBOOST;
+  const double rows = (double)rows_, groups = (double)n_groups_, rec = TRAIN_LEAF_REC_BYTES;
+  const double n_sub = xgb ? (double)cols : (double)train_feature_subset(cols, cfg.sampling, 0, 0).size();
+  const double column_cells = 256.0 * 20.0;   // of one (slot, column) histogram: G and H i64, C u32
+  const double bins = rows * cols;
+  const double per_row = 51.0 * rows;         // g, h, q_g, q_h, score and best score (8 each), leaf / node (2), label (1)
+  const double group_lists = 12.0 * groups;   // the offsets (8) and the by-size lists (4)
+  const double row_slots = xgb ? 2.0 * rows : 0.0;   // xgboost, a u16 per row: hist_slot (training), the row's node (validation)
+  if (which == 1) return bins + per_row + group_lists + row_slots + (9.0 * rows + 8.0 * groups);   // gains (8), rel (1); the metric per group
+  // numLeaves histograms - or two resident levels of train_level_cap nodes, each with a record per (node, column) - and the scan's two
+  // rows of records per column (counted for both backends, as it always was: LevelGrower holds one level's records, not two and two rows)
+  const double hist = xgb ? (column_cells + rec) * n_sub * 2.0 * (double)train_level_cap(cfg, rows_) : column_cells * n_sub * (double)cfg.num_leaves;
+  const double scan_records = 2.0 * rec * n_sub;
+  return bins + per_row + group_lists + row_slots + hist + scan_records;
+}
+
 std::vector<uint8_t> train_check_labels(const double *labels, int64_t rows) {
   if (!labels) throw StatusError(MRK_ERR_INVALID_ARG, "train: null labels");
   std::vector<uint8_t> out((size_t)rows);

@@ -1,5 +1,5 @@
-// Host half of the LambdaMART fit (capi_train.cpp; the algorithm: include/mrk.h): config, bins, feature subsets, the
-// sigmoid table, the quantisation exponents, the tree book-keeping and the model text.  No HIP in here:
+// Host half of the LambdaMART fit (train_fit.cpp, capi_train.cpp; the algorithm: include/mrk.h): config, bins, feature
+// subsets, the sigmoid table, the quantisation exponents, the memory budget, the tree book-keeping and the model text.  No HIP in here:
 // tests/native/train_host_test.cpp compiles this file with g++ alone.
 // Reference: LambdaMARTPredictor.makeBooster (ml/rank/LambdaMARTRanker.scala:161-190), LightGBMConfig (config/BoosterConfig.scala:19-28).
 #pragma once
@@ -102,6 +102,13 @@ MRK_TRAIN_HD inline bool train_row_sampled(double sampling, int seed, int tree, 
 
 // the columns of tree `tree`, ascending
 std::vector<int32_t> train_feature_subset(int cols, double sampling, int seed, int tree);
+
+constexpr int TRAIN_LEAF_REC_BYTES = 112;   // sizeof(LeafRec) (train.hpp: no HIP in here; train_fit.hpp asserts the two agree)
+// backend "xgboost": the most nodes of one level that is scanned (depth < maxDepth; every node holds a sampled row)
+int64_t train_level_cap(const TrainConfig &cfg, int64_t rows);
+// the device memory a set of that shape holds through the fit (which: 0 training, 1 validation), in bytes: what mrk_train_set asks
+// the device for before it uploads anything.  The training set's figure includes the buffers of the backend's grower
+double train_fit_bytes(const TrainConfig &cfg, int which, int64_t rows, int cols, int64_t n_groups);
 
 struct SigmoidTable {
   double lo, f;

@@ -126,6 +126,15 @@ int main() {
     for (const double *bad : {half, big, neg, nn}) CHECK(status_of([&] { train_check_labels(bad, 1); }) == MRK_ERR_INVALID_ARG);
     CHECK(status_of([] { train_check_labels(nullptr, 0); }) == MRK_ERR_INVALID_ARG);
   }
+  {  // the memory budget of mrk_train_set, every figure worked out by hand from the terms in train_fit_bytes' comments
+    const TrainConfig lgb = parse("{}"), xgb = parse(R"({"backend":"xgboost"})");   // 16 leaves, sampling 0.8: 8 of 10 columns; maxDepth 8
+    CHECK(train_level_cap(xgb, 1000) == 128 && train_level_cap(xgb, 50) == 50 && train_level_cap(xgb, 0) == 1);
+    CHECK(train_fit_bytes(lgb, 0, 1000, 10, 50) == 718752.0);     // 10 000 + 51 000 + 600 + 5 120 x 8 x 16 + 224 x 8
+    CHECK(train_fit_bytes(lgb, 1, 1000, 10, 50) == 71000.0);      // 61 600 + 9 000 + 400
+    CHECK(train_fit_bytes(xgb, 0, 1000, 10, 50) == 13459760.0);   // 61 600 + 2 000 + 5 232 x 10 x 2 x 128 + 224 x 10
+    CHECK(train_fit_bytes(xgb, 1, 1000, 10, 50) == 73000.0);      // 61 600 + 2 000 + 9 000 + 400
+    CHECK(train_fit_bytes(xgb, 0, 50, 3, 5) == 1573132.0);        // rows < 2^7, 50 nodes a level: 2 760 + 100 + 5 232 x 3 x 100 + 224 x 3
+  }
   {  // numbering and the text
     TrainTree t;
     CHECK(t.split(0, 3, 1, 0.5, false, 2.0) == 1);   // node 0: leaves 0 | 1

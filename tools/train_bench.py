@@ -90,7 +90,7 @@ def main():
     t.close()
     for name in timers:
         out[name + "_ms"], out[name + "_launches"] = parts[name]
-    out["trees"] = hist["iterations_run"]
+    out["trees"], out["best_iteration"] = hist["iterations_run"], hist["best_iteration"]
     out["model_sha256"] = hashlib.sha256(model).hexdigest()               # (two builds that fit the same forest print the same digest)
     if xgb:
         return finish_xgboost(a, ctx, out, parts, hist, model, X, y, off, rows)
