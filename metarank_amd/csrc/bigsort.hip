@@ -26,6 +26,7 @@
 #include <mutex>
 #include <vector>
 
+#include "rank_launch.hpp"
 #include "runtime.hpp"
 #include "sort_device.hpp"
 

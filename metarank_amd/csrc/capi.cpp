@@ -1,5 +1,6 @@
 // C ABI (include/mrk.h): lifecycle, model handles, predictMat replacement, profiling.
-// Feature store / rank entry points live in capi_rank.cpp.
+// Config / feature store entry points live in capi_store.cpp, the batch pipeline in capi_rank.cpp, mrk_rank in rank_front.cpp,
+// the serving queue in capi_serve.cpp.
 #include <cmath>
 #include <cstddef>
 #include <cstdlib>

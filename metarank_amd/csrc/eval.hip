@@ -23,14 +23,12 @@
 #include "eval.hpp"
 #include "eval_host.hpp"
 #include "rank.hpp"
+#include "rank_launch.hpp"
 #include "runtime.hpp"
 #include "sort_device.hpp"
 #include "wave_device.hpp"
 
 namespace mrk {
-
-void launch_big_sort(mrk_ctx *ctx, hipStream_t stream, const SortSrc &src, int n, int *out_order, void *scratch);  // bigsort.hip
-size_t big_sort_scratch_bytes(int n);
 
 static_assert(EVAL_GROUP_ITEMS == SORT_MAX_ITEMS, "the workgroup kernel takes what one workgroup sorts");
 static_assert(EVAL_GROUP_ITEMS <= 65536, "the workgroup kernel keeps indices as u16");

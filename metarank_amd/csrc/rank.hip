@@ -27,6 +27,7 @@
 
 #include "launch_shape.hpp"
 #include "rank_device.hpp"
+#include "rank_launch.hpp"
 #include "sort_device.hpp"
 #include "runtime.hpp"
 
@@ -255,8 +256,6 @@ normalize_kernel(BatchDev b, int dim, int col, int mode) {
 }
 
 }  // namespace
-
-void launch_big_sort(mrk_ctx *ctx, hipStream_t stream, const SortSrc &src, int n, int *out_order, void *scratch);  // bigsort.hip
 
 // A specialised kernel (a hipFunction_t of jit.cpp) with its arguments, by value, in the kernel's parameter order.
 template <typename... Args>

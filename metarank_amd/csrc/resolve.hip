@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include "rank.hpp"
+#include "rank_launch.hpp"
 #include "runtime.hpp"
 
 namespace mrk {

@@ -16,6 +16,7 @@
 
 #include "../../include/mrk.h"
 #include "forest.hpp"
+#include "serve_sync.hpp"
 #include "status.hpp"
 #include "switches.hpp"
 
@@ -28,7 +29,7 @@ namespace mrk {
       throw ::mrk::StatusError(MRK_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(_e)); \
   } while (0)
 
-// hipFree / hipHostFree wait for EVERY resident kernel of the device.  While gangs of the serving queue are resident (capi_rank.cpp:
+// hipFree / hipHostFree wait for EVERY resident kernel of the device.  While gangs of the serving queue are resident (capi_serve.cpp:
 // they stay up to MRK_SERVE_LIFE_US and are relaunched at once under traffic, so with 8 of them the device is hardly ever idle) a
 // buffer that regrows - the scratch batches of mrk_rank's front finding their sizes - stalled its caller for 70 ... 190 ms
 // (profiles/r06_al_front_trace.txt: the `build` phase of a combined batch).  So while any gang is resident, memory is not given
@@ -103,8 +104,12 @@ struct KernelTimer {
 
 struct Store;     // store.hpp
 struct Registry;  // features.hpp
+struct RankTicket;  // rank_front.cpp
 
 }  // namespace mrk
+
+struct mrk_batch;   // rank_host.hpp
+struct mrk_server;  // capi_serve.cpp
 
 struct mrk_ctx {
   // owner reference (dropped by mrk_shutdown) + one per live model / batch: the context outlives its handles
@@ -124,7 +129,7 @@ struct mrk_ctx {
   std::shared_mutex store_mu;
   // libstdc++'s shared_mutex prefers readers; since round 6 several leaders of mrk_rank's front hold the store shared at
   // overlapping times, so a put could wait for ever.  Writers announce themselves (StoreWriteLock) and new readers
-  // (StoreAccess, capi_rank.cpp) let them pass first.
+  // (StoreAccess, rank_host.hpp) let them pass first.
   std::atomic<int> store_writers{0};
   // scratch for predict_f64
   mrk::DevBuf d_x, d_out, d_flag;
@@ -140,10 +145,10 @@ struct mrk_ctx {
   // mrk_rank's scratch batches ("lanes": grow-only mrk_batch objects, lane 0 on the context stream, the others on streams of
   // their own; owned, freed by mrk::free_rank_state).  A lane is held by one leader of the batching front at a time (qmu).
   static constexpr int RANK_LANES_MAX = 8;
-  void *rank_lane[RANK_LANES_MAX] = {};
+  mrk_batch *rank_lane[RANK_LANES_MAX] = {};
   bool lane_busy[RANK_LANES_MAX] = {};
   // mrk_values' scratch batch (a grow-only mrk_batch on a stream of its own; owned, freed by mrk::free_rank_state): one caller at a time
-  void *values_lane = nullptr;
+  mrk_batch *values_lane = nullptr;
   std::mutex values_mu;               // lock order: values_mu before store_mu
   // multi-GPU (comm.cpp): the RCCL communicator this context's device belongs to (ncclComm_t), nullptr = a world of one
   void *comm = nullptr;
@@ -152,18 +157,16 @@ struct mrk_ctx {
   // EVERY collective on `comm` is issued under this lock (RCCL does not allow concurrent calls on one communicator).  The
   // host must also issue collectives in the same order on every rank (mrk.h): the lock makes a mistake a wait, not a race.
   std::mutex comm_mu;
-  std::mutex servers_mu;              // the serving queues of this context (capi_rank.cpp mrk_serve_*): a store flush stops their workgroups
-  std::vector<void *> servers;        // mrk_server*
+  std::mutex servers_mu;              // the serving queues of this context (capi_serve.cpp mrk_serve_*): a store flush stops their workgroups
+  std::vector<mrk_server *> servers;
   std::atomic<int> n_servers{0};      // its size, for mrk_rank's lock-free "is there a queue at all"
-  std::atomic<void *> hot_server{nullptr};   // the most recently started one: mrk_rank's way in without the mutex ...
-  std::atomic<uint32_t> hot_epoch{0};        // ... guarded by reader counts per epoch parity (capi_rank.cpp rank_through_server)
-  std::atomic<int> hot_readers[2] = {{0}, {0}};
-  std::mutex hot_stop_mu;
+  std::atomic<mrk_server *> hot_server{nullptr};   // the most recently started one: mrk_rank's way in without the mutex ...
+  mrk::ReaderGate hot_gate;                        // ... guarded by reader counts per epoch parity (capi_serve.cpp rank_through_server)
   // batching front of mrk_rank: concurrent callers are combined into device batches by whichever waiting caller finds a
-  // free lane (capi_rank.cpp); several batches are in flight at once - one per lane
+  // free lane (rank_front.cpp); several batches are in flight at once - one per lane
   std::mutex qmu;
   std::condition_variable qcv;
-  std::vector<void *> rank_queue;     // RankTicket*
+  std::vector<mrk::RankTicket *> rank_queue;
   mrk_ctx();
   ~mrk_ctx();
 };

@@ -19,6 +19,7 @@
 #include <cstdlib>
 #include <string>
 
+#include "rank_launch.hpp"
 #include "runtime.hpp"
 #include "walk_device.hpp"
 

@@ -23,11 +23,10 @@
 
 #include "launch_shape.hpp"
 #include "qs_device.hpp"
+#include "rank_launch.hpp"
 #include "runtime.hpp"
 
 namespace mrk {
-
-QsDev qs_device_view(const mrk_model *m);
 
 namespace {
 

@@ -24,14 +24,12 @@
 #include <algorithm>
 
 #include "rank.hpp"
+#include "rank_launch.hpp"
 #include "runtime.hpp"
 #include "sort_device.hpp"
 #include "trending.hpp"
 
 namespace mrk {
-
-void launch_big_sort(mrk_ctx *ctx, hipStream_t stream, const SortSrc &src, int n, int *out_order, void *scratch);  // bigsort.hip
-size_t big_sort_scratch_bytes(int n);
 
 namespace {
 

@@ -240,6 +240,64 @@ def test_serving_gangs_leave_and_come_back_as_a_whole():
 
 
 @pytest.mark.gpu
+def test_serving_gang_lifecycle_in_exact_counts():
+    """One gang's life, counted exactly.  9 slots = two gangs (8 + 1); idle and life time (2 s) are longer than the case, so a
+    workgroup leaves only when it is told to.  Sequential callers are always handed slot 0 (the free slots are a stack), so only
+    its gang is ever launched: once for the first request, not at all for a request the queue does not take, and once more after a
+    store flush has drained it.  Stopping the queue drains the resident gang well inside its 5 s deadline, and mrk_rank answers
+    afterwards.  Every result equals the oracle's."""
+    import time
+
+    # (MRK_RANK_JIT=auto, the library's default: no request waits for the compiler - what is counted here is the host's side)
+    saved = with_env({"MRK_RANK_JIT": "auto", "MRK_SERVE_IDLE_US": "2000000", "MRK_SERVE_LIFE_US": "2000000"})
+    cfg = ranklens.ranklens_config()
+    orc, hip = OracleBackend(cfg, "xgboost"), HipBackend(cfg, "xgboost")
+    srv = None
+    try:
+        for b in (orc, hip):
+            ranklens.load_state(b, ranklens.generate_state(N_ITEMS, N_SESS))
+        small = ranklens.generate_requests(3, 100, N_ITEMS, N_SESS, seed=95) + ranklens.generate_requests(1, 7, N_ITEMS, N_SESS, seed=96)
+        big = ranklens.generate_requests(1, 129, N_ITEMS, N_SESS, seed=97)[0]
+        q = ranklens.column_quantiles(np.concatenate([orc.matrix(ev) for ev in small[:3]]))
+        blob = synth.synthetic_lgbm_model(n_trees=50, n_features=24, quantiles=q, missing="per_feature")
+        orc.load_model(blob, 0)
+        hip.load_model(blob, 0)
+        exp_small = [orc.rerank(ev) for ev in small]
+        exp_big = orc.rerank(big)
+        srv = hip.ranker.serve("xgboost", hip.booster, n_slots=9)
+        for k, ev in enumerate(small):
+            s, o = srv.rerank(ev)
+            assert same(s, exp_small[k][1]) and o.tolist() == exp_small[k][2].tolist(), k
+        st = srv.stats()
+        assert (st["queue"], st["fallback"], st["launches"]) == (4, 0, 1), st
+        s, o = srv.rerank(big)   # one candidate too many for a slot: the batching front, and no gang is touched
+        assert same(s, exp_big[1]) and o.tolist() == exp_big[2].tolist()
+        st = srv.stats()
+        assert (st["queue"], st["fallback"], st["launches"]) == (4, 1, 1), st
+        # a put: the next request's flush drains the gang, the request itself revives it
+        it = small[0]["items"][0]["id"]
+        for b in (orc, hip):
+            b.put_double(f"item={it}/popularity", 987654.0)
+        _, es, eo = orc.rerank(small[0])
+        assert not same(es, exp_small[0][1])   # (the put is one the forest sees)
+        s, o = srv.rerank(small[0])
+        assert same(s, es) and o.tolist() == eo.tolist()
+        st = srv.stats()
+        assert (st["queue"], st["fallback"], st["launches"]) == (5, 1, 2), st
+        t0 = time.perf_counter()
+        srv.close()
+        srv = None
+        assert time.perf_counter() - t0 < 2.0
+        _, s, o = hip.rerank(small[0])
+        assert same(s, es) and o.tolist() == eo.tolist()
+    finally:
+        if srv is not None:
+            srv.close()
+        restore_env(saved)
+        hip.close()
+
+
+@pytest.mark.gpu
 def test_busy_serving_workgroups_do_not_stall_reallocations():
     """A persistent workgroup is a resident kernel, and hipFree / a reallocation on ANY thread waits for resident kernels.
     Under sustained traffic a slot never idles (the most recently used slot is handed out first), so the workgroup must
