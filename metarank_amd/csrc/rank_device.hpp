@@ -97,7 +97,7 @@ constexpr int DIV_GROUP = MRK_DIV_GROUP;   // diversity entries the wave-local s
 // (Round 6, measured and removed: the first 6 tokens of every entry's / field's list fetched together ahead of the inserts - one
 //  trip per group instead of one per entry.  No gain under load (c2 assembly 0.206 vs 0.208 ms), the diversity section 12 k cycles
 //  SLOWER on an unloaded request, +25 KB of unrolled insert loops: profiles/r06_m_prepass_ab.txt.)
-constexpr int PREP_INTS = 96;       // ints of LDS scratch: wave_tot[PREP_WAVES][PREP_GROUP] | first[FUSED_MAX_PREP] | misc[4] | tokens[DIV_GROUP]
+constexpr int PREP_INTS = 96;       // ints of LDS scratch: wave_tot[PREP_WAVES][PREP_GROUP] | first[FUSED_MAX_PREP] | misc[4] (misc[3]: the claim counter of prepass_interacted_tasks) | tokens[DIV_GROUP]
 
 struct PrepScratch {   // LDS scratch of one workgroup
   double *vals;        // vals_cap doubles: diversity median
@@ -288,8 +288,98 @@ __device__ __forceinline__ void prepass_interacted_with(const StoreDev &st, cons
 
 }
 
+// ---- A request's pre-pass on ALL lanes of its workgroup (round 25; the workgroup-per-request batch kernels only: PRE is named in
+// exactly one place, FusedCellsPrepass of rank_fused_cells_body).  The sections above keep a lane per candidate / per interacted
+// item and walk their entries one after the other: 20 of 64 lanes insert in the diversity section, and the slower section decides.
+//   PRE_SIDE  - the string entries of a diversity group side by side on the lanes of wavefront 0 (lane = (entry, j-th candidate of
+//               the type): one insert loop per pass instead of one per entry), the first 64 candidates' records carried from group to
+//               group; the interacted_with section as tasks (interacted item, field), one list per lane (wave_device.hpp iw_task_of).
+//   PRE_SHARE - the rounds of those tasks are claimed from a counter in LDS (misc[3]); wavefront 0 joins when its diversity section
+//               is done.  (Implies the task form.)
+// Inserts are commutative counts into disjoint tables: who inserts what changes no entry.
+#ifndef MRK_PRE_SIDE
+#define MRK_PRE_SIDE 1
+#endif
+#ifndef MRK_PRE_SHARE
+#define MRK_PRE_SHARE 0   // measured: no gain of its own, +0.7 M items/s on top of MRK_PRE_SIDE, inside the spread (LOG.md round 25)
+#endif
+constexpr int PRE_SIDE = 1, PRE_SHARE = 2;
+
+// the next round of tasks: one atomic by one lane of the wavefront, broadcast
+__device__ __forceinline__ uint32_t wave_claim(int *counter) {
+  int v = 0;
+  if ((threadIdx.x & 63) == 0) v = atomicAdd(counter, 1);
+  return (uint32_t)__builtin_amdgcn_readfirstlane(v);
+}
+
+// lane `src`'s v (all lanes of the wavefront take part)
+__device__ __forceinline__ uint32_t wave_read_lane(uint32_t v, int src) { return (uint32_t)__builtin_amdgcn_ds_bpermute(src << 2, (int)v); }
+
+// the interacted_with section as tasks, run by whole wavefronts: SHARE - every calling wavefront claims its rounds from *s_claim;
+// else this wavefront takes rounds first, first + stride, ... (numbered through all lists of the program)
+template <bool SHARE, typename Prog, typename T>
+__device__ __forceinline__ void prepass_interacted_tasks(const StoreDev &st, const Prog &prog, const BatchDev &b, int r, const ReqDev &rq,
+                                                         T *tab_base, uint32_t tab_sub, PrepOut *po_out, int *s_claim, uint32_t first, uint32_t stride) {
+  const uint32_t lane = threadIdx.x & 63;
+  const int n_prep = prog.n_prep;
+  uint32_t mine = SHARE ? wave_claim(s_claim) : first;
+  uint32_t round0 = 0;   // the number of the first round of this list
+  for (int e0 = 0; e0 < n_prep;) {
+    const PrepEntry pe0 = prog.prep[e0];
+    if (pe0.kind != PREP_IW_FIELD) { ++e0; continue; }
+    int n = 1;  // consecutive entries on the same bounded list
+    while (n < PREP_GROUP && e0 + n < n_prep) {
+      const PrepEntry q = prog.prep[e0 + n];
+      if (q.kind != PREP_IW_FIELD || q.list_scope != pe0.list_scope || q.list_col.tag != pe0.list_col.tag || q.list_col.val != pe0.list_col.val) break;
+      ++n;
+    }
+    const int vslot = pe0.list_scope == SC_SESSION ? rq.session_slot : rq.user_slot;
+    const Cell lc = load_cell(record(st, pe0.list_scope, vslot), pe0.list_col);
+    const uint32_t off = lc.lo(), len = lc.tag != TAG_MISSING ? lc.hi() : 0u;
+    const uint32_t rounds = iw_task_rounds(len, (uint32_t)n);
+    if (mine < round0 + rounds) {   // (uniform)
+      // the list's first 128 item slots, one trip for all rounds of this wavefront: a task reads its own from the lane that holds it
+      const int s0 = lane < len ? (int)st.slot_pool[off + lane] : -1;
+      const int s1 = lane + 64u < len ? (int)st.slot_pool[off + lane + 64u] : -1;
+      do {
+        uint32_t k, u;
+        const bool valid = iw_task_of(mine - round0, lane, len, (uint32_t)n, k, u);
+        const int lo_slot = (int)wave_read_lane((uint32_t)s0, (int)(k & 63u)), hi_slot = (int)wave_read_lane((uint32_t)s1, (int)(k & 63u));
+        int slot = k < 64u ? lo_slot : hi_slot;
+        if (valid && k >= 128u) slot = (int)st.slot_pool[off + k];
+        const uint8_t *irec = record(st, SC_ITEM, valid ? slot : -1);
+        ColRef col = prog.prep[e0].item_col;   // this lane's field, table and capacity
+        uint32_t toff = po_out[e0].tab_off - tab_sub, cap = po_out[e0].tab_cap;
+#pragma unroll
+        for (int v = 1; v < PREP_GROUP; ++v) {
+          const int e = e0 + (v < n ? v : 0);
+          const ColRef cv = prog.prep[e].item_col;
+          const bool me = u == (uint32_t)v;
+          col.tag = me ? cv.tag : col.tag;
+          col.val = me ? cv.val : col.val;
+          toff = me ? po_out[e].tab_off - tab_sub : toff;
+          cap = me ? po_out[e].tab_cap : cap;
+        }
+        const Cell ic = load_cell(irec, col);
+        const bool list = ic.tag == TAG_STRING_LIST;
+        if (table_add_list(list_tokens(st, irec, ic.lo()), tab_base + toff, cap, list ? ic.hi() : 0u)) atomicOr(&b.status[r], ST_TABLE_FULL);
+        mine = SHARE ? wave_claim(s_claim) : mine + stride;
+      } while (mine < round0 + rounds);
+    }
+    round0 += rounds;
+    e0 += n;
+  }
+}
+
+// (what prepass_diversity_wave<true> carries from one group of entries to the next; the lane-per-candidate form carries nothing)
+template <bool SIDE> struct DivCarry {};
+template <> struct DivCarry<true> {
+  const uint8_t *rec = nullptr;
+  bool have = false;
+};
+
 // the diversity section of prepass_request, run by ONE wavefront (all 64 lanes)
-template <typename Prog, typename T>
+template <bool SIDE = false, typename Prog, typename T>
 __device__ __forceinline__ void prepass_diversity_wave(const StoreDev &st, const Prog &prog, const BatchDev &b, int r, const ReqDev &rq,
                                                        T *tab_base, uint32_t tab_sub, PrepOut *po_out, const PrepScratch &sc) {
   const int lane = threadIdx.x & 63;
@@ -299,6 +389,7 @@ __device__ __forceinline__ void prepass_diversity_wave(const StoreDev &st, const
 #ifdef MRK_PHASE_CLOCKS
   unsigned long long dv_t = clock64(), dv_acc[3] = {0, 0, 0};
 #endif
+  DivCarry<SIDE> carry;   // SIDE: the record of candidate `lane`, found by the first group
   for (int e0 = 0; e0 < n_prep;) {
     if (prog.prep[e0].kind != PREP_DIVERSITY || po_out[e0].preset) { ++e0; continue; }
     int ent[DIV_GROUP];
@@ -329,7 +420,10 @@ __device__ __forceinline__ void prepass_diversity_wave(const StoreDev &st, const
     for (int base = 0; base < rq.n_items; base += 64) {
       const int i = base + lane;
       if (i < rq.n_items) {
-        const uint8_t *irec = record(st, SC_ITEM, b.item_slot[rq.item_begin + i]);
+        // (SIDE: a later group does not repeat the trips item slot -> record for the first 64 candidates)
+        const uint8_t *irec;
+        if constexpr (SIDE) irec = base == 0 && carry.have ? carry.rec : record(st, SC_ITEM, b.item_slot[rq.item_begin + i]);
+        else irec = record(st, SC_ITEM, b.item_slot[rq.item_begin + i]);
         Cell c[DIV_GROUP];
 #pragma unroll
         for (int u = 0; u < DIV_GROUP; ++u) {
@@ -358,6 +452,10 @@ __device__ __forceinline__ void prepass_diversity_wave(const StoreDev &st, const
       const int htag = first != 0x7fffffff ? (first & 255) : (int)TAG_MISSING;
       mode[u] = (htag == TAG_STRING || htag == TAG_STRING_LIST) ? DIV_STRING : (htag == TAG_DOUBLE ? DIV_DOUBLE : DIV_EMPTY);
     }
+    if constexpr (SIDE) {
+      carry.rec = keep_rec;
+      carry.have = rq.n_items > 0;
+    }
     MRK_PHASE(dv_t, dv_acc[0]);
     // (b) string entries: the first `top` candidates of that type, in request order
     bool any_string = false;
@@ -369,7 +467,64 @@ __device__ __forceinline__ void prepass_diversity_wave(const StoreDev &st, const
       int running[DIV_GROUP];
 #pragma unroll
       for (int u = 0; u < DIV_GROUP; ++u) running[u] = 0;
-      for (int base = 0; base < rq.n_items; base += 64) {
+      if constexpr (SIDE) {
+        // The first 64 candidates, whose cells are in registers: the string entries side by side.  The wavefront is `per` segments of
+        // `width` lanes (the largest `top` of the group's string entries), a segment per entry; lane j of a segment takes the j-th candidate of the
+        // type (wave_device.hpp wave_seg_source), reads its cell and record from the lane that holds them and inserts ONE value or
+        // list into its entry's table: one insert loop for `per` entries.  Candidates past the 64th: the loop below, as before.
+        unsigned long long ball[DIV_GROUP];
+        int q_of[DIV_GROUP];
+        int n_str = 0, width = 1;
+#pragma unroll
+        for (int u = 0; u < DIV_GROUP; ++u) {
+          const bool s = u < n && mode[u] == DIV_STRING;   // uniform
+          ball[u] = __ballot(s && (keep[u].tag == TAG_STRING || keep[u].tag == TAG_STRING_LIST));
+          q_of[u] = s ? n_str : -1;
+          n_str += s ? 1 : 0;
+          if (s) width = max(width, min(top[u], 64));
+        }
+        const int per = 64 / width;
+        const int seg = lane / width;
+        for (int q0 = 0; q0 < n_str; q0 += per) {
+          int mu = -1, mtop = 0;   // this lane's entry
+          unsigned long long mball = 0ull;
+          uint32_t moff = 0u, mcap = 0u;
+#pragma unroll
+          for (int u = 0; u < DIV_GROUP; ++u) {
+            const bool me = q_of[u] == q0 + seg;
+            mu = me ? u : mu;
+            mtop = me ? top[u] : mtop;
+            mball = me ? ball[u] : mball;
+            moff = me ? (uint32_t)(tab[u] - tab_base) : moff;
+            mcap = me ? cap[u] : mcap;
+          }
+          const int src = wave_seg_source(mball, lane, width, per, mtop);
+          const bool valid = src >= 0;
+          const int from = valid ? src : lane;
+          Cell c;
+          c.tag = TAG_MISSING;
+          c.bits = 0;
+#pragma unroll
+          for (int u = 0; u < DIV_GROUP; ++u) {
+            if (u < n && mode[u] == DIV_STRING) {  // uniform
+              const uint32_t tg = wave_read_lane(keep[u].tag, from), lo = wave_read_lane(keep[u].lo(), from), hi = wave_read_lane(keep[u].hi(), from);
+              if (mu == u) { c.tag = tg; c.bits = (uint64_t)lo | ((uint64_t)hi << 32); }
+            }
+          }
+          const uint64_t rec_bits = (uint64_t)keep_rec;
+          const uint8_t *irec = (const uint8_t *)((uint64_t)wave_read_lane((uint32_t)rec_bits, from) | ((uint64_t)wave_read_lane((uint32_t)(rec_bits >> 32), from) << 32));
+          const bool one = valid && c.tag == TAG_STRING;
+          const uint32_t tlen = valid && !one ? c.hi() : 0u;
+          T *mtab = tab_base + moff;
+          uint32_t failed = TableOps<T>::add(mtab, mcap, c.lo(), one) ? 0u : 1u;
+          failed += table_add_list(list_tokens(st, irec, c.lo()), mtab, mcap, tlen);
+          if (failed) atomicOr(&b.status[r], ST_TABLE_FULL);
+          if (valid) atomicAdd(&s_tokens[mu], one ? 1 : (int)tlen);
+        }
+#pragma unroll
+        for (int u = 0; u < DIV_GROUP; ++u) running[u] = (int)__popcll(ball[u]);
+      }
+      for (int base = SIDE ? 64 : 0; base < rq.n_items; base += 64) {
         bool more = false;
 #pragma unroll
         for (int u = 0; u < DIV_GROUP; ++u) more = more || (u < n && mode[u] == DIV_STRING && running[u] < top[u]);
@@ -414,9 +569,70 @@ __device__ __forceinline__ void prepass_diversity_wave(const StoreDev &st, const
     wave_lds_sync();   // (the next group zeroes s_tokens)
     MRK_PHASE(dv_t, dv_acc[1]);
     // (c) numeric entries: the first `top` (<= 64) present values in request order, then their median
+    bool side_done[DIV_GROUP];
+#pragma unroll
+    for (int u = 0; u < DIV_GROUP; ++u) side_done[u] = false;
+    if constexpr (SIDE) {
+      // Two or more numeric entries whose first `top` values all lie among the first 64 candidates: scan and median side by side, a
+      // segment of `width` lanes per entry, the values in registers (wave_seg_source, wave_seg_median_of - no median scratch, which
+      // holds ONE entry's values).  An entry that has to look past the 64th candidate, and a group's only numeric entry, take the
+      // loop below as before.
+      unsigned long long ball[DIV_GROUP];
+      int q_of[DIV_GROUP];
+      int n_num = 0, width = 1;
+#pragma unroll
+      for (int u = 0; u < DIV_GROUP; ++u) {
+        const bool d = u < n && mode[u] == DIV_DOUBLE;   // uniform
+        ball[u] = __ballot(d && keep[u].tag == TAG_DOUBLE);
+        const int have = (int)__popcll(ball[u]);
+        const bool ok = d && top[u] >= 1 && min(have, top[u]) <= sc.vals_cap && (have >= top[u] || rq.n_items <= 64);   // (past vals_cap: ST_TOO_MANY, below)
+        q_of[u] = ok ? n_num : -1;
+        n_num += ok ? 1 : 0;
+        if (ok) width = max(width, top[u]);
+      }
+      const int per = 64 / width;
+      if (n_num >= 2 && per >= 2) {
+        const int seg = lane / width, j = lane - seg * width;
+        const auto read_double = [](double x, int src_lane) {
+          const unsigned long long xb = (unsigned long long)__double_as_longlong(x);
+          return __longlong_as_double((long long)((uint64_t)wave_read_lane((uint32_t)xb, src_lane) | ((uint64_t)wave_read_lane((uint32_t)(xb >> 32), src_lane) << 32)));
+        };
+        for (int q0 = 0; q0 < n_num; q0 += per) {
+          int mu = -1, mtop = 0, ment = 0;   // this lane's entry
+          unsigned long long mball = 0ull;
+#pragma unroll
+          for (int u = 0; u < DIV_GROUP; ++u) {
+            const bool me = q_of[u] == q0 + seg;
+            mu = me ? u : mu;
+            mtop = me ? top[u] : mtop;
+            ment = me ? ent[u] : ment;
+            mball = me ? ball[u] : mball;
+          }
+          const int src = wave_seg_source(mball, lane, width, per, mtop);
+          const int from = src >= 0 ? src : lane;
+          uint32_t lo = 0u, hi = 0u;
+#pragma unroll
+          for (int u = 0; u < DIV_GROUP; ++u) {
+            if (q_of[u] >= q0 && q_of[u] < q0 + per) {  // uniform
+              const uint32_t l = wave_read_lane(keep[u].lo(), from), h = wave_read_lane(keep[u].hi(), from);
+              if (mu == u) { lo = l; hi = h; }
+            }
+          }
+          const double mine = __longlong_as_double((long long)((uint64_t)lo | ((uint64_t)hi << 32)));
+          const int segs = min(per, n_num - q0);
+          const double scalar = wave_seg_median_of(mine, mu >= 0 ? min((int)__popcll(mball), mtop) : 0, width, segs, read_double);
+          if (mu >= 0 && seg < segs && j == 0) {
+            po_out[ment].mode = DIV_DOUBLE;
+            po_out[ment].scalar = scalar;
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < DIV_GROUP; ++u) side_done[u] = q_of[u] >= 0;
+      }
+    }
 #pragma unroll
     for (int u = 0; u < DIV_GROUP; ++u) {
-      if (u >= n || mode[u] != DIV_DOUBLE) continue;
+      if (u >= n || mode[u] != DIV_DOUBLE || side_done[u]) continue;
       int running = 0;
       for (int base = 0; base < rq.n_items && running < top[u]; base += 64) {
         const int i = base + lane;
@@ -461,7 +677,7 @@ __device__ __forceinline__ void prepass_diversity_wave(const StoreDev &st, const
 //   * the diversity entries share the pass that finds each one's first candidate with state, the load that
 //     decides string vs number, and - for the string ones - the pass over the first `top` candidates
 //     (one multi-flag prefix scan keeps request order); numeric ones then take their median one by one.
-template <typename Prog, typename T>
+template <int PRE = 0, typename Prog, typename T>
 __device__ __forceinline__ void prepass_request(const StoreDev &st, const Prog &prog, const BatchDev &b, int r, const ReqDev &rq,
                                 T *tab_base, uint32_t tab_sub, PrepOut *po_out, const PrepScratch &sc) {
   const int tid = threadIdx.x;
@@ -481,12 +697,34 @@ __device__ __forceinline__ void prepass_request(const StoreDev &st, const Prog &
     }
     for (uint32_t i = lo + tid; i < hi; i += nthr) tab_base[i] = (T)0;
     for (int e = tid; e < n_prep; e += nthr) s_first[e] = 0x7fffffff;
+    if constexpr ((PRE & PRE_SHARE) != 0)
+      if (tid == 0) s_misc[3] = 0;   // the next round of interacted_with tasks
   }
   __syncthreads();
   MRK_PHASE(sc.clk, sc.acc[0]);
   if (prepass_waves_ok(prog)) {   // (uniform) the sections side by side on different wavefronts
     const bool lone = nthr <= 64;   // a one-wavefront workgroup runs both, one after the other
     const int wave = tid >> 6;
+    if constexpr (PRE != 0) {
+      if (!lone) {   // the sections on all lanes (above): wavefronts 1.. start on the tasks at once, wavefront 0 joins after its own section
+        constexpr bool SHARE = (PRE & PRE_SHARE) != 0;
+        if (wave == 0) {
+          prepass_diversity_wave<(PRE & PRE_SIDE) != 0>(st, prog, b, r, rq, tab_base, tab_sub, po_out, sc);
+#ifdef MRK_PHASE_CLOCKS
+          if (tid == 0) atomicAdd(&mrk_phase_clocks[3], clock64() - sc.clk);    // the diversity section alone (wavefront 0)
+#endif
+        }
+        if (SHARE || wave != 0)   // (one call for all wavefronts: the task loop is compiled once)
+          prepass_interacted_tasks<SHARE>(st, prog, b, r, rq, tab_base, tab_sub, po_out, &s_misc[3], (uint32_t)(wave - 1), (uint32_t)(((nthr + 63) >> 6) - 1));
+#ifdef MRK_PHASE_CLOCKS
+        if (tid == 64) atomicAdd(&mrk_phase_clocks[2], clock64() - sc.clk);   // wavefront 1 until no task is left
+        if (tid == 0) atomicAdd(&mrk_phase_clocks[11], clock64() - sc.clk);   // wavefront 0: its section + its share of the tasks
+#endif
+        __syncthreads();
+        MRK_PHASE(sc.clk, sc.acc[1]);
+        return;
+      }
+    }
     if (lone || wave != 0) prepass_interacted_with(st, prog, b, r, rq, tab_base, tab_sub, po_out, lone ? tid : tid - 64, lone ? nthr : nthr - 64);
     if (wave == 0) prepass_diversity_wave(st, prog, b, r, rq, tab_base, tab_sub, po_out, sc);
 #ifdef MRK_PHASE_CLOCKS
@@ -1802,7 +2040,7 @@ __device__ __forceinline__ void assemble_item(const StoreDev &st, const Prog &pr
 // lds_skip: bytes at the start of the dynamic LDS that belong to the caller (the one-launch kernel keeps the scorer's slab there).
 // rt_src / rt_doubles: compact threshold tables the workgroup copies into the threshold region before its pre-pass (0: none - the
 // region is per-wavefront staging buffers); make_sink gets both views of the region.
-template <bool SPLIT, typename T = unsigned long long, typename Prog, typename SinkMaker>
+template <bool SPLIT, typename T = unsigned long long, int PRE = 0, typename Prog, typename SinkMaker>
 __device__ __forceinline__ void rank_fused_body(const StoreDev &st, const Prog &prog, const BatchDev &b, uint32_t tab_entries,
                                                 int vals_cap, uint32_t thr_cap, int mode, const SinkMaker &make_sink, uint32_t lds_skip = 0,
                                                 const double *rt_src = nullptr, uint32_t rt_doubles = 0, int blk = -1) {
@@ -1838,7 +2076,7 @@ __device__ __forceinline__ void rank_fused_body(const StoreDev &st, const Prog &
 #ifdef MRK_PHASE_CLOCKS
   sc.clk = clock64();
 #endif
-  prepass_request(st, prog, b, r, rq, s_tab, (uint32_t)rq.arena_begin, s_po, sc);
+  prepass_request<PRE>(st, prog, b, r, rq, s_tab, (uint32_t)rq.arena_begin, s_po, sc);
   const int og = (int)threadIdx.x / item_lanes, il = (int)threadIdx.x % item_lanes;
   for (int base = slice_lo; base < slice_hi; base += item_lanes) {
     const int i = base + il;
@@ -2021,15 +2259,18 @@ __device__ __forceinline__ void rank_values_body(const StoreDev &st, const Prog 
 //  and the 8-byte ones in the op-split / sliced kernel and its interpreting twin)
 template <bool SPLIT> struct FusedCellsEntry { typedef unsigned long long type; };
 template <> struct FusedCellsEntry<false> { typedef uint32_t type; };
-template <bool F64, bool SPLIT = false, typename QS = QsDyn, typename T = typename FusedCellsEntry<SPLIT>::type, typename Prog>
+// (how the pre-pass uses the workgroup's lanes - prepass_request's PRE: the two workgroup-per-request batch kernels and their
+//  interpreting twin only; every other kernel keeps a lane per candidate / per interacted item)
+template <bool SPLIT> struct FusedCellsPrepass { static constexpr int value = (MRK_PRE_SIDE ? PRE_SIDE : 0) | (MRK_PRE_SHARE ? PRE_SHARE : 0); };
+template <bool F64, bool SPLIT = false, typename QS = QsDyn, typename T = typename FusedCellsEntry<SPLIT>::type, int PRE = FusedCellsPrepass<SPLIT>::value, typename Prog>
 __device__ __forceinline__ void rank_fused_cells_body(const StoreDev &st, const Prog &prog, const BatchDev &b, uint32_t tab_entries,
                                                       int vals_cap, const QsDev &q, uint16_t *cells, int mode = 1) {
   if constexpr (qs_fused_rt<QS, SPLIT>()) {   // the forest's compact tables fit: resident, searched four columns at a time (CellSinkRT)
-    rank_fused_body<SPLIT, T>(st, prog, b, tab_entries, vals_cap, qs_thr_cap<QS>(q), mode, [&](int gi, int r, bool active, qs_lds_double *, qs_lds_double *s_all) {
+    rank_fused_body<SPLIT, T, PRE>(st, prog, b, tab_entries, vals_cap, qs_thr_cap<QS>(q), mode, [&](int gi, int r, bool active, qs_lds_double *, qs_lds_double *s_all) {
       return CellSinkRT<F64, QS, !SPLIT>{q, cells + (size_t)(gi / QS_TILE_ROWS) * QS::n_views * QS_TILE_ROWS + (gi % QS_TILE_ROWS), &b.status[r], s_all, active};
     }, 0u, q.thr_rt, QS::rt_total);
   } else {
-    rank_fused_body<SPLIT, T>(st, prog, b, tab_entries, vals_cap, qs_thr_cap<QS>(q), mode, [&](int gi, int r, bool active, qs_lds_double *s_thr, qs_lds_double *) {
+    rank_fused_body<SPLIT, T, PRE>(st, prog, b, tab_entries, vals_cap, qs_thr_cap<QS>(q), mode, [&](int gi, int r, bool active, qs_lds_double *s_thr, qs_lds_double *) {
       return CellSink<F64, QS>{q, cells + (size_t)(gi / QS_TILE_ROWS) * qs_n_views<QS>(q) * QS_TILE_ROWS + (gi % QS_TILE_ROWS), &b.status[r], s_thr, active};
     });
   }

@@ -16,7 +16,7 @@ from workloads import ranklens, synth
 wl = sys.argv[1] if len(sys.argv) > 1 else "c2"
 n_req, n_items = (3840, 100) if wl == "c2" else (384, 1000)
 if len(sys.argv) > 2:
-    n_req = int(sys.argv[2])   # few requests: every workgroup alone on its CU - the cycles are the critical path itself
+    n_req = int(sys.argv[2])   # few requests: every workgroup alone on its CU - the cycles are the critical path itself (with MRK_FUSED_SPLIT=1: batches of <= 64 requests take the op-split kernel otherwise, which has no clocks)
 ctx = M.Context(0)
 cfg = ranklens.c3_config() if wl == "c3" else ranklens.ranklens_config()
 ranker = M.HipRanker(cfg, ctx)
@@ -56,6 +56,7 @@ for i, n in enumerate(names):
     print(f"  {n:28s} {v[i] / wg:10.0f}  {100 * v[i] / wg / tot:5.1f} %")
 print(f"  {'  of which issuing trips':28s} {v[7] / wg:10.0f}")
 print(f"  diversity section: find-first {v[8] / wg:.0f}, strings {v[9] / wg:.0f}, numeric medians {v[10] / wg:.0f}")
+print(f"  wavefront 0, its section + its share of the interacted_with tasks (all-lanes pre-pass; 0: not that form) {v[11] / wg:.0f}")
 print(f"  {'total':28s} {tot:10.0f}")
 model_feats = cfg["models"]["xgboost"]["features"]
 ops = v[16:16 + len(model_feats)]
