@@ -51,6 +51,8 @@
  * Still ABI 9, new symbols only: mrk_als_* (the similar-items recommender's fit: eALS factors on the device).
  * Still ABI 9, no new symbol and no struct change: mrk_train_* takes the config key "backend" ("xgboost": the level-wise fit that
  * returns XGBoost JSON) and its keys lambda, gamma, min_child_weight; without the key a fit gives the bytes it gave before.
+ * Still ABI 9, new symbols only: mrk_train_append_device, mrk_train_seal (the trainer's matrix from device memory, its bins found on
+ * the device) and mrk_train_bounds.
  */
 #ifndef MRK_H
 #define MRK_H
@@ -864,9 +866,13 @@ int mrk_model_eval(mrk_model *model, const int *metrics, const int *cutoffs, int
                    const double *random_scores, double *out, double *out_scores);
 
 /* ---- Training: LambdaMART forests fitted on the device ------------------------------------------------------------------------------
- * LambdaMARTPredictor.makeBooster (M/ml/rank/LambdaMARTRanker.scala:161-190) for the LightGBM backend: the row matrix mrk_values
- * wrote stays where it is, the forest comes back as LightGBM's text format (objective=lambdarank) and loads through mrk_model_load
- * like any other.  New symbols only, no new struct.
+ * LambdaMARTPredictor.makeBooster (M/ml/rank/LambdaMARTRanker.scala:161-190) for the LightGBM backend: the forest comes back as
+ * LightGBM's text format (objective=lambdarank) and loads through mrk_model_load like any other.  New symbols only, no new struct.
+ * A trainer takes its matrix in one of two ways.  mrk_train_set takes it from HOST memory: a matrix mrk_values wrote is fetched
+ * first (mrk_batch_fetch), its bins are found on the host (steps 2, 2x, 2c) and it is uploaded in pieces - it never has to fit the
+ * device.  mrk_train_append_device + mrk_train_seal take it from DEVICE memory, where mrk_values wrote it (mrk_batch_device_outputs'
+ * d_matrix): the rows stay where they are, and steps 2, 2x and 2c run on the device (step 2d) - the whole matrix must then fit the
+ * device beside the fit's working memory, and mrk_train_set stays the fallback when it does not.
  * ASSUMPTIONS (unpinned): neither LightGBM nor its sources are in the reference tree, so this is NOT LightGBM's bit stream.  The
  * algorithm below is this project's: LightGBM's lambdarank objective and leaf-wise histogram learner where the rules are public,
  * and two departures that make every result independent of the order anything arrives in - (a) whatever is summed across rows is
@@ -895,6 +901,15 @@ int mrk_model_eval(mrk_model *model, const int *metrics, const int *cutoffs, int
  *              ALWAYS goes right - what CategoricalDecision does with NaN, a negative value and an id outside the bitset - so the
  *              trainer's routing and the model's prediction agree for every possible cell.  Rows are binned on the device through
  *              a dense id -> bin byte table per column (at most 32765 bytes).  The validation set uses the training set's table.
+ *  2d bins of a matrix that was appended from device memory (mrk_train_append_device, mrk_train_seal): the device finds the SAME
+ *              bounds, bit for bit, and the same kept categories.  The appended pieces are kept column-major; per numeric column
+ *              the cells become sort keys (narrowed to f32 for step 2x, -0.0 as +0.0, NaN last), are ordered as (key, row) pairs
+ *              - one workgroup up to 4096 cells, the sample sort of the large requests above -, and the positions of steps 2 / 2x
+ *              are taken from the sorted cells: over a sorted array the first p >= t with v[p] != v[p - 1] is t itself or the
+ *              first index holding a value above v[t], one binary search per bound.  Per categorical column the device counts
+ *              ids 0 ... 32764 with integer atomics and the host keeps the most frequent as in step 2c.  The refusals of steps 1,
+ *              2x and 2c keep their statuses and name the lowest (column, row) that holds such a cell.  The bins written are the
+ *              bytes mrk_train_set writes for the same rows, so the fit and the model are the same too.
  *  3 gradients per group of n rows: pi = the order of mrk_eval_scores; gain(y) = 2^y - 1; k = min(truncation, n); inv = 1 /
  *              (sum over i < k of sorted-descending gain_i / lg[i], added in order from 0.0), 0 when that sum is 0; lg[i] =
  *              log2(i + 2).  A pair of ranks (r, q) counts when the labels differ and min(r, q) < k; with hi / lo the item of the
@@ -995,6 +1010,25 @@ int mrk_train_begin(mrk_ctx *ctx, const char *config_json, mrk_trainer **out);
  * cols x 256 cells of 20 B) beyond what the device has free. */
 int mrk_train_set(mrk_trainer *t, int which, const double *rowmajor, int64_t rows, int cols, const double *labels, const int64_t *group_offsets,
                   int64_t n_groups);
+/* Step 2d, the matrix from device memory.  Copies rows x cols f64 cells from d_rowmajor - a DEVICE pointer on the trainer's device:
+ * a batch's d_matrix (mrk_batch_device_outputs), or d_matrix + first_row * cols to take a range of its rows - into staging the
+ * trainer owns (column-major; rows x cols x 8 bytes).  The work that wrote the cells must have finished (mrk_batch_sync); d_rowmajor
+ * may be rewritten as soon as the call returns.  Any number of calls per set; the first one fixes cols.  MRK_ERR_INVALID_ARG: a bad
+ * `which`, a fitted trainer, a null pointer, rows / cols < 1, cols other than the pieces before.  MRK_ERR_UNSUPPORTED, with the sizes
+ * in mrk_last_error: staged rows reaching 2^31, cols > 65535, staging beyond what the device has free (mrk_train_set, which never
+ * needs the matrix resident, is the way then).  mrk_train_set(which) drops what was appended to that set and not sealed. */
+int mrk_train_append_device(mrk_trainer *t, int which, const double *d_rowmajor, int64_t rows, int cols);
+/* Ends an appended set: labels and group_offsets are HOST arrays under mrk_train_set's rules (the offsets end at the number of
+ * appended rows), every check and status is mrk_train_set's.  which = 0: finds the bins on the device (step 2d; beside the staging
+ * it needs the keys and the sort's scratch of ONE column, about 34 bytes per row), bins the cells and frees the staging.  which = 1:
+ * after a training set (from either path, same cols); checks the cells on the device and bins them with the training set's tables.
+ * Afterwards the trainer is where mrk_train_set would have left it; a trainer may take one set from the host and the other from the
+ * device.  A seal that fails drops the appended rows all the same. */
+int mrk_train_seal(mrk_trainer *t, int which, const double *labels, const int64_t *group_offsets, int64_t n_groups);
+/* The trainer's bounds of numeric column col of the training set, whichever path found them (backend "xgboost": the f32 bounds
+ * widened, as mrk_train_bins returns them): *n_bounds of them, copied when cap >= *n_bounds.  MRK_ERR_INVALID_ARG: a categorical
+ * column, a column outside the matrix, no training set yet. */
+int mrk_train_bounds(mrk_trainer *t, int col, double *out_bounds, int cap, int *n_bounds);
 /* Runs the fit (steps 3 - 8). */
 int mrk_train_fit(mrk_trainer *t);
 /* The model text (LightGBM's text format, or XGBoost's JSON with backend "xgboost").  *needed: its length in bytes; copies it when cap >= *needed (out may be NULL to ask for the length). */

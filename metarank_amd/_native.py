@@ -283,6 +283,9 @@ SIGNATURES = {
     "mrk_model_eval": (_I, [_V, _P, _P, _I, _I, C.c_double, _P, _I, _P, _P, C.c_int64, _P, _P, _P]),
     "mrk_train_begin": (_I, [_V, _S, C.POINTER(_V)]),
     "mrk_train_set": (_I, [_V, _I, _P, C.c_int64, _I, _P, _P, C.c_int64]),
+    "mrk_train_append_device": (_I, [_V, _I, _P, C.c_int64, _I]),
+    "mrk_train_seal": (_I, [_V, _I, _P, _P, C.c_int64]),
+    "mrk_train_bounds": (_I, [_V, _I, _P, _I, C.POINTER(_I)]),
     "mrk_train_fit": (_I, [_V]),
     "mrk_train_model": (_I, [_V, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "mrk_train_history": (_I, [_V, C.POINTER(_I), C.POINTER(_I), _P, _I]),

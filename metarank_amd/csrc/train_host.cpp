@@ -138,7 +138,7 @@ TrainConfig train_parse_config(const char *text, size_t len) {
   return c;
 }
 
-static std::string g17(double x) {
+std::string train_g17(double x) {
   char buf[40];
   snprintf(buf, sizeof buf, "%.17g", x);
   return buf;
@@ -161,6 +161,8 @@ static std::vector<int64_t> bin_cuts(const std::vector<T> &v, int max_bin) {
   return cuts;
 }
 
+std::string train_numeric_info(int64_t m, double lo, double hi) { return m == 0 || lo == hi ? "none" : "[" + train_g17(lo) + ":" + train_g17(hi) + "]"; }
+
 std::vector<double> train_bin_bounds(const double *col, int64_t n, int64_t stride, int max_bin, std::string *info) {
   std::vector<double> v;
   v.reserve((size_t)std::max<int64_t>(n, 0));
@@ -173,7 +175,7 @@ std::vector<double> train_bin_bounds(const double *col, int64_t n, int64_t strid
   }
   std::sort(v.begin(), v.end());
   const int64_t m = (int64_t)v.size();
-  if (info) *info = m == 0 || v.front() == v.back() ? "none" : "[" + g17(v.front()) + ":" + g17(v.back()) + "]";
+  if (info) *info = train_numeric_info(m, m ? v.front() : 0.0, m ? v.back() : 0.0);
   std::vector<double> out;
   for (int64_t p : bin_cuts(v, max_bin)) {
     const double a = v[(size_t)p - 1], b = v[(size_t)p];
@@ -188,7 +190,7 @@ std::vector<double> train_bin_bounds(const double *col, int64_t n, int64_t strid
 static float narrowed(double x, int64_t row, int column) {
   const float f = (float)x;   // round to nearest even
   if (std::isinf(f))
-    throw StatusError(MRK_ERR_INVALID_ARG, "train: column " + std::to_string(column) + ", row " + std::to_string(row) + " holds " + g17(x) + ", which is not finite as an f32");
+    throw StatusError(MRK_ERR_INVALID_ARG, "train: column " + std::to_string(column) + ", row " + std::to_string(row) + " holds " + train_g17(x) + ", which is not finite as an f32");
   return f;
 }
 
@@ -224,7 +226,7 @@ static int32_t category_of(double x, int64_t row, int column) {
   if (x != x) return -1;
   if (std::isinf(x)) throw StatusError(MRK_ERR_INVALID_ARG, "train: cell " + std::to_string(row) + " of a column is infinite");
   if (x >= (double)(TRAIN_MAX_CATEGORY + 1))
-    throw StatusError(MRK_ERR_UNSUPPORTED, "train: categorical column " + std::to_string(column) + ", row " + std::to_string(row) + " holds " + g17(x) +
+    throw StatusError(MRK_ERR_UNSUPPORTED, "train: categorical column " + std::to_string(column) + ", row " + std::to_string(row) + " holds " + train_g17(x) +
                                                " (the largest category is " + std::to_string(TRAIN_MAX_CATEGORY) + ")");
   return x <= -1.0 ? -1 : (int32_t)x;   // (the conversion truncates: -0.5 is category 0)
 }
@@ -235,6 +237,10 @@ std::vector<int32_t> train_kept_categories(const double *col, int64_t n, int64_t
     const int32_t c = category_of(col[i * stride], i, column);
     if (c >= 0) count[(size_t)c] += 1;
   }
+  return train_kept_from_counts(count, max_bin, info);
+}
+
+std::vector<int32_t> train_kept_from_counts(const std::vector<int64_t> &count, int max_bin, std::string *info) {
   std::vector<int32_t> ids;
   for (int32_t c = 0; c <= TRAIN_MAX_CATEGORY; ++c)
     if (count[(size_t)c] > 0) ids.push_back(c);
@@ -329,7 +335,7 @@ std::vector<uint8_t> train_check_labels(const double *labels, int64_t rows) {
   for (int64_t i = 0; i < rows; ++i) {
     const double y = labels[i];
     if (!(y >= 0.0 && y <= (double)TRAIN_MAX_LABEL) || y != std::floor(y))
-      throw StatusError(MRK_ERR_INVALID_ARG, "train: label " + std::to_string(i) + " is " + g17(y) + ", not an integer in 0 ... " + std::to_string(TRAIN_MAX_LABEL));
+      throw StatusError(MRK_ERR_INVALID_ARG, "train: label " + std::to_string(i) + " is " + train_g17(y) + ", not an integer in 0 ... " + std::to_string(TRAIN_MAX_LABEL));
     out[(size_t)i] = (uint8_t)y;
   }
   return out;
@@ -388,7 +394,7 @@ std::string train_write_model(const std::vector<TrainTree> &trees, size_t n_tree
   };
   auto f64s = [](std::string &o, const char *key, const std::vector<double> &a, size_t n) {
     o += key;
-    for (size_t i = 0; i < n; ++i) o += (i ? " " : "") + g17(a[i]);
+    for (size_t i = 0; i < n; ++i) o += (i ? " " : "") + train_g17(a[i]);
     o += "\n";
   };
   std::vector<std::string> blocks;
@@ -434,7 +440,7 @@ std::string train_write_model(const std::vector<TrainTree> &trees, size_t n_tree
       ints(b, "cat_boundaries=", boundaries, boundaries.size());
       ints(b, "cat_threshold=", words, words.size());
     }
-    b += "is_linear=0\nshrinkage=" + g17(lr);
+    b += "is_linear=0\nshrinkage=" + train_g17(lr);
     blocks.push_back(std::move(b));
   }
   std::string o = "tree\nversion=v4\nnum_class=1\nnum_tree_per_iteration=1\nlabel_index=0\nmax_feature_idx=" + std::to_string(cols - 1) + "\nobjective=lambdarank\nfeature_names=";

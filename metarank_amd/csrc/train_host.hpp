@@ -65,6 +65,11 @@ TrainConfig train_parse_config(const char *json, size_t len);
 // An infinite cell: MRK_ERR_INVALID_ARG.  info: LightGBM's feature_infos entry ("none" or "[min:max]").
 std::vector<double> train_bin_bounds(const double *col, int64_t n, int64_t stride, int max_bin, std::string *info = nullptr);
 
+// the feature_infos entry of a numeric column with m non-NaN values, the least lo and the greatest hi
+std::string train_numeric_info(int64_t m, double lo, double hi);
+// %.17g
+std::string train_g17(double x);
+
 // step 2x: the bounds of one column for the xgboost backend, f32 values widened to f64: the cells are narrowed to f32 first, the bound
 // between neighbours a < b is b (bin(x) = the number of bounds <= (float) x, so x < bound goes left: the model's own test).  A finite
 // cell that narrows to +-inf, or an infinite one: MRK_ERR_INVALID_ARG naming `column` and the row.
@@ -79,6 +84,8 @@ int train_bin_f32(double x, const double *bounds, int n_bounds);
 // negative ones have none.  An infinite cell: MRK_ERR_INVALID_ARG; a category beyond TRAIN_MAX_CATEGORY: MRK_ERR_UNSUPPORTED, naming
 // `column`, the row and the value.  info: LightGBM's feature_infos entry (the ids joined by ':', or "none").
 std::vector<int32_t> train_kept_categories(const double *col, int64_t n, int64_t stride, int max_bin, int column, std::string *info = nullptr);
+// the tail of step 2c, from the count of every id 0 ... TRAIN_MAX_CATEGORY (TRAIN_MAX_CATEGORY + 1 counts: the device's histogram too)
+std::vector<int32_t> train_kept_from_counts(const std::vector<int64_t> &count, int max_bin, std::string *info = nullptr);
 // the cells of a categorical column of another set than the one the ids were kept from: the same two refusals
 void train_check_categories(const double *col, int64_t n, int64_t stride, int column);
 // id -> bin for ids 0 ... kept.back(), TRAIN_NAN_BIN where the id has none; empty without a kept id
@@ -88,6 +95,37 @@ std::vector<uint8_t> train_category_table(const std::vector<int32_t> &kept);
 MRK_TRAIN_HD inline int train_category_bin(double x, const uint8_t *table, int len) {
   if (!(x > -1.0) || !(x < (double)len)) return TRAIN_NAN_BIN;   // (NaN fails both; -1 < x < 0 truncates to category 0)
   return table[(int)x];
+}
+
+// Steps 2 and 2x over values that are ALREADY sorted (step 2d: the device's bin finder, train_bins.hip; tests/native/train_cuts_test.cpp
+// holds it against train_bin_bounds on the unsorted cells).  v(p), 0 <= p < m: the sorted non-NaN values as f64 (an f32 value
+// widened, f32 = true).  Returns the first position p >= max(t, 1) with v(p) != v(p - 1) - the cut bin_cuts takes for the target t -
+// or m when there is none, and writes the bound between v(p - 1) and v(p).  Over a sorted array that position is t itself when
+// v(t) != v(t - 1), else the first index that holds a value above v(t): one binary search.
+// The targets: with at most max_bin - 2 changes every change is a cut (t = the change itself, or the cut before it + 1); else
+// t = train_cut_target(m, max_bin, i) for i = 1 ... max_bin - 2, up to the first i without a cut, a cut equal to the one before dropped.
+MRK_TRAIN_HD inline int64_t train_cut_target(int64_t m, int max_bin, int i) { return (int64_t)i * m / (max_bin - 1); }
+template <typename V>
+MRK_TRAIN_HD inline int64_t train_cut_at(const V &v, int64_t m, int64_t t, bool f32, double *bound) {
+  if (t < 1) t = 1;
+  if (t >= m) return m;
+  int64_t p = t;
+  const double x = v(t);
+  if (!(v(t - 1) != x)) {
+    int64_t lo = t + 1, hi = m;   // the first index in (t, m) whose value is above x, m when none is
+    while (lo < hi) {
+      const int64_t mid = lo + (hi - lo) / 2;
+      if (v(mid) > x) hi = mid;
+      else lo = mid + 1;
+    }
+    if (lo >= m) return m;
+    p = lo;
+  }
+  const double a = v(p - 1), b = v(p);
+  double mid = (a + b) / 2.0;
+  if (!(mid < b)) mid = a;   // (also a sum that overflowed)
+  *bound = f32 ? b : mid;
+  return p;
 }
 
 // step 7x: is row `row` in the sample of tree `tree`?  The histogram kernels call this too.

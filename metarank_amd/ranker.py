@@ -95,6 +95,7 @@ class Batch:
 
     def run(self, booster: HipBooster | None):
         N.check(N.lib().mrk_batch_run(self._h, booster.handle if booster is not None else None))
+        self.matrix_on_device = getattr(self, "_matrix_asked", False)   # (a run before the matrix was asked for may not have written it there)
 
     def run_shard(self, booster: HipBooster | None, shard_index: int, shard_count: int):
         """assemble + score batch items [index * chunk, (index + 1) * chunk) only; no sort (mrk_batch_run_shard)"""
@@ -133,6 +134,7 @@ class Batch:
         """device pointers (scores, order, matrix | None); asking for the matrix makes later runs write it"""
         s, o, m = C.c_void_p(), C.c_void_p(), C.c_void_p()
         N.check(N.lib().mrk_batch_device_outputs(self._h, C.byref(s), C.byref(o), C.byref(m) if matrix else None))
+        self._matrix_asked = getattr(self, "_matrix_asked", False) or matrix
         return s.value, o.value, (m.value if matrix else None)
 
     def fetch(self, matrix: bool = False):

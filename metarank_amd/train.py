@@ -76,7 +76,8 @@ def lambdarank_gradients(scores, labels, group_offsets, ctx: Context | None = No
 
 
 class Trainer:
-    """mrk_trainer: set(0, ...), optionally set(1, ...), fit(), then model() / history() / scores()"""
+    """mrk_trainer: set(0, ...), optionally set(1, ...), fit(), then model() / history() / scores().  A set whose rows are in device
+    memory - a values batch's matrix - is given in pieces instead: append_device / append_batch any number of times, then seal."""
 
     def __init__(self, config=None, ctx: Context | None = None):
         self.ctx = ctx or default_context()
@@ -94,6 +95,42 @@ class Trainer:
             raise N.MrkError(N.ERR_INVALID_ARG, f"{rows} rows, {y.size} labels")
         N.check(N.lib().mrk_train_set(self._h, which, X.ctypes.data, rows, cols, y.ctypes.data, off.ctypes.data, len(off) - 1))
         self._rows[which] = rows
+
+    def append_device(self, which: int, d_ptr: int, rows: int, cols: int):
+        """mrk_train_append_device: rows x cols f64 cells, row-major, at the DEVICE address d_ptr, into the trainer's staging of set
+        `which`; the work that wrote them has finished, and they may be rewritten once this returns"""
+        N.check(N.lib().mrk_train_append_device(self._h, which, d_ptr, rows, cols))
+
+    def append_batch(self, which: int, batch, first_row: int = 0, rows: int | None = None):
+        """rows [first_row, first_row + rows) of a values batch's device matrix (every row by default): how a host keeps some
+        click-throughs and skips others without the matrix leaving the device.  The batch must have been asked for its device matrix
+        BEFORE the run that assembled the rows - load_values -> device_outputs(matrix=True) -> run(None) -, as mrk_batch_device_outputs
+        says: a small values run otherwise writes its rows to the host alone."""
+        if not getattr(batch, "matrix_on_device", False):
+            raise N.MrkError(N.ERR_INVALID_ARG, "the batch ran before device_outputs(matrix=True) asked for its matrix: the rows may not be in device memory")
+        batch.sync()
+        d_matrix = batch.device_outputs(matrix=True)[2]
+        rows = batch.total_items - first_row if rows is None else rows
+        if first_row < 0 or rows < 1 or first_row + rows > batch.total_items:
+            raise N.MrkError(N.ERR_INVALID_ARG, f"rows {first_row} ... {first_row + rows} of a batch of {batch.total_items}")
+        self.append_device(which, d_matrix + first_row * batch.dim * 8, rows, batch.dim)
+
+    def seal(self, which: int, labels, group_offsets):
+        """mrk_train_seal: ends the appended set with its labels and group offsets (host arrays); the bins are found on the device"""
+        y, off = _f64(labels), _offsets(group_offsets)
+        rows = int(off[-1]) if len(off) else 0
+        if y.size != rows:
+            raise N.MrkError(N.ERR_INVALID_ARG, f"the offsets end at {rows}, {y.size} labels")
+        N.check(N.lib().mrk_train_seal(self._h, which, y.ctypes.data, off.ctypes.data, len(off) - 1))
+        self._rows[which] = rows
+
+    def bounds(self, col: int) -> np.ndarray:
+        """mrk_train_bounds: the trainer's bounds of a numeric column of the training set, whichever path found them"""
+        n = C.c_int(0)
+        N.check(N.lib().mrk_train_bounds(self._h, col, None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=np.float64)
+        N.check(N.lib().mrk_train_bounds(self._h, col, out.ctypes.data, n.value, C.byref(n)))
+        return out
 
     def fit(self):
         N.check(N.lib().mrk_train_fit(self._h))

@@ -17,8 +17,14 @@ the phases are then train_level_hist, train_level_scan (scan + pick), train_leve
 level), train_level_readback (the level's records copied back: one stream synchronisation each) and train_apply; `launches` holds the
 launch count of every phase and the bounds they must keep - for T trees of depth D at most T x D histogram launches, scan launches and
 read-backs - and the tool exits 1 when a count is above its bound.  The restatement is then tests/train_xgb_reference.py.
-  python tools/train_bench.py [--json] [--backend lightgbm|xgboost] [--depth D] [--groups N] [--min-items N] [--max-items N] [--iterations N] [--leaves N] [--ref-groups N] [--valid]
-                              [--categorical N]
+--device-set measures the hand-over alone, on the same matrix, alternating three times in one call: (a) mrk_train_set from the host
+(bins on the host, upload in pieces) and (b) the matrix already in device memory - placed there outside the clock, as a values batch
+leaves it -, appended in 16 pieces and sealed (include/mrk.h step 2d: bins on the device).  Per run: the host clock around the
+hand-over, the HIP-event phases of step 2d's kernels (train_stage, train_check, train_keys, train_sort, train_cuts,
+train_cat_counts, train_bin), the clock around the fit and the SHA-256 of the fitted model; the tool exits 1 unless every model is
+the same.
+  python tools/train_bench.py [--json] [--device-set] [--backend lightgbm|xgboost] [--depth D] [--groups N] [--min-items N] [--max-items N] [--iterations N] [--leaves N] [--ref-groups N] [--valid]
+                              [--categorical N] [--device-set]
 """
 import argparse
 import hashlib
@@ -57,6 +63,7 @@ def main():
     ap.add_argument("--categorical", type=int, default=0, help="declare the last N columns categorical; their cells are rounded to ids 0 ... 49 (NaN stays)")
     ap.add_argument("--backend", choices=("lightgbm", "xgboost"), default="lightgbm")
     ap.add_argument("--depth", type=int, default=8, help="maxDepth of the xgboost backend")
+    ap.add_argument("--device-set", action="store_true", help="mrk_train_set from the host against append + seal from device memory, three runs each")
     a = ap.parse_args()
     xgb = a.backend == "xgboost"
     timers = LEVEL_TIMERS if xgb else TIMERS
@@ -72,6 +79,8 @@ def main():
         cfg["categorical"] = cats
     out = {"groups": a.groups, "rows": rows, "items_per_group": [a.min_items, a.max_items], "columns": COLS, "iterations": a.iterations, "leaves": a.leaves,
            "backend": a.backend, "depth": a.depth if xgb else None, "categorical": cats, "build": N.lib().mrk_build_id().decode()}
+    if a.device_set:
+        return device_set(a, ctx, cfg, out, X, y, off)
 
     ctx.profile_enable(True)
     t = Trainer(cfg, ctx)
@@ -122,6 +131,63 @@ def main():
         out["sklearn_hist_gbr_ms_per_tree"] = (time.perf_counter() - t0) * 1e3 / trees
     ctx.close()
     print(json.dumps(out) if a.json else json.dumps(out, indent=1))
+
+
+SET_TIMERS = ("train_stage", "train_check", "train_keys", "train_sort", "train_cuts", "train_cat_counts", "train_bin")
+DEVICE_PIECES = 16
+
+
+def device_set(a, ctx, cfg, out, X, y, off):
+    import ctypes as C
+
+    hip = C.CDLL("libamdhip64.so")
+    hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    hip.hipFree.argtypes = [C.c_void_p]
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    rows, cols = X.shape
+    d = C.c_void_p()
+    assert hip.hipMalloc(C.byref(d), X.nbytes) == 0 and hip.hipMemcpy(d, X.ctypes.data, X.nbytes, 1) == 0   # outside the clock
+    cuts = [rows * i // DEVICE_PIECES for i in range(DEVICE_PIECES + 1)]
+    runs = {"host": [], "device": []}
+    for _ in range(3):
+        for path in ("host", "device"):
+            ctx.profile_enable(True)                                      # (clears the phases)
+            t = Trainer(cfg, ctx)
+            t0 = time.perf_counter()
+            if path == "host":
+                t.set(0, X, y, off)
+            else:
+                for lo, hi in zip(cuts[:-1], cuts[1:]):
+                    if hi > lo:
+                        t.append_device(0, d.value + lo * cols * 8, hi - lo, cols)
+                t.seal(0, y, off)
+            run = {"set_call_ms": (time.perf_counter() - t0) * 1e3}
+            for name in SET_TIMERS:
+                run[name + "_ms"], run[name + "_launches"] = ctx.profile_get(name)
+            t0 = time.perf_counter()
+            t.fit()
+            run["fit_call_ms"] = (time.perf_counter() - t0) * 1e3
+            run["model_sha256"] = hashlib.sha256(t.model()).hexdigest()
+            t.close()
+            ctx.profile_enable(False)
+            runs[path].append(run)
+    hip.hipFree(d)
+    out["device_pieces"] = DEVICE_PIECES
+    out["runs"] = runs
+    for path in runs:
+        for key in ("set_call_ms", "fit_call_ms"):
+            v = [r[key] for r in runs[path]]
+            out[f"{path}_{key}"] = {"min": min(v), "median": sorted(v)[1], "max": max(v)}
+    out["device_phases_ms"] = {name: sorted(r[name + "_ms"] for r in runs["device"])[1] for name in SET_TIMERS}
+    hashes = {r["model_sha256"] for path in runs for r in runs[path]}
+    out["model_sha256"] = {path: runs[path][0]["model_sha256"] for path in runs}
+    out["models_equal"] = len(hashes) == 1
+    out["set_speedup_median"] = out["host_set_call_ms"]["median"] / out["device_set_call_ms"]["median"]
+    ctx.close()
+    print(json.dumps(out) if a.json else json.dumps(out, indent=1))
+    if not out["models_equal"]:
+        sys.exit(1)
 
 
 def finish_xgboost(a, ctx, out, parts, hist, model, X, y, off, rows):
