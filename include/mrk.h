@@ -918,8 +918,25 @@ int mrk_model_eval(mrk_model *model, const int *metrics, const int *cutoffs, int
  *              eta = (((sigma * sigma) * rho) * (1 - rho)) * w; g[hi] -= lambda, g[lo] += lambda, h[both] += eta.  An item adds
  *              its pairs in ascending partner rank from 0.0.  T[t] = 1 / (1 + exp(sigma * (lo + t / f))), BINS =
  *              MRK_TRAIN_SIGMOID_BINS, lo = -25 / sigma, f = BINS / (50 / sigma).  Every operation f64, correctly rounded, never
- *              fused.  No lambdarank_norm, no position debias.
- *  4 quantise  e_g = 61 - bitlen(rows) - E(max |g|), frexp(x) = m * 2^E; q_g = (int64) nearbyint(ldexp(g, e_g)), ties to even; h
+ *              fused.  No lambdarank_norm.  Position debias: step 3b, off unless the config says position_bias.
+ *  3b position bias (Unbiased LambdaMART, Hu et al., WWW 2019; the method behind `debias` of both reference boosters).  This project's
+ *              algorithm, UNPINNED against LightGBM's and libxgboost's bit streams like the rest; both reproducibility rules hold (int64
+ *              sums of quantised values across rows; exp, log and pow are the host's libm, through tables or on the host; every device
+ *              operation f64, correctly rounded, never fused).  Config: "position_bias" absent or null (off: every fit gives the bytes it
+ *              gave before the key existed) or an object {positions [32]: 1 ... 4096 else MRK_ERR_INVALID_ARG; norm [1.0]: finite and
+ *              >= 0 else MRK_ERR_INVALID_ARG}; an unknown key inside or a value of the wrong type is MRK_ERR_PARSE; either backend.
+ *              `debias: true` stays MRK_ERR_UNSUPPORTED (the Boolean carries neither number): a host sends "position_bias": {}.
+ *              pos(row) = min(row - group_offsets[group], P - 1), the item's place in the list as shown.  State: t_plus[P], t_minus[P],
+ *              f64, all 1.0 before the first iteration.  For a pair (hi, lo) that step 3 counts, i = pos(hi), j = pos(lo):
+ *              c = t_plus[i] * t_minus[j]; lambda' = lambda / c and eta' = eta / c, divided after step 3's products; cost = L[t] * w
+ *              with t the index of rho, L[t] = log1p(exp(-sigma * (lo + t / f))); hi adds cost / t_minus[j] to its cp, lo adds cost /
+ *              t_plus[i] to its cm, both in ascending partner rank from 0.0 like g and h.  Position sums: max cp and max cm give step
+ *              4's exponents e_p, e_m and quantisation; Qp[pos], Qm[pos] are int64 sums over all training rows.  Update, on the host
+ *              after the iteration's gradients are taken: Sp[i] = ldexp((double) Qp[i], -e_p); Sp[0] == 0 keeps every t_plus; else
+ *              t_plus[i] = pow(Sp[i] / Sp[0], 1 / (norm + 1)) for every i with Sp[i] > 0, the others keep theirs; t_minus likewise
+ *              from Qm.  The tree of iteration k grows from gradients that used the factors of iterations < k.  The validation metric,
+ *              early stopping, steps 4 - 8 and the model text are untouched.  tests/train_bias_reference.py restates it.
+ *  4 quantise e_g = 61 - bitlen(rows) - E(max |g|), frexp(x) = m * 2^E; q_g = (int64) nearbyint(ldexp(g, e_g)), ties to even; h
  *              likewise with max h.  max |g| == 0 ends training.
  *  5 tree      leaf-wise.  Per leaf and column of the tree's subset a histogram (sum q_g, sum q_h, count) per bin.  Candidates b =
  *              0 ... nbins - 2, left = bins <= b; NaN goes right, and with rows in bin 255 also left.  Real sums are ldexp((double)
@@ -1043,6 +1060,14 @@ void mrk_train_free(mrk_trainer *t);
  * host that keeps lib_lightgbm.  A non-finite score is MRK_ERR_INVALID_ARG. */
 int mrk_train_gradients(mrk_ctx *ctx, const char *config_json, const double *scores, const double *labels, const int64_t *group_offsets,
                         int64_t n_groups, double *out_g, double *out_h);
+/* Step 3b's factors after the last iteration run: *n = positions (0 when the config has no position_bias), copied into out_plus and
+ * out_minus when cap >= *n.  MRK_ERR_NOT_FOUND before the fit. */
+int mrk_train_position_bias(mrk_trainer *t, double *out_plus, double *out_minus, int cap, int *n);
+/* Steps 3 and 3b alone, the stateless twin of mrk_train_gradients: the config must hold position_bias; t_plus / t_minus: `positions`
+ * factors each, finite and > 0 (else MRK_ERR_INVALID_ARG); out_cost_plus / out_cost_minus: cp and cm, one f64 per row. */
+int mrk_train_bias_gradients(mrk_ctx *ctx, const char *config_json, const double *scores, const double *labels, const int64_t *group_offsets,
+                             int64_t n_groups, const double *t_plus, const double *t_minus, double *out_g, double *out_h, double *out_cost_plus,
+                             double *out_cost_minus);
 /* Step 2 (step 2x when the config says backend "xgboost") for one column of n cells (host only, no context): *n_bounds bounds, copied
  * when cap >= *n_bounds. */
 int mrk_train_bins(const char *config_json, const double *column, int64_t n, double *out_bounds, int cap, int *n_bounds);

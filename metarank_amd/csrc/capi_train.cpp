@@ -518,41 +518,89 @@ void mrk_train_free(mrk_trainer *t) {
   ctx_release(ctx);
 }
 
+int mrk_train_position_bias(mrk_trainer *t, double *out_plus, double *out_minus, int cap, int *n) {
+  return guard([&] {
+    check_trainer(t);
+    need(n != nullptr, "n is null");
+    std::lock_guard<std::mutex> lk(t->mu);
+    if (!t->fitted) throw StatusError(MRK_ERR_NOT_FOUND, "train: not fitted yet");
+    *n = (int)t->t_plus.size();
+    if (out_plus && out_minus && cap >= *n && *n > 0) {
+      memcpy(out_plus, t->t_plus.data(), t->t_plus.size() * 8);
+      memcpy(out_minus, t->t_minus.data(), t->t_minus.size() * 8);
+    }
+  });
+}
+
+}  // extern "C"
+
+// step 3 for mrk_train_gradients (t_plus null) and steps 3 + 3b for mrk_train_bias_gradients
+static void gradients_call(mrk_ctx *ctx, const char *config_json, const double *scores, const double *labels, const int64_t *group_offsets, int64_t n_groups,
+                           const double *t_plus, const double *t_minus, double *out_g, double *out_h, double *out_cp, double *out_cm) {
+  const bool bias = t_plus != nullptr;
+  need(config_json != nullptr, "null config");
+  const TrainConfig cfg = train_parse_config(config_json, strlen(config_json));
+  need(scores != nullptr && out_g != nullptr && out_h != nullptr, "train: null scores / outputs");
+  if (bias) {
+    need(cfg.position_bias, "train: the config has no position_bias");
+    need(t_minus != nullptr && out_cp != nullptr && out_cm != nullptr, "train: null factors / cost outputs");
+    for (int i = 0; i < cfg.bias_positions; ++i)
+      if (!(t_plus[i] > 0.0 && t_minus[i] > 0.0) || !std::isfinite(t_plus[i]) || !std::isfinite(t_minus[i]))
+        throw StatusError(MRK_ERR_INVALID_ARG, "train: the factors of position " + std::to_string(i) + " are not finite numbers above 0");
+  }
+  const EvalShape sh = eval_check_groups(group_offsets, n_groups);
+  const std::vector<uint8_t> y = train_check_labels(labels, sh.rows);
+  for (int64_t i = 0; i < sh.rows; ++i)
+    if (!std::isfinite(scores[i])) throw StatusError(MRK_ERR_INVALID_ARG, "train: score " + std::to_string(i) + " is not finite");
+  if (sh.max_len > TRAIN_MAX_GROUP)
+    throw StatusError(MRK_ERR_UNSUPPORTED, "train: a group of " + std::to_string(sh.max_len) + " rows (limit " + std::to_string(TRAIN_MAX_GROUP) + ")");
+  need(ctx != nullptr, "null context");
+  const EvalBins by_size = eval_bins(group_offsets, n_groups, EVAL_WAVE_ITEMS);
+  DeviceLock lk(ctx);
+  hipStream_t st = lk.stream;
+  const size_t rows = (size_t)sh.rows;
+  check_free((bias ? 49.0 : 33.0) * (double)rows + 12.0 * (double)n_groups + 16.0 * (double)sh.max_len + (bias ? 16.0 : 8.0) * TRAIN_SIGMOID_BINS + 65536.0,
+             std::to_string(rows) + " rows in " + std::to_string(n_groups) + " groups");
+  GradTables tab;
+  tab.make(cfg, sh.max_len, st);
+  DevBuf d_scores, d_labels, d_off, d_wave, d_group, d_g, d_h;
+  d_scores.reserve(rows * 8), d_off.reserve((size_t)(n_groups + 1) * 8), d_g.reserve(rows * 8), d_h.reserve(rows * 8);
+  MRK_HIP(hipMemcpyAsync(d_scores.p, scores, rows * 8, hipMemcpyHostToDevice, st));
+  MRK_HIP(hipMemcpyAsync(d_off.p, group_offsets, (size_t)(n_groups + 1) * 8, hipMemcpyHostToDevice, st));
+  upload(d_labels, y, st);
+  if (!by_size.wave.empty()) upload(d_wave, by_size.wave, st);
+  if (!by_size.group.empty()) upload(d_group, by_size.group, st);
+  GradDev gd = tab.dev(cfg);
+  gd.scores = d_scores.as<double>(), gd.labels = d_labels.as<uint8_t>(), gd.offsets = d_off.as<long long>(), gd.g = d_g.as<double>(), gd.h = d_h.as<double>();
+  BiasTables bt;
+  if (bias) {
+    bt.make(cfg, sh.rows, st);
+    std::copy(t_plus, t_plus + bt.positions, bt.t_plus());
+    std::copy(t_minus, t_minus + bt.positions, bt.t_minus());
+    launch_bias_gradients(ctx, st, gd, bt.dev(st), by_size, d_wave, d_group);
+    MRK_HIP(hipMemcpyAsync(out_cp, bt.d_cp.p, rows * 8, hipMemcpyDeviceToHost, st));
+    MRK_HIP(hipMemcpyAsync(out_cm, bt.d_cm.p, rows * 8, hipMemcpyDeviceToHost, st));
+  } else {
+    launch_gradients(ctx, st, gd, by_size, d_wave, d_group);
+  }
+  MRK_HIP(hipMemcpyAsync(out_g, d_g.p, rows * 8, hipMemcpyDeviceToHost, st));
+  MRK_HIP(hipMemcpyAsync(out_h, d_h.p, rows * 8, hipMemcpyDeviceToHost, st));
+  MRK_HIP(hipStreamSynchronize(st));
+  drain_profile_events(ctx);
+}
+
+extern "C" {
+
 int mrk_train_gradients(mrk_ctx *ctx, const char *config_json, const double *scores, const double *labels, const int64_t *group_offsets, int64_t n_groups,
                         double *out_g, double *out_h) {
+  return guard([&] { gradients_call(ctx, config_json, scores, labels, group_offsets, n_groups, nullptr, nullptr, out_g, out_h, nullptr, nullptr); });
+}
+
+int mrk_train_bias_gradients(mrk_ctx *ctx, const char *config_json, const double *scores, const double *labels, const int64_t *group_offsets, int64_t n_groups,
+                             const double *t_plus, const double *t_minus, double *out_g, double *out_h, double *out_cost_plus, double *out_cost_minus) {
   return guard([&] {
-    need(config_json != nullptr, "null config");
-    const TrainConfig cfg = train_parse_config(config_json, strlen(config_json));
-    need(scores != nullptr && out_g != nullptr && out_h != nullptr, "train: null scores / outputs");
-    const EvalShape sh = eval_check_groups(group_offsets, n_groups);
-    const std::vector<uint8_t> y = train_check_labels(labels, sh.rows);
-    for (int64_t i = 0; i < sh.rows; ++i)
-      if (!std::isfinite(scores[i])) throw StatusError(MRK_ERR_INVALID_ARG, "train: score " + std::to_string(i) + " is not finite");
-    if (sh.max_len > TRAIN_MAX_GROUP)
-      throw StatusError(MRK_ERR_UNSUPPORTED, "train: a group of " + std::to_string(sh.max_len) + " rows (limit " + std::to_string(TRAIN_MAX_GROUP) + ")");
-    need(ctx != nullptr, "null context");
-    const EvalBins by_size = eval_bins(group_offsets, n_groups, EVAL_WAVE_ITEMS);
-    DeviceLock lk(ctx);
-    hipStream_t st = lk.stream;
-    const size_t rows = (size_t)sh.rows;
-    check_free(33.0 * (double)rows + 12.0 * (double)n_groups + 16.0 * (double)sh.max_len + 8.0 * TRAIN_SIGMOID_BINS + 65536.0,
-               std::to_string(rows) + " rows in " + std::to_string(n_groups) + " groups");
-    GradTables tab;
-    tab.make(cfg, sh.max_len, st);
-    DevBuf d_scores, d_labels, d_off, d_wave, d_group, d_g, d_h;
-    d_scores.reserve(rows * 8), d_off.reserve((size_t)(n_groups + 1) * 8), d_g.reserve(rows * 8), d_h.reserve(rows * 8);
-    MRK_HIP(hipMemcpyAsync(d_scores.p, scores, rows * 8, hipMemcpyHostToDevice, st));
-    MRK_HIP(hipMemcpyAsync(d_off.p, group_offsets, (size_t)(n_groups + 1) * 8, hipMemcpyHostToDevice, st));
-    upload(d_labels, y, st);
-    if (!by_size.wave.empty()) upload(d_wave, by_size.wave, st);
-    if (!by_size.group.empty()) upload(d_group, by_size.group, st);
-    GradDev gd = tab.dev(cfg);
-    gd.scores = d_scores.as<double>(), gd.labels = d_labels.as<uint8_t>(), gd.offsets = d_off.as<long long>(), gd.g = d_g.as<double>(), gd.h = d_h.as<double>();
-    launch_gradients(ctx, st, gd, by_size, d_wave, d_group);
-    MRK_HIP(hipMemcpyAsync(out_g, d_g.p, rows * 8, hipMemcpyDeviceToHost, st));
-    MRK_HIP(hipMemcpyAsync(out_h, d_h.p, rows * 8, hipMemcpyDeviceToHost, st));
-    MRK_HIP(hipStreamSynchronize(st));
-    drain_profile_events(ctx);
+    need(t_plus != nullptr, "train: null factors");
+    gradients_call(ctx, config_json, scores, labels, group_offsets, n_groups, t_plus, t_minus, out_g, out_h, out_cost_plus, out_cost_minus);
   });
 }
 

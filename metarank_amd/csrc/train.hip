@@ -9,6 +9,9 @@
 //   train_grad_wave / train_grad_group   a group ordered by score (sort_key / pair_lt: the order /rank and eval.hip answer in), then
 //                                        one lane per item adds its pairs in ascending partner rank.  n <= 64: one wavefront per
 //                                        group, ranks by counting; n <= 4096: one workgroup, the LDS bitonic.  44.1 KiB of LDS.
+//   train_grad_wave_bias / _group_bias   the same with step 3b (position_bias): every pair divided by t_plus[pos(hi)] *
+//                                        t_minus[pos(lo)], and the pair costs cp, cm per item.  Then train_pos_sum: cp / cm quantised
+//                                        and added per position, int64 LDS histograms flushed with global integer atomics
 //   train_max, train_quantise            max |g|, max h as integer maxima of bit patterns; q = (int64) rint(ldexp(v, e))
 //   train_hist                           per (TRAIN_HIST_ROWS rows, TRAIN_HIST_FEATS columns): LDS histograms of the rows of one
 //                                        leaf, non-empty bins flushed with global integer atomics
@@ -31,6 +34,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "bitonic_device.hpp"
 #include "runtime.hpp"
@@ -63,14 +67,42 @@ __device__ double inv_max_dcg(const int *s_cnt, const double *__restrict__ lg, i
   return acc == 0.0 ? 0.0 : __ddiv_rn(1.0, acc);
 }
 
-// the pairs of the item at rank r: s_key / s_lab in rank order; (g, h) of that item
-__device__ __forceinline__ void item_pairs(const GradDev &d, const u64 *s_key, const unsigned char *s_lab, int n, int k, int r, double inv, double &g_out,
-                                           double &h_out) {
+// Step 3b: where a kernel finds the position of a rank and the factors.  NoBias is the plain kernels': item_pairs<NoBias> holds no line
+// of step 3b, a template parameter and not a branch in the pair loop.
+struct NoBias {};
+// the wavefront kernel: the clamped position of every rank and every factor the group can reach sit in the wavefront's LDS slice
+struct WaveBias {
+  const unsigned char *s_pos;
+  const double *s_tp, *s_tm, *cost;
+  __device__ __forceinline__ int pos(int q) const { return s_pos[q]; }
+  __device__ __forceinline__ double tp(int i) const { return s_tp[i]; }
+  __device__ __forceinline__ double tm(int i) const { return s_tm[i]; }
+};
+// the workgroup kernel: s_idx already holds the rank's place in the list; the first TRAIN_BIAS_LDS_POS factors per side are in LDS
+struct GroupBias {
+  const unsigned short *s_idx;
+  const double *s_tp, *s_tm, *g_tp, *g_tm, *cost;
+  int last;   // positions - 1
+  __device__ __forceinline__ int pos(int q) const { return min((int)s_idx[q], last); }
+  __device__ __forceinline__ double tp(int i) const { return i < TRAIN_BIAS_LDS_POS ? s_tp[i] : g_tp[i]; }
+  __device__ __forceinline__ double tm(int i) const { return i < TRAIN_BIAS_LDS_POS ? s_tm[i] : g_tm[i]; }
+};
+
+// the pairs of the item at rank r: s_key / s_lab in rank order; (g, h) of that item and, under step 3b, its (cp, cm)
+template <typename B>
+__device__ __forceinline__ void item_pairs(const GradDev &d, const B &b, const u64 *s_key, const unsigned char *s_lab, int n, int k, int r, double inv,
+                                           double &g_out, double &h_out, double &cp_out, double &cm_out) {
+  constexpr bool BIAS = !std::is_same<B, NoBias>::value;
   const int y = s_lab[r];
   const double sr = -asc_value(s_key[r]);   // sort_key(s) = asc_key(-s)
   const double gr = gain_of(y), ilr = d.invlg[r];
   const int qn = r < k ? n : k;             // a pair counts when min(r, q) < k
   double g = 0.0, h = 0.0;
+  double cp = 0.0, cm = 0.0, own_p = 1.0, own_m = 1.0;   // 3b: this item's t_plus and t_minus, read once
+  if constexpr (BIAS) {
+    const int pr = b.pos(r);
+    own_p = b.tp(pr), own_m = b.tm(pr);
+  }
   for (int q = 0; q < qn; ++q) {
     const int yq = s_lab[q];
     if (yq == y) continue;                  // (q == r too)
@@ -80,16 +112,33 @@ __device__ __forceinline__ void item_pairs(const GradDev &d, const u64 *s_key, c
     const double delta = hi ? __dsub_rn(sr, sq) : __dsub_rn(sq, sr);
     const double t = fmin(fmax(__dmul_rn(__dsub_rn(delta, d.lo), d.f), 0.0), (double)(TRAIN_SIGMOID_BINS - 1));
     const double rho = d.sigmoid[(int)t];
+    // 3b: both table reads go out with one index before anything waits for either; the partner's factor comes from LDS meanwhile
+    double L = 0.0, x = 1.0;
+    if constexpr (BIAS) {
+      L = b.cost[(int)t];
+      const int pq = b.pos(q);
+      x = hi ? b.tm(pq) : b.tp(pq);   // the partner's side of c = t_plus[pos(hi)] * t_minus[pos(lo)]
+    }
     const double dg = hi ? __dsub_rn(gr, gq) : __dsub_rn(gq, gr);
     const double dl = fabs(hi ? __dsub_rn(ilr, ilq) : __dsub_rn(ilq, ilr));
     const double w = __dmul_rn(__dmul_rn(dg, dl), inv);
-    const double lam = __dmul_rn(__dmul_rn(d.sigma, rho), w);
-    const double eta = __dmul_rn(__dmul_rn(__dmul_rn(d.sigma2, rho), __dsub_rn(1.0, rho)), w);
+    double lam = __dmul_rn(__dmul_rn(d.sigma, rho), w);
+    double eta = __dmul_rn(__dmul_rn(__dmul_rn(d.sigma2, rho), __dsub_rn(1.0, rho)), w);
+    if constexpr (BIAS) {   // three divisions that do not depend on each other: their refinement steps interleave
+      const double c = __dmul_rn(hi ? own_p : own_m, x);
+      lam = __ddiv_rn(lam, c);
+      eta = __ddiv_rn(eta, c);
+      const double share = __ddiv_rn(__dmul_rn(L, w), x);   // cost / t_minus[j] for the clicked side, cost / t_plus[i] for the other
+      cp = hi ? __dadd_rn(cp, share) : cp;
+      cm = hi ? cm : __dadd_rn(cm, share);
+    }
     g = hi ? __dsub_rn(g, lam) : __dadd_rn(g, lam);
     h = __dadd_rn(h, eta);
   }
   g_out = g;
   h_out = h;
+  cp_out = cp;
+  cm_out = cm;
 }
 
 __global__ void __launch_bounds__(TG_WAVES * 64)
@@ -122,8 +171,8 @@ train_grad_wave_kernel(GradDev d, const int *__restrict__ groups, int count) {
   if (lane == 0) s_inv[wave] = inv_max_dcg(s_cnt[wave], d.lg, k);
   wave_lds_sync();
   if (mine) {
-    double gg, hh;
-    item_pairs(d, s_key[wave], s_lab[wave], n, k, rank, s_inv[wave], gg, hh);
+    double gg, hh, cp, cm;
+    item_pairs(d, NoBias{}, s_key[wave], s_lab[wave], n, k, rank, s_inv[wave], gg, hh, cp, cm);
     d.g[base + lane] = gg;
     d.h[base + lane] = hh;
   }
@@ -161,10 +210,154 @@ train_grad_group_kernel(GradDev d, const int *__restrict__ groups) {
   __syncthreads();
   const double inv = s_inv;
   for (int r = tid; r < n; r += T) {
-    double gg, hh;
-    item_pairs(d, s_key, s_lab, n, k, r, inv, gg, hh);
+    double gg, hh, cp, cm;
+    item_pairs(d, NoBias{}, s_key, s_lab, n, k, r, inv, gg, hh, cp, cm);
     d.g[base + s_idx[r]] = gg;
     d.h[base + s_idx[r]] = hh;
+  }
+}
+
+// Step 3b's variants of the two kernels above: the same steps, item_pairs under WaveBias / GroupBias, and 3b's staging.  They are kernels
+// of their own and not one templated body behind both pairs: a body behind a function call makes the plain kernels load their arguments
+// in one piece and changes their machine code.
+// One wavefront per group of <= 64 rows: the lane index before ranking is the item's place in the list; it goes to LDS beside the key
+// and the label of its rank, with the min(positions, n) factors per side the group can reach.
+__global__ void __launch_bounds__(TG_WAVES * 64)
+train_grad_wave_bias_kernel(GradDev d, BiasDev b, const int *__restrict__ groups, int count) {
+  __shared__ u64 s_tmp[TG_WAVES][64], s_key[TG_WAVES][64];
+  __shared__ unsigned char s_lab[TG_WAVES][64], s_pos[TG_WAVES][64];
+  __shared__ int s_cnt[TG_WAVES][32];
+  __shared__ double s_inv[TG_WAVES], s_tp[TG_WAVES][64], s_tm[TG_WAVES][64];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int gi = blockIdx.x * TG_WAVES + wave;
+  if (gi >= count) return;   // (a whole wavefront, as above)
+  const int g = groups[gi];
+  const long long base = d.offsets[g];
+  const int n = (int)(d.offsets[g + 1] - base);   // 1 ... 64
+  const bool mine = lane < n;
+  const int k = min(d.truncation, n);
+  const u64 key = mine ? sort_key(d.scores[base + lane]) : ~0ull;
+  const int y = mine ? d.labels[base + lane] : 0;
+  s_tmp[wave][lane] = key;
+  if (lane < 32) s_cnt[wave][lane] = 0;
+  if (lane < min(b.positions, n)) {
+    s_tp[wave][lane] = b.t_plus[lane];
+    s_tm[wave][lane] = b.t_minus[lane];
+  }
+  wave_lds_sync();
+  int rank = 0;
+  if (mine) {
+    for (int j = 0; j < n; ++j) rank += pair_lt(s_tmp[wave][j], j, key, lane) ? 1 : 0;
+    s_key[wave][rank] = key;
+    s_lab[wave][rank] = (unsigned char)y;
+    s_pos[wave][rank] = (unsigned char)min(lane, b.positions - 1);
+    atomicAdd(&s_cnt[wave][y], 1);
+  }
+  wave_lds_sync();
+  if (lane == 0) s_inv[wave] = inv_max_dcg(s_cnt[wave], d.lg, k);
+  wave_lds_sync();
+  if (mine) {
+    double gg, hh, cp, cm;
+    item_pairs(d, WaveBias{s_pos[wave], s_tp[wave], s_tm[wave], b.cost}, s_key[wave], s_lab[wave], n, k, rank, s_inv[wave], gg, hh, cp, cm);
+    d.g[base + lane] = gg;
+    d.h[base + lane] = hh;
+    b.cp[base + lane] = cp;
+    b.cm[base + lane] = cm;
+  }
+}
+
+// One workgroup per group; blockDim.x: a multiple of 64 up to 1024.  s_idx is the position before clamping; the first min(positions, n,
+// TRAIN_BIAS_LDS_POS) factors per side are staged in LDS (60.1 KiB with them), a longer list reads the rest from memory.
+__global__ void __launch_bounds__(1024)
+train_grad_group_bias_kernel(GradDev d, BiasDev b, const int *__restrict__ groups) {
+  __shared__ u64 s_key[TRAIN_MAX_GROUP];
+  __shared__ unsigned short s_idx[TRAIN_MAX_GROUP];
+  __shared__ unsigned char s_lab[TRAIN_MAX_GROUP];
+  __shared__ int s_cnt[32];
+  __shared__ double s_inv, s_tp[TRAIN_BIAS_LDS_POS], s_tm[TRAIN_BIAS_LDS_POS];
+  const int tid = threadIdx.x, T = blockDim.x;
+  const int g = groups[blockIdx.x];
+  const long long base = d.offsets[g];
+  const int n = (int)(d.offsets[g + 1] - base);   // 1 ... TRAIN_MAX_GROUP
+  const int k = min(d.truncation, n);
+  int p2 = 1;
+  while (p2 < n) p2 <<= 1;
+  for (int i = tid; i < p2; i += T) {
+    s_key[i] = i < n ? sort_key(d.scores[base + i]) : ~0ull;   // (a pad sorts behind every score)
+    s_idx[i] = (unsigned short)(i < n ? i : 0xffff);
+  }
+  if (tid < 32) s_cnt[tid] = 0;
+  for (int i = tid; i < min(min(b.positions, n), TRAIN_BIAS_LDS_POS); i += T) {
+    s_tp[i] = b.t_plus[i];
+    s_tm[i] = b.t_minus[i];
+  }
+  __syncthreads();
+  lds_bitonic<true>(s_key, s_idx, p2);
+  for (int r = tid; r < n; r += T) {
+    const int y = d.labels[base + s_idx[r]];
+    s_lab[r] = (unsigned char)y;
+    atomicAdd(&s_cnt[y], 1);
+  }
+  __syncthreads();
+  if (tid == 0) s_inv = inv_max_dcg(s_cnt, d.lg, k);
+  __syncthreads();
+  const double inv = s_inv;
+  const GroupBias gb{s_idx, s_tp, s_tm, b.t_plus, b.t_minus, b.cost, b.positions - 1};
+  for (int r = tid; r < n; r += T) {
+    double gg, hh, cp, cm;
+    item_pairs(d, gb, s_key, s_lab, n, k, r, inv, gg, hh, cp, cm);
+    d.g[base + s_idx[r]] = gg;
+    d.h[base + s_idx[r]] = hh;
+    b.cp[base + s_idx[r]] = cp;
+    b.cm[base + s_idx[r]] = cm;
+  }
+}
+
+// Step 3b's position sums.  A workgroup takes `run` consecutive groups, a wavefront one group at a time, a lane the rows 64 apart: the
+// row's place in its list is then the loop counter.  cp / cm are quantised on the way (train_quantise's rounding) into an int64 LDS
+// histogram per side; a lane keeps what falls on the clamped last position in registers - with few positions that is most rows, and
+// they would queue on one LDS address - and adds it once.  Non-zero bins are flushed with global integer atomics (train_hist's pattern).
+__global__ void __launch_bounds__(TRAIN_ROW_THREADS)
+train_pos_sum_kernel(const double *__restrict__ cp, const double *__restrict__ cm, const long long *__restrict__ offsets, long long n_groups, int run,
+                     int positions, int e_p, int e_m, u64 *__restrict__ Qp, u64 *__restrict__ Qm) {
+  __shared__ u64 s_p[TRAIN_POS_LDS_BINS], s_m[TRAIN_POS_LDS_BINS];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int last = positions - 1, lds_n = min(positions, TRAIN_POS_LDS_BINS);
+  for (int i = tid; i < lds_n; i += TRAIN_ROW_THREADS) {
+    s_p[i] = 0;
+    s_m[i] = 0;
+  }
+  __syncthreads();
+  const long long g0 = (long long)blockIdx.x * run, g1 = min(g0 + run, n_groups);
+  u64 tail_p = 0, tail_m = 0;   // (two's complement: the unsigned sum is the signed one)
+  for (long long g = g0 + wave; g < g1; g += TRAIN_ROW_THREADS / 64) {
+    const long long base = offsets[g];
+    const int n = (int)(offsets[g + 1] - base);
+    for (int i = lane; i < n; i += 64) {
+      const u64 qp = (u64)(long long)rint(ldexp(cp[base + i], e_p)), qm = (u64)(long long)rint(ldexp(cm[base + i], e_m));
+      if (i >= last) {
+        tail_p += qp;
+        tail_m += qm;
+      } else if (i < TRAIN_POS_LDS_BINS) {
+        if (qp) atomicAdd(&s_p[i], qp);
+        if (qm) atomicAdd(&s_m[i], qm);
+      } else {
+        if (qp) atomicAdd(&Qp[i], qp);
+        if (qm) atomicAdd(&Qm[i], qm);
+      }
+    }
+  }
+  if (last < TRAIN_POS_LDS_BINS) {
+    if (tail_p) atomicAdd(&s_p[last], tail_p);
+    if (tail_m) atomicAdd(&s_m[last], tail_m);
+  } else {
+    if (tail_p) atomicAdd(&Qp[last], tail_p);
+    if (tail_m) atomicAdd(&Qm[last], tail_m);
+  }
+  __syncthreads();
+  for (int i = tid; i < lds_n; i += TRAIN_ROW_THREADS) {
+    if (s_p[i]) atomicAdd(&Qp[i], s_p[i]);
+    if (s_m[i]) atomicAdd(&Qm[i], s_m[i]);
   }
 }
 
@@ -713,6 +906,32 @@ void train_launch_grad_group(mrk_ctx *ctx, hipStream_t s, const GradDev &d, cons
   ScopedKernelTimer timer(ctx, "train_grad");
   const int threads = max_len <= 512 ? 256 : max_len <= 2048 ? 512 : 1024;   // (eval_launch_group's sizes: a sort stage over 128 pairs keeps 256 lanes busy)
   hipLaunchKernelGGL(train_grad_group_kernel, dim3((unsigned)count), dim3(threads), 0, s, d, groups);
+  MRK_HIP(hipGetLastError());
+}
+
+void train_launch_grad_wave_bias(mrk_ctx *ctx, hipStream_t s, const GradDev &d, const BiasDev &b, const int *groups, int count) {
+  if (count <= 0) return;
+  ScopedKernelTimer timer(ctx, "train_grad_bias");
+  hipLaunchKernelGGL(train_grad_wave_bias_kernel, dim3((unsigned)((count + TG_WAVES - 1) / TG_WAVES)), dim3(TG_WAVES * 64), 0, s, d, b, groups, count);
+  MRK_HIP(hipGetLastError());
+}
+
+void train_launch_grad_group_bias(mrk_ctx *ctx, hipStream_t s, const GradDev &d, const BiasDev &b, const int *groups, int count, int max_len) {
+  if (count <= 0) return;
+  ScopedKernelTimer timer(ctx, "train_grad_bias");
+  const int threads = max_len <= 512 ? 256 : max_len <= 2048 ? 512 : 1024;   // (train_launch_grad_group's sizes)
+  hipLaunchKernelGGL(train_grad_group_bias_kernel, dim3((unsigned)count), dim3(threads), 0, s, d, b, groups);
+  MRK_HIP(hipGetLastError());
+}
+
+void train_launch_pos_sum(mrk_ctx *ctx, hipStream_t s, const double *cp, const double *cm, const long long *offsets, long long n_groups, int positions, int e_p,
+                          int e_m, long long *Qp, long long *Qm) {
+  if (n_groups <= 0) return;
+  ScopedKernelTimer timer(ctx, "train_pos_sum");
+  // at most 1024 workgroups flush into the same bins; a small set still spreads over several (a run is at least 4 groups, one per wavefront)
+  const int run = (int)std::max<long long>(4, (n_groups + 1023) / 1024);
+  hipLaunchKernelGGL(train_pos_sum_kernel, dim3((unsigned)((n_groups + run - 1) / run)), dim3(TRAIN_ROW_THREADS), 0, s, cp, cm, offsets, n_groups, run, positions, e_p,
+                     e_m, (u64 *)Qp, (u64 *)Qm);
   MRK_HIP(hipGetLastError());
 }
 

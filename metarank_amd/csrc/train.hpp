@@ -31,6 +31,24 @@ void train_launch_grad_wave(mrk_ctx *ctx, hipStream_t s, const GradDev &d, const
 // groups[0, count): groups of <= TRAIN_MAX_GROUP rows (the longest has max_len), one workgroup each
 void train_launch_grad_group(mrk_ctx *ctx, hipStream_t s, const GradDev &d, const int *groups, int count, int max_len);
 
+// step 3b, the position-bias correction: what its variants of the two LambdaRank kernels read and write beside GradDev (which keeps
+// its layout: the plain kernels' arguments and machine code stay what they were)
+struct BiasDev {
+  const double *t_plus, *t_minus;   // `positions` factors per side
+  const double *cost;               // L: MRK_TRAIN_SIGMOID_BINS entries under the sigmoid table's index (made on the host)
+  int positions;
+  double *cp, *cm;                  // per row: the item's cost as the clicked / the unclicked side of its pairs
+};
+constexpr int TRAIN_BIAS_LDS_POS = 1024;   // factors per side the workgroup kernel stages in LDS (16 KiB); further positions are read from memory
+void train_launch_grad_wave_bias(mrk_ctx *ctx, hipStream_t s, const GradDev &d, const BiasDev &b, const int *groups, int count);
+void train_launch_grad_group_bias(mrk_ctx *ctx, hipStream_t s, const GradDev &d, const BiasDev &b, const int *groups, int count, int max_len);
+
+// Qp[pos] += (int64) rint(ldexp(cp[row], e_p)), Qm likewise with cm and e_m, pos = min(row - offsets[group], positions - 1), over all
+// rows; the caller zeroes Qp and Qm (`positions` int64 each).  Integer atomics only: the sums do not depend on any order
+constexpr int TRAIN_POS_LDS_BINS = 1024;   // bins per side of a workgroup's LDS histogram (16 KiB); further positions go to memory directly
+void train_launch_pos_sum(mrk_ctx *ctx, hipStream_t s, const double *cp, const double *cm, const long long *offsets, long long n_groups, int positions, int e_p,
+                          int e_m, long long *Qp, long long *Qm);
+
 // a piece of the row-major matrix into the column-major byte matrix: bins[c * rows + row0 + i] = the number of bounds of column c
 // below x[i * cols + c], or 255 for NaN.  bounds of column c: bounds[bound_off[c] ... bound_off[c + 1]).
 // cat_idx (null: no categorical column): per column (offset, length) of its id -> bin table in cat_tables, offset < 0 for a numeric

@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <cstring>
 #include <memory>
+#include <utility>
 
 #include "eval.hpp"
 
@@ -33,7 +34,72 @@ void launch_gradients(mrk_ctx *ctx, hipStream_t st, const GradDev &d, const Eval
   train_launch_grad_group(ctx, st, d, d_group.as<int>(), (int)by_size.group.size(), (int)by_size.group_max_len);
 }
 
+void BiasTables::make(const TrainConfig &cfg, int64_t rows, hipStream_t st) {
+  positions = cfg.bias_positions;
+  const std::vector<double> cost = train_cost_table(cfg.sigma);
+  upload(d_cost, cost, st);
+  d_factors.reserve(2 * (size_t)positions * 8), h_factors.reserve(2 * (size_t)positions * 8);
+  d_cp.reserve((size_t)rows * 8), d_cm.reserve((size_t)rows * 8);
+  std::fill(t_plus(), t_plus() + 2 * (size_t)positions, 1.0);
+  MRK_HIP(hipStreamSynchronize(st));   // cost is a local
+}
+
+BiasDev BiasTables::dev(hipStream_t st) {
+  MRK_HIP(hipMemcpyAsync(d_factors.p, h_factors.p, 2 * (size_t)positions * 8, hipMemcpyHostToDevice, st));
+  return BiasDev{d_factors.as<double>(), d_factors.as<double>() + positions, d_cost.as<double>(), positions, d_cp.as<double>(), d_cm.as<double>()};
+}
+
+void launch_bias_gradients(mrk_ctx *ctx, hipStream_t st, const GradDev &d, const BiasDev &b, const EvalBins &by_size, const DevBuf &d_wave, const DevBuf &d_group) {
+  train_launch_grad_wave_bias(ctx, st, d, b, d_wave.as<int>(), (int)by_size.wave.size());
+  train_launch_grad_group_bias(ctx, st, d, b, d_group.as<int>(), (int)by_size.group.size(), (int)by_size.group_max_len);
+}
+
 namespace {
+
+// Step 3 (and 3b) of one iteration for both growers: the gradients, their maxima and - with position_bias - the position sums and the
+// update of the factors.  The stream is waited for once for the maxima and, with position_bias, once more for the 2 x positions sums.
+struct GradientStep {
+  bool bias = false;
+  double norm = 1.0;
+  BiasTables tab;
+  DevBuf d_maxes, d_sums;
+  PinBuf h_maxes, h_sums;   // max |g|, max h (, max cp, max cm) as the bit patterns of f64 >= 0; Qp then Qm
+
+  void reserve(const TrainConfig &cfg, int64_t rows, hipStream_t st) {
+    bias = cfg.position_bias, norm = cfg.bias_norm;
+    d_maxes.reserve(32), h_maxes.reserve(32);
+    if (!bias) return;
+    tab.make(cfg, rows, st);
+    d_sums.reserve(2 * (size_t)tab.positions * 8), h_sums.reserve(2 * (size_t)tab.positions * 8);
+  }
+
+  // -> (max |g|, max h) of the gradients now in gd.g / gd.h
+  std::pair<double, double> take(mrk_ctx *ctx, hipStream_t st, const GradDev &gd, const TrainSet &tr) {
+    const size_t n_max = bias ? 4 : 2;
+    if (bias) launch_bias_gradients(ctx, st, gd, tab.dev(st), tr.by_size, tr.d_wave, tr.d_group);
+    else launch_gradients(ctx, st, gd, tr.by_size, tr.d_wave, tr.d_group);
+    MRK_HIP(hipMemsetAsync(d_maxes.p, 0, n_max * 8, st));
+    train_launch_max(ctx, st, gd.g, gd.h, tr.rows, d_maxes.as<unsigned long long>());
+    if (bias) train_launch_max(ctx, st, tab.d_cp.as<double>(), tab.d_cm.as<double>(), tr.rows, d_maxes.as<unsigned long long>() + 2);
+    MRK_HIP(hipMemcpyAsync(h_maxes.p, d_maxes.p, n_max * 8, hipMemcpyDeviceToHost, st));
+    MRK_HIP(hipStreamSynchronize(st));
+    const double *m = h_maxes.as<double>();
+    if (bias) {
+      const int P = tab.positions, e_p = train_exponent(m[2], tr.rows), e_m = train_exponent(m[3], tr.rows);
+      MRK_HIP(hipMemsetAsync(d_sums.p, 0, 2 * (size_t)P * 8, st));
+      train_launch_pos_sum(ctx, st, tab.d_cp.as<double>(), tab.d_cm.as<double>(), tr.d_off.as<long long>(), tr.n_groups, P, e_p, e_m, d_sums.as<long long>(),
+                           d_sums.as<long long>() + P);
+      {
+        ScopedKernelTimer timer(ctx, "train_bias_readback");
+        MRK_HIP(hipMemcpyAsync(h_sums.p, d_sums.p, 2 * (size_t)P * 8, hipMemcpyDeviceToHost, st));
+      }
+      MRK_HIP(hipStreamSynchronize(st));   // (the factors have left the host too: they may change now)
+      train_bias_update(h_sums.as<int64_t>(), e_p, norm, tab.t_plus(), P);
+      train_bias_update(h_sums.as<int64_t>() + P, e_m, norm, tab.t_minus(), P);
+    }
+    return {m[0], m[1]};
+  }
+};
 
 // backend "lightgbm": the buffers of the leaf-wise grower, one tree's growth (steps 5, 5c, 6) and the forest.  One histogram per leaf
 // and subset column is resident: a split builds the smaller child's, the scan turns the parent's into the sibling's.
@@ -329,12 +395,11 @@ void train_fit(TrainState &t) {
   LevelGrower level;
   if (xgb) level.reserve(t);
   else leaf.reserve(t);
-  DevBuf d_g, d_h, d_qg, d_qh, d_leaf_of, d_maxes;
+  DevBuf d_g, d_h, d_qg, d_qh, d_leaf_of;
   d_g.reserve((size_t)rows * 8), d_h.reserve((size_t)rows * 8), d_qg.reserve((size_t)rows * 8), d_qh.reserve((size_t)rows * 8);
-  d_leaf_of.reserve((size_t)rows * 2), d_maxes.reserve(16);
-  PinBuf h_back;   // the two maxima of an iteration: train_launch_max leaves the bit patterns of two f64 >= 0
-  h_back.reserve(16);
-  const double *h_maxes = h_back.as<double>();
+  d_leaf_of.reserve((size_t)rows * 2);
+  GradientStep step;   // the loop owns step 3b's factors: both growers see gradients alone
+  step.reserve(cfg, rows, st);
   ValidMetric metric;
   if (va.given) metric.make(cfg, va, tab.d_lg.as<double>(), st);
   GradDev gd = tab.dev(cfg);
@@ -350,12 +415,7 @@ void train_fit(TrainState &t) {
       lk.reset();
       lk.reset(new DeviceLock(ctx));
     }
-    launch_gradients(ctx, st, gd, tr.by_size, tr.d_wave, tr.d_group);
-    MRK_HIP(hipMemsetAsync(d_maxes.p, 0, 16, st));
-    train_launch_max(ctx, st, gd.g, gd.h, rows, d_maxes.as<unsigned long long>());
-    MRK_HIP(hipMemcpyAsync(h_back.p, d_maxes.p, 16, hipMemcpyDeviceToHost, st));
-    MRK_HIP(hipStreamSynchronize(st));
-    const double gmax = h_maxes[0], hmax = h_maxes[1];
+    const auto [gmax, hmax] = step.take(ctx, st, gd, tr);
     if (gmax == 0.0) break;
     ScanParams sp{train_exponent(gmax, rows), train_exponent(hmax, rows), cfg.min_data_in_leaf, cfg.min_sum_hessian, cfg.lambda_l2,
                   cfg.max_cat_to_onehot, cfg.max_cat_threshold, std::max(cfg.min_data_in_leaf, cfg.min_data_per_group), cfg.cat_smooth, cfg.lambda_l2 + cfg.cat_l2, 0.0};
@@ -384,6 +444,7 @@ void train_fit(TrainState &t) {
   }
   MRK_HIP(hipStreamSynchronize(st));
   drain_profile_events(ctx);
+  if (step.bias) t.t_plus.assign(step.tab.t_plus(), step.tab.t_plus() + step.tab.positions), t.t_minus.assign(step.tab.t_minus(), step.tab.t_minus() + step.tab.positions);
   t.model = xgb ? level.model(t) : leaf.model(t);
 }
 

@@ -43,6 +43,7 @@ struct TrainState {
   std::vector<double> history;
   int best_iteration = 0;
   std::string model;
+  std::vector<double> t_plus, t_minus;   // step 3b: the factors after the last iteration run (empty without position_bias)
 };
 
 // the tables of step 3 on the device
@@ -53,6 +54,19 @@ struct GradTables {
   GradDev dev(const TrainConfig &cfg) const;
 };
 void launch_gradients(mrk_ctx *ctx, hipStream_t st, const GradDev &d, const EvalBins &by_size, const DevBuf &d_wave, const DevBuf &d_group);
+
+// step 3b on the device: the cost table, the factors (t_plus then t_minus, `positions` each; the host's copy is pinned and is the one
+// that is updated) and the two costs per row
+struct BiasTables {
+  int positions = 0;
+  DevBuf d_cost, d_factors, d_cp, d_cm;
+  PinBuf h_factors;
+  void make(const TrainConfig &cfg, int64_t rows, hipStream_t st);   // every factor 1.0
+  double *t_plus() { return h_factors.as<double>(); }
+  double *t_minus() { return h_factors.as<double>() + positions; }
+  BiasDev dev(hipStream_t st);   // sends the factors; they must not change until the stream has been waited for
+};
+void launch_bias_gradients(mrk_ctx *ctx, hipStream_t st, const GradDev &d, const BiasDev &b, const EvalBins &by_size, const DevBuf &d_wave, const DevBuf &d_group);
 
 // The caller holds nothing of t.ctx: its lock is taken here, per iteration.  t.set[0] is given.
 void train_fit(TrainState &t);

@@ -23,7 +23,7 @@ TrainConfig train_parse_config(const char *text, size_t len) {
   TrainConfig c;
   static const char *known[] = {"iterations", "learningRate", "ndcgCutoff", "maxDepth", "seed", "numLeaves", "sampling", "debias", "max_bin", "truncation",
                                 "sigma", "min_data_in_leaf", "min_sum_hessian", "lambda_l2", "early_stopping", "categorical", "max_cat_to_onehot",
-                                "max_cat_threshold", "cat_smooth", "cat_l2", "min_data_per_group", "backend", "lambda", "gamma", "min_child_weight"};
+                                "max_cat_threshold", "cat_smooth", "cat_l2", "min_data_per_group", "backend", "lambda", "gamma", "min_child_weight", "position_bias"};
   for (auto &kv : root.obj) {
     bool ok = false;
     for (const char *k : known) ok = ok || kv.first == k;
@@ -103,6 +103,24 @@ TrainConfig train_parse_config(const char *text, size_t len) {
         c.categorical.push_back((int32_t)d);
       }
     }
+  if (const json::Value *v = root.find("position_bias"))
+    if (!v->is_null()) {   // step 3b: an object switches the correction on, its keys are optional
+      if (!v->is_object()) bad("'position_bias' is not an object");
+      c.position_bias = true;
+      for (auto &kv : v->obj) {
+        const json::Value &e = kv.second;
+        if (kv.first != "positions" && kv.first != "norm") bad("unknown key '" + kv.first + "' in position_bias");
+        if (e.is_null()) continue;
+        if (!e.is_number()) bad("position_bias: '" + kv.first + "' is not a number");
+        const double d = e.as_double();
+        if (kv.first == "norm") c.bias_norm = d;
+        else if (!(d == std::floor(d)) || d < -2147483648.0 || d > 2147483647.0) bad("position_bias: 'positions' is not an Int");
+        else c.bias_positions = (int)d;
+      }
+      if (c.bias_positions < 1 || c.bias_positions > TRAIN_MAX_GROUP)
+        range("position_bias: positions = " + std::to_string(c.bias_positions) + " (1 ... " + std::to_string(TRAIN_MAX_GROUP) + ")");
+      if (!(c.bias_norm >= 0.0) || !std::isfinite(c.bias_norm)) range("position_bias: norm is not a finite number >= 0");
+    }
   auto at_least = [&](const char *key, int v, int lo) {
     if (v < lo) range(std::string(key) + " = " + std::to_string(v) + " (at least " + std::to_string(lo) + ")");
   };
@@ -132,7 +150,7 @@ TrainConfig train_parse_config(const char *text, size_t len) {
     range("maxDepth = " + std::to_string(c.max_depth) + " (at most " + std::to_string(TRAIN_XGB_MAX_DEPTH) + " with the xgboost backend)");
   if (c.backend == TRAIN_BACKEND_XGBOOST && !c.categorical.empty())
     throw StatusError(MRK_ERR_UNSUPPORTED, "train config: categorical columns are not built for the xgboost backend (set-membership splits in XGBoost JSON)");
-  if (c.debias) throw StatusError(MRK_ERR_UNSUPPORTED, "train config: debias (position-bias correction) is not built");
+  if (c.debias) throw StatusError(MRK_ERR_UNSUPPORTED, "train config: debias carries neither the number of positions nor the norm: use position_bias");
   if (c.num_leaves > TRAIN_MAX_LEAVES)
     throw StatusError(MRK_ERR_UNSUPPORTED, "train config: numLeaves = " + std::to_string(c.num_leaves) + " (limit " + std::to_string(TRAIN_MAX_LEAVES) + ")");
   return c;
@@ -301,6 +319,27 @@ SigmoidTable train_sigmoid_table(double sigma) {
   return s;
 }
 
+std::vector<double> train_cost_table(double sigma) {
+  const SigmoidTable s = train_sigmoid_table(sigma);   // (its lo and f: one index serves both tables)
+  std::vector<double> L(TRAIN_SIGMOID_BINS);
+  for (int t = 0; t < TRAIN_SIGMOID_BINS; ++t) {
+    const double x = s.lo + (double)t / s.f;
+    const double z = -sigma * x;
+    L[(size_t)t] = std::log1p(std::exp(z));
+  }
+  return L;
+}
+
+void train_bias_update(const int64_t *Q, int e, double norm, double *t, int positions) {
+  const double s0 = std::ldexp((double)Q[0], -e);
+  if (s0 == 0.0) return;
+  const double p = 1.0 / (norm + 1.0);
+  for (int i = 0; i < positions; ++i) {
+    const double si = std::ldexp((double)Q[i], -e);
+    if (si > 0.0) t[i] = std::pow(si / s0, p);
+  }
+}
+
 int train_exponent(double vmax, int64_t rows) {
   if (vmax == 0.0) return 0;
   int bitlen = 0;
@@ -318,7 +357,8 @@ double train_fit_bytes(const TrainConfig &cfg, int which, int64_t rows_, int col
   const double n_sub = xgb ? (double)cols : (double)train_feature_subset(cols, cfg.sampling, 0, 0).size();
   const double column_cells = 256.0 * 20.0;   // of one (slot, column) histogram: G and H i64, C u32
   const double bins = rows * cols;
-  const double per_row = 51.0 * rows;         // g, h, q_g, q_h, score and best score (8 each), leaf / node (2), label (1)
+  // g, h, q_g, q_h, score and best score (8 each), leaf / node (2), label (1); step 3b: the two costs of a training row
+  const double per_row = (which == 0 && cfg.position_bias ? 67.0 : 51.0) * rows;
   const double group_lists = 12.0 * groups;   // the offsets (8) and the by-size lists (4)
   const double row_slots = xgb ? 2.0 * rows : 0.0;   // xgboost, a u16 per row: hist_slot (training), the row's node (validation)
   if (which == 1) return bins + per_row + group_lists + row_slots + (9.0 * rows + 8.0 * groups);   // gains (8), rel (1); the metric per group

@@ -52,13 +52,18 @@ struct TrainConfig {
   double lambda = 1.0;                // the three keys of the xgboost backend alone
   double gamma = 0.0;
   double min_child_weight = 1.0;
+  bool position_bias = false;         // "position_bias": an object (step 3b) - its keys: positions, norm
+  int bias_positions = 32;
+  double bias_norm = 1.0;
 };
 constexpr int TRAIN_BACKEND_LIGHTGBM = 0, TRAIN_BACKEND_XGBOOST = 1;
 constexpr int TRAIN_XGB_MAX_DEPTH = 15;     // a node id is a u16: a complete tree of depth 15 has 65535 nodes
 // malformed JSON, a value of the wrong type or an unknown key: MRK_ERR_PARSE; a value out of range: MRK_ERR_INVALID_ARG;
 // debias = true or numLeaves > TRAIN_MAX_LEAVES: MRK_ERR_UNSUPPORTED.  backend "xgboost": numLeaves, min_data_in_leaf,
 // min_sum_hessian, lambda_l2 and the categorical keys but `categorical` are MRK_ERR_INVALID_ARG naming the key, a non-empty
-// `categorical` is MRK_ERR_UNSUPPORTED; backend "lightgbm": lambda, gamma and min_child_weight are MRK_ERR_INVALID_ARG
+// `categorical` is MRK_ERR_UNSUPPORTED; backend "lightgbm": lambda, gamma and min_child_weight are MRK_ERR_INVALID_ARG.
+// position_bias (either backend): not an object, a key inside other than positions / norm or one that is no number: MRK_ERR_PARSE;
+// positions outside 1 ... TRAIN_MAX_GROUP, norm negative or not finite: MRK_ERR_INVALID_ARG
 TrainConfig train_parse_config(const char *json, size_t len);
 
 // the upper bounds of the bins of one column but the last (bin(x) = the number of bounds < x), from col[i * stride], i < n.
@@ -153,6 +158,12 @@ struct SigmoidTable {
   std::vector<double> t;
 };
 SigmoidTable train_sigmoid_table(double sigma);
+
+// step 3b: L[t] = log1p(exp(-sigma * (lo + t / f))), the pair cost under the sigmoid table's index
+std::vector<double> train_cost_table(double sigma);
+// step 3b's update of one side: S[i] = ldexp((double) Q[i], -e); S[0] == 0 keeps every factor, else t[i] = pow(S[i] / S[0],
+// 1 / (norm + 1)) where S[i] > 0
+void train_bias_update(const int64_t *Q, int e, double norm, double *t, int positions);
 
 // 61 - bitlen(rows) - E(vmax), frexp(vmax) = m * 2^E; 0 for vmax == 0
 int train_exponent(double vmax, int64_t rows);

@@ -62,8 +62,9 @@ def categorical_columns(columns) -> list:
     return [int(first) for _, first, _, kind in columns if kind == "category"]
 
 
-def lambdarank_gradients(scores, labels, group_offsets, ctx: Context | None = None, **config):
-    """mrk_train_gradients: (g, h) of the lambdarank objective, one f64 per row"""
+def lambdarank_gradients(scores, labels, group_offsets, ctx: Context | None = None, t_plus=None, t_minus=None, **config):
+    """mrk_train_gradients: (g, h) of the lambdarank objective, one f64 per row.  With t_plus and t_minus - `positions` factors each, and
+    position_bias in the config - mrk_train_bias_gradients: (g, h, cost_plus, cost_minus) of include/mrk.h's step 3b"""
     s, y, off = _f64(scores), _f64(labels), _offsets(group_offsets)
     n_groups = len(off) - 1
     rows = int(off[-1]) if n_groups >= 1 else 0
@@ -71,8 +72,17 @@ def lambdarank_gradients(scores, labels, group_offsets, ctx: Context | None = No
         raise N.MrkError(N.ERR_INVALID_ARG, f"{s.size} scores / {y.size} labels, the offsets end at {rows}")
     ctx = ctx or default_context()
     g, h = np.zeros(max(rows, 1), dtype=np.float64), np.zeros(max(rows, 1), dtype=np.float64)
-    N.check(N.lib().mrk_train_gradients(ctx.handle, _config(config), s.ctypes.data, y.ctypes.data, off.ctypes.data, n_groups, g.ctypes.data, h.ctypes.data))
-    return g[:rows], h[:rows]
+    if t_plus is None and t_minus is None:
+        N.check(N.lib().mrk_train_gradients(ctx.handle, _config(config), s.ctypes.data, y.ctypes.data, off.ctypes.data, n_groups, g.ctypes.data, h.ctypes.data))
+        return g[:rows], h[:rows]
+    tp, tm = _f64(t_plus), _f64(t_minus)
+    positions = (config.get("position_bias") or {}).get("positions") or 32
+    if tp.size != positions or tm.size != positions:
+        raise N.MrkError(N.ERR_INVALID_ARG, f"{tp.size} / {tm.size} factors for {positions} positions")
+    cp, cm = np.zeros_like(g), np.zeros_like(g)
+    N.check(N.lib().mrk_train_bias_gradients(ctx.handle, _config(config), s.ctypes.data, y.ctypes.data, off.ctypes.data, n_groups, tp.ctypes.data, tm.ctypes.data,
+                                             g.ctypes.data, h.ctypes.data, cp.ctypes.data, cm.ctypes.data))
+    return g[:rows], h[:rows], cp[:rows], cm[:rows]
 
 
 class Trainer:
@@ -154,6 +164,14 @@ class Trainer:
         N.check(N.lib().mrk_train_scores(self._h, which, out.ctypes.data))
         return out
 
+    def position_bias(self):
+        """mrk_train_position_bias: (t_plus, t_minus) after the last iteration run; two empty arrays without position_bias"""
+        n = C.c_int(0)
+        N.check(N.lib().mrk_train_position_bias(self._h, None, None, 0, C.byref(n)))
+        tp, tm = np.zeros(n.value, dtype=np.float64), np.zeros(n.value, dtype=np.float64)
+        N.check(N.lib().mrk_train_position_bias(self._h, tp.ctypes.data, tm.ctypes.data, n.value, C.byref(n)))
+        return tp, tm
+
     def close(self):
         if self._h:
             N.lib().mrk_train_free(self._h)
@@ -172,6 +190,8 @@ def fit_lambdamart(X, labels, group_offsets, valid=None, ctx: Context | None = N
     the best iteration).  A fit that ends without a tree has no forest to load: the booster is None.
     Categorical columns (set-membership splits, include/mrk.h steps 2c and 5c) are named by the config:
     fit_lambdamart(X, y, off, categorical=categorical_columns(ranker.values_columns())).
+    position_bias={"positions": 32, "norm": 1.0} (either backend; what the reference's `debias` stands for): include/mrk.h step 3b;
+    history["position_bias"] is (t_plus, t_minus) after the last iteration.
     backend="xgboost": the level-wise fit; the model is XGBoost's JSON and the booster is loaded as an XGBoost one; scores are the f32
     sums the model predicts (from its base_score 0.5), widened."""
     ctx = ctx or default_context()
@@ -185,6 +205,7 @@ def fit_lambdamart(X, labels, group_offsets, valid=None, ctx: Context | None = N
         hist["model"] = t.model()
         hist["scores"] = t.scores(0)
         hist["valid_scores"] = t.scores(1) if valid is not None else None
+        hist["position_bias"] = t.position_bias()
     finally:
         t.close()
     booster = HipBooster(hist["model"], XGBOOST if config.get("backend") == "xgboost" else LIGHTGBM, ctx) if hist["best_iteration"] > 0 else None

@@ -47,7 +47,19 @@ from workloads import synth  # noqa: E402
 
 TIMERS = ("train_bin", "train_grad", "train_hist", "train_scan", "train_apply", "train_eval")
 LEVEL_TIMERS = ("train_bin", "train_grad", "train_level_hist", "train_level_scan", "train_level_split", "train_level_readback", "train_apply", "train_eval")
+BIAS_TIMERS = ("train_grad_bias", "train_pos_sum", "train_bias_readback")   # step 3b: the biased LambdaRank kernels, the position sums, their copy back
 COLS = 24
+
+
+def bias_launches(parts, trees):
+    """step 3b's launches against their derived bounds: per iteration that took gradients (the trees, and one more when the fit ended on an
+    iteration without a tree) the biased kernels in place of the plain ones, two maxima launches and one quantise under train_grad, ONE
+    position-sum launch and ONE read-back of the sums"""
+    n = trees + 1
+    got = {"train_grad_bias": int(parts["train_grad_bias"][1]), "train_grad": int(parts["train_grad"][1]), "train_pos_sum": int(parts["train_pos_sum"][1]),
+           "train_bias_readback": int(parts["train_bias_readback"][1])}
+    bound = {"train_grad_bias": 2 * n, "train_grad": 3 * n, "train_pos_sum": n, "train_bias_readback": n}
+    return {"counts": got, "bounds": bound, "within_bound": all(got[k] <= bound[k] for k in got) and got["train_pos_sum"] >= trees}
 
 
 def main():
@@ -64,15 +76,18 @@ def main():
     ap.add_argument("--backend", choices=("lightgbm", "xgboost"), default="lightgbm")
     ap.add_argument("--depth", type=int, default=8, help="maxDepth of the xgboost backend")
     ap.add_argument("--device-set", action="store_true", help="mrk_train_set from the host against append + seal from device memory, three runs each")
+    ap.add_argument("--position-bias", action="store_true", help='fit with "position_bias": {} (step 3b) and count its launches')
     a = ap.parse_args()
     xgb = a.backend == "xgboost"
-    timers = LEVEL_TIMERS if xgb else TIMERS
+    timers = (LEVEL_TIMERS if xgb else TIMERS) + (BIAS_TIMERS if a.position_bias else ())
     ctx = M.Context(0)
     X, y, off = synth.synthetic_ranking_rows(a.groups, a.min_items, a.max_items, COLS, seed=0)
     rows = int(off[-1])
     cfg = {"iterations": a.iterations, "numLeaves": a.leaves, "early_stopping": a.iterations}
     if xgb:
         cfg = {"backend": "xgboost", "iterations": a.iterations, "maxDepth": a.depth, "early_stopping": a.iterations}
+    if a.position_bias:
+        cfg["position_bias"] = {}
     cats = list(range(COLS - a.categorical, COLS))
     if cats:                                                              # (without the option the config has no `categorical` key)
         X[:, cats] = np.clip(np.rint((X[:, cats] + 3.0) * (49.0 / 6.0)), 0.0, 49.0)
@@ -101,6 +116,11 @@ def main():
         out[name + "_ms"], out[name + "_launches"] = parts[name]
     out["trees"], out["best_iteration"] = hist["iterations_run"], hist["best_iteration"]
     out["model_sha256"] = hashlib.sha256(model).hexdigest()               # (two builds that fit the same forest print the same digest)
+    if a.position_bias:
+        out["position_bias_launches"] = bias_launches(parts, hist["iterations_run"])
+        if not out["position_bias_launches"]["within_bound"]:
+            print(json.dumps(out))
+            sys.exit(1)
     if xgb:
         return finish_xgboost(a, ctx, out, parts, hist, model, X, y, off, rows)
     out["categorical_nodes"] = sum(int(b.split("num_cat=")[1].split("\n")[0]) for b in model.decode().split("Tree=")[1:])
@@ -121,6 +141,8 @@ def main():
         out["restatement_us_per_row_iteration"] = out["restatement_one_iteration_ms"] * 1e3 / r
         out["device_us_per_row_iteration"] = out["fit_call_ms"] * 1e3 / (rows * max(hist["iterations_run"], 1))
     try:
+        if a.ref_groups == 0:                                             # (no host comparisons asked for)
+            raise ImportError
         from sklearn.ensemble import HistGradientBoostingRegressor
     except ImportError:
         out["sklearn"] = None
