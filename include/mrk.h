@@ -983,15 +983,30 @@ int mrk_model_eval(mrk_model *model, const int *metrics, const int *cutoffs, int
  * [false; true is MRK_ERR_UNSUPPORTED], and max_bin [255], truncation [30], sigma [1.0], early_stopping [20], lambda [1.0, >= 0], gamma
  * [0.0, >= 0], min_child_weight [1.0, >= 0].  numLeaves, min_data_in_leaf, min_sum_hessian, lambda_l2, max_cat_to_onehot,
  * max_cat_threshold, cat_smooth, cat_l2 and min_data_per_group are MRK_ERR_INVALID_ARG naming the key (a setting that would do
- * nothing); so are lambda, gamma and min_child_weight under the default backend.  A non-empty `categorical` is MRK_ERR_UNSUPPORTED
- * (set-membership splits in XGBoost JSON are not built; an undeclared category column splits as a number).  Steps 1, 3, 4 and 8 are the
- * ones above; step 3 and step 8's metric read the widened f32 scores of 6x.
+ * nothing); so are lambda, gamma, min_child_weight and feature_types under the default backend.  A non-empty `categorical` is
+ * MRK_ERR_UNSUPPORTED: this backend names its categorical columns in XGBoost's own spelling, feature_types [absent: all "q"] - an
+ * array of strings, one per column, "q" numeric or "c" categorical (steps 2cx, 5cx: the reference runs treeMethod "exact" because
+ * "hist/approx do not work with categories", LambdaMARTRanker.scala:176-188).  Another string is MRK_ERR_INVALID_ARG, a value that is
+ * no array or an entry that is no string MRK_ERR_PARSE; a length other than `cols` is MRK_ERR_INVALID_ARG naming both numbers, at
+ * mrk_train_set and at mrk_train_append_device.  Absent, null or all "q": the bytes of a fit without the key.  libxgboost's two caps
+ * are fixed at its defaults, max_cat_to_onehot = 4 and max_cat_threshold = 64 (XGBoostConfig exposes neither).  Steps 1, 3, 4 and 8
+ * are the ones above; step 3 and step 8's metric read the widened f32 scores of 6x.
  *  2x bins     per column, on the host: the cells are narrowed to f32 (round to nearest even; -0.0f counts as +0.0f); a finite f64 that
  *              narrows to +-inf is MRK_ERR_INVALID_ARG naming column and row (predictMat refuses such a cell), in either set.  v = the
  *              sorted non-NaN narrowed cells; the positions are step 2's.  The bound between neighbours a < b is b ITSELF, an f32:
  *              XGBoost's cut convention is x < cut.  bin(x) = the number of bounds <= (float) x; NaN is bin 255.  Candidate c sends left
  *              exactly the cells with (float) x < bound[c] - the emitted model's own test - so every possible cell, seen in training or
  *              not, is routed the same way by the trainer and by the model.  mrk_train_bins returns these bounds widened to f64.
+ *  2cx bins of a "c" column (tests/train_xgb_cat_reference.py restates 2cx, 5cx and their model text).  The category of a cell: v =
+ *              (float) x, as the model sees it; NaN is bin 255; v < 0, v >= 2^24 or (int) v > 32764 is bin 254, "other" - exactly the
+ *              cells the model's test sends LEFT whatever the node's set is (invalid, or beyond every bitset the trainer can write);
+ *              else the category is (int) v.  Nothing is refused for being large or negative; an infinite f64 cell keeps step 1's
+ *              refusal.  Counted over the training set, the min(distinct, max_bin - 2) most frequent categories are kept, ties to the
+ *              lower id; they take bins 0 ... K - 1 in ascending id, every other category is bin 254; the validation set uses the
+ *              training set's table.  Bin 254 ALWAYS goes left, bin 255 follows the node's learned default_left: trainer and emitted
+ *              model route every possible cell alike.  On the device through step 2c's dense id -> bin byte table; for a matrix
+ *              handed over with mrk_train_append_device, step 2d's id-count kernel applies the same validity rule to the narrowed
+ *              cell: both ways of handing over a matrix give the same bin bytes.
  *  7x rows     row r is in tree t's sample when sampling >= 1 or (z >> 11) * 2^-53 < sampling, z = the first splitmix64 output from
  *              the state ((uint64) (uint32) seed << 32 | t) ^ (r * 0xD6E8FEB86659FD93).  Computed where it is used; no list exists.  A
  *              row outside the sample adds nothing to any histogram (neither its count nor q_g, q_h); it is still routed and scored.
@@ -1005,6 +1020,15 @@ int mrk_model_eval(mrk_model *model, const int *metrics, const int *cutoffs, int
  *              bin, NaN right.  EVERY open node with an admitted candidate splits - nodes do not compete -, the others are leaves.
  *              weight = -G / (H + lambda) (H + lambda == 0: MRK_ERR_INVALID_ARG at mrk_train_fit); a leaf's value is (float) (weight *
  *              learningRate).  A tree whose root cannot split ends training and is not emitted.
+ *  5cx "c" column at an open node: from the same (sum q_g, sum q_h, count) histogram over the sampled rows.  A candidate is a set R of kept
+ *              bins that goes RIGHT; left is every kept bin outside R, bin 254 and - when tried there - NaN.  NaN is tried on either
+ *              side when the node has sampled NaN rows, else it goes right and default_left is false (step 5).  K < 4: one category
+ *              against the rest, R = {b} for b < K.  Else a kept bin is eligible when its sampled count is > 0 and H_b + lambda > 0; its
+ *              key is G_b / (H_b + lambda); the m eligible bins are ordered ascending by (key, bin); the candidates are the first i
+ *              bins (direction 0) and the last i bins (direction 1), i = 1 ... min(64, m), each judged on its own.  Gain and admission
+ *              are step 5x's (lambda, min_child_weight, a sampled row on both sides, gain > gamma), the gain's sum taken left + right.
+ *              Best within the column: the highest gain, then direction 0, then the smaller i (one against the rest: the lower bin),
+ *              then NaN right.  Across columns unchanged: the highest gain, then the lowest column.
  *  6x scores   f32, as the model predicts them: s = 0.5f (the base_score), then s = s + leaf in f32, in tree order.  Training rows -
  *              the unsampled ones too - and validation rows take the leaf their bins route them to.  mrk_train_scores returns the
  *              widened value, equal to mrk_model_predict_f64 of the emitted model bit for bit; without a tree every score is 0.5.
@@ -1012,7 +1036,11 @@ int mrk_model_eval(mrk_model *model, const int *metrics, const int *cutoffs, int
  *              empty categorical arrays), no whitespace.  Per tree split_conditions = the bound or the leaf value, base_weights =
  *              (float) weight, loss_changes = (float) gain (0 for a leaf: Booster.weights() works), sum_hessian = (float) H, parents
  *              2147483647 for the root, default_left = NaN goes left, split_type all 0.  Every f32 is printed as %.9g of its widened
- *              value.  mrk_model_load(MRK_BACKEND_XGBOOST) reads it. */
+ *              value.  mrk_model_load(MRK_BACKEND_XGBOOST) reads it.  A categorical node (5cx) has split_type 1 and split_conditions 0;
+ *              `categories` holds the ascending category IDS of R for the tree's categorical nodes in ascending node id, beside
+ *              categories_nodes (the node ids), categories_segments (where each node's ids start) and categories_sizes; the learner's
+ *              feature_types carries the configured list when it has a "c".  A tree without such a node is written byte for byte as
+ *              before. */
 #define MRK_TRAIN_SIGMOID_BINS 65536
 typedef struct mrk_trainer mrk_trainer;
 

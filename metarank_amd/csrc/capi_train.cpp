@@ -85,6 +85,12 @@ void check_free(double want, const std::string &what) {
 
 // ---- mrk_train_set, one function per step ---------------------------------------------------------------------------------------
 
+// feature_types (backend "xgboost") has one entry per column
+void check_feature_types(const mrk_trainer *t, int cols) {
+  if (t->cfg.feature_types >= 0 && t->cfg.feature_types != cols)
+    throw StatusError(MRK_ERR_INVALID_ARG, "train: feature_types has " + std::to_string(t->cfg.feature_types) + " entries, the matrix has " + std::to_string(cols) + " columns");
+}
+
 EvalShape check_set_args(const mrk_trainer *t, int which, const double *x, int64_t rows, int cols, const int64_t *off, int64_t n_groups) {
   need(which == 0 || which == 1, "train: which is neither 0 (train) nor 1 (validation)");
   need(!t->fitted, "train: the trainer has been fitted");
@@ -92,6 +98,7 @@ EvalShape check_set_args(const mrk_trainer *t, int which, const double *x, int64
   need(rows >= 1 && cols >= 1, "train: rows / cols < 1");
   if (cols > TRAIN_MAX_COLS) throw StatusError(MRK_ERR_UNSUPPORTED, "train: " + std::to_string(cols) + " columns (limit " + std::to_string(TRAIN_MAX_COLS) + ")");
   if (rows >= (int64_t(1) << 31)) throw StatusError(MRK_ERR_UNSUPPORTED, "train: " + std::to_string(rows) + " rows (limit 2^31 - 1)");
+  check_feature_types(t, cols);
   for (int32_t c : t->cfg.categorical)
     if (c >= cols) throw StatusError(MRK_ERR_INVALID_ARG, "train: categorical holds the index " + std::to_string(c) + ", the matrix has " + std::to_string(cols) + " columns");
   const EvalShape sh = eval_check_groups(off, n_groups);
@@ -102,14 +109,15 @@ EvalShape check_set_args(const mrk_trainer *t, int which, const double *x, int64
 }
 
 // What the backend decides about bins, here and nowhere else in a set: xgboost (step 2x) narrows every cell to f32, finds its bounds
-// with train_bin_bounds_f32 and bins with train_launch_bin_f32; lightgbm (steps 2, 2c) finds f64 bounds or, for a categorical column,
-// the kept ids, and bins with train_launch_bin.
+// with train_bin_bounds_f32 - for a "c" column (step 2cx) the kept ids with train_xgb_kept_categories - and bins with
+// train_launch_bin_f32; lightgbm (steps 2, 2c) finds f64 bounds or, for a categorical column, the kept ids, and bins with train_launch_bin.
 bool bins_in_f32(const mrk_trainer *t) { return t->cfg.backend == TRAIN_BACKEND_XGBOOST; }
 
 // the training set's column c on the host: its bounds, or its kept category ids
 void find_bins(mrk_trainer *t, const double *x, int64_t rows, int c) {
   const size_t k = (size_t)c;
-  if (bins_in_f32(t)) t->bounds[k] = train_bin_bounds_f32(x + c, rows, t->cols, t->cfg.max_bin, c);
+  if (bins_in_f32(t) && t->is_cat[k]) t->kept[k] = train_xgb_kept_categories(x + c, rows, t->cols, t->cfg.max_bin, c);
+  else if (bins_in_f32(t)) t->bounds[k] = train_bin_bounds_f32(x + c, rows, t->cols, t->cfg.max_bin, c);
   else if (t->is_cat[k]) t->kept[k] = train_kept_categories(x + c, rows, t->cols, t->cfg.max_bin, c, &t->infos[k]);
   else t->bounds[k] = train_bin_bounds(x + c, rows, t->cols, t->cfg.max_bin, &t->infos[k]);
 }
@@ -118,16 +126,22 @@ void find_bins(mrk_trainer *t, const double *x, int64_t rows, int c) {
 void check_other_cells(const mrk_trainer *t, const double *x, int64_t rows, int cols) {
   for (int64_t i = 0; i < rows * cols; ++i)
     if (std::isinf(x[i])) throw StatusError(MRK_ERR_INVALID_ARG, "train: cell " + std::to_string(i) + " of the validation matrix is infinite");
-  for (int32_t c : t->cfg.categorical) train_check_categories(x + c, rows, cols, c);
-  if (bins_in_f32(t)) for_columns(cols, [&](int c) { train_check_f32_cells(x + c, rows, cols, c); });
+  if (!bins_in_f32(t))
+    for (int32_t c : t->cfg.categorical) train_check_categories(x + c, rows, cols, c);
+  else   // (step 2cx refuses nothing: a cell of a "c" column that is not finite as an f32 is "other")
+    for_columns(cols, [&](int c) {
+      if (!t->is_cat[(size_t)c]) train_check_f32_cells(x + c, rows, cols, c);
+    });
 }
 
 // a piece of the caller's matrix, already in d_x, into the set's column-major bins
 void launch_bin_piece(const mrk_trainer *t, hipStream_t st, const double *d_x, const EvalPiece &pc, TrainSet &s) {
-  if (bins_in_f32(t)) train_launch_bin_f32(t->ctx, st, d_x, pc.rows, t->cols, t->d_bounds.as<double>(), t->d_bound_off.as<int>(), s.d_bins.as<uint8_t>(), s.rows, pc.row0);
+  const int *cat_idx = t->any_cat ? t->d_cat_idx.as<int>() : nullptr;
+  const uint8_t *cat_tables = t->any_cat ? t->d_cat_tables.as<uint8_t>() : nullptr;
+  if (bins_in_f32(t))
+    train_launch_bin_f32(t->ctx, st, d_x, pc.rows, t->cols, t->d_bounds.as<double>(), t->d_bound_off.as<int>(), cat_idx, cat_tables, s.d_bins.as<uint8_t>(), s.rows, pc.row0);
   else
-    train_launch_bin(t->ctx, st, d_x, pc.rows, t->cols, t->d_bounds.as<double>(), t->d_bound_off.as<int>(), t->any_cat ? t->d_cat_idx.as<int>() : nullptr,
-                     t->any_cat ? t->d_cat_tables.as<uint8_t>() : nullptr, s.d_bins.as<uint8_t>(), s.rows, pc.row0);
+    train_launch_bin(t->ctx, st, d_x, pc.rows, t->cols, t->d_bounds.as<double>(), t->d_bound_off.as<int>(), cat_idx, cat_tables, s.d_bins.as<uint8_t>(), s.rows, pc.row0);
 }
 
 // a new training set: the trainer's columns start over, the validation set goes
@@ -164,7 +178,7 @@ void upload_tables(mrk_trainer *t, hipStream_t st) {
   std::vector<int> cat_idx((size_t)cols * 2, -1);   // per column (offset, length) of its id -> bin table
   std::vector<uint8_t> tables;
   for (int32_t c : t->cfg.categorical) {
-    const std::vector<uint8_t> table = train_category_table(t->kept[(size_t)c]);
+    const std::vector<uint8_t> table = train_category_table(t->kept[(size_t)c], bins_in_f32(t) ? TRAIN_OTHER_BIN : TRAIN_NAN_BIN);
     cat_idx[(size_t)c * 2] = (int)tables.size(), cat_idx[(size_t)c * 2 + 1] = (int)table.size();
     tables.insert(tables.end(), table.begin(), table.end());
   }
@@ -248,6 +262,7 @@ void append_locked(mrk_trainer *t, int which, const double *d_x, int64_t rows, i
   need(!t->fitted, "train: the trainer has been fitted");
   need(d_x != nullptr, "train: null matrix");
   need(rows >= 1 && cols >= 1, "train: rows / cols < 1");
+  check_feature_types(t, cols);
   Staging &sg = t->stage[which];
   need(sg.pieces.empty() || cols == sg.cols, "train: an appended piece has other columns than the pieces before it");
   if (cols > TRAIN_MAX_COLS) throw StatusError(MRK_ERR_UNSUPPORTED, "train: " + std::to_string(cols) + " columns (limit " + std::to_string(TRAIN_MAX_COLS) + ")");
@@ -322,7 +337,7 @@ void bin_columns_on_device(mrk_trainer *t, const Staging &sg, hipStream_t st) {
   }
   for (int c = 0; c < cols; ++c) {
     if (t->is_cat[(size_t)c]) {
-      for (const StagePiece &pc : sg.pieces) train_launch_category_counts(t->ctx, st, pc.column(c), pc.rows, d_counts.as<unsigned>() + (size_t)cat_slot[(size_t)c] * ids);
+      for (const StagePiece &pc : sg.pieces) train_launch_category_counts(t->ctx, st, pc.column(c), pc.rows, bins_in_f32(t), d_counts.as<unsigned>() + (size_t)cat_slot[(size_t)c] * ids);
       continue;
     }
     for (const StagePiece &pc : sg.pieces) train_launch_keys(t->ctx, st, pc.column(c), pc.rows, bins_in_f32(t), d_keys.as<unsigned long long>() + pc.row0);
@@ -337,7 +352,7 @@ void bin_columns_on_device(mrk_trainer *t, const Staging &sg, hipStream_t st) {
     const size_t k = (size_t)c;
     if (t->is_cat[k]) {
       const unsigned *h = counts.data() + (size_t)cat_slot[k] * ids;
-      t->kept[k] = train_kept_from_counts(std::vector<int64_t>(h, h + ids), t->cfg.max_bin, &t->infos[k]);
+      t->kept[k] = train_kept_from_counts(std::vector<int64_t>(h, h + ids), bins_in_f32(t) ? t->cfg.max_bin - 1 : t->cfg.max_bin, &t->infos[k]);   // (2cx keeps max_bin - 2)
       continue;
     }
     const TrainColumnCuts &cc = cuts[k];

@@ -22,14 +22,17 @@
 //   train_apply                          score += leaf value (training rows by leaf_of, validation rows by walking the tree)
 // train_bin (once per fit) turns the f64 matrix into column-major bytes (a categorical column through its id -> bin table, step 2c).
 // backend "xgboost" (steps 2x, 5x, 6x, 7x) grows LEVEL-wise with the same gradients, quantisation and scan body:
-//   train_bin_f32                        the cell narrowed to f32, bin = the number of f32 bounds <= it
+//   train_bin_f32                        the cell narrowed to f32, bin = the number of f32 bounds <= it; a "c" column (step 2cx)
+//                                        through its id -> bin byte table, "other" 254, NaN 255
 //   train_level_begin                    per tree: node_of = 0, hist_slot = 0 for a sampled row, 0xFFFF for the others
 //   train_level_hist                     one launch per level, per (row tile, column, chunk of built nodes): LDS histograms of the rows
 //                                        whose hist_slot lies in the chunk, non-empty bins flushed with global integer atomics
 //   train_level_scan (+ train_pick)      per (node of the level, column): sibling = parent - built child, then scan_column under step
-//                                        5x's admission rule; per node the best column; the level's records are read back once
+//                                        5x's admission rule - a "c" column (step 5cx): scan_cat_column_xgb, a counting rank and one
+//                                        scan over its bins -; per node the best column; the level's records are read back once
 //   train_level_split                    one row pass per level: the level's records in LDS, a row moves to its child and gets the
-//                                        child's built slot (0xFFFF when the child is not built or the row is outside the sample)
+//                                        child's built slot (0xFFFF when the child is not built or the row is outside the sample);
+//                                        <true>: a level with a categorical node, its masks over bins in LDS beside the records
 //   train_level_apply, train_level_base  score = (double) ((float) score + leaf[node_of]); score = 0.5, the base_score
 #include <hip/hip_runtime.h>
 
@@ -648,6 +651,118 @@ __device__ void scan_cat_column(long long g, long long h, long long c, int nb, i
   __syncthreads();   // (everything in LDS is written again by the next call)
 }
 
+// Step 5cx (backend "xgboost"): lane b holds bin b of one (node, "c" column) - b < nb a kept category, 254 "other", which ALWAYS goes
+// left, 255 NaN, which is tried on either side.  A candidate is a set R of kept bins that goes RIGHT (the model's set-membership test:
+// member -> right).  nb < TRAIN_XGB_MAX_CAT_TO_ONEHOT: lane b judges R = {b}.  Else the bins with a sampled row and H + lambda > 0,
+// ordered ascending by (G / (H + lambda), bin): lane i judges the first i + 1 of them (direction 0) and the last i + 1 (direction 1),
+// i < min(TRAIN_XGB_MAX_CAT_THRESHOLD, m), each on its own, under both NaN placements - four candidates a lane.
+// Data movement, scan_cat_column's: the order is a counting rank - every lane compares its key with all nb keys, read as LDS
+// broadcasts (one address per instruction: no bank conflict) behind ONE barrier; the bins that are not eligible are parked behind the
+// eligible ones, and lanes 254 / 255 hand their sums over through s_nan and carry zeros, so ONE block_scan yields every prefix, the
+// eligible total (position m - 1) and the kept bins' total (position 255).  The node's total is that plus "other" plus NaN; "other"
+// is on the left of every candidate because left = total - right.  The winner's R leaves as four ballots over BINS.
+// Ties: the highest gain, then direction 0, then the smaller i (one-vs-rest: the lower bin), then NaN right.
+__device__ void scan_cat_column_xgb(long long g, long long h, long long c, int nb, int col, const ScanParams &p, LeafRec *out, long long (*s_buf)[3][256],
+                                    double *s_gain, int *s_code, long long *s_nan, u64 *s_mask) {
+  const int tid = threadIdx.x;
+  const bool onehot = nb < TRAIN_XGB_MAX_CAT_TO_ONEHOT;
+  if (tid >= TRAIN_OTHER_BIN) {   // (nb <= 253: neither lane holds a kept bin)
+    long long *to = s_nan + (tid == TRAIN_NAN_BIN ? 0 : 3);
+    to[0] = g, to[1] = h, to[2] = c;
+    g = 0, h = 0, c = 0;
+  }
+  const long long own_g = g, own_h = h, own_c = c;   // bin b's sums: one-vs-rest's right side
+  bool elig = false;
+  int pos = tid, m = 0;   // pos: where this lane's bin stands in the order; m: eligible bins
+  if (!onehot) {
+    const double den = __dadd_rn(real_of(h, p.e_h), p.l2);
+    elig = tid < nb && c > 0 && den > 0.0;
+    const double key = elig ? __ddiv_rn(real_of(g, p.e_g), den) : 0.0;   // finite, never -0.0
+    s_gain[tid] = key;
+    s_code[tid] = elig ? 1 : 0;
+    __syncthreads();
+    int below = 0, before = 0;   // eligible bins that stand before this one in the order; eligible bins of a lower index
+    for (int j = 0; j < nb; ++j) {
+      const double kj = s_gain[j];
+      const int ej = s_code[j];
+      m += ej;
+      before += (ej && j < tid) ? 1 : 0;
+      below += (ej && (kj < key || (kj == key && j < tid))) ? 1 : 0;
+    }
+    pos = elig ? below : m + (tid - before);   // (a permutation of 0 ... 255)
+    s_buf[0][0][pos] = g;
+    s_buf[0][1][pos] = h;
+    s_buf[0][2][pos] = c;
+    __syncthreads();
+    g = s_buf[0][0][tid];
+    h = s_buf[0][1][tid];
+    c = s_buf[0][2][tid];
+  }
+  long long pg = g, ph = h, pc = c;
+  block_scan(pg, ph, pc, s_buf);   // (its first barrier: every lane has read its position; s_nan is published)
+  s_buf[0][0][tid] = pg;
+  s_buf[0][1][tid] = ph;
+  s_buf[0][2][tid] = pc;
+  __syncthreads();
+  const long long ng = s_nan[0], nh = s_nan[1], nc = s_nan[2];
+  const long long Tg = s_buf[0][0][255] + s_nan[3] + ng, Th = s_buf[0][1][255] + s_nan[4] + nh, Tc = s_buf[0][2][255] + s_nan[5] + nc;
+  const int n_cand = onehot ? nb : min(TRAIN_XGB_MAX_CAT_THRESHOLD, m);
+  double best = 0.0;
+  int code = -1;
+  long long bl_g = 0, bl_h = 0, bl_c = 0;
+  if (tid < n_cand) {
+    const double parent = side_term(Tg, Th, p);
+    for (int dir = 0; dir <= (onehot ? 0 : 1); ++dir) {
+      long long sg, sh, sc;   // R's sums
+      if (onehot) sg = own_g, sh = own_h, sc = own_c;
+      else if (dir == 0) sg = pg, sh = ph, sc = pc;
+      else {   // the last tid + 1 of the m eligible bins: their total minus the first m - 1 - tid
+        const int k = m - 2 - tid;
+        sg = s_buf[0][0][m - 1] - (k >= 0 ? s_buf[0][0][k] : 0);
+        sh = s_buf[0][1][m - 1] - (k >= 0 ? s_buf[0][1][k] : 0);
+        sc = s_buf[0][2][m - 1] - (k >= 0 ? s_buf[0][2][k] : 0);
+      }
+      for (int nl = 0; nl <= (nc > 0 ? 1 : 0); ++nl) {   // NaN right first: it wins a tie
+        const long long rg = sg + (nl ? 0 : ng), rh = sh + (nl ? 0 : nh), rc = sc + (nl ? 0 : nc);
+        const long long lg_ = Tg - rg, lh = Th - rh, lc = Tc - rc;
+        const double HL = real_of(lh, p.e_h), HR = real_of(rh, p.e_h);
+        const double gain = __dsub_rn(__dadd_rn(side_term(lg_, lh, p), side_term(rg, rh, p)), parent);
+        const bool ok = lc >= p.min_data && rc >= p.min_data && HL >= p.min_hess && HR >= p.min_hess && gain > p.min_gain;
+        if (ok && (code < 0 || gain > best)) {   // (the earlier of a lane's four wins a tie: direction 0, then NaN right)
+          best = gain;
+          code = dir * 512 + tid * 2 + nl;
+          bl_g = lg_, bl_h = lh, bl_c = lc;
+        }
+      }
+    }
+  }
+  const int win = block_best(best, code, s_gain, s_code);   // (the lowest code of the highest gain: direction, then i, then NaN right)
+  const int wdir = win >> 9, wi = (win >> 1) & 255;
+  if (win >= 0 && tid == wi) s_nan[0] = bl_g, s_nan[1] = bl_h, s_nan[2] = bl_c;   // (every lane read s_nan before block_best's barriers)
+  // the winner's right set as a mask over BINS: lane b knows where bin b stands
+  const bool member = win >= 0 && (onehot ? tid == wi : (elig && (wdir == 0 ? pos <= wi : pos >= m - 1 - wi)));
+  const u64 wave_mask = __ballot(member);
+  if ((tid & 63) == 0) s_mask[tid >> 6] = wave_mask;
+  __syncthreads();
+  if (tid == 0) {
+    LeafRec r;
+    r.gain = win < 0 ? 0.0 : s_gain[0];
+    r.valid = win < 0 ? 0 : 1;
+    r.col = col;
+    r.bin = 0;
+    r.nan_left = win < 0 ? 0 : (win & 1);
+    r.gl = win < 0 ? 0 : s_nan[0], r.hl = win < 0 ? 0 : s_nan[1], r.cl = win < 0 ? 0 : s_nan[2];
+    r.g = Tg, r.h = Th, r.c = Tc;
+    r.is_cat = 1;
+    for (int w = 0; w < 4; ++w) {
+      r.cat_mask[2 * w] = (unsigned)s_mask[w];
+      r.cat_mask[2 * w + 1] = (unsigned)(s_mask[w] >> 32);
+    }
+    *out = r;
+  }
+  __syncthreads();   // (everything in LDS is written again by the next call)
+}
+
 // one workgroup per subset column j, lane b = bin b
 __global__ void __launch_bounds__(256)
 train_scan_kernel(HistDev hd, const int *__restrict__ subset, const int *__restrict__ nbins, const int *__restrict__ is_cat, int leaf_a, int leaf_b,
@@ -762,11 +877,15 @@ train_apply_kernel(TreeDev t, const uint16_t *__restrict__ leaf_of, const uint8_
 // step 2x: the cell narrowed to f32 (round to nearest even), its bin the number of bounds <= it
 __global__ void __launch_bounds__(TRAIN_BIN_ROWS)
 train_bin_f32_kernel(const double *__restrict__ x, int piece_rows, int cols, const double *__restrict__ bounds, const int *__restrict__ bound_off,
-                     uint8_t *__restrict__ bins, long long rows, long long row0) {
+                     const int *__restrict__ cat_idx, const uint8_t *__restrict__ cat_tables, uint8_t *__restrict__ bins, long long rows, long long row0) {
   const int i = blockIdx.x * TRAIN_BIN_ROWS + threadIdx.x;
   if (i >= piece_rows) return;
   const double *row = x + (long long)i * cols;
   for (int c = 0; c < cols; ++c) {
+    if (cat_idx && cat_idx[2 * c] >= 0) {   // (the same for every lane: a "c" column, step 2cx)
+      bins[(long long)c * rows + row0 + i] = (uint8_t)train_xgb_category_bin(row[c], cat_tables + cat_idx[2 * c], cat_idx[2 * c + 1]);
+      continue;
+    }
     const float v = __double2float_rn(row[c]);
     int a = bound_off[c], b = bound_off[c + 1];
     const int first = a;
@@ -831,11 +950,13 @@ train_level_hist_kernel(const uint8_t *__restrict__ bins, long long rows, const 
 // blockIdx: (node of the level, column); lane b = bin b.  A node that was not built gets parent - sibling first (its sibling's
 // workgroups only read the sibling's slot), then step 5's candidate loop under the caller's admission rule
 __global__ void __launch_bounds__(256)
-train_level_scan_kernel(HistDev hd, const int *__restrict__ nbins, const LevelNode *__restrict__ nodes, ScanParams p, LeafRec *__restrict__ feat_best) {
+train_level_scan_kernel(HistDev hd, const int *__restrict__ nbins, const int *__restrict__ is_cat, const LevelNode *__restrict__ nodes, ScanParams p,
+                        LeafRec *__restrict__ feat_best) {
   __shared__ long long s_buf[2][3][256];
   __shared__ double s_gain[256];
   __shared__ int s_code[256];
-  __shared__ long long s_nan[6];
+  __shared__ long long s_nan[6];   // the NaN bin's sums and the node's totals; step 5cx: the NaN bin's and the "other" bin's
+  __shared__ u64 s_mask[4];        // a categorical winner's right bins: one ballot per wavefront
   const int tid = threadIdx.x, j = blockIdx.y;
   const LevelNode nd = nodes[blockIdx.x];
   const size_t at = ((size_t)nd.slot * hd.n_sub + j) * 256 + tid;
@@ -847,14 +968,28 @@ train_level_scan_kernel(HistDev hd, const int *__restrict__ nbins, const LevelNo
   } else {
     g = hd.G[at], h = hd.H[at], c = hd.C[at];
   }
-  scan_column(g, h, c, nbins[j], j, p, &feat_best[(size_t)blockIdx.x * hd.n_sub + j], s_buf, s_gain, s_code, s_nan);
+  LeafRec *out = &feat_best[(size_t)blockIdx.x * hd.n_sub + j];
+  if (is_cat[j]) scan_cat_column_xgb(g, h, c, nbins[j], j, p, out, s_buf, s_gain, s_code, s_nan, s_mask);   // (the same for the whole workgroup)
+  else scan_column(g, h, c, nbins[j], j, p, out, s_buf, s_gain, s_code, s_nan);
 }
 
+// CAT: the level has a categorical record (the host picks the form; the numeric one has no line of step 5cx and reads no mask).  The
+// masks of the level's categorical nodes are staged in LDS beside the records when at most TRAIN_LEVEL_LDS_MASKS of them exist - a
+// row's word is then one ds_read at (index * 8 + bin / 32) - and read from memory otherwise
+template <bool CAT>
 __global__ void __launch_bounds__(TRAIN_ROW_THREADS)
 train_level_split_kernel(const uint8_t *__restrict__ bins, long long rows, uint16_t *__restrict__ node_of, uint16_t *__restrict__ hist_slot,
-                         const LevelRec *__restrict__ recs, int first, int n, double sampling, int seed, int tree) {
+                         const LevelRec *__restrict__ recs, int first, int n, double sampling, int seed, int tree, const unsigned *__restrict__ masks,
+                         int n_masks) {
   __shared__ LevelRec s_recs[TRAIN_LEVEL_LDS_RECS];
+  __shared__ unsigned s_masks[CAT ? TRAIN_LEVEL_LDS_MASKS * 8 : 1];
   const bool in_lds = n <= TRAIN_LEVEL_LDS_RECS;   // (the same for every lane)
+  const bool masks_in_lds = CAT && n_masks <= TRAIN_LEVEL_LDS_MASKS;
+  if constexpr (CAT) {
+    if (masks_in_lds)
+      for (int k = threadIdx.x; k < n_masks * 8; k += TRAIN_ROW_THREADS) s_masks[k] = masks[k];
+    if (masks_in_lds && !in_lds) __syncthreads();
+  }
   if (in_lds) {
     for (int k = threadIdx.x; k < n; k += TRAIN_ROW_THREADS) s_recs[k] = recs[k];
     __syncthreads();
@@ -868,8 +1003,16 @@ train_level_split_kernel(const uint8_t *__restrict__ bins, long long rows, uint1
     if (hist_slot) hist_slot[i] = (uint16_t)TRAIN_NO_SLOT;
     return;
   }
-  const int b = bins[(long long)r.col * rows + i];
-  const bool left = b <= r.bin || (b == TRAIN_NAN_BIN && r.nan_left);
+  bool left;
+  if (CAT && (r.col & TRAIN_LEVEL_CAT)) {
+    const int b = bins[(long long)(r.col & 0xFFFF) * rows + i];
+    const int at = (r.col >> TRAIN_LEVEL_MASK_SHIFT) * 8 + (b >> 5);   // (below n_masks * 8: the host numbered the masks)
+    const unsigned word = masks_in_lds ? s_masks[at] : masks[at];
+    left = b == TRAIN_NAN_BIN ? r.nan_left != 0 : !((word >> (b & 31)) & 1u);   // (bit 255 is never set; "other", 254, neither: left)
+  } else {
+    const int b = bins[(long long)r.col * rows + i];
+    left = b <= r.bin || (b == TRAIN_NAN_BIN && r.nan_left);
+  }
   node_of[i] = (uint16_t)(r.left + (left ? 0 : 1));
   if (hist_slot) {
     const unsigned to = left ? r.slot_l : r.slot_r;
@@ -998,12 +1141,12 @@ void train_launch_apply(mrk_ctx *ctx, hipStream_t s, const TreeDev &t, const uin
   MRK_HIP(hipGetLastError());
 }
 
-void train_launch_bin_f32(mrk_ctx *ctx, hipStream_t s, const double *x, int piece_rows, int cols, const double *bounds, const int *bound_off, uint8_t *bins,
-                          long long rows, long long row0) {
+void train_launch_bin_f32(mrk_ctx *ctx, hipStream_t s, const double *x, int piece_rows, int cols, const double *bounds, const int *bound_off, const int *cat_idx,
+                          const uint8_t *cat_tables, uint8_t *bins, long long rows, long long row0) {
   if (piece_rows <= 0 || cols <= 0) return;
   ScopedKernelTimer timer(ctx, "train_bin");
   hipLaunchKernelGGL(train_bin_f32_kernel, dim3((unsigned)((piece_rows + TRAIN_BIN_ROWS - 1) / TRAIN_BIN_ROWS)), dim3(TRAIN_BIN_ROWS), 0, s, x, piece_rows, cols, bounds,
-                     bound_off, bins, rows, row0);
+                     bound_off, cat_idx, cat_tables, bins, rows, row0);
   MRK_HIP(hipGetLastError());
 }
 
@@ -1022,20 +1165,25 @@ void train_launch_level_hist(mrk_ctx *ctx, hipStream_t s, const uint8_t *bins, l
   MRK_HIP(hipGetLastError());
 }
 
-void train_launch_level_scan(mrk_ctx *ctx, hipStream_t s, const HistDev &hd, const int *nbins, const LevelNode *nodes, int n_nodes, const ScanParams &p,
-                             LeafRec *feat_best, LeafRec *out) {
+void train_launch_level_scan(mrk_ctx *ctx, hipStream_t s, const HistDev &hd, const int *nbins, const int *is_cat, const LevelNode *nodes, int n_nodes,
+                             const ScanParams &p, LeafRec *feat_best, LeafRec *out) {
   ScopedKernelTimer timer(ctx, "train_level_scan");
-  hipLaunchKernelGGL(train_level_scan_kernel, dim3((unsigned)n_nodes, (unsigned)hd.n_sub), dim3(256), 0, s, hd, nbins, nodes, p, feat_best);
+  hipLaunchKernelGGL(train_level_scan_kernel, dim3((unsigned)n_nodes, (unsigned)hd.n_sub), dim3(256), 0, s, hd, nbins, is_cat, nodes, p, feat_best);
   MRK_HIP(hipGetLastError());
   hipLaunchKernelGGL(train_pick_kernel, dim3((unsigned)n_nodes), dim3(64), 0, s, (const LeafRec *)feat_best, hd.n_sub, out);
   MRK_HIP(hipGetLastError());
 }
 
 void train_launch_level_split(mrk_ctx *ctx, hipStream_t s, const uint8_t *bins, long long rows, uint16_t *node_of, uint16_t *hist_slot, const LevelRec *recs, int first,
-                              int n, double sampling, int seed, int tree) {
+                              int n, double sampling, int seed, int tree, const unsigned *masks, int n_masks) {
   if (rows <= 0) return;
   ScopedKernelTimer timer(ctx, "train_level_split");
-  hipLaunchKernelGGL(train_level_split_kernel, dim3(row_grid(rows)), dim3(TRAIN_ROW_THREADS), 0, s, bins, rows, node_of, hist_slot, recs, first, n, sampling, seed, tree);
+  if (n_masks > 0)
+    hipLaunchKernelGGL(train_level_split_kernel<true>, dim3(row_grid(rows)), dim3(TRAIN_ROW_THREADS), 0, s, bins, rows, node_of, hist_slot, recs, first, n, sampling, seed,
+                       tree, masks, n_masks);
+  else
+    hipLaunchKernelGGL(train_level_split_kernel<false>, dim3(row_grid(rows)), dim3(TRAIN_ROW_THREADS), 0, s, bins, rows, node_of, hist_slot, recs, first, n, sampling, seed,
+                       tree, masks, n_masks);
   MRK_HIP(hipGetLastError());
 }
 

@@ -78,7 +78,8 @@ struct LeafRec {
   int valid, col, bin, nan_left;
   long long gl, hl, cl;        // the left side's sums
   long long g, h, c;           // the leaf's
-  int is_cat;                  // a categorical candidate: cat_mask bit b <=> bin b goes left (bin, nan_left unused)
+  int is_cat;                  // a categorical candidate: cat_mask bit b <=> bin b goes left (bin, nan_left unused) - step 5c.  Step 5cx
+                               // (train_launch_level_scan): bit b <=> bin b goes RIGHT, and nan_left is the learned default_left
   unsigned cat_mask[8];
 };
 struct ScanParams {
@@ -125,11 +126,14 @@ void train_launch_apply(mrk_ctx *ctx, hipStream_t s, const TreeDev &t, const uin
 constexpr int TRAIN_LEVEL_ROWS = 8192;        // rows per workgroup of the level histogram kernel (256 lanes x 32 rows): zeroing and flushing 40 KiB of LDS is paid per tile
 constexpr int TRAIN_LEVEL_CHUNK = 8;          // built nodes per workgroup of the level histogram kernel: 8 x 256 x 20 B = 40 KiB of LDS
 constexpr int TRAIN_LEVEL_LDS_RECS = 1024;    // split records of a level the routing kernel holds in LDS (12 KiB); more are read from memory
+constexpr int TRAIN_LEVEL_LDS_MASKS = 64;     // masks of a level's categorical nodes its categorical form holds in LDS beside them (2 KiB: a workgroup
+                                              // of 256 rows stages them for 256 one-word reads); more are read from memory
 constexpr unsigned TRAIN_NO_SLOT = 0xFFFFu;
 
-// as train_launch_bin for step 2x: the cell is narrowed to f32, its bin is the number of bounds (f32 values widened) <= it
-void train_launch_bin_f32(mrk_ctx *ctx, hipStream_t s, const double *x, int piece_rows, int cols, const double *bounds, const int *bound_off, uint8_t *bins,
-                          long long rows, long long row0);
+// as train_launch_bin for step 2x: the cell is narrowed to f32, its bin is the number of bounds (f32 values widened) <= it.
+// cat_idx / cat_tables as train_launch_bin's: a cell of a "c" column gets train_xgb_category_bin under its table (step 2cx)
+void train_launch_bin_f32(mrk_ctx *ctx, hipStream_t s, const double *x, int piece_rows, int cols, const double *bounds, const int *bound_off, const int *cat_idx,
+                          const uint8_t *cat_tables, uint8_t *bins, long long rows, long long row0);
 
 // node_of = 0; hist_slot = 0 for a row of tree `tree`'s sample, TRAIN_NO_SLOT for the others
 void train_launch_level_begin(mrk_ctx *ctx, hipStream_t s, long long rows, double sampling, int seed, int tree, uint16_t *node_of, uint16_t *hist_slot);
@@ -144,20 +148,27 @@ struct LevelNode {
   int slot, parent_slot, sibling_slot;
 };
 // per (node, column) scan_column under ScanParams (step 5x: min_data 1, min_hess min_child_weight, l2 lambda, min_gain gamma), then per
-// node the best column.  feat_best: scratch of n_nodes * hd.n_sub records; out: n_nodes records
-void train_launch_level_scan(mrk_ctx *ctx, hipStream_t s, const HistDev &hd, const int *nbins, const LevelNode *nodes, int n_nodes, const ScanParams &p,
-                             LeafRec *feat_best, LeafRec *out);
+// node the best column.  feat_best: scratch of n_nodes * hd.n_sub records; out: n_nodes records.  is_cat: per column; a "c" column
+// (nbins: its kept categories) is searched by step 5cx, scan_cat_column_xgb
+void train_launch_level_scan(mrk_ctx *ctx, hipStream_t s, const HistDev &hd, const int *nbins, const int *is_cat, const LevelNode *nodes, int n_nodes,
+                             const ScanParams &p, LeafRec *feat_best, LeafRec *out);
 
 // what a row needs to leave a node of the level: col < 0 a leaf (the row stays); else bin <= `bin` (NaN when nan_left) goes to node
-// `left`, the others to left + 1; slot_l / slot_r: the children's index among the next level's built nodes or TRAIN_NO_SLOT
+// `left`, the others to left + 1; slot_l / slot_r: the children's index among the next level's built nodes or TRAIN_NO_SLOT.
+// A categorical node (step 5cx) keeps the 12 bytes: col = column | TRAIN_LEVEL_CAT | index << TRAIN_LEVEL_MASK_SHIFT, the index of its
+// 8-word mask in the level's mask table (a column is below 2^16, a level has at most 2^14 nodes); a bin whose bit is set goes RIGHT,
+// NaN (bin 255) left when nan_left, every other bin - "other", 254, among them - left
+constexpr int TRAIN_LEVEL_CAT = 1 << 16, TRAIN_LEVEL_MASK_SHIFT = 17;
 struct LevelRec {
   int col;
   uint16_t left, slot_l, slot_r;
   uint8_t bin, nan_left;
 };
-// rows whose node_of is first ... first + n - 1 move to their child.  hist_slot null: routing alone (the validation rows)
+// rows whose node_of is first ... first + n - 1 move to their child.  hist_slot null: routing alone (the validation rows).
+// n_masks > 0: the level has categorical records and `masks` holds n_masks x 8 words - the kernel's categorical form is launched; the
+// numeric form reads neither
 void train_launch_level_split(mrk_ctx *ctx, hipStream_t s, const uint8_t *bins, long long rows, uint16_t *node_of, uint16_t *hist_slot, const LevelRec *recs, int first,
-                              int n, double sampling, int seed, int tree);
+                              int n, double sampling, int seed, int tree, const unsigned *masks = nullptr, int n_masks = 0);
 
 // step 6x: scores[row] = (double) ((float) scores[row] + value[node_of[row]])
 void train_launch_level_apply(mrk_ctx *ctx, hipStream_t s, const float *value, const uint16_t *node_of, long long rows, double *scores);

@@ -7,7 +7,8 @@
 //   train_changes          m = the non-NaN cells, the number of positions p with v[p] != v[p - 1], and up to 256 of them in any
 //                          order (integer atomics; a list that is read holds ALL changes, and is ranked before use)
 //   train_cuts             one workgroup, one lane per cut: train_cut_at (train_host.hpp), the body the host test checks
-//   train_category_counts  step 2c's histogram over ids 0 ... 32764, one integer atomic per distinct id of a wavefront
+//   train_category_counts  step 2c's histogram over ids 0 ... 32764, one integer atomic per distinct id of a wavefront; <true>: step
+//                          2cx's, the category of the cell narrowed to f32 under the model's validity rule
 //   train_bin_staged       train_bin / train_bin_f32 (train.hip) reading the column-major staging
 // No float atomics, nothing that depends on the order anything runs in.
 #include <hip/hip_runtime.h>
@@ -66,8 +67,9 @@ train_check_cells_kernel(const double *__restrict__ stage, int rows, long long r
     atomicMin(&flags->infinite, at);
     return;
   }
-  if (f32 && isinf(__double2float_rn(x))) atomicMin(&flags->narrow, at);
-  if (is_cat && is_cat[c] && x >= (double)(TRAIN_MAX_CATEGORY + 1)) atomicMin(&flags->category, at);
+  const bool cat = is_cat && is_cat[c];
+  if (f32 && !cat && isinf(__double2float_rn(x))) atomicMin(&flags->narrow, at);   // (step 2cx refuses nothing: such a cell of a "c" column is "other")
+  if (!f32 && cat && x >= (double)(TRAIN_MAX_CATEGORY + 1)) atomicMin(&flags->category, at);
 }
 
 // the cell as steps 2 / 2x order it
@@ -180,11 +182,15 @@ train_cuts_kernel(const double *__restrict__ sorted, const CutCounters *__restri
   if (tid == 0) out->n_bounds = total;
 }
 
+// F32 (step 2cx): the category of the cell narrowed to f32, train_xgb_category's validity rule - what train_bin_f32 bins by
+template <bool F32>
 __global__ void __launch_bounds__(TB_THREADS)
 train_category_counts_kernel(const double *__restrict__ col, int rows, unsigned *hist) {
   const int i = blockIdx.x * TB_THREADS + threadIdx.x;
   const double x = i < rows ? col[i] : -1.0;
-  const int id = x > -1.0 && x < (double)(TRAIN_MAX_CATEGORY + 1) ? (int)x : -1;   // (NaN fails both; -1 < x < 0 truncates to category 0)
+  int id;
+  if (F32) id = train_xgb_category(x);   // (< 0: NaN or "other"; -1.0 is "other")
+  else id = x > -1.0 && x < (double)(TRAIN_MAX_CATEGORY + 1) ? (int)x : -1;   // (NaN fails both; -1 < x < 0 truncates to category 0)
   const int lane = threadIdx.x & 63;
   u64 todo = __ballot(id >= 0);
   while (todo) {   // (uniform) one atomic per distinct id of the wavefront
@@ -204,8 +210,9 @@ train_bin_staged_kernel(const double *__restrict__ stage, int piece_rows, const 
   if (i >= piece_rows) return;
   const double x = stage[(long long)c * piece_rows + i];
   uint8_t *out = bins + (long long)c * rows + row0 + i;
-  if (!F32 && cat_idx && cat_idx[2 * c] >= 0) {   // (the same for every lane: a categorical column, step 2c)
-    *out = (uint8_t)train_category_bin(x, cat_tables + cat_idx[2 * c], cat_idx[2 * c + 1]);
+  if (cat_idx && cat_idx[2 * c] >= 0) {   // (the same for every lane: a categorical column, step 2c / 2cx)
+    const uint8_t *table = cat_tables + cat_idx[2 * c];
+    *out = (uint8_t)(F32 ? train_xgb_category_bin(x, table, cat_idx[2 * c + 1]) : train_category_bin(x, table, cat_idx[2 * c + 1]));
     return;
   }
   int a = bound_off[c], b = bound_off[c + 1];
@@ -284,9 +291,11 @@ void train_launch_cuts(mrk_ctx *ctx, hipStream_t s, const unsigned long long *ke
   MRK_HIP(hipGetLastError());
 }
 
-void train_launch_category_counts(mrk_ctx *ctx, hipStream_t s, const double *col, int rows, unsigned *hist) {
+void train_launch_category_counts(mrk_ctx *ctx, hipStream_t s, const double *col, int rows, bool f32, unsigned *hist) {
   ScopedKernelTimer timer(ctx, "train_cat_counts");
-  hipLaunchKernelGGL(train_category_counts_kernel, dim3((unsigned)((rows + TB_THREADS - 1) / TB_THREADS)), dim3(TB_THREADS), 0, s, col, rows, hist);
+  const dim3 grid((unsigned)((rows + TB_THREADS - 1) / TB_THREADS));
+  if (f32) hipLaunchKernelGGL(train_category_counts_kernel<true>, grid, dim3(TB_THREADS), 0, s, col, rows, hist);
+  else hipLaunchKernelGGL(train_category_counts_kernel<false>, grid, dim3(TB_THREADS), 0, s, col, rows, hist);
   MRK_HIP(hipGetLastError());
 }
 

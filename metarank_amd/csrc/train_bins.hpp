@@ -20,10 +20,10 @@ void train_launch_stage(mrk_ctx *ctx, hipStream_t s, const double *x, int rows, 
 struct TrainCellFlags {
   unsigned long long infinite;   // +-inf
   unsigned long long narrow;     // f32: finite, +-inf as an f32
-  unsigned long long category;   // a categorical column: finite and >= TRAIN_MAX_CATEGORY + 1
+  unsigned long long category;   // a categorical column of the lightgbm backend: finite and >= TRAIN_MAX_CATEGORY + 1
 };
 // one staged piece (rows x cols column-major, its first row is row0 of the set) into *flags by integer atomic min; the caller has set
-// *flags to ~0.  is_cat (null: no categorical column): per column
+// *flags to ~0.  is_cat (null: no categorical column): per column; with f32 (step 2cx) a cell of such a column is refused only when infinite
 void train_launch_check_cells(mrk_ctx *ctx, hipStream_t s, const double *stage, int rows, int cols, long long row0, bool f32, const int *is_cat,
                               TrainCellFlags *flags);
 
@@ -43,10 +43,11 @@ size_t train_cuts_scratch_bytes(long long n);
 // train_cut_at (train_host.hpp).  Enqueued on s; scratch and keys must stay untouched until the launches have run
 void train_launch_cuts(mrk_ctx *ctx, hipStream_t s, const unsigned long long *keys, int n, int max_bin, bool f32, void *scratch, TrainColumnCuts *out);
 
-// hist[id] += 1 for every cell of the column with a category (0 <= trunc(x) <= TRAIN_MAX_CATEGORY); the caller zeroes hist
-void train_launch_category_counts(mrk_ctx *ctx, hipStream_t s, const double *col, int rows, unsigned *hist);
+// hist[id] += 1 for every cell of the column with a category (0 <= trunc(x) <= TRAIN_MAX_CATEGORY; f32, step 2cx: train_xgb_category(x) >= 0);
+// the caller zeroes hist
+void train_launch_category_counts(mrk_ctx *ctx, hipStream_t s, const double *col, int rows, bool f32, unsigned *hist);
 
-// train_launch_bin / train_launch_bin_f32 (train.hpp) for a staged piece: the same bins from stage[c * piece_rows + i]
+// train_launch_bin / train_launch_bin_f32 (train.hpp) for a staged piece: the same bins from stage[c * piece_rows + i] (f32 with cat_idx: step 2cx)
 void train_launch_bin_staged(mrk_ctx *ctx, hipStream_t s, const double *stage, int piece_rows, int cols, bool f32, const double *bounds, const int *bound_off,
                              const int *cat_idx, const uint8_t *cat_tables, uint8_t *bins, long long rows, long long row0);
 

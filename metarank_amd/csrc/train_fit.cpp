@@ -217,15 +217,16 @@ struct LeafGrower {
   std::string model(const TrainState &t) const { return train_write_model(trees, (size_t)t.best_iteration, t.cols, t.infos, t.cfg.learning_rate, &t.kept); }
 };
 
-// backend "xgboost": the buffers of the level-wise grower, one tree's growth (step 5x) and the forest.  Two levels of histograms are
+// backend "xgboost": the buffers of the level-wise grower, one tree's growth (steps 5x, 5cx) and the forest.  Two levels of histograms are
 // resident - the level being built and its parents' (sibling = parent - built child) - in slots [buf * cap, buf * cap + cap) of one HistDev.
 struct LevelGrower {
   int64_t cap = 0;   // train_level_cap
   int cols = 0;
   DevBuf d_G, d_H, d_C, d_feat_best, d_recs, d_tables, d_value, d_hist_slot, d_vnode_of;
   PinBuf h_recs, h_tables, h_value;
-  // one block per level, host -> device in one copy: the level's split records, the next level's built slots and scan nodes
-  size_t off_build = 0, off_nodes = 0, table_bytes = 0;
+  // one block per level, host -> device in one copy: the level's split records, the next level's built slots and scan nodes and -
+  // with a "c" column - the masks over bins of the level's categorical records (step 5cx), 8 words each
+  size_t off_build = 0, off_nodes = 0, off_masks = 0, table_bytes = 0;
   std::vector<TrainXgbTree> trees;
 
   void reserve(const TrainState &t) {
@@ -235,7 +236,8 @@ struct LevelGrower {
     d_G.reserve(cells * 8), d_H.reserve(cells * 8), d_C.reserve(cells * 4);
     d_feat_best.reserve((size_t)cap * (size_t)cols * sizeof(LeafRec));
     d_recs.reserve((size_t)cap * sizeof(LeafRec)), h_recs.reserve((size_t)cap * sizeof(LeafRec));
-    off_build = (size_t)cap * sizeof(LevelRec), off_nodes = off_build + (size_t)cap * 4, table_bytes = off_nodes + (size_t)cap * sizeof(LevelNode);
+    off_build = (size_t)cap * sizeof(LevelRec), off_nodes = off_build + (size_t)cap * 4, off_masks = off_nodes + (size_t)cap * sizeof(LevelNode);
+    table_bytes = off_masks + (t.any_cat ? (size_t)cap * 32 : 0);
     d_tables.reserve(table_bytes), h_tables.reserve(table_bytes);
     const size_t max_nodes = std::min<size_t>((size_t(2) << cfg.max_depth), 4 * (size_t)cap + 1);   // (a level has at most twice the nodes of the one above)
     d_value.reserve(max_nodes * 4), h_value.reserve(max_nodes * 4);
@@ -257,6 +259,8 @@ struct LevelGrower {
     const LevelRec *d_lrec = (const LevelRec *)d_tables.as<uint8_t>();
     const int *d_build = (const int *)(d_tables.as<uint8_t>() + off_build);
     const LevelNode *d_nodes = (const LevelNode *)(d_tables.as<uint8_t>() + off_nodes);
+    uint32_t *h_masks = (uint32_t *)(h_tables.as<uint8_t>() + off_masks);
+    const unsigned *d_masks = (const unsigned *)(d_tables.as<uint8_t>() + off_masks);
     const LeafRec *recs = h_recs.as<LeafRec>();
     auto zero_level = [&](int buf, size_t n) {
       const size_t at = (size_t)buf * (size_t)cap * (size_t)cols * 256, cells = n * (size_t)cols * 256;
@@ -279,7 +283,7 @@ struct LevelGrower {
     train_launch_level_hist(ctx, st, tr.d_bins.as<uint8_t>(), tr.rows, hist_slot, qg, qh, d_build, 1, hd);
     for (int d = 0, buf = 0; d < cfg.max_depth; ++d, buf ^= 1) {
       const int n = (int)ids.size();
-      train_launch_level_scan(ctx, st, hd, t.d_nbins.as<int>(), d_nodes, n, sp, d_feat_best.as<LeafRec>(), d_recs.as<LeafRec>());
+      train_launch_level_scan(ctx, st, hd, t.d_nbins.as<int>(), t.d_is_cat.as<int>(), d_nodes, n, sp, d_feat_best.as<LeafRec>(), d_recs.as<LeafRec>());
       {
         ScopedKernelTimer timer(ctx, "train_level_readback");
         MRK_HIP(hipMemcpyAsync(h_recs.p, d_recs.p, (size_t)n * sizeof(LeafRec), hipMemcpyDeviceToHost, st));
@@ -288,7 +292,7 @@ struct LevelGrower {
       if (d == 0) totals[0] = TrainSums{recs[0].g, recs[0].h, recs[0].c};
       const bool build_next = d + 1 < cfg.max_depth;
       std::vector<int> next;
-      int n_build = 0;
+      int n_build = 0, n_masks = 0;   // n_masks: the level's categorical records so far
       for (int k = 0; k < n; ++k) {
         const LeafRec &c = recs[k];
         LevelRec &lr = h_lrec[k];
@@ -296,11 +300,16 @@ struct LevelGrower {
         if (!c.valid) continue;
         const int node = ids[(size_t)k];
         const TrainSums whole = totals[(size_t)node];
-        tree.split(node, c.col, c.bin, (float)t.bounds[(size_t)c.col][(size_t)c.bin], c.nan_left != 0, (float)c.gain);
+        if (c.is_cat) tree.split_cat(node, c.col, c.cat_mask, c.nan_left != 0, (float)c.gain);
+        else tree.split(node, c.col, c.bin, (float)t.bounds[(size_t)c.col][(size_t)c.bin], c.nan_left != 0, (float)c.gain);
         const int l = tree.num_nodes() - 2;
         const TrainSums left{c.gl, c.hl, c.cl}, right{whole.g - c.gl, whole.h - c.hl, whole.c - c.cl};
         totals.push_back(left), totals.push_back(right);
         lr.col = c.col, lr.left = (uint16_t)l, lr.bin = (uint8_t)c.bin, lr.nan_left = (uint8_t)(c.nan_left != 0);
+        if (c.is_cat) {
+          lr.col |= TRAIN_LEVEL_CAT | (n_masks << TRAIN_LEVEL_MASK_SHIFT);
+          memcpy(h_masks + (size_t)n_masks++ * 8, c.cat_mask, 32);
+        }
         if (build_next) {   // the child with fewer sampled rows is built (ties: the left), its sibling is parent - built
           const int kl = (int)next.size(), parent_slot = buf * (int)cap + k, slot_l = (buf ^ 1) * (int)cap + kl;
           const bool left_built = left.c <= right.c;
@@ -313,8 +322,11 @@ struct LevelGrower {
       }
       if (next.empty()) break;
       MRK_HIP(hipMemcpyAsync(d_tables.p, h_tables.p, table_bytes, hipMemcpyHostToDevice, st));
-      train_launch_level_split(ctx, st, tr.d_bins.as<uint8_t>(), tr.rows, node_of, hist_slot, d_lrec, ids[0], n, cfg.sampling, cfg.seed, tree_index);
-      if (va.given) train_launch_level_split(ctx, st, va.d_bins.as<uint8_t>(), va.rows, d_vnode_of.as<uint16_t>(), nullptr, d_lrec, ids[0], n, cfg.sampling, cfg.seed, tree_index);
+      train_launch_level_split(ctx, st, tr.d_bins.as<uint8_t>(), tr.rows, node_of, hist_slot, d_lrec, ids[0], n, cfg.sampling, cfg.seed, tree_index,
+                               d_masks, n_masks);
+      if (va.given)
+        train_launch_level_split(ctx, st, va.d_bins.as<uint8_t>(), va.rows, d_vnode_of.as<uint16_t>(), nullptr, d_lrec, ids[0], n, cfg.sampling, cfg.seed, tree_index,
+                                 d_masks, n_masks);
       if (build_next) {
         zero_level(buf ^ 1, next.size());
         train_launch_level_hist(ctx, st, tr.d_bins.as<uint8_t>(), tr.rows, hist_slot, qg, qh, d_build, n_build, hd);
@@ -336,7 +348,7 @@ struct LevelGrower {
     return true;
   }
 
-  std::string model(const TrainState &t) const { return train_write_xgb_model(trees, (size_t)t.best_iteration, t.cols); }
+  std::string model(const TrainState &t) const { return train_write_xgb_model(trees, (size_t)t.best_iteration, t.cols, &t.kept, &t.is_cat); }
 };
 
 // the validation metric: eval.hip's kernels on the validation scores (the number mrk_eval_scores gives)

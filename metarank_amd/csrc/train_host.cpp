@@ -23,7 +23,8 @@ TrainConfig train_parse_config(const char *text, size_t len) {
   TrainConfig c;
   static const char *known[] = {"iterations", "learningRate", "ndcgCutoff", "maxDepth", "seed", "numLeaves", "sampling", "debias", "max_bin", "truncation",
                                 "sigma", "min_data_in_leaf", "min_sum_hessian", "lambda_l2", "early_stopping", "categorical", "max_cat_to_onehot",
-                                "max_cat_threshold", "cat_smooth", "cat_l2", "min_data_per_group", "backend", "lambda", "gamma", "min_child_weight", "position_bias"};
+                                "max_cat_threshold", "cat_smooth", "cat_l2", "min_data_per_group", "backend", "lambda", "gamma", "min_child_weight", "position_bias",
+                                "feature_types"};
   for (auto &kv : root.obj) {
     bool ok = false;
     for (const char *k : known) ok = ok || kv.first == k;
@@ -39,7 +40,7 @@ TrainConfig train_parse_config(const char *text, size_t len) {
   {  // a key of the other backend is refused, not ignored: it would be a setting that silently does nothing
     static const char *lgb_only[] = {"numLeaves", "min_data_in_leaf", "min_sum_hessian", "lambda_l2", "max_cat_to_onehot", "max_cat_threshold", "cat_smooth", "cat_l2",
                                      "min_data_per_group"};
-    static const char *xgb_only[] = {"lambda", "gamma", "min_child_weight"};
+    static const char *xgb_only[] = {"lambda", "gamma", "min_child_weight", "feature_types"};
     auto refuse = [&](const char *key, const char *backend) {
       const json::Value *v = root.find(key);
       if (v && !v->is_null()) range(std::string(key) + " is not a key of the " + backend + " backend");
@@ -150,6 +151,17 @@ TrainConfig train_parse_config(const char *text, size_t len) {
     range("maxDepth = " + std::to_string(c.max_depth) + " (at most " + std::to_string(TRAIN_XGB_MAX_DEPTH) + " with the xgboost backend)");
   if (c.backend == TRAIN_BACKEND_XGBOOST && !c.categorical.empty())
     throw StatusError(MRK_ERR_UNSUPPORTED, "train config: categorical columns are not built for the xgboost backend (set-membership splits in XGBoost JSON)");
+  if (const json::Value *v = root.find("feature_types"))
+    if (!v->is_null()) {   // (backend "xgboost": refused above under the other) XGBoost's own spelling, one entry per column
+      if (!v->is_array()) bad("'feature_types' is not an array");
+      for (const json::Value &e : v->arr) {
+        if (e.type != json::Type::String) bad("'feature_types' holds something that is not a string");
+        if (e.str != "q" && e.str != "c") range("feature_types holds '" + e.str + "' (q: numeric, c: categorical)");
+      }
+      c.feature_types = (int)v->arr.size();
+      for (size_t k = 0; k < v->arr.size(); ++k)
+        if (v->arr[k].str == "c") c.categorical.push_back((int32_t)k);
+    }
   if (c.debias) throw StatusError(MRK_ERR_UNSUPPORTED, "train config: debias carries neither the number of positions nor the norm: use position_bias");
   if (c.num_leaves > TRAIN_MAX_LEAVES)
     throw StatusError(MRK_ERR_UNSUPPORTED, "train config: numLeaves = " + std::to_string(c.num_leaves) + " (limit " + std::to_string(TRAIN_MAX_LEAVES) + ")");
@@ -278,10 +290,21 @@ void train_check_categories(const double *col, int64_t n, int64_t stride, int co
   for (int64_t i = 0; i < n; ++i) (void)category_of(col[i * stride], i, column);
 }
 
-std::vector<uint8_t> train_category_table(const std::vector<int32_t> &kept) {
-  std::vector<uint8_t> table(kept.empty() ? 0 : (size_t)kept.back() + 1, (uint8_t)TRAIN_NAN_BIN);
+std::vector<uint8_t> train_category_table(const std::vector<int32_t> &kept, int none) {
+  std::vector<uint8_t> table(kept.empty() ? 0 : (size_t)kept.back() + 1, (uint8_t)none);
   for (size_t k = 0; k < kept.size(); ++k) table[(size_t)kept[k]] = (uint8_t)k;
   return table;
+}
+
+std::vector<int32_t> train_xgb_kept_categories(const double *col, int64_t n, int64_t stride, int max_bin, int column) {
+  std::vector<int64_t> count((size_t)TRAIN_MAX_CATEGORY + 1, 0);
+  for (int64_t i = 0; i < n; ++i) {
+    const double x = col[i * stride];
+    if (std::isinf(x)) throw StatusError(MRK_ERR_INVALID_ARG, "train: column " + std::to_string(column) + ", row " + std::to_string(i) + " is infinite");
+    const int id = train_xgb_category(x);
+    if (id >= 0) count[(size_t)id] += 1;
+  }
+  return train_kept_from_counts(count, max_bin - 1);   // (keeps its max_bin - 1: here max_bin - 2, bin 254 is "other")
 }
 
 static uint64_t splitmix64(uint64_t &state) {
@@ -366,7 +389,9 @@ double train_fit_bytes(const TrainConfig &cfg, int which, int64_t rows_, int col
   // rows of records per column (counted for both backends, as it always was: LevelGrower holds one level's records, not two and two rows)
   const double hist = xgb ? (column_cells + rec) * n_sub * 2.0 * (double)train_level_cap(cfg, rows_) : column_cells * n_sub * (double)cfg.num_leaves;
   const double scan_records = 2.0 * rec * n_sub;
-  return bins + per_row + group_lists + row_slots + hist + scan_records;
+  // step 5cx: the level's table of 32-byte masks, one per node of the level at most
+  const double level_masks = xgb && !cfg.categorical.empty() ? 32.0 * (double)train_level_cap(cfg, rows_) : 0.0;
+  return bins + per_row + group_lists + row_slots + hist + scan_records + level_masks;
 }
 
 std::vector<uint8_t> train_check_labels(const double *labels, int64_t rows) {
@@ -498,7 +523,14 @@ std::string train_write_model(const std::vector<TrainTree> &trees, size_t n_tree
 int TrainXgbTree::add(int parent_) {
   left.push_back(-1), right.push_back(-1), parent.push_back(parent_), col.push_back(0), bin.push_back(0), default_left.push_back(0);
   cond.push_back(0.0f), base_weight.push_back(0.0f), loss_change.push_back(0.0f), sum_hessian.push_back(0.0f);
+  is_cat.push_back(0);
   return num_nodes() - 1;
+}
+
+void TrainXgbTree::split_cat(int node, int col_, const uint32_t *mask8, bool nan_left, float gain) {
+  split(node, col_, 0, 0.0f, nan_left, gain);
+  is_cat[(size_t)node] = 1;
+  cat_mask.insert(cat_mask.end(), mask8, mask8 + 8);
 }
 
 void TrainXgbTree::split(int node, int col_, int bin_, float bound, bool nan_left, float gain) {
@@ -521,7 +553,8 @@ void TrainXgbTree::weigh(int node, const TrainSums &q, int e_g, int e_h, double 
   }
 }
 
-std::string train_write_xgb_model(const std::vector<TrainXgbTree> &trees, size_t n_trees, int cols) {
+std::string train_write_xgb_model(const std::vector<TrainXgbTree> &trees, size_t n_trees, int cols, const std::vector<std::vector<int32_t>> *kept,
+                                  const std::vector<int32_t> *is_cat) {
   auto ints = [](std::string &o, const char *key, const std::vector<int32_t> &a) {
     o += std::string("\"") + key + "\":[";
     for (size_t i = 0; i < a.size(); ++i) o += (i ? "," : "") + std::to_string(a[i]);
@@ -537,17 +570,36 @@ std::string train_write_xgb_model(const std::vector<TrainXgbTree> &trees, size_t
     o += "],";
   };
   const std::string n = std::to_string(n_trees), nf = std::to_string(cols);
-  std::string o = "{\"learner\":{\"attributes\":{},\"feature_names\":[],\"feature_types\":[],\"gradient_booster\":{\"model\":{\"gbtree_model_param\":{\"num_parallel_tree\":\"1\",\"num_trees\":\"" + n + "\"},\"iteration_indptr\":[";
+  std::string types;   // the configured list when it has a "c"
+  for (int c = 0; is_cat && c < cols; ++c)
+    if ((*is_cat)[(size_t)c]) {
+      for (int k = 0; k < cols; ++k) types += std::string(k ? "," : "") + ((*is_cat)[(size_t)k] ? "\"c\"" : "\"q\"");
+      break;
+    }
+  std::string o = "{\"learner\":{\"attributes\":{},\"feature_names\":[],\"feature_types\":[" + types + "],\"gradient_booster\":{\"model\":{\"gbtree_model_param\":{\"num_parallel_tree\":\"1\",\"num_trees\":\"" + n + "\"},\"iteration_indptr\":[";
   for (size_t i = 0; i <= n_trees; ++i) o += (i ? "," : "") + std::to_string(i);
   o += "],\"tree_info\":[";
   for (size_t i = 0; i < n_trees; ++i) o += i ? ",0" : "0";
   o += "],\"trees\":[";
   for (size_t i = 0; i < n_trees; ++i) {
     const TrainXgbTree &t = trees[i];
-    const std::vector<int32_t> zeros((size_t)t.num_nodes(), 0);
     o += i ? ",{" : "{";
     f32s(o, "base_weights", t.base_weight);
-    o += "\"categories\":[],\"categories_nodes\":[],\"categories_segments\":[],\"categories_sizes\":[],";
+    std::vector<int32_t> ids, nodes, segments, sizes, types_of((size_t)t.num_nodes(), 0);
+    for (int node = 0, k = 0; node < t.num_nodes(); ++node) {   // a mask over bins back to category ids: both ascend
+      if (!t.is_cat[(size_t)node]) continue;
+      if (!kept) throw StatusError(MRK_ERR_INVALID_ARG, "train: a categorical node without the tables of kept ids");
+      const std::vector<int32_t> &of = (*kept)[(size_t)t.col[(size_t)node]];
+      nodes.push_back(node), segments.push_back((int32_t)ids.size()), types_of[(size_t)node] = 1;
+      for (size_t b = 0; b < of.size(); ++b)
+        if (t.cat_mask[(size_t)k * 8 + b / 32] >> (b % 32) & 1u) ids.push_back(of[b]);
+      sizes.push_back((int32_t)ids.size() - segments.back());
+      ++k;
+    }
+    ints(o, "categories", ids);
+    ints(o, "categories_nodes", nodes);
+    ints(o, "categories_segments", segments);
+    ints(o, "categories_sizes", sizes);
     ints(o, "default_left", t.default_left);
     o += "\"id\":" + std::to_string(i) + ",";
     ints(o, "left_children", t.left);
@@ -556,7 +608,7 @@ std::string train_write_xgb_model(const std::vector<TrainXgbTree> &trees, size_t
     ints(o, "right_children", t.right);
     f32s(o, "split_conditions", t.cond);
     ints(o, "split_indices", t.col);
-    ints(o, "split_type", zeros);
+    ints(o, "split_type", types_of);
     f32s(o, "sum_hessian", t.sum_hessian);
     o += "\"tree_param\":{\"num_deleted\":\"0\",\"num_feature\":\"" + nf + "\",\"num_nodes\":\"" + std::to_string(t.num_nodes()) + "\",\"size_leaf_vector\":\"1\"}}";
   }

@@ -19,6 +19,11 @@ constexpr int TRAIN_MAX_COLS = 65535;
 constexpr int TRAIN_MAX_LEAVES = 4096;
 constexpr int TRAIN_MAX_LABEL = 30;
 constexpr int TRAIN_MAX_CATEGORY = 32764;   // 0x7FFC: the largest id the scorers' categorical cell holds exactly (forest.hpp, QV_CAT)
+// backend "xgboost", steps 2cx / 5cx: libxgboost's two caps at its defaults (the reference's XGBoostConfig exposes neither), and the bin
+// of every cell of a "c" column that the model sends LEFT whatever the node's set is
+constexpr int TRAIN_XGB_MAX_CAT_TO_ONEHOT = 4;    // fewer kept categories than this: one category against the rest
+constexpr int TRAIN_XGB_MAX_CAT_THRESHOLD = 64;   // the most categories on the smaller end of a sorted partition
+constexpr int TRAIN_OTHER_BIN = 254;              // a "c" column keeps at most max_bin - 2 <= 253 categories: bins 254 and 255 are free
 
 #ifdef __HIPCC__
 #define MRK_TRAIN_HD __host__ __device__
@@ -42,7 +47,8 @@ struct TrainConfig {
   double min_sum_hessian = 1e-3;
   double lambda_l2 = 0.0;
   int early_stopping = 20;
-  std::vector<int32_t> categorical;   // column indices, distinct, >= 0 (below `cols`: judged by mrk_train_set)
+  std::vector<int32_t> categorical;   // column indices, distinct, >= 0 (below `cols`: judged by mrk_train_set); backend "xgboost": the "c" entries of feature_types
+  int feature_types = -1;             // backend "xgboost", "feature_types": how many entries the array has (mrk_train_set: == cols), -1 when absent or null
   int max_cat_to_onehot = 4;
   int max_cat_threshold = 32;
   double cat_smooth = 10.0;
@@ -61,7 +67,9 @@ constexpr int TRAIN_XGB_MAX_DEPTH = 15;     // a node id is a u16: a complete tr
 // malformed JSON, a value of the wrong type or an unknown key: MRK_ERR_PARSE; a value out of range: MRK_ERR_INVALID_ARG;
 // debias = true or numLeaves > TRAIN_MAX_LEAVES: MRK_ERR_UNSUPPORTED.  backend "xgboost": numLeaves, min_data_in_leaf,
 // min_sum_hessian, lambda_l2 and the categorical keys but `categorical` are MRK_ERR_INVALID_ARG naming the key, a non-empty
-// `categorical` is MRK_ERR_UNSUPPORTED; backend "lightgbm": lambda, gamma and min_child_weight are MRK_ERR_INVALID_ARG.
+// `categorical` is MRK_ERR_UNSUPPORTED; backend "lightgbm": lambda, gamma, min_child_weight and feature_types are MRK_ERR_INVALID_ARG.
+// feature_types (backend "xgboost"): not an array or an entry that is no string: MRK_ERR_PARSE; an entry other than "q" / "c":
+// MRK_ERR_INVALID_ARG.  Its "c" entries become `categorical` (steps 2cx, 5cx)
 // position_bias (either backend): not an object, a key inside other than positions / norm or one that is no number: MRK_ERR_PARSE;
 // positions outside 1 ... TRAIN_MAX_GROUP, norm negative or not finite: MRK_ERR_INVALID_ARG
 TrainConfig train_parse_config(const char *json, size_t len);
@@ -93,14 +101,32 @@ std::vector<int32_t> train_kept_categories(const double *col, int64_t n, int64_t
 std::vector<int32_t> train_kept_from_counts(const std::vector<int64_t> &count, int max_bin, std::string *info = nullptr);
 // the cells of a categorical column of another set than the one the ids were kept from: the same two refusals
 void train_check_categories(const double *col, int64_t n, int64_t stride, int column);
-// id -> bin for ids 0 ... kept.back(), TRAIN_NAN_BIN where the id has none; empty without a kept id
-std::vector<uint8_t> train_category_table(const std::vector<int32_t> &kept);
+// id -> bin for ids 0 ... kept.back(), `none` where the id has no bin; empty without a kept id
+std::vector<uint8_t> train_category_table(const std::vector<int32_t> &kept, int none = TRAIN_NAN_BIN);
 // the bin of a cell of a categorical column under a table of `len` bytes: NaN, a negative category and an id without a bin are
 // TRAIN_NAN_BIN (which always goes right: what CategoricalDecision does with them).  The binning kernel calls this too.
 MRK_TRAIN_HD inline int train_category_bin(double x, const uint8_t *table, int len) {
   if (!(x > -1.0) || !(x < (double)len)) return TRAIN_NAN_BIN;   // (NaN fails both; -1 < x < 0 truncates to category 0)
   return table[(int)x];
 }
+
+// step 2cx: the category of a cell of a "c" column of the xgboost backend, as the model's decide32 sees it: the cell narrowed to f32;
+// -1 for NaN, -2 for a cell the model sends left whatever the set is (negative, >= 2^24, or beyond TRAIN_MAX_CATEGORY: no bitset the
+// trainer writes reaches it).  Nothing is refused here.  The binning and counting kernels call this too.
+MRK_TRAIN_HD inline int train_xgb_category(double x) {
+  const float v = (float)x;   // round to nearest even
+  if (v != v) return -1;
+  if (v < 0.0f || v >= 16777216.0f || (int)v > TRAIN_MAX_CATEGORY) return -2;
+  return (int)v;
+}
+// its bin under the id -> bin table (train_category_table with none = TRAIN_OTHER_BIN)
+MRK_TRAIN_HD inline int train_xgb_category_bin(double x, const uint8_t *table, int len) {
+  const int id = train_xgb_category(x);
+  return id == -1 ? TRAIN_NAN_BIN : id < 0 || id >= len ? TRAIN_OTHER_BIN : table[id];
+}
+// the kept ids of a "c" column, ascending: the min(distinct, max_bin - 2) most frequent categories, ties to the lower id.  An infinite
+// f64 cell: MRK_ERR_INVALID_ARG (step 1's refusal)
+std::vector<int32_t> train_xgb_kept_categories(const double *col, int64_t n, int64_t stride, int max_bin, int column);
 
 // Steps 2 and 2x over values that are ALREADY sorted (step 2d: the device's bin finder, train_bins.hip; tests/native/train_cuts_test.cpp
 // holds it against train_bin_bounds on the unsorted cells).  v(p), 0 <= p < m: the sorted non-NaN values as f64 (an f32 value
@@ -207,14 +233,21 @@ std::string train_write_model(const std::vector<TrainTree> &trees, size_t n_tree
 struct TrainXgbTree {
   std::vector<int32_t> left, right, parent, col, bin, default_left;   // left / right -1 for a leaf; parent 2147483647 for the root
   std::vector<float> cond, base_weight, loss_change, sum_hessian;
+  std::vector<int32_t> is_cat;                                      // per node: a set-membership split (step 5cx)
+  std::vector<uint32_t> cat_mask;                                   // per CATEGORICAL node, in ascending node id, 8 words: bit b <=> bin b goes RIGHT
   int num_nodes() const { return (int)left.size(); }
   int add(int parent_);                                             // a new leaf -> its id
   void split(int node, int col_, int bin_, float bound, bool nan_left, float gain);   // -> children num_nodes() - 2, num_nodes() - 1
+  void split_cat(int node, int col_, const uint32_t *mask8, bool nan_left, float gain);   // nodes split in ascending id (a level at a time)
   // weight = -G / (H + lambda) of a node's quantised sums into base_weight / sum_hessian; a leaf's cond = (float)(weight * lr).
   // H + lambda == 0 (no finite weight): MRK_ERR_INVALID_ARG
   void weigh(int node, const TrainSums &q, int e_g, int e_h, double lambda, double lr);
 };
-// XGBoost's JSON (version [2,1,0], objective rank:ndcg, base_score 5E-1), no whitespace; every f32 as %.9g of its widened value
-std::string train_write_xgb_model(const std::vector<TrainXgbTree> &trees, size_t n_trees, int cols);
+// XGBoost's JSON (version [2,1,0], objective rank:ndcg, base_score 5E-1), no whitespace; every f32 as %.9g of its widened value.
+// kept: per column the kept ids of step 2cx (empty for a "q" column).  With a "c" column the learner's feature_types holds "q" / "c"
+// per column; a categorical node has split_type 1 and split_conditions 0, and the ascending category IDS of its right set stand in
+// `categories` - node by node in ascending id, beside categories_nodes / _segments / _sizes.  Without one: the bytes of before
+std::string train_write_xgb_model(const std::vector<TrainXgbTree> &trees, size_t n_trees, int cols, const std::vector<std::vector<int32_t>> *kept = nullptr,
+                                  const std::vector<int32_t> *is_cat = nullptr);
 
 }  // namespace mrk

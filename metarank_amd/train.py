@@ -62,6 +62,17 @@ def categorical_columns(columns) -> list:
     return [int(first) for _, first, _, kind in columns if kind == "category"]
 
 
+def feature_types(columns, dim=None) -> list:
+    """the `feature_types` key of a backend="xgboost" fit on mrk_values' rows: "c" for every column of a `category` feature of
+    HipRanker.values_columns(), "q" for the others (dim: the matrix's columns, by default the end of the last feature)"""
+    columns = list(columns)
+    out = ["q"] * (max(first + width for _, first, width, _ in columns) if dim is None else dim)
+    for _, first, width, kind in columns:
+        if kind == "category":
+            out[first:first + width] = ["c"] * width
+    return out
+
+
 def lambdarank_gradients(scores, labels, group_offsets, ctx: Context | None = None, t_plus=None, t_minus=None, **config):
     """mrk_train_gradients: (g, h) of the lambdarank objective, one f64 per row.  With t_plus and t_minus - `positions` factors each, and
     position_bias in the config - mrk_train_bias_gradients: (g, h, cost_plus, cost_minus) of include/mrk.h's step 3b"""
@@ -89,9 +100,13 @@ class Trainer:
     """mrk_trainer: set(0, ...), optionally set(1, ...), fit(), then model() / history() / scores().  A set whose rows are in device
     memory - a values batch's matrix - is given in pieces instead: append_device / append_batch any number of times, then seal."""
 
-    def __init__(self, config=None, ctx: Context | None = None):
+    def __init__(self, config=None, ctx: Context | None = None, feature_types=None):
+        """feature_types (backend "xgboost"): one "q" (numeric) or "c" (categorical: set-membership splits, include/mrk.h steps 2cx and
+        5cx) per column, XGBoost's own spelling; the same as the config's key of that name"""
         self.ctx = ctx or default_context()
         self._h = C.c_void_p()
+        if feature_types is not None:
+            config = dict(config or {}, feature_types=list(feature_types))
         N.check(N.lib().mrk_train_begin(self.ctx.handle, _config(config), C.byref(self._h)))
         self._rows = {}
 
@@ -192,6 +207,7 @@ def fit_lambdamart(X, labels, group_offsets, valid=None, ctx: Context | None = N
     fit_lambdamart(X, y, off, categorical=categorical_columns(ranker.values_columns())).
     position_bias={"positions": 32, "norm": 1.0} (either backend; what the reference's `debias` stands for): include/mrk.h step 3b;
     history["position_bias"] is (t_plus, t_minus) after the last iteration.
+    backend="xgboost" names them per column instead: feature_types=feature_types(ranker.values_columns()), "q" or "c" each.
     backend="xgboost": the level-wise fit; the model is XGBoost's JSON and the booster is loaded as an XGBoost one; scores are the f32
     sums the model predicts (from its base_score 0.5), widened."""
     ctx = ctx or default_context()

@@ -91,7 +91,10 @@ def main():
     cats = list(range(COLS - a.categorical, COLS))
     if cats:                                                              # (without the option the config has no `categorical` key)
         X[:, cats] = np.clip(np.rint((X[:, cats] + 3.0) * (49.0 / 6.0)), 0.0, 49.0)
-        cfg["categorical"] = cats
+        if xgb:                                                           # (this backend names them per column: steps 2cx, 5cx)
+            cfg["feature_types"] = ["c" if c in cats else "q" for c in range(COLS)]
+        else:
+            cfg["categorical"] = cats
     out = {"groups": a.groups, "rows": rows, "items_per_group": [a.min_items, a.max_items], "columns": COLS, "iterations": a.iterations, "leaves": a.leaves,
            "backend": a.backend, "depth": a.depth if xgb else None, "categorical": cats, "build": N.lib().mrk_build_id().decode()}
     if a.device_set:
@@ -216,6 +219,7 @@ def finish_xgboost(a, ctx, out, parts, hist, model, X, y, off, rows):
     trees = json.loads(model)["learner"]["gradient_booster"]["model"]["trees"]
     out["nodes"] = sum(int(t["tree_param"]["num_nodes"]) for t in trees)
     out["splits"] = sum(sum(1 for l in t["left_children"] if l >= 0) for t in trees)
+    out["categorical_nodes"] = sum(len(t["categories_nodes"]) for t in trees)
     bound = hist["iterations_run"] * a.depth                             # derived: one launch / read-back per level that can still split
     counts = {name: int(parts[name][1]) for name in LEVEL_TIMERS}
     out["launches"] = {"per_phase": counts, "bound_trees_x_depth": bound, "histogram": counts["train_level_hist"], "scan": counts["train_level_scan"],
