@@ -1029,6 +1029,29 @@ int mrk_model_eval(mrk_model *model, const int *metrics, const int *cutoffs, int
  *              are step 5x's (lambda, min_child_weight, a sampled row on both sides, gain > gamma), the gain's sum taken left + right.
  *              Best within the column: the highest gain, then direction 0, then the smaller i (one against the rest: the lower bin),
  *              then NaN right.  Across columns unchanged: the highest gain, then the lowest column.
+ *  tree_method ["hist"; backend "xgboost" alone - under the default backend the key is MRK_ERR_INVALID_ARG naming itself]: XGBoost's own
+ *              spelling.  Absent, null or "hist": steps 2x / 5x, the bytes of a fit without the key.  "exact" - what the reference runs
+ *              (treeMethod = "exact", LambdaMARTRanker.scala:176-188): steps 2e / 5e in their place, everything else unchanged.  Another
+ *              string is MRK_ERR_INVALID_ARG naming key and value, a value that is no string MRK_ERR_PARSE.  Under "exact" max_bin is
+ *              ignored, and these are MRK_ERR_UNSUPPORTED naming tree_method: a "c" in feature_types, mrk_train_append_device,
+ *              mrk_train_seal, mrk_train_bounds and mrk_train_bins.  tests/train_xgb_exact_reference.py restates 2e and 5e.
+ *  2e no bins  the cells are narrowed to f32 exactly as in 2x (round to nearest even, -0.0f as +0.0f, a finite f64 that narrows to
+ *              +-inf refused naming column and row, in either set).  The f32 matrix stays on the device, column-major, and every
+ *              column's rows are ordered ONCE by (narrowed value, row), NaN last - step 2d's keys and sort.
+ *              Device memory: rows x cols x 16 bytes (the f32 cell, the sorted order every tree starts from and the two permutations
+ *              a level's partition goes between) plus the sums per (column, tile of 1024 positions) and per (column, node of a level);
+ *              checked against free memory at mrk_train_set, MRK_ERR_UNSUPPORTED with the sizes.
+ *  5e tree     5x with "bin" read as "position among the node's distinct values".  At an open node and a column there is a candidate
+ *              between every pair of neighbouring DISTINCT non-NaN values a < b that occur in the node's rows - sampled and unsampled
+ *              rows alike say where values change (as a bin that holds only unsampled rows does in 5x); only sampled rows carry sums
+ *              and counts.  The bound is b ITSELF, an f32, and the test is (float) x < b: 2x's convention and the emitted model's own
+ *              test, kept in place of libxgboost's midpoint (a + b) / 2 because trainer and model then route every possible cell
+ *              alike.  The NaN rule, the admission rule, the gain (f64, correctly rounded, never fused, from ldexp((double) Q, -e) of
+ *              int64 sums), the preference (the highest gain, then the lowest column, the lowest bound, NaN right), "every open node
+ *              with an admitted candidate splits", the numbering, the weights and the leaf values are 5x's word for word.
+ *              Consequence: where no bin of 2x holds two values AND every node that splits holds rows at both global neighbours of
+ *              its bound (5x names the lowest bound of a run of empty bins, 5e the node's own next value - the same partition of the
+ *              node's rows, another number in the model), "exact" emits the bytes of "hist".
  *  6x scores   f32, as the model predicts them: s = 0.5f (the base_score), then s = s + leaf in f32, in tree order.  Training rows -
  *              the unsampled ones too - and validation rows take the leaf their bins route them to.  mrk_train_scores returns the
  *              widened value, equal to mrk_model_predict_f64 of the emitted model bit for bit; without a tree every score is 0.5.

@@ -54,6 +54,10 @@ def embed_jit_sources() -> str:
     return path
 
 
+# flags of single sources beside the common ones: no packed f32 arithmetic in the exact grower's kernels
+FILE_FLAGS = {"train_exact.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+
+
 def write_build_id() -> str:
     """csrc/build_id.inc: a string literal with the digest of every source of the library (csrc/ without the generated
     files, include/mrk.h) - what mrk_build_id() returns.  Generated, not committed; only capi.cpp includes it."""
@@ -98,7 +102,7 @@ def build(force: bool = False) -> str:
         obj = os.path.join(objdir, os.path.basename(src) + ".o")
         newest = max(os.path.getmtime(src), hdr_time, os.path.getmtime(build_id) if src.endswith("capi.cpp") else 0)
         if force or not os.path.exists(obj) or os.path.getmtime(obj) < newest:
-            subprocess.check_call([hipcc] + flags + ["-c", src, "-o", obj])
+            subprocess.check_call([hipcc] + flags + FILE_FLAGS.get(os.path.basename(src), []) + ["-c", src, "-o", obj])
             return obj, True
         return obj, False
 

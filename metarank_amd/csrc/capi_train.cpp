@@ -16,6 +16,7 @@
 #include "runtime.hpp"
 #include "train.hpp"
 #include "train_bins.hpp"
+#include "train_exact.hpp"
 #include "train_fit.hpp"
 #include "train_host.hpp"
 
@@ -112,11 +113,17 @@ EvalShape check_set_args(const mrk_trainer *t, int which, const double *x, int64
 // with train_bin_bounds_f32 - for a "c" column (step 2cx) the kept ids with train_xgb_kept_categories - and bins with
 // train_launch_bin_f32; lightgbm (steps 2, 2c) finds f64 bounds or, for a categorical column, the kept ids, and bins with train_launch_bin.
 bool bins_in_f32(const mrk_trainer *t) { return t->cfg.backend == TRAIN_BACKEND_XGBOOST; }
+// tree_method "exact" (step 2e): no bins at all - the set keeps its f32 cells, the training set every column's order beside them
+bool by_order(const mrk_trainer *t) { return t->cfg.tree_method == TRAIN_TREE_EXACT; }
+void refuse_by_order(const mrk_trainer *t, const char *what) {
+  if (by_order(t)) throw StatusError(MRK_ERR_UNSUPPORTED, std::string("train: ") + what + " is not built for tree_method 'exact'");
+}
 
 // the training set's column c on the host: its bounds, or its kept category ids
 void find_bins(mrk_trainer *t, const double *x, int64_t rows, int c) {
   const size_t k = (size_t)c;
-  if (bins_in_f32(t) && t->is_cat[k]) t->kept[k] = train_xgb_kept_categories(x + c, rows, t->cols, t->cfg.max_bin, c);
+  if (by_order(t)) train_check_f32_cells(x + c, rows, t->cols, c);   // step 2e keeps step 2x's refusal and finds nothing
+  else if (bins_in_f32(t) && t->is_cat[k]) t->kept[k] = train_xgb_kept_categories(x + c, rows, t->cols, t->cfg.max_bin, c);
   else if (bins_in_f32(t)) t->bounds[k] = train_bin_bounds_f32(x + c, rows, t->cols, t->cfg.max_bin, c);
   else if (t->is_cat[k]) t->kept[k] = train_kept_categories(x + c, rows, t->cols, t->cfg.max_bin, c, &t->infos[k]);
   else t->bounds[k] = train_bin_bounds(x + c, rows, t->cols, t->cfg.max_bin, &t->infos[k]);
@@ -138,7 +145,8 @@ void check_other_cells(const mrk_trainer *t, const double *x, int64_t rows, int 
 void launch_bin_piece(const mrk_trainer *t, hipStream_t st, const double *d_x, const EvalPiece &pc, TrainSet &s) {
   const int *cat_idx = t->any_cat ? t->d_cat_idx.as<int>() : nullptr;
   const uint8_t *cat_tables = t->any_cat ? t->d_cat_tables.as<uint8_t>() : nullptr;
-  if (bins_in_f32(t))
+  if (by_order(t)) train_launch_exact_cells(t->ctx, st, d_x, pc.rows, t->cols, s.d_cells.as<float>(), s.rows, pc.row0);
+  else if (bins_in_f32(t))
     train_launch_bin_f32(t->ctx, st, d_x, pc.rows, t->cols, t->d_bounds.as<double>(), t->d_bound_off.as<int>(), cat_idx, cat_tables, s.d_bins.as<uint8_t>(), s.rows, pc.row0);
   else
     train_launch_bin(t->ctx, st, d_x, pc.rows, t->cols, t->d_bounds.as<double>(), t->d_bound_off.as<int>(), cat_idx, cat_tables, s.d_bins.as<uint8_t>(), s.rows, pc.row0);
@@ -193,9 +201,11 @@ void upload_tables(mrk_trainer *t, hipStream_t st) {
 void check_budget(const mrk_trainer *t, int which, int64_t rows, int cols, int64_t n_groups, size_t piece_bytes) {
   const bool xgb = t->cfg.backend == TRAIN_BACKEND_XGBOOST;
   const int n_sub = xgb ? cols : (int)train_feature_subset(cols, t->cfg.sampling, 0, 0).size();
-  check_free(train_fit_bytes(t->cfg, which, rows, cols, n_groups) + (double)piece_bytes + 1048576.0,
+  const size_t order_bytes = by_order(t) && which == 0 ? train_exact_order_scratch_bytes(rows) : 0;   // (while a column is ordered)
+  check_free(train_fit_bytes(t->cfg, which, rows, cols, n_groups) + (double)std::max(piece_bytes, order_bytes) + 1048576.0,
              std::to_string(rows) + " rows x " + std::to_string(cols) + " columns in " + std::to_string(n_groups) + " groups, " +
-                 (xgb ? "2 levels x " + std::to_string(train_level_cap(t->cfg, rows)) + " nodes x " : std::to_string(t->cfg.num_leaves) + " leaves x ") + std::to_string(n_sub) +
+                 (by_order(t) ? "tree_method 'exact': f32 cells and 3 permutations (16 bytes a cell), the sums of " + std::to_string(train_level_cap(t->cfg, rows)) + " nodes x "
+                  : xgb ? "2 levels x " + std::to_string(train_level_cap(t->cfg, rows)) + " nodes x " : std::to_string(t->cfg.num_leaves) + " leaves x ") + std::to_string(n_sub) +
                  " columns of histograms");
 }
 
@@ -204,7 +214,8 @@ void upload_rows_and_groups(TrainSet &s, hipStream_t st);
 // the matrix in pieces through the binning kernel, then the labels and the lists of groups
 void upload_set(const mrk_trainer *t, TrainSet &s, const double *x, const std::vector<EvalPiece> &pieces, size_t piece_bytes, hipStream_t st) {
   const size_t cols = (size_t)t->cols;
-  s.d_bins.reserve((size_t)s.rows * cols);
+  if (by_order(t)) s.d_cells.reserve((size_t)s.rows * cols * 4);
+  else s.d_bins.reserve((size_t)s.rows * cols);
   DevBuf d_x;
   d_x.reserve(piece_bytes);
   for (const EvalPiece &pc : pieces) {
@@ -213,6 +224,16 @@ void upload_set(const mrk_trainer *t, TrainSet &s, const double *x, const std::v
   }
   upload_rows_and_groups(s, st);
   MRK_HIP(hipStreamSynchronize(st));     // the caller's matrix is not kept; d_x goes
+}
+
+// step 2e: every column of the training set ordered once by (narrowed value, row), NaN last
+void order_columns(const mrk_trainer *t, TrainSet &s, hipStream_t st) {
+  const size_t rows = (size_t)s.rows;
+  s.d_order.reserve(rows * (size_t)t->cols * 4);
+  DevBuf d_scratch;
+  d_scratch.reserve(train_exact_order_scratch_bytes(s.rows));
+  for (int c = 0; c < t->cols; ++c) train_launch_exact_order(t->ctx, st, s.d_cells.as<float>() + (size_t)c * rows, (int)s.rows, d_scratch.p, s.d_order.as<int>() + (size_t)c * rows);
+  MRK_HIP(hipStreamSynchronize(st));     // d_scratch goes
 }
 
 // the labels and the lists of groups; d_score and d_best are reserved here and first written by the fit
@@ -251,6 +272,7 @@ void set_locked(mrk_trainer *t, int which, const double *x, int64_t rows, int co
   check_budget(t, which, rows, cols, n_groups, piece_bytes);
   if (which == 0) upload_tables(t, lk.stream);
   upload_set(t, s, x, pieces, piece_bytes, lk.stream);
+  if (by_order(t) && which == 0) order_columns(t, s, lk.stream);
   drain_profile_events(t->ctx);
   s.given = true;
 }
@@ -262,6 +284,7 @@ void append_locked(mrk_trainer *t, int which, const double *d_x, int64_t rows, i
   need(!t->fitted, "train: the trainer has been fitted");
   need(d_x != nullptr, "train: null matrix");
   need(rows >= 1 && cols >= 1, "train: rows / cols < 1");
+  refuse_by_order(t, "mrk_train_append_device");
   check_feature_types(t, cols);
   Staging &sg = t->stage[which];
   need(sg.pieces.empty() || cols == sg.cols, "train: an appended piece has other columns than the pieces before it");
@@ -365,6 +388,7 @@ void bin_columns_on_device(mrk_trainer *t, const Staging &sg, hipStream_t st) {
 void seal_locked(mrk_trainer *t, int which, const double *labels, const int64_t *off, int64_t n_groups) {
   need(which == 0 || which == 1, "train: which is neither 0 (train) nor 1 (validation)");
   need(!t->fitted, "train: the trainer has been fitted");
+  refuse_by_order(t, "mrk_train_seal");
   need(!t->stage[which].pieces.empty(), "train: nothing was appended to this set");
   // a seal ends the staging whether it succeeds or not: what it refuses, it refuses about these rows
   struct Drop {
@@ -408,6 +432,7 @@ void seal_locked(mrk_trainer *t, int which, const double *labels, const int64_t 
 }
 
 void bounds_locked(mrk_trainer *t, int col, double *out, int cap, int *n_bounds) {
+  refuse_by_order(t, "mrk_train_bounds (there are no bins)");
   need(t->set[0].given, "train: no training set");
   need(col >= 0 && col < t->cols, "train: no such column");
   need(!t->is_cat[(size_t)col], "train: a categorical column has no bounds");
@@ -625,6 +650,7 @@ int mrk_train_bins(const char *config_json, const double *column, int64_t n, dou
     const TrainConfig cfg = train_parse_config(config_json, strlen(config_json));
     need(n_bounds != nullptr, "n_bounds is null");
     need(n >= 0 && (column != nullptr || n == 0), "train: null column");
+    if (cfg.tree_method == TRAIN_TREE_EXACT) throw StatusError(MRK_ERR_UNSUPPORTED, "train: mrk_train_bins is not built for tree_method 'exact' (there are no bins)");
     const std::vector<double> b = cfg.backend == TRAIN_BACKEND_XGBOOST ? train_bin_bounds_f32(column, n, 1, cfg.max_bin, 0) : train_bin_bounds(column, n, 1, cfg.max_bin);
     *n_bounds = (int)b.size();
     if (out_bounds && cap >= (int)b.size() && !b.empty()) memcpy(out_bounds, b.data(), b.size() * 8);

@@ -1,5 +1,5 @@
-// The boosting loop of the LambdaMART fit and its two growers (train_fit.hpp).  Per iteration the stream is waited for once for the
-// maxima, once per split (LeafGrower) or per level (LevelGrower) for the records, and once when the tree is finished.
+// The boosting loop of the LambdaMART fit and its growers (train_fit.hpp).  Per iteration the stream is waited for once for the
+// maxima, once per split (LeafGrower) or per level (LevelGrower, ExactGrower) for the records, and once when the tree is finished.
 #include "train_fit.hpp"
 
 #include <algorithm>
@@ -8,6 +8,7 @@
 #include <utility>
 
 #include "eval.hpp"
+#include "train_exact.hpp"
 
 namespace mrk {
 
@@ -351,6 +352,118 @@ struct LevelGrower {
   std::string model(const TrainState &t) const { return train_write_xgb_model(trees, (size_t)t.best_iteration, t.cols, &t.kept, &t.is_cat); }
 };
 
+// backend "xgboost", tree_method "exact" (steps 2e, 5e): LevelGrower's tree from sorted columns.  Every column keeps a
+// permutation of the rows ordered by (node segment, value, row); a level is searched by prefix sums over it (train_launch_exact_search),
+// read back once, routed, and - when its children are searched too - partitioned from one permutation buffer into the other.  The
+// segments stay on the device: the partition writes the children's.
+struct ExactGrower {
+  int64_t cap = 0;   // train_level_cap
+  int cols = 0, n_tiles = 0;
+  DevBuf d_perm[2], d_seg[2], d_tile, d_nan, d_base, d_feat, d_edge, d_recs, d_par, d_tcount, d_lbase, d_lend, d_tables, d_value, d_vnode_of;
+  PinBuf h_recs, h_tables, h_value;
+  size_t off_tot = 0, table_bytes = 0;   // one block per level, host -> device in one copy: the level's routes, the next level's totals
+  std::vector<TrainXgbTree> trees;
+
+  void reserve(const TrainState &t) {
+    const TrainConfig &cfg = t.cfg;
+    const size_t rows = (size_t)t.set[0].rows;
+    cap = train_level_cap(cfg, t.set[0].rows), cols = t.cols, n_tiles = (int)((rows + TRAIN_EXACT_TILE - 1) / TRAIN_EXACT_TILE);
+    const size_t nc = (size_t)cap * (size_t)cols, tc = (size_t)n_tiles * (size_t)cols, half = (size_t)cap / 2 + 1;
+    for (DevBuf &b : d_perm) b.reserve(rows * (size_t)cols * 4);
+    for (DevBuf &b : d_seg) b.reserve((size_t)cap * sizeof(ExactSeg));
+    d_tile.reserve(tc * sizeof(ExactSums)), d_nan.reserve(nc * sizeof(ExactSums)), d_base.reserve(nc * sizeof(ExactSums));
+    d_feat.reserve(nc * sizeof(ExactCand)), d_edge.reserve(tc * 2 * sizeof(ExactCand));
+    d_recs.reserve((size_t)cap * sizeof(ExactRec)), h_recs.reserve((size_t)cap * sizeof(ExactRec));
+    d_par.reserve(half * sizeof(ExactSeg)), d_tcount.reserve(tc * 4), d_lbase.reserve(half * (size_t)cols * 4), d_lend.reserve(half * (size_t)cols * 4);
+    off_tot = ((size_t)cap * sizeof(ExactRoute) + 7) / 8 * 8, table_bytes = off_tot + (size_t)cap * sizeof(ExactSums);
+    d_tables.reserve(table_bytes), h_tables.reserve(table_bytes);
+    const size_t max_nodes = std::min<size_t>((size_t(2) << cfg.max_depth), 4 * (size_t)cap + 1);   // (LevelGrower's bound)
+    d_value.reserve(max_nodes * 4), h_value.reserve(max_nodes * 4);
+    if (t.set[1].given) d_vnode_of.reserve((size_t)t.set[1].rows * 2);
+  }
+
+  // -> false when the root cannot split.  node_of: per training row, 0 on entry (train_launch_quantise); on return every row's node.
+  // The stream is waited for once per level that is searched (the level's records), never per node.
+  bool grow(TrainState &t, hipStream_t st, int tree_index, const ScanParams &sp, const long long *qg, const long long *qh, uint16_t *node_of) {
+    mrk_ctx *ctx = t.ctx;
+    const TrainConfig &cfg = t.cfg;
+    TrainSet &tr = t.set[0], &va = t.set[1];
+    ExactRoute *h_route = (ExactRoute *)h_tables.as<uint8_t>();
+    ExactSums *h_tot = (ExactSums *)(h_tables.as<uint8_t>() + off_tot);
+    const ExactRoute *d_route = (const ExactRoute *)d_tables.as<uint8_t>();
+    ExactSums *d_tot = (ExactSums *)(d_tables.as<uint8_t>() + off_tot);
+    const ExactRec *recs = h_recs.as<ExactRec>();
+
+    train_launch_exact_begin(ctx, st, tr.rows, d_seg[0].as<ExactSeg>());
+    if (va.given) MRK_HIP(hipMemsetAsync(d_vnode_of.p, 0, (size_t)va.rows * 2, st));
+    trees.emplace_back();
+    TrainXgbTree &tree = trees.back();
+    tree.add(2147483647);
+    std::vector<TrainSums> totals(1);   // per node
+    std::vector<int> ids{0};            // the nodes of the level, ascending: their segments ascend with them
+    const int *perm = tr.d_order.as<int>();   // every tree starts from the sorted columns
+    for (int d = 0, buf = 0, out = 0; d < cfg.max_depth; ++d) {
+      const int n = (int)ids.size();
+      const ExactDev dev{tr.d_cells.as<float>(), perm, node_of, qg, qh, tr.rows, cols, n_tiles, cfg.sampling, cfg.seed, tree_index};
+      const ExactLevel lv{ids[0], n, n, d_seg[buf].as<ExactSeg>(), d_tot, d_tile.as<ExactSums>(), d_nan.as<ExactSums>(), d_base.as<ExactSums>(),
+                          d_feat.as<ExactCand>(), d_edge.as<ExactCand>(), d_recs.as<ExactRec>()};
+      MRK_HIP(hipMemsetAsync(d_nan.p, 0, (size_t)cols * (size_t)n * sizeof(ExactSums), st));
+      train_launch_exact_search(ctx, st, dev, lv, sp, d == 0);
+      {
+        ScopedKernelTimer timer(ctx, "train_level_readback");
+        MRK_HIP(hipMemcpyAsync(h_recs.p, d_recs.p, (size_t)n * sizeof(ExactRec), hipMemcpyDeviceToHost, st));
+      }
+      MRK_HIP(hipStreamSynchronize(st));   // (h_tables is free again too)
+      if (d == 0) totals[0] = TrainSums{recs[0].g, recs[0].h, recs[0].c};
+      const bool search_next = d + 1 < cfg.max_depth;
+      std::vector<int> next;
+      for (int k = 0; k < n; ++k) {
+        const ExactRec &c = recs[k];
+        h_route[k] = ExactRoute{-1, 0.0f, 0, 0, 0};
+        if (!c.valid) continue;
+        const int node = ids[(size_t)k];
+        const TrainSums whole = totals[(size_t)node];
+        tree.split(node, c.col, 0, c.bound, c.nan_left != 0, (float)c.gain);
+        const int l = tree.num_nodes() - 2;
+        const TrainSums left{c.gl, c.hl, c.cl}, right{whole.g - c.gl, whole.h - c.hl, whole.c - c.cl};
+        totals.push_back(left), totals.push_back(right);
+        h_route[k] = ExactRoute{c.col, c.bound, (uint16_t)l, (uint8_t)(c.nan_left != 0), 0};
+        if (search_next) {
+          h_tot[next.size()] = ExactSums{left.g, left.h, left.c};
+          h_tot[next.size() + 1] = ExactSums{right.g, right.h, right.c};
+        }
+        next.push_back(l), next.push_back(l + 1);
+      }
+      if (next.empty()) break;
+      MRK_HIP(hipMemcpyAsync(d_tables.p, h_tables.p, table_bytes, hipMemcpyHostToDevice, st));
+      train_launch_exact_route(ctx, st, tr.d_cells.as<float>(), tr.rows, node_of, d_route, ids[0], n);
+      if (va.given) train_launch_exact_route(ctx, st, va.d_cells.as<float>(), va.rows, d_vnode_of.as<uint16_t>(), d_route, ids[0], n);
+      if (search_next) {
+        const ExactPart pt{d_route, d_seg[buf].as<ExactSeg>(), ids[0], n, next[0], (int)next.size(), d_par.as<ExactSeg>(), d_seg[buf ^ 1].as<ExactSeg>(),
+                           d_tcount.as<unsigned>(), d_lbase.as<unsigned>(), d_lend.as<unsigned>(), d_perm[out].as<int>()};
+        train_launch_exact_partition(ctx, st, dev, pt);
+        perm = d_perm[out].as<int>(), out ^= 1, buf ^= 1;
+      }
+      ids.swap(next);
+    }
+    if (tree.num_nodes() == 1) {
+      trees.pop_back();
+      return false;
+    }
+    float *value = h_value.as<float>();
+    for (int node = 0; node < tree.num_nodes(); ++node) {
+      tree.weigh(node, totals[(size_t)node], sp.e_g, sp.e_h, cfg.lambda, cfg.learning_rate);
+      value[node] = tree.cond[(size_t)node];   // (read for leaves alone)
+    }
+    MRK_HIP(hipMemcpyAsync(d_value.p, h_value.p, (size_t)tree.num_nodes() * 4, hipMemcpyHostToDevice, st));
+    train_launch_level_apply(ctx, st, d_value.as<float>(), node_of, tr.rows, tr.d_score.as<double>());
+    if (va.given) train_launch_level_apply(ctx, st, d_value.as<float>(), d_vnode_of.as<uint16_t>(), va.rows, va.d_score.as<double>());
+    return true;
+  }
+
+  std::string model(const TrainState &t) const { return train_write_xgb_model(trees, (size_t)t.best_iteration, t.cols, &t.kept, &t.is_cat); }
+};
+
 // the validation metric: eval.hip's kernels on the validation scores (the number mrk_eval_scores gives)
 struct ValidMetric {
   DevBuf d_vgains, d_vrel, d_met, d_cut, d_metric;
@@ -405,7 +518,10 @@ void train_fit(TrainState &t) {
   tab.make(cfg, std::max(tr.max_len, va.given ? va.max_len : 0), st);
   LeafGrower leaf;     // only the backend's grower holds buffers
   LevelGrower level;
-  if (xgb) level.reserve(t);
+  ExactGrower exact;
+  const bool by_order = xgb && cfg.tree_method == TRAIN_TREE_EXACT;
+  if (by_order) exact.reserve(t);
+  else if (xgb) level.reserve(t);
   else leaf.reserve(t);
   DevBuf d_g, d_h, d_qg, d_qh, d_leaf_of;
   d_g.reserve((size_t)rows * 8), d_h.reserve((size_t)rows * 8), d_qg.reserve((size_t)rows * 8), d_qh.reserve((size_t)rows * 8);
@@ -433,7 +549,7 @@ void train_fit(TrainState &t) {
                   cfg.max_cat_to_onehot, cfg.max_cat_threshold, std::max(cfg.min_data_in_leaf, cfg.min_data_per_group), cfg.cat_smooth, cfg.lambda_l2 + cfg.cat_l2, 0.0};
     if (xgb) sp.min_data = 1, sp.min_hess = cfg.min_child_weight, sp.l2 = cfg.lambda, sp.min_gain = cfg.gamma;   // step 5x's admission rule
     train_launch_quantise(ctx, st, gd.g, gd.h, rows, sp.e_g, sp.e_h, qg, qh, leaf_of);
-    if (!(xgb ? level.grow(t, st, it, sp, qg, qh, leaf_of) : leaf.grow(t, st, it, sp, qg, qh, leaf_of))) break;
+    if (!(by_order ? exact.grow(t, st, it, sp, qg, qh, leaf_of) : xgb ? level.grow(t, st, it, sp, qg, qh, leaf_of) : leaf.grow(t, st, it, sp, qg, qh, leaf_of))) break;
     if (va.given) metric.launch(ctx, st, va);
     MRK_HIP(hipStreamSynchronize(st));   // the tree's arrays have left the host; the metric has arrived
     const int n_trees = t.iterations_run = it + 1;   // (every iteration so far has grown a tree)
@@ -457,7 +573,7 @@ void train_fit(TrainState &t) {
   MRK_HIP(hipStreamSynchronize(st));
   drain_profile_events(ctx);
   if (step.bias) t.t_plus.assign(step.tab.t_plus(), step.tab.t_plus() + step.tab.positions), t.t_minus.assign(step.tab.t_minus(), step.tab.t_minus() + step.tab.positions);
-  t.model = xgb ? level.model(t) : leaf.model(t);
+  t.model = by_order ? exact.model(t) : xgb ? level.model(t) : leaf.model(t);
 }
 
 }  // namespace mrk

@@ -1,6 +1,7 @@
 // The LambdaMART fit behind mrk_train_fit (include/mrk.h): one boosting loop (train_fit) over one of two growers -
 // LeafGrower, LightGBM's leaf-wise tree (per split one histogram launch, one scan, two records read back), and LevelGrower, XGBoost's
-// level-wise tree (per level one histogram launch, one scan, the level's records read back once).  The kernels are train.hip, the
+// level-wise tree (per level one histogram launch, one scan, the level's records read back once) - or, tree_method "exact", ExactGrower:
+// the same level-wise tree from sorted columns (train_exact.hip).  The kernels are train.hip, the
 // host half train_host.cpp; capi_train.cpp holds the trainer handle, mrk_train_set and the C ABI.
 #pragma once
 #include <string>
@@ -22,6 +23,7 @@ struct TrainSet {
   std::vector<int64_t> offsets;
   EvalBins by_size;
   DevBuf d_bins, d_labels, d_off, d_wave, d_group, d_score, d_best;   // d_score, d_best: reserved by mrk_train_set, first written by train_fit
+  DevBuf d_cells, d_order;          // tree_method "exact" (step 2e) in place of d_bins: the f32 matrix [cols][rows]; the training set: every column's rows by (value, row)
   std::vector<double> gains;        // the validation set: what eval.hip reads (eval_pack_labels, relpow)
   std::vector<uint8_t> rel;
   std::vector<double> scores;       // at the best iteration, after the fit

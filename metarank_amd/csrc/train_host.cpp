@@ -24,7 +24,7 @@ TrainConfig train_parse_config(const char *text, size_t len) {
   static const char *known[] = {"iterations", "learningRate", "ndcgCutoff", "maxDepth", "seed", "numLeaves", "sampling", "debias", "max_bin", "truncation",
                                 "sigma", "min_data_in_leaf", "min_sum_hessian", "lambda_l2", "early_stopping", "categorical", "max_cat_to_onehot",
                                 "max_cat_threshold", "cat_smooth", "cat_l2", "min_data_per_group", "backend", "lambda", "gamma", "min_child_weight", "position_bias",
-                                "feature_types"};
+                                "feature_types", "tree_method"};
   for (auto &kv : root.obj) {
     bool ok = false;
     for (const char *k : known) ok = ok || kv.first == k;
@@ -40,7 +40,7 @@ TrainConfig train_parse_config(const char *text, size_t len) {
   {  // a key of the other backend is refused, not ignored: it would be a setting that silently does nothing
     static const char *lgb_only[] = {"numLeaves", "min_data_in_leaf", "min_sum_hessian", "lambda_l2", "max_cat_to_onehot", "max_cat_threshold", "cat_smooth", "cat_l2",
                                      "min_data_per_group"};
-    static const char *xgb_only[] = {"lambda", "gamma", "min_child_weight", "feature_types"};
+    static const char *xgb_only[] = {"lambda", "gamma", "min_child_weight", "feature_types", "tree_method"};
     auto refuse = [&](const char *key, const char *backend) {
       const json::Value *v = root.find(key);
       if (v && !v->is_null()) range(std::string(key) + " is not a key of the " + backend + " backend");
@@ -162,6 +162,14 @@ TrainConfig train_parse_config(const char *text, size_t len) {
       for (size_t k = 0; k < v->arr.size(); ++k)
         if (v->arr[k].str == "c") c.categorical.push_back((int32_t)k);
     }
+  if (const json::Value *v = root.find("tree_method"))
+    if (!v->is_null()) {   // (backend "xgboost": refused above under the other) XGBoost's own spelling
+      if (v->type != json::Type::String) bad("'tree_method' is not a string");
+      if (v->str == "exact") c.tree_method = TRAIN_TREE_EXACT;
+      else if (v->str != "hist") range("tree_method = '" + v->str + "' (hist or exact)");
+    }
+  if (c.tree_method == TRAIN_TREE_EXACT && !c.categorical.empty())
+    throw StatusError(MRK_ERR_UNSUPPORTED, "train config: tree_method 'exact' has no categorical splits: feature_types holds a 'c'");
   if (c.debias) throw StatusError(MRK_ERR_UNSUPPORTED, "train config: debias carries neither the number of positions nor the norm: use position_bias");
   if (c.num_leaves > TRAIN_MAX_LEAVES)
     throw StatusError(MRK_ERR_UNSUPPORTED, "train config: numLeaves = " + std::to_string(c.num_leaves) + " (limit " + std::to_string(TRAIN_MAX_LEAVES) + ")");
@@ -374,7 +382,18 @@ int train_exponent(double vmax, int64_t rows) {
 
 int64_t train_level_cap(const TrainConfig &cfg, int64_t rows) { return std::max<int64_t>(1, std::min<int64_t>(int64_t(1) << (cfg.max_depth - 1), rows)); }
 
+// step 2e / 5e: no bins and no histograms.  Per cell the f32 value (4) and - the training set - three permutations (the sorted order every
+// tree starts from and the two a level's partition goes between); per (column, tile) a triple of sums (24), a left count (4) and two
+// edge records (2 x 48); per (column, node of a level) the NaN sums, the base (24 each), a record (48) and the partition's two counts
+static double train_exact_bytes(const TrainConfig &cfg, int which, double rows, double cols, double groups, int64_t rows_) {
+  const double per_row = (which == 0 && cfg.position_bias ? 67.0 : 51.0) * rows + 2.0 * rows, group_lists = 12.0 * groups;
+  if (which == 1) return 4.0 * rows * cols + per_row + group_lists + (9.0 * rows + 8.0 * groups);
+  const double tiles = std::ceil(rows / 1024.0), cap = (double)train_level_cap(cfg, rows_);
+  return 16.0 * rows * cols + per_row + group_lists + cols * tiles * 124.0 + cols * cap * 104.0 + cap * 256.0;
+}
+
 double train_fit_bytes(const TrainConfig &cfg, int which, int64_t rows_, int cols, int64_t n_groups_) {
+  if (cfg.tree_method == TRAIN_TREE_EXACT) return train_exact_bytes(cfg, which, (double)rows_, (double)cols, (double)n_groups_, rows_);
   const bool xgb = cfg.backend == TRAIN_BACKEND_XGBOOST;
   const double rows = (double)rows_, groups = (double)n_groups_, rec = TRAIN_LEAF_REC_BYTES;
   const double n_sub = xgb ? (double)cols : (double)train_feature_subset(cols, cfg.sampling, 0, 0).size();

@@ -61,8 +61,10 @@ struct TrainConfig {
   bool position_bias = false;         // "position_bias": an object (step 3b) - its keys: positions, norm
   int bias_positions = 32;
   double bias_norm = 1.0;
+  int tree_method = 0;                // backend "xgboost", "tree_method": 0 "hist" (steps 2x, 5x), 1 "exact" (steps 2e, 5e: no bins, max_bin unused)
 };
 constexpr int TRAIN_BACKEND_LIGHTGBM = 0, TRAIN_BACKEND_XGBOOST = 1;
+constexpr int TRAIN_TREE_HIST = 0, TRAIN_TREE_EXACT = 1;
 constexpr int TRAIN_XGB_MAX_DEPTH = 15;     // a node id is a u16: a complete tree of depth 15 has 65535 nodes
 // malformed JSON, a value of the wrong type or an unknown key: MRK_ERR_PARSE; a value out of range: MRK_ERR_INVALID_ARG;
 // debias = true or numLeaves > TRAIN_MAX_LEAVES: MRK_ERR_UNSUPPORTED.  backend "xgboost": numLeaves, min_data_in_leaf,
@@ -70,6 +72,8 @@ constexpr int TRAIN_XGB_MAX_DEPTH = 15;     // a node id is a u16: a complete tr
 // `categorical` is MRK_ERR_UNSUPPORTED; backend "lightgbm": lambda, gamma, min_child_weight and feature_types are MRK_ERR_INVALID_ARG.
 // feature_types (backend "xgboost"): not an array or an entry that is no string: MRK_ERR_PARSE; an entry other than "q" / "c":
 // MRK_ERR_INVALID_ARG.  Its "c" entries become `categorical` (steps 2cx, 5cx)
+// tree_method (backend "xgboost"): not a string: MRK_ERR_PARSE; a string other than "hist" / "exact": MRK_ERR_INVALID_ARG; "exact" with a
+// "c" in feature_types: MRK_ERR_UNSUPPORTED
 // position_bias (either backend): not an object, a key inside other than positions / norm or one that is no number: MRK_ERR_PARSE;
 // positions outside 1 ... TRAIN_MAX_GROUP, norm negative or not finite: MRK_ERR_INVALID_ARG
 TrainConfig train_parse_config(const char *json, size_t len);

@@ -209,7 +209,9 @@ def fit_lambdamart(X, labels, group_offsets, valid=None, ctx: Context | None = N
     history["position_bias"] is (t_plus, t_minus) after the last iteration.
     backend="xgboost" names them per column instead: feature_types=feature_types(ranker.values_columns()), "q" or "c" each.
     backend="xgboost": the level-wise fit; the model is XGBoost's JSON and the booster is loaded as an XGBoost one; scores are the f32
-    sums the model predicts (from its base_score 0.5), widened."""
+    sums the model predicts (from its base_score 0.5), widened.  tree_method="exact" (XGBoost's spelling, what the reference runs):
+    a candidate between every two neighbouring values of a node's rows instead of at most 254 bounds a column (include/mrk.h steps 2e,
+    5e); "hist", the default, is the histogram grower."""
     ctx = ctx or default_context()
     t = Trainer(config, ctx)
     try:

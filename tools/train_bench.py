@@ -23,7 +23,7 @@ leaves it -, appended in 16 pieces and sealed (include/mrk.h step 2d: bins on th
 hand-over, the HIP-event phases of step 2d's kernels (train_stage, train_check, train_keys, train_sort, train_cuts,
 train_cat_counts, train_bin), the clock around the fit and the SHA-256 of the fitted model; the tool exits 1 unless every model is
 the same.
-  python tools/train_bench.py [--json] [--device-set] [--backend lightgbm|xgboost] [--depth D] [--groups N] [--min-items N] [--max-items N] [--iterations N] [--leaves N] [--ref-groups N] [--valid]
+  python tools/train_bench.py [--json] [--device-set] [--backend lightgbm|xgboost] [--tree-method hist|exact] [--depth D] [--groups N] [--min-items N] [--max-items N] [--iterations N] [--leaves N] [--ref-groups N] [--valid]
                               [--categorical N] [--device-set]
 """
 import argparse
@@ -47,6 +47,10 @@ from workloads import synth  # noqa: E402
 
 TIMERS = ("train_bin", "train_grad", "train_hist", "train_scan", "train_apply", "train_eval")
 LEVEL_TIMERS = ("train_bin", "train_grad", "train_level_hist", "train_level_scan", "train_level_split", "train_level_readback", "train_apply", "train_eval")
+# --tree-method exact (steps 2e, 5e): per level the sums (2 launches), the candidates and the pick (2), one read-back, the routing passes
+# and - when the children are searched too - the partition (4)
+EXACT_TIMERS = ("train_bin", "train_sort", "train_grad", "train_exact_sums", "train_exact_candidates", "train_exact_route", "train_exact_partition",
+                "train_level_readback", "train_apply", "train_eval")
 BIAS_TIMERS = ("train_grad_bias", "train_pos_sum", "train_bias_readback")   # step 3b: the biased LambdaRank kernels, the position sums, their copy back
 COLS = 24
 
@@ -75,17 +79,21 @@ def main():
     ap.add_argument("--categorical", type=int, default=0, help="declare the last N columns categorical; their cells are rounded to ids 0 ... 49 (NaN stays)")
     ap.add_argument("--backend", choices=("lightgbm", "xgboost"), default="lightgbm")
     ap.add_argument("--depth", type=int, default=8, help="maxDepth of the xgboost backend")
+    ap.add_argument("--tree-method", choices=("hist", "exact"), default="hist", help="the xgboost backend's split search: histograms or sorted columns")
     ap.add_argument("--device-set", action="store_true", help="mrk_train_set from the host against append + seal from device memory, three runs each")
     ap.add_argument("--position-bias", action="store_true", help='fit with "position_bias": {} (step 3b) and count its launches')
     a = ap.parse_args()
     xgb = a.backend == "xgboost"
-    timers = (LEVEL_TIMERS if xgb else TIMERS) + (BIAS_TIMERS if a.position_bias else ())
+    by_order = xgb and a.tree_method == "exact"
+    timers = (EXACT_TIMERS if by_order else LEVEL_TIMERS if xgb else TIMERS) + (BIAS_TIMERS if a.position_bias else ())
     ctx = M.Context(0)
     X, y, off = synth.synthetic_ranking_rows(a.groups, a.min_items, a.max_items, COLS, seed=0)
     rows = int(off[-1])
     cfg = {"iterations": a.iterations, "numLeaves": a.leaves, "early_stopping": a.iterations}
     if xgb:
         cfg = {"backend": "xgboost", "iterations": a.iterations, "maxDepth": a.depth, "early_stopping": a.iterations}
+    if by_order:
+        cfg["tree_method"] = "exact"
     if a.position_bias:
         cfg["position_bias"] = {}
     cats = list(range(COLS - a.categorical, COLS))
@@ -96,7 +104,7 @@ def main():
         else:
             cfg["categorical"] = cats
     out = {"groups": a.groups, "rows": rows, "items_per_group": [a.min_items, a.max_items], "columns": COLS, "iterations": a.iterations, "leaves": a.leaves,
-           "backend": a.backend, "depth": a.depth if xgb else None, "categorical": cats, "build": N.lib().mrk_build_id().decode()}
+           "backend": a.backend, "tree_method": a.tree_method if xgb else None, "depth": a.depth if xgb else None, "categorical": cats, "build": N.lib().mrk_build_id().decode()}
     if a.device_set:
         return device_set(a, ctx, cfg, out, X, y, off)
 
@@ -221,6 +229,8 @@ def finish_xgboost(a, ctx, out, parts, hist, model, X, y, off, rows):
     out["splits"] = sum(sum(1 for l in t["left_children"] if l >= 0) for t in trees)
     out["categorical_nodes"] = sum(len(t["categories_nodes"]) for t in trees)
     bound = hist["iterations_run"] * a.depth                             # derived: one launch / read-back per level that can still split
+    if a.tree_method == "exact":
+        return finish_exact(a, ctx, out, parts, hist, bound)
     counts = {name: int(parts[name][1]) for name in LEVEL_TIMERS}
     out["launches"] = {"per_phase": counts, "bound_trees_x_depth": bound, "histogram": counts["train_level_hist"], "scan": counts["train_level_scan"],
                        "record_readbacks": counts["train_level_readback"]}
@@ -238,6 +248,23 @@ def finish_xgboost(a, ctx, out, parts, hist, model, X, y, off, rows):
         out["restatement_rows"] = r
         out["restatement_us_per_row_iteration"] = out["restatement_one_iteration_ms"] * 1e3 / r
         out["device_us_per_row_iteration"] = out["fit_call_ms"] * 1e3 / (rows * max(hist["iterations_run"], 1))
+    ctx.close()
+    print(json.dumps(out) if a.json else json.dumps(out, indent=1))
+    if not out["launches"]["within_bound"]:
+        sys.exit(1)
+
+
+def finish_exact(a, ctx, out, parts, hist, bound):
+    """per level that can still split: ONE search (its timers span 2 launches each), ONE read-back, at most ONE partition (4 launches)"""
+    counts = {name: int(parts[name][1]) for name in EXACT_TIMERS}
+    out["launches"] = {"per_phase": counts, "bound_trees_x_depth": bound, "sums": counts["train_exact_sums"], "candidates": counts["train_exact_candidates"],
+                       "partitions": counts["train_exact_partition"], "record_readbacks": counts["train_level_readback"]}
+    out["launches"]["within_bound"] = all(out["launches"][k] <= bound for k in ("sums", "candidates", "partitions", "record_readbacks"))
+    device_ms = sum(parts[name][0] for name in EXACT_TIMERS if name not in ("train_bin", "train_sort"))
+    out["phase_ms"] = {name: parts[name][0] for name in EXACT_TIMERS}
+    out["fit_device_phases_ms"] = device_ms
+    out["fit_host_and_sync_ms_per_readback"] = (out["fit_call_ms"] - device_ms) / max(counts["train_level_readback"], 1)
+    out["fit_ms_per_tree"] = out["fit_call_ms"] / max(hist["iterations_run"], 1)
     ctx.close()
     print(json.dumps(out) if a.json else json.dumps(out, indent=1))
     if not out["launches"]["within_bound"]:
