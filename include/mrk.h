@@ -1033,14 +1033,24 @@ int mrk_model_eval(mrk_model *model, const int *metrics, const int *cutoffs, int
  *              spelling.  Absent, null or "hist": steps 2x / 5x, the bytes of a fit without the key.  "exact" - what the reference runs
  *              (treeMethod = "exact", LambdaMARTRanker.scala:176-188): steps 2e / 5e in their place, everything else unchanged.  Another
  *              string is MRK_ERR_INVALID_ARG naming key and value, a value that is no string MRK_ERR_PARSE.  Under "exact" max_bin is
- *              ignored, and these are MRK_ERR_UNSUPPORTED naming tree_method: a "c" in feature_types, mrk_train_append_device,
- *              mrk_train_seal, mrk_train_bounds and mrk_train_bins.  tests/train_xgb_exact_reference.py restates 2e and 5e.
+ *              ignored, and these are MRK_ERR_UNSUPPORTED naming tree_method: a "c" in feature_types without enable_categorical,
+ *              mrk_train_append_device, mrk_train_seal, mrk_train_bounds and mrk_train_bins.  tests/train_xgb_exact_reference.py
+ *              restates 2e and 5e.
+ *  enable_categorical [false; tree_method "exact" alone]: XGBoost's own spelling.  true admits "c" entries of feature_types under
+ *              "exact" - the configuration the reference runs - by steps 2ec / 5ec; absent, null or false the refusal above stands.
+ *              Not a Boolean: MRK_ERR_PARSE.  Under the default backend, or under tree_method "hist" whether spelled or defaulted (it
+ *              trains a "c" column without the key: the key would do nothing), MRK_ERR_INVALID_ARG naming itself.  With an all-"q"
+ *              list the key changes no byte.  tests/train_xgb_exact_cat_reference.py restates 2ec and 5ec by composing the two others.
  *  2e no bins  the cells are narrowed to f32 exactly as in 2x (round to nearest even, -0.0f as +0.0f, a finite f64 that narrows to
  *              +-inf refused naming column and row, in either set).  The f32 matrix stays on the device, column-major, and every
  *              column's rows are ordered ONCE by (narrowed value, row), NaN last - step 2d's keys and sort.
  *              Device memory: rows x cols x 16 bytes (the f32 cell, the sorted order every tree starts from and the two permutations
  *              a level's partition goes between) plus the sums per (column, tile of 1024 positions) and per (column, node of a level);
  *              checked against free memory at mrk_train_set, MRK_ERR_UNSUPPORTED with the sizes.
+ *  2ec "c"     (enable_categorical) a "c" column's cells are narrowed, refused (an f32-infinite cell, in a "c" column too) and ordered
+ *              exactly as 2e's; their category, the kept ids (counted on the training cells at mrk_train_set; max_bin - 2 of them,
+ *              253 by default), "other" (bin 254, always left) and NaN (bin 255) are 2cx's word for word.  One more byte a training
+ *              cell and, per "c" column and node of the widest level, 256 sums and a mask are held on the device: in the check above.
  *  5e tree     5x with "bin" read as "position among the node's distinct values".  At an open node and a column there is a candidate
  *              between every pair of neighbouring DISTINCT non-NaN values a < b that occur in the node's rows - sampled and unsampled
  *              rows alike say where values change (as a bin that holds only unsampled rows does in 5x); only sampled rows carry sums
@@ -1052,6 +1062,11 @@ int mrk_model_eval(mrk_model *model, const int *metrics, const int *cutoffs, int
  *              Consequence: where no bin of 2x holds two values AND every node that splits holds rows at both global neighbours of
  *              its bound (5x names the lowest bound of a run of empty bins, 5e the node's own next value - the same partition of the
  *              node's rows, another number in the model), "exact" emits the bytes of "hist".
+ *  5ec tree    (enable_categorical) a "q" column is searched by 5e, a "c" column is judged by 5cx - the same candidates (one against
+ *              the rest below 4 kept categories, else the sorted partitions of at most 64), the same sums over the sampled rows, the
+ *              same ties, the same model text: none of it loses anything to bins.  Across columns the highest gain wins, then the
+ *              lowest column, "q" and "c" alike.  A categorical record's left sums include "other", and NaN when it goes left.
+ *              Consequence: a fit whose columns are all "c" emits the bytes of "hist".
  *  6x scores   f32, as the model predicts them: s = 0.5f (the base_score), then s = s + leaf in f32, in tree order.  Training rows -
  *              the unsampled ones too - and validation rows take the leaf their bins route them to.  mrk_train_scores returns the
  *              widened value, equal to mrk_model_predict_f64 of the emitted model bit for bit; without a tree every score is 0.5.

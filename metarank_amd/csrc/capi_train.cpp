@@ -122,8 +122,10 @@ void refuse_by_order(const mrk_trainer *t, const char *what) {
 // the training set's column c on the host: its bounds, or its kept category ids
 void find_bins(mrk_trainer *t, const double *x, int64_t rows, int c) {
   const size_t k = (size_t)c;
-  if (by_order(t)) train_check_f32_cells(x + c, rows, t->cols, c);   // step 2e keeps step 2x's refusal and finds nothing
-  else if (bins_in_f32(t) && t->is_cat[k]) t->kept[k] = train_xgb_kept_categories(x + c, rows, t->cols, t->cfg.max_bin, c);
+  if (by_order(t)) {   // step 2e keeps step 2x's refusal - in a "c" column too - and finds nothing but a "c" column's kept ids (step 2ec: 2cx's count)
+    train_check_f32_cells(x + c, rows, t->cols, c);
+    if (t->is_cat[k]) t->kept[k] = train_xgb_kept_categories(x + c, rows, t->cols, t->cfg.max_bin, c);
+  } else if (bins_in_f32(t) && t->is_cat[k]) t->kept[k] = train_xgb_kept_categories(x + c, rows, t->cols, t->cfg.max_bin, c);
   else if (bins_in_f32(t)) t->bounds[k] = train_bin_bounds_f32(x + c, rows, t->cols, t->cfg.max_bin, c);
   else if (t->is_cat[k]) t->kept[k] = train_kept_categories(x + c, rows, t->cols, t->cfg.max_bin, c, &t->infos[k]);
   else t->bounds[k] = train_bin_bounds(x + c, rows, t->cols, t->cfg.max_bin, &t->infos[k]);
@@ -135,9 +137,9 @@ void check_other_cells(const mrk_trainer *t, const double *x, int64_t rows, int 
     if (std::isinf(x[i])) throw StatusError(MRK_ERR_INVALID_ARG, "train: cell " + std::to_string(i) + " of the validation matrix is infinite");
   if (!bins_in_f32(t))
     for (int32_t c : t->cfg.categorical) train_check_categories(x + c, rows, cols, c);
-  else   // (step 2cx refuses nothing: a cell of a "c" column that is not finite as an f32 is "other")
+  else   // (step 2cx refuses nothing: a cell of a "c" column that is not finite as an f32 is "other"; step 2e refuses it in every column)
     for_columns(cols, [&](int c) {
-      if (!t->is_cat[(size_t)c]) train_check_f32_cells(x + c, rows, cols, c);
+      if (by_order(t) || !t->is_cat[(size_t)c]) train_check_f32_cells(x + c, rows, cols, c);
     });
 }
 
@@ -204,7 +206,9 @@ void check_budget(const mrk_trainer *t, int which, int64_t rows, int cols, int64
   const size_t order_bytes = by_order(t) && which == 0 ? train_exact_order_scratch_bytes(rows) : 0;   // (while a column is ordered)
   check_free(train_fit_bytes(t->cfg, which, rows, cols, n_groups) + (double)std::max(piece_bytes, order_bytes) + 1048576.0,
              std::to_string(rows) + " rows x " + std::to_string(cols) + " columns in " + std::to_string(n_groups) + " groups, " +
-                 (by_order(t) ? "tree_method 'exact': f32 cells and 3 permutations (16 bytes a cell), the sums of " + std::to_string(train_level_cap(t->cfg, rows)) + " nodes x "
+                 (by_order(t) ? "tree_method 'exact': f32 cells and 3 permutations (16 bytes a cell), " +
+                                    (t->cfg.categorical.empty() ? std::string() : std::to_string(t->cfg.categorical.size()) + " 'c' columns (a byte a cell, 256 sums of 24 bytes and a mask of 32 a node), ") +
+                                    "the sums of " + std::to_string(train_level_cap(t->cfg, rows)) + " nodes x "
                   : xgb ? "2 levels x " + std::to_string(train_level_cap(t->cfg, rows)) + " nodes x " : std::to_string(t->cfg.num_leaves) + " leaves x ") + std::to_string(n_sub) +
                  " columns of histograms");
 }
@@ -234,6 +238,19 @@ void order_columns(const mrk_trainer *t, TrainSet &s, hipStream_t st) {
   d_scratch.reserve(train_exact_order_scratch_bytes(s.rows));
   for (int c = 0; c < t->cols; ++c) train_launch_exact_order(t->ctx, st, s.d_cells.as<float>() + (size_t)c * rows, (int)s.rows, d_scratch.p, s.d_order.as<int>() + (size_t)c * rows);
   MRK_HIP(hipStreamSynchronize(st));     // d_scratch goes
+}
+
+// step 2ec: the "c" columns' lists and the training cells' bins, one byte each, [n_cat][rows] in the place the histogram growers keep theirs
+void bin_categories_by_order(mrk_trainer *t, TrainSet &s, hipStream_t st) {
+  std::vector<int> cat_of((size_t)t->cols, -1);
+  for (size_t j = 0; j < t->cfg.categorical.size(); ++j) cat_of[(size_t)t->cfg.categorical[j]] = (int)j;   // (feature_types' "c" entries: ascending)
+  upload(t->d_cat_cols, t->cfg.categorical, st);
+  upload(t->d_cat_of, cat_of, st);
+  s.d_bins.reserve((size_t)s.rows * t->cfg.categorical.size());
+  ExactCat cat{};
+  cat.n_cat = (int)t->cfg.categorical.size(), cat.cols = t->d_cat_cols.as<int>(), cat.cat_idx = t->d_cat_idx.as<int>(), cat.cat_tables = t->d_cat_tables.as<uint8_t>();
+  train_launch_exact_cat_bins(t->ctx, st, s.d_cells.as<float>(), s.rows, cat, s.d_bins.as<uint8_t>());
+  MRK_HIP(hipStreamSynchronize(st));     // cat_of is a local
 }
 
 // the labels and the lists of groups; d_score and d_best are reserved here and first written by the fit
@@ -273,6 +290,7 @@ void set_locked(mrk_trainer *t, int which, const double *x, int64_t rows, int co
   if (which == 0) upload_tables(t, lk.stream);
   upload_set(t, s, x, pieces, piece_bytes, lk.stream);
   if (by_order(t) && which == 0) order_columns(t, s, lk.stream);
+  if (by_order(t) && which == 0 && t->any_cat) bin_categories_by_order(t, s, lk.stream);
   drain_profile_events(t->ctx);
   s.given = true;
 }

@@ -13,7 +13,10 @@
 //                             that hold that gain, then that one lane writes the record - of the node when it lies inside the tile, of
 //                             the tile's edge when it goes on before or behind it
 //   train_exact_pick          per node: the best over columns and the tiles it spans (gain, then column, then position, then NaN right)
-//   train_exact_route         a row pass: (float) x < bound, NaN by nan_left
+//   train_exact_route<CAT>    a row pass: (float) x < bound, NaN by nan_left; <true>: a level with a categorical route, its masks over bins in LDS
+//   train_exact_cat_bins / _cat_sums / _cat_scan   "c" columns (enable_categorical; steps 2ec, 5ec): a byte per training cell;
+//                             per level the sums per (node, bin) from the RUNS of equal categories in the column's order - one atomic triple
+//                             per piece of a run inside a tile -, then step 5cx's scan over them (train_scan_device.hpp: train.hip's text)
 //   train_exact_parents / _count / _count_offsets / _scatter   the stable partition: per column a prefix count of the rows that went
 //                             left, the same prefix-minus-base trick; the left ROW count of a node fixes its children's segments
 // Integer sums only, nothing depends on the order anything runs in; every gain is f64, correctly rounded, never fused.
@@ -27,6 +30,7 @@
 #include "sort_device.hpp"
 #include "train_exact.hpp"
 #include "train_host.hpp"
+#include "train_scan_device.hpp"
 
 namespace mrk {
 
@@ -71,11 +75,15 @@ train_exact_small_sort_kernel(const u64 *__restrict__ keys, int n, int *__restri
   for (int i = threadIdx.x; i < n; i += 1024) order[i] = s_idx[i];
 }
 
-__device__ __forceinline__ double real_of(long long q, int e) { return ldexp((double)q, -e); }   // (the conversion rounds to nearest even)
+// (real_of and side_term: train_scan_device.hpp)
 
-__device__ __forceinline__ double side_term(long long qg, long long qh, const ScanParams &p) {
-  const double G = real_of(qg, p.e_g), H = real_of(qh, p.e_h);
-  return __ddiv_rn(__dmul_rn(G, G), __dadd_rn(H, p.l2));
+// plane[j][row]: the bin of step 2cx of the f32 cell.  blockIdx: (256 rows, "c" column)
+__global__ void __launch_bounds__(TRAIN_BIN_ROWS)
+train_exact_cat_bins_kernel(const float *__restrict__ cells, long long rows, ExactCat cat, uint8_t *__restrict__ plane) {
+  const long long i = (long long)blockIdx.x * TRAIN_BIN_ROWS + threadIdx.x;
+  if (i >= rows) return;
+  const int j = blockIdx.y, col = cat.cols[j];
+  plane[(long long)j * rows + i] = (uint8_t)train_xgb_category_bin((double)cells[(long long)col * rows + i], cat.cat_tables + cat.cat_idx[2 * col], cat.cat_idx[2 * col + 1]);
 }
 
 // every lane brings the sum of its own positions and leaves with the sum of the lanes before it; tot: the workgroup's.  One barrier
@@ -116,10 +124,13 @@ __device__ __forceinline__ unsigned block_excl_scan1(unsigned v, unsigned *s_w, 
   return x - v + before;
 }
 
-// blockIdx: (tile, column).  CAND false: the first pass of a level; true: its candidates
-template <bool CAND>
+// blockIdx: (tile, column).  CAND false: the first pass of a level; true: its candidates.  CATS: the fit has "c" columns (the host picks
+// the form: without one the kernels hold no line of step 5ec and are the instructions they were before it)
+template <bool CAND, bool CATS>
 __global__ void __launch_bounds__(EX_THREADS)
-train_exact_scan_kernel(ExactDev d, ExactLevel lv, ScanParams sp) {
+train_exact_scan_kernel(ExactDev d, ExactLevel lv, ScanParams sp, const int *__restrict__ cat_of) {
+  if constexpr (CATS)
+    if (cat_of[blockIdx.y] >= 0) return;   // a "c" column (the same for the whole workgroup): step 5ec searches it
   __shared__ float s_val[EX_TILE + 1];
   __shared__ int s_k[EX_TILE + 1];          // a position's node slot, -1: none (a finished leaf, or behind the last row)
   __shared__ long long s_w[3][EX_THREADS / 64];
@@ -276,14 +287,18 @@ __device__ __forceinline__ void column_excl_scan3(ExactSums *vals, int n, long l
   }
 }
 
+// root: 0, or 1 + the column whose total becomes the root's (the first "q" column)
+template <bool CATS>
 __global__ void __launch_bounds__(EX_THREADS)
-train_exact_offsets_kernel(ExactLevel lv, int n_tiles, int root) {
+train_exact_offsets_kernel(ExactLevel lv, int n_tiles, int root, const int *__restrict__ cat_of) {
   __shared__ long long s_w[3][EX_THREADS / 64];
   const int col = blockIdx.x;
+  if constexpr (CATS)
+    if (cat_of[col] >= 0) return;   // (the first pass wrote nothing for a "c" column)
   ExactSums *tile = lv.tile + (size_t)col * (size_t)n_tiles;
   long long tot[3];
   column_excl_scan3(tile, n_tiles, s_w, tot);
-  if (root && col == 0 && threadIdx.x == 0) lv.tot[0] = ExactSums{tot[0], tot[1], tot[2]};
+  if (col == root - 1 && threadIdx.x == 0) lv.tot[0] = ExactSums{tot[0], tot[1], tot[2]};
   __syncthreads();   // (the prefixes were written by other lanes of this workgroup)
   for (int k = threadIdx.x; k < lv.n; k += EX_THREADS) {
     const ExactSums tp = tile[lv.seg[k].start / EX_TILE];
@@ -292,9 +307,107 @@ train_exact_offsets_kernel(ExactLevel lv, int n_tiles, int root) {
   }
 }
 
-// one workgroup per node: the best record over the columns and - for a node that spans tiles - over their edge records
+// Step 5ec's sums.  blockIdx: (tile, "c" column).  Ordered by value, the rows of one category are a RUN inside a node's segment, so the
+// level's sums per (node, bin) come from the tile's prefix sums and not from the rows one by one: a PIECE is a maximal stretch of equal
+// (slot, bin) inside the tile; the lane that holds a piece's last position adds incl[last] - excl[first] to hist[column][slot][bin]
+// with three 64-bit integer atomics, where the pieces of a run that straddles tiles meet.  A row outside the tree's sample stays inside
+// its piece and adds nothing - it would otherwise cut a run in two wherever it stands -; a piece without a sampled row adds nothing; a
+// row of a finished leaf belongs to no piece.  Where a piece began: a max-scan over "my own index where a piece starts here, else -1" -
+// lane-local over four positions, shuffles inside the wavefront, four wavefront carries through LDS.  The inclusive prefixes go through
+// LDS (3 x 8 B x 1024 = 24 KiB) for the one read at first - 1.  Integer sums: nothing depends on the order the workgroups run in.
 __global__ void __launch_bounds__(EX_THREADS)
-train_exact_pick_kernel(ExactLevel lv, int cols, int n_tiles) {
+train_exact_cat_sums_kernel(ExactDev d, ExactLevel lv, ExactCat cat) {
+  __shared__ long long s_incl[3][EX_TILE];
+  __shared__ int s_key[EX_TILE];               // slot * 256 + bin, -1: no piece
+  __shared__ long long s_w[3][EX_THREADS / 64];
+  __shared__ int s_first[EX_THREADS / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, tile = blockIdx.x, j = blockIdx.y;
+  const long long tile0 = (long long)tile * EX_TILE;
+  const int *perm = d.perm + (long long)cat.cols[j] * d.rows;
+  const uint8_t *plane = cat.plane + (long long)j * d.rows;
+  long long g[EX_PER], h[EX_PER], c[EX_PER];   // the lane's own triples, then their running sums
+  int key[EX_PER];
+#pragma unroll
+  for (int q = 0; q < EX_PER; ++q) {
+    const int i = tid * EX_PER + q;
+    const long long p = tile0 + i;
+    g[q] = 0, h[q] = 0, c[q] = 0, key[q] = -1;
+    if (p < d.rows) {
+      const int row = min(max(perm[p], 0), (int)d.rows - 1);   // (a permutation: the clamp changes nothing and keeps every gather inside)
+      const unsigned s = (unsigned)d.node_of[row] - (unsigned)lv.first;
+      if (s < (unsigned)lv.n) {
+        key[q] = (int)s * 256 + plane[row];
+        if (train_row_sampled(d.sampling, d.seed, d.tree, (u64)row)) g[q] = d.qg[row], h[q] = d.qh[row], c[q] = 1;
+      }
+    }
+    s_key[i] = key[q];
+  }
+#pragma unroll
+  for (int q = 1; q < EX_PER; ++q) g[q] += g[q - 1], h[q] += h[q - 1], c[q] += c[q - 1];
+  long long eg = g[EX_PER - 1], eh = h[EX_PER - 1], ec = c[EX_PER - 1], tot[3];
+  block_excl_scan3(eg, eh, ec, s_w, tot);   // (its barrier publishes s_key)
+  int first[EX_PER], run = -1;               // the latest piece start among the lane's positions up to q, -1: none yet
+#pragma unroll
+  for (int q = 0; q < EX_PER; ++q) {
+    const int i = tid * EX_PER + q;
+    s_incl[0][i] = eg + g[q], s_incl[1][i] = eh + h[q], s_incl[2][i] = ec + c[q];
+    const int prev = q ? key[q - 1] : tid ? s_key[i - 1] : -2;   // (-2: no key - position 0 starts a piece)
+    if (key[q] != prev) run = i;
+    first[q] = run;
+  }
+  int m = run;
+  for (int dd = 1; dd < 64; dd <<= 1) {
+    const int t = __shfl_up(m, dd, 64);
+    if (lane >= dd) m = max(m, t);
+  }
+  if (lane == 63) s_first[wave] = m;
+  int before = __shfl_up(m, 1, 64);   // the latest start among the positions of the lanes before this one
+  if (lane == 0) before = -1;
+  __syncthreads();   // s_incl, s_first
+  for (int w = 0; w < wave; ++w) before = max(before, s_first[w]);
+#pragma unroll
+  for (int q = 0; q < EX_PER; ++q) {
+    const int i = tid * EX_PER + q;
+    const int next = q + 1 < EX_PER ? key[q + 1] : i + 1 < EX_TILE ? s_key[i + 1] : -2;
+    if (key[q] < 0 || key[q] == next) continue;   // not a piece's last position
+    const int f = max(first[q], before);          // (0 <= f <= i: position 0 starts a piece)
+    const long long sg = s_incl[0][i] - (f > 0 ? s_incl[0][f - 1] : 0), sh = s_incl[1][i] - (f > 0 ? s_incl[1][f - 1] : 0),
+                    sc = s_incl[2][i] - (f > 0 ? s_incl[2][f - 1] : 0);
+    if (sc == 0) continue;
+    ExactSums *to = cat.hist + ((size_t)j * (size_t)lv.cap + (size_t)(key[q] >> 8)) * 256 + (size_t)(key[q] & 255);
+    atomicAdd((u64 *)&to->g, (u64)sg);   // (two's complement: the unsigned sum is the signed one)
+    atomicAdd((u64 *)&to->h, (u64)sh);
+    atomicAdd((u64 *)&to->c, (u64)sc);
+  }
+}
+
+// Step 5ec's search.  blockIdx: (slot, "c" column); lane b loads bin b of the level's sums and runs step 5cx's body - the text the
+// histogram grower compiles (train_scan_device.hpp) - into a record in LDS; the candidate then goes where the pick reads a column's,
+// lv.feat[slot][column] (code: nan_left), its right set into the side table.  root_tot: no "q" column exists - the root's total is this
+// scan's (of "c" column 0)
+__global__ void __launch_bounds__(256)
+train_exact_cat_scan_kernel(ExactLevel lv, ExactCat cat, ScanParams sp, int cols, int root_tot) {
+  __shared__ long long s_buf[2][3][256];
+  __shared__ double s_gain[256];
+  __shared__ int s_code[256];
+  __shared__ long long s_nan[6];
+  __shared__ u64 s_mask[4];
+  __shared__ LeafRec s_rec;
+  const int tid = threadIdx.x, k = blockIdx.x, j = blockIdx.y, col = cat.cols[j];
+  const ExactSums b = cat.hist[((size_t)j * (size_t)lv.cap + (size_t)k) * 256 + (size_t)tid];
+  scan_cat_column_xgb(b.g, b.h, b.c, cat.nbins[col], col, sp, &s_rec, s_buf, s_gain, s_code, s_nan, s_mask);   // (its last barrier publishes s_rec)
+  if (tid == 0) {
+    lv.feat[(size_t)k * (size_t)cols + (size_t)col] = ExactCand{s_rec.gain, s_rec.gl, s_rec.hl, s_rec.cl, (unsigned)s_rec.nan_left, 0.0f, s_rec.valid, 0};
+    if (root_tot && j == 0) lv.tot[0] = ExactSums{s_rec.g, s_rec.h, s_rec.c};
+  }
+  if (tid < 8) cat.masks[((size_t)k * (size_t)cat.n_cat + (size_t)j) * 8 + (size_t)tid] = s_rec.cat_mask[tid];
+}
+
+// one workgroup per node: the best record over the columns and - for a node that spans tiles - over their edge records.
+// CATS false: cat_of, masks, n_cat unread
+template <bool CATS>
+__global__ void __launch_bounds__(EX_THREADS)
+train_exact_pick_kernel(ExactLevel lv, int cols, int n_tiles, const int *__restrict__ cat_of, const unsigned *__restrict__ masks, int n_cat) {
   __shared__ double s_gain[EX_THREADS];
   __shared__ int s_col[EX_THREADS];
   __shared__ unsigned s_code[EX_THREADS];
@@ -308,7 +421,9 @@ train_exact_pick_kernel(ExactLevel lv, int cols, int n_tiles) {
   const ExactCand *bat = nullptr;
   for (long long it = tid; it < (long long)cols * span; it += EX_THREADS) {
     const int c = (int)(it / span), t = t0 + (int)(it % span);
-    const ExactCand *r = span == 1 ? &lv.feat[(size_t)k * (size_t)cols + (size_t)c]
+    const bool by_runs = CATS && cat_of[c] >= 0;   // a "c" column: ONE record whatever the node spans, never an edge record
+    if (by_runs && t != t0) continue;
+    const ExactCand *r = span == 1 || by_runs ? &lv.feat[(size_t)k * (size_t)cols + (size_t)c]
                                    : &lv.edge[((size_t)c * (size_t)n_tiles + (size_t)t) * 2 + ((long long)sg.start < (long long)t * EX_TILE ? 0 : 1)];
     if (!r->valid) continue;
     const double gn = r->gain;
@@ -326,13 +441,31 @@ train_exact_pick_kernel(ExactLevel lv, int cols, int n_tiles) {
   const ExactSums T = lv.tot[k];
   ExactRec out{0.0, 0, 0, 0, T.g, T.h, T.c, 0, 0, 0, 0.0f};
   if (bcol >= 0) out = ExactRec{best, bat->gl, bat->hl, bat->cl, T.g, T.h, T.c, 1, bcol, (int)(bcode & 1u), bat->bound};
+  if (CATS && bcol >= 0 && cat_of[bcol] >= 0) {   // the winner's right set rides behind the level's records: still one read-back
+    out.valid = EXACT_VALID_CAT;
+    const unsigned *from = masks + ((size_t)k * (size_t)n_cat + (size_t)cat_of[bcol]) * 8;
+    unsigned *to = (unsigned *)(lv.recs + lv.n) + (size_t)k * 8;
+    for (int w = 0; w < 8; ++w) to[w] = from[w];
+  }
   lv.recs[k] = out;
 }
 
+// CAT: the level has a categorical route (the host picks the form; the numeric one has no line of step 5ec and reads no mask).  As
+// train_level_split_kernel: the masks are staged in LDS when at most TRAIN_LEVEL_LDS_MASKS exist - a row's word is one ds_read - and
+// read from memory otherwise.  A row's bin comes from its f32 cell and the column's id -> bin table
+template <bool CAT>
 __global__ void __launch_bounds__(TRAIN_ROW_THREADS)
-train_exact_route_kernel(const float *__restrict__ cells, long long rows, uint16_t *__restrict__ node_of, const ExactRoute *__restrict__ routes, int first, int n) {
+train_exact_route_kernel(const float *__restrict__ cells, long long rows, uint16_t *__restrict__ node_of, const ExactRoute *__restrict__ routes, int first, int n,
+                         const unsigned *__restrict__ masks, int n_masks, const int *__restrict__ cat_idx, const uint8_t *__restrict__ cat_tables) {
   __shared__ ExactRoute s_routes[TRAIN_EXACT_LDS_ROUTES];
+  __shared__ unsigned s_masks[CAT ? TRAIN_LEVEL_LDS_MASKS * 8 : 1];
   const bool in_lds = n <= TRAIN_EXACT_LDS_ROUTES;   // (the same for every lane)
+  const bool masks_in_lds = CAT && n_masks <= TRAIN_LEVEL_LDS_MASKS;
+  if constexpr (CAT) {
+    if (masks_in_lds)
+      for (int k = threadIdx.x; k < n_masks * 8; k += TRAIN_ROW_THREADS) s_masks[k] = masks[k];
+    if (masks_in_lds && !in_lds) __syncthreads();
+  }
   if (in_lds) {
     for (int k = threadIdx.x; k < n; k += TRAIN_ROW_THREADS) s_routes[k] = routes[k];
     __syncthreads();
@@ -343,8 +476,17 @@ train_exact_route_kernel(const float *__restrict__ cells, long long rows, uint16
   if (s >= (unsigned)n) return;   // a row of a finished leaf
   const ExactRoute r = in_lds ? s_routes[s] : routes[s];
   if (r.col < 0) return;
-  const float x = cells[(long long)r.col * rows + i];
-  const bool left = x != x ? r.nan_left != 0 : x < r.bound;
+  bool left;
+  if (CAT && (r.col & TRAIN_LEVEL_CAT)) {
+    const int col = r.col & 0xFFFF;
+    const int b = train_xgb_category_bin((double)cells[(long long)col * rows + i], cat_tables + cat_idx[2 * col], cat_idx[2 * col + 1]);
+    const int at = (r.col >> TRAIN_LEVEL_MASK_SHIFT) * 8 + (b >> 5);   // (below n_masks * 8: the host numbered the masks)
+    const unsigned word = masks_in_lds ? s_masks[at] : masks[at];
+    left = b == TRAIN_NAN_BIN ? r.nan_left != 0 : !((word >> (b & 31)) & 1u);   // (bit 255 is never set; "other", 254, neither: left)
+  } else {
+    const float x = cells[(long long)r.col * rows + i];
+    left = x != x ? r.nan_left != 0 : x < r.bound;
+  }
   node_of[i] = (uint16_t)(r.left + (left ? 0 : 1));
 }
 
@@ -476,25 +618,52 @@ void train_launch_exact_order(mrk_ctx *ctx, hipStream_t s, const float *col_cell
   MRK_HIP(hipGetLastError());
 }
 
-void train_launch_exact_search(mrk_ctx *ctx, hipStream_t s, const ExactDev &d, const ExactLevel &lv, const ScanParams &p, bool root) {
-  const dim3 grid((unsigned)d.n_tiles, (unsigned)d.cols);
-  {
-    ScopedKernelTimer timer(ctx, "train_exact_sums");
-    hipLaunchKernelGGL(train_exact_scan_kernel<false>, grid, dim3(EX_THREADS), 0, s, d, lv, p);
-    hipLaunchKernelGGL(train_exact_offsets_kernel, dim3((unsigned)d.cols), dim3(EX_THREADS), 0, s, lv, d.n_tiles, root ? 1 : 0);
-    MRK_HIP(hipGetLastError());
-  }
-  ScopedKernelTimer timer(ctx, "train_exact_candidates");
-  hipLaunchKernelGGL(train_exact_scan_kernel<true>, grid, dim3(EX_THREADS), 0, s, d, lv, p);
-  hipLaunchKernelGGL(train_exact_pick_kernel, dim3((unsigned)lv.n), dim3(EX_THREADS), 0, s, lv, d.cols, d.n_tiles);
+void train_launch_exact_cat_bins(mrk_ctx *ctx, hipStream_t s, const float *cells, long long rows, const ExactCat &cat, uint8_t *plane) {
+  if (rows <= 0 || cat.n_cat <= 0) return;
+  ScopedKernelTimer timer(ctx, "train_bin");
+  hipLaunchKernelGGL(train_exact_cat_bins_kernel, dim3((unsigned)((rows + TRAIN_BIN_ROWS - 1) / TRAIN_BIN_ROWS), (unsigned)cat.n_cat), dim3(TRAIN_BIN_ROWS), 0, s, cells, rows,
+                     cat, plane);
   MRK_HIP(hipGetLastError());
 }
 
-void train_launch_exact_route(mrk_ctx *ctx, hipStream_t s, const float *cells, long long rows, uint16_t *node_of, const ExactRoute *routes, int first, int n) {
+void train_launch_exact_search(mrk_ctx *ctx, hipStream_t s, const ExactDev &d, const ExactLevel &lv, const ScanParams &p, bool root, const ExactCat &cat) {
+  const dim3 grid((unsigned)d.n_tiles, (unsigned)d.cols);
+  const int *cat_of = cat.cat_of;
+  const bool cats = cat.n_cat > 0;
+  const bool numeric = cat.n_cat < d.cols;   // (a fit of "c" columns alone launches no numeric search: the root's total is the categorical scan's)
+  if (numeric) {
+    ScopedKernelTimer timer(ctx, "train_exact_sums");
+    hipLaunchKernelGGL((cats ? train_exact_scan_kernel<false, true> : train_exact_scan_kernel<false, false>), grid, dim3(EX_THREADS), 0, s, d, lv, p, cat_of);
+    hipLaunchKernelGGL((cats ? train_exact_offsets_kernel<true> : train_exact_offsets_kernel<false>), dim3((unsigned)d.cols), dim3(EX_THREADS), 0, s, lv, d.n_tiles,
+                       root ? 1 + (cats ? cat.first_q : 0) : 0, cat_of);
+    MRK_HIP(hipGetLastError());
+  }
+  if (cats) {
+    ScopedKernelTimer timer(ctx, "train_exact_cat_sums");
+    hipLaunchKernelGGL(train_exact_cat_sums_kernel, dim3((unsigned)d.n_tiles, (unsigned)cat.n_cat), dim3(EX_THREADS), 0, s, d, lv, cat);
+    MRK_HIP(hipGetLastError());
+  }
+  if (cats) {
+    ScopedKernelTimer timer(ctx, "train_exact_cat_scan");
+    hipLaunchKernelGGL(train_exact_cat_scan_kernel, dim3((unsigned)lv.n, (unsigned)cat.n_cat), dim3(256), 0, s, lv, cat, p, d.cols, root && !numeric ? 1 : 0);
+    MRK_HIP(hipGetLastError());
+  }
+  ScopedKernelTimer timer(ctx, "train_exact_candidates");
+  if (numeric) hipLaunchKernelGGL((cats ? train_exact_scan_kernel<true, true> : train_exact_scan_kernel<true, false>), grid, dim3(EX_THREADS), 0, s, d, lv, p, cat_of);
+  hipLaunchKernelGGL((cats ? train_exact_pick_kernel<true> : train_exact_pick_kernel<false>), dim3((unsigned)lv.n), dim3(EX_THREADS), 0, s, lv, d.cols, d.n_tiles, cat_of,
+                     (const unsigned *)cat.masks, cat.n_cat);
+  MRK_HIP(hipGetLastError());
+}
+
+void train_launch_exact_route(mrk_ctx *ctx, hipStream_t s, const float *cells, long long rows, uint16_t *node_of, const ExactRoute *routes, int first, int n,
+                              const unsigned *masks, int n_masks, const int *cat_idx, const uint8_t *cat_tables) {
   if (rows <= 0) return;
   ScopedKernelTimer timer(ctx, "train_exact_route");
-  hipLaunchKernelGGL(train_exact_route_kernel, dim3((unsigned)((rows + TRAIN_ROW_THREADS - 1) / TRAIN_ROW_THREADS)), dim3(TRAIN_ROW_THREADS), 0, s, cells, rows, node_of,
-                     routes, first, n);
+  const dim3 grid((unsigned)((rows + TRAIN_ROW_THREADS - 1) / TRAIN_ROW_THREADS));
+  if (n_masks > 0)
+    hipLaunchKernelGGL(train_exact_route_kernel<true>, grid, dim3(TRAIN_ROW_THREADS), 0, s, cells, rows, node_of, routes, first, n, masks, n_masks, cat_idx, cat_tables);
+  else
+    hipLaunchKernelGGL(train_exact_route_kernel<false>, grid, dim3(TRAIN_ROW_THREADS), 0, s, cells, rows, node_of, routes, first, n, masks, n_masks, cat_idx, cat_tables);
   MRK_HIP(hipGetLastError());
 }
 

@@ -34,7 +34,9 @@ struct ExactCand {
   float bound;            // the value at position + 1: (float) x < bound goes left
   int valid, pad;
 };
-// a node's best over all columns, and the node's totals
+// a node's best over all columns, and the node's totals.  valid == EXACT_VALID_CAT: a "c" column won - bound is unused and the 8 words
+// of its mask over bins (bit b <=> bin b goes RIGHT) stand behind the level's n records, at ((unsigned *) (recs + n)) + slot * 8
+constexpr int EXACT_VALID_CAT = 2;
 struct ExactRec {
   double gain;
   long long gl, hl, cl;
@@ -43,7 +45,9 @@ struct ExactRec {
   float bound;
 };
 // what a row needs to leave a node of the level: col < 0 a leaf (the row stays); else (float) x < bound (NaN when nan_left) goes to node
-// `left`, the others to left + 1
+// `left`, the others to left + 1.  A categorical node (step 5ec) keeps the 12 bytes, as LevelRec does: col = column | TRAIN_LEVEL_CAT |
+// index << TRAIN_LEVEL_MASK_SHIFT, the index of its 8-word mask over bins in the level's mask table; a bin whose bit is set goes RIGHT,
+// NaN (bin 255) left when nan_left, every other bin - "other", 254, among them - left
 struct ExactRoute {
   int col;
   float bound;
@@ -83,12 +87,38 @@ struct ExactLevel {
   ExactCand *edge;             // [cols][n_tiles][2]: the piece of a node that began before the tile (0) / goes on behind it (1)
   ExactRec *recs;              // per slot
 };
-// the three launches of a level's search and the pick: tile sums, NaN sums and bases; the prefix over the tiles; the candidates; per node
-// the best over columns and tiles.  root: the level is node 0 alone and lv.tot[0] is written first
-void train_launch_exact_search(mrk_ctx *ctx, hipStream_t s, const ExactDev &d, const ExactLevel &lv, const ScanParams &p, bool root);
+// The "c" columns of an enable_categorical fit (steps 2ec, 5ec).  Their cells keep their place in the f32 matrix and
+// their permutations - ordered by value, equal categories are contiguous inside a node's segment -; beside them the training set holds
+// one byte per cell, the bin of step 2cx.  Per level train_exact_cat_sums turns the runs of equal (node, bin) into the level's
+// [n_cat][n][256] sums - one integer atomic triple per piece of a run inside a tile, not one per row - and train_exact_cat_scan judges
+// them with step 5cx's own body (train_scan_device.hpp).  n_cat == 0: no kernel reads any of this
+struct ExactCat {
+  int n_cat, first_q;          // first_q: the first "q" column, -1 when every column is a "c"
+  const int *cols;             // [n_cat]: the column of every "c" column, ascending
+  const int *cat_of;           // [cols]: a column's index among the "c" columns, -1 for a "q" column
+  const int *nbins;            // [cols]: a "c" column's kept categories
+  const uint8_t *plane;        // [n_cat][rows]: the training cells' bins (254 "other", 255 NaN)
+  ExactSums *hist;             // [n_cat][n][256], n the level's nodes; the caller zeroes it
+  unsigned *masks;             // [n][n_cat][8]: the right set of every (node, "c" column) candidate
+  const int *cat_idx;          // [cols][2] and cat_tables: the id -> bin tables (train_launch_bin_f32's)
+  const uint8_t *cat_tables;
+};
+// plane[j][row] = train_xgb_category_bin of the f32 cell of "c" column j, every row of the set
+void train_launch_exact_cat_bins(mrk_ctx *ctx, hipStream_t s, const float *cells, long long rows, const ExactCat &cat, uint8_t *plane);
 
-// rows whose node_of is first ... first + n - 1 move to their child under routes[slot]; cells: the set's own f32 matrix
-void train_launch_exact_route(mrk_ctx *ctx, hipStream_t s, const float *cells, long long rows, uint16_t *node_of, const ExactRoute *routes, int first, int n);
+// the three launches of a level's search and the pick: tile sums, NaN sums and bases; the prefix over the tiles; the candidates; per node
+// the best over columns and tiles.  root: the level is node 0 alone and lv.tot[0] is written first.
+// cat.n_cat > 0 (step 5ec): the numeric launches leave the "c" columns' workgroups at once; two more launches - the sums of the runs,
+// then per (node, "c" column) step 5cx's scan, which writes lv.feat[slot][column] - come before the pick, which reads a "c" column's
+// feat record whatever the node spans and copies the winner's mask behind the records
+void train_launch_exact_search(mrk_ctx *ctx, hipStream_t s, const ExactDev &d, const ExactLevel &lv, const ScanParams &p, bool root, const ExactCat &cat);
+
+// rows whose node_of is first ... first + n - 1 move to their child under routes[slot]; cells: the set's own f32 matrix.
+// n_masks > 0: the level has categorical routes and `masks` holds n_masks x 8 words - the kernel's categorical form is launched: a row's
+// bin is train_xgb_category_bin of its f32 cell under the column's table (exact: the cell is the value the table was counted on), so
+// the training and the validation rows take one path and no second plane exists; the numeric form reads none of it
+void train_launch_exact_route(mrk_ctx *ctx, hipStream_t s, const float *cells, long long rows, uint16_t *node_of, const ExactRoute *routes, int first, int n,
+                              const unsigned *masks = nullptr, int n_masks = 0, const int *cat_idx = nullptr, const uint8_t *cat_tables = nullptr);
 
 // the stable partition of every column's permutation after a routing pass: inside the segment of every node that split, the rows that
 // went left in order, then the others in order; everything else stays.  next_first / n_next: the children, in pairs (left, right) in

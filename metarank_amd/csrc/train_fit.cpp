@@ -356,9 +356,14 @@ struct LevelGrower {
 // permutation of the rows ordered by (node segment, value, row); a level is searched by prefix sums over it (train_launch_exact_search),
 // read back once, routed, and - when its children are searched too - partitioned from one permutation buffer into the other.  The
 // segments stay on the device: the partition writes the children's.
+// With "c" columns (enable_categorical; steps 2ec, 5ec) a level's search has two more launches - the sums of the runs of
+// equal categories, step 5cx's scan over them -, a categorical record's mask is read back behind the records, and a level with such a
+// record is routed by the kernel's categorical form.  A fit without one launches nothing of it.
 struct ExactGrower {
   int64_t cap = 0;   // train_level_cap
-  int cols = 0, n_tiles = 0;
+  int cols = 0, n_tiles = 0, n_cat = 0, first_q = -1;
+  DevBuf d_cat_masks;   // [level's nodes][n_cat][8]
+  size_t off_masks = 0;
   DevBuf d_perm[2], d_seg[2], d_tile, d_nan, d_base, d_feat, d_edge, d_recs, d_par, d_tcount, d_lbase, d_lend, d_tables, d_value, d_vnode_of;
   PinBuf h_recs, h_tables, h_value;
   size_t off_tot = 0, table_bytes = 0;   // one block per level, host -> device in one copy: the level's routes, the next level's totals
@@ -371,11 +376,18 @@ struct ExactGrower {
     const size_t nc = (size_t)cap * (size_t)cols, tc = (size_t)n_tiles * (size_t)cols, half = (size_t)cap / 2 + 1;
     for (DevBuf &b : d_perm) b.reserve(rows * (size_t)cols * 4);
     for (DevBuf &b : d_seg) b.reserve((size_t)cap * sizeof(ExactSeg));
-    d_tile.reserve(tc * sizeof(ExactSums)), d_nan.reserve(nc * sizeof(ExactSums)), d_base.reserve(nc * sizeof(ExactSums));
+    n_cat = (int)cfg.categorical.size();
+    for (int c = cols - 1; c >= 0; --c)
+      if (!t.is_cat[(size_t)c]) first_q = c;
+    // (the level's sums per ("c" column, node, bin) stand behind the NaN sums: one memset clears both)
+    d_tile.reserve(tc * sizeof(ExactSums)), d_nan.reserve((nc + (size_t)n_cat * (size_t)cap * 256) * sizeof(ExactSums)), d_base.reserve(nc * sizeof(ExactSums));
     d_feat.reserve(nc * sizeof(ExactCand)), d_edge.reserve(tc * 2 * sizeof(ExactCand));
-    d_recs.reserve((size_t)cap * sizeof(ExactRec)), h_recs.reserve((size_t)cap * sizeof(ExactRec));
+    const size_t rec_bytes = sizeof(ExactRec) + (n_cat ? 32 : 0);   // (a categorical record's mask rides behind the records)
+    d_recs.reserve((size_t)cap * rec_bytes), h_recs.reserve((size_t)cap * rec_bytes);
+    if (n_cat) d_cat_masks.reserve((size_t)cap * (size_t)n_cat * 32);
     d_par.reserve(half * sizeof(ExactSeg)), d_tcount.reserve(tc * 4), d_lbase.reserve(half * (size_t)cols * 4), d_lend.reserve(half * (size_t)cols * 4);
-    off_tot = ((size_t)cap * sizeof(ExactRoute) + 7) / 8 * 8, table_bytes = off_tot + (size_t)cap * sizeof(ExactSums);
+    off_tot = ((size_t)cap * sizeof(ExactRoute) + 7) / 8 * 8, off_masks = off_tot + (size_t)cap * sizeof(ExactSums);
+    table_bytes = off_masks + (n_cat ? (size_t)cap * 32 : 0);
     d_tables.reserve(table_bytes), h_tables.reserve(table_bytes);
     const size_t max_nodes = std::min<size_t>((size_t(2) << cfg.max_depth), 4 * (size_t)cap + 1);   // (LevelGrower's bound)
     d_value.reserve(max_nodes * 4), h_value.reserve(max_nodes * 4);
@@ -393,6 +405,13 @@ struct ExactGrower {
     const ExactRoute *d_route = (const ExactRoute *)d_tables.as<uint8_t>();
     ExactSums *d_tot = (ExactSums *)(d_tables.as<uint8_t>() + off_tot);
     const ExactRec *recs = h_recs.as<ExactRec>();
+    uint32_t *h_masks = (uint32_t *)(h_tables.as<uint8_t>() + off_masks);
+    const unsigned *d_masks = (const unsigned *)(d_tables.as<uint8_t>() + off_masks);
+    ExactCat cat{};
+    if (n_cat) {
+      cat.n_cat = n_cat, cat.first_q = first_q, cat.cols = t.d_cat_cols.as<int>(), cat.cat_of = t.d_cat_of.as<int>(), cat.nbins = t.d_nbins.as<int>();
+      cat.plane = tr.d_bins.as<uint8_t>(), cat.masks = d_cat_masks.as<unsigned>(), cat.cat_idx = t.d_cat_idx.as<int>(), cat.cat_tables = t.d_cat_tables.as<uint8_t>();
+    }
 
     train_launch_exact_begin(ctx, st, tr.rows, d_seg[0].as<ExactSeg>());
     if (va.given) MRK_HIP(hipMemsetAsync(d_vnode_of.p, 0, (size_t)va.rows * 2, st));
@@ -407,27 +426,36 @@ struct ExactGrower {
       const ExactDev dev{tr.d_cells.as<float>(), perm, node_of, qg, qh, tr.rows, cols, n_tiles, cfg.sampling, cfg.seed, tree_index};
       const ExactLevel lv{ids[0], n, n, d_seg[buf].as<ExactSeg>(), d_tot, d_tile.as<ExactSums>(), d_nan.as<ExactSums>(), d_base.as<ExactSums>(),
                           d_feat.as<ExactCand>(), d_edge.as<ExactCand>(), d_recs.as<ExactRec>()};
-      MRK_HIP(hipMemsetAsync(d_nan.p, 0, (size_t)cols * (size_t)n * sizeof(ExactSums), st));
-      train_launch_exact_search(ctx, st, dev, lv, sp, d == 0);
+      cat.hist = d_nan.as<ExactSums>() + (size_t)cols * (size_t)n;
+      MRK_HIP(hipMemsetAsync(d_nan.p, 0, ((size_t)cols + (size_t)n_cat * 256) * (size_t)n * sizeof(ExactSums), st));
+      train_launch_exact_search(ctx, st, dev, lv, sp, d == 0, cat);
       {
         ScopedKernelTimer timer(ctx, "train_level_readback");
-        MRK_HIP(hipMemcpyAsync(h_recs.p, d_recs.p, (size_t)n * sizeof(ExactRec), hipMemcpyDeviceToHost, st));
+        MRK_HIP(hipMemcpyAsync(h_recs.p, d_recs.p, (size_t)n * (sizeof(ExactRec) + (n_cat ? 32 : 0)), hipMemcpyDeviceToHost, st));
       }
       MRK_HIP(hipStreamSynchronize(st));   // (h_tables is free again too)
       if (d == 0) totals[0] = TrainSums{recs[0].g, recs[0].h, recs[0].c};
       const bool search_next = d + 1 < cfg.max_depth;
       std::vector<int> next;
+      const uint32_t *rec_masks = (const uint32_t *)(recs + n);   // per slot 8 words, written for a categorical record
+      int n_masks = 0;                                             // the level's categorical records so far
       for (int k = 0; k < n; ++k) {
         const ExactRec &c = recs[k];
         h_route[k] = ExactRoute{-1, 0.0f, 0, 0, 0};
         if (!c.valid) continue;
         const int node = ids[(size_t)k];
         const TrainSums whole = totals[(size_t)node];
-        tree.split(node, c.col, 0, c.bound, c.nan_left != 0, (float)c.gain);
+        const bool by_set = c.valid == EXACT_VALID_CAT;
+        if (by_set) tree.split_cat(node, c.col, rec_masks + (size_t)k * 8, c.nan_left != 0, (float)c.gain);
+        else tree.split(node, c.col, 0, c.bound, c.nan_left != 0, (float)c.gain);
         const int l = tree.num_nodes() - 2;
         const TrainSums left{c.gl, c.hl, c.cl}, right{whole.g - c.gl, whole.h - c.hl, whole.c - c.cl};
         totals.push_back(left), totals.push_back(right);
         h_route[k] = ExactRoute{c.col, c.bound, (uint16_t)l, (uint8_t)(c.nan_left != 0), 0};
+        if (by_set) {
+          h_route[k].col |= TRAIN_LEVEL_CAT | (n_masks << TRAIN_LEVEL_MASK_SHIFT), h_route[k].bound = 0.0f;
+          memcpy(h_masks + (size_t)n_masks++ * 8, rec_masks + (size_t)k * 8, 32);
+        }
         if (search_next) {
           h_tot[next.size()] = ExactSums{left.g, left.h, left.c};
           h_tot[next.size() + 1] = ExactSums{right.g, right.h, right.c};
@@ -436,8 +464,9 @@ struct ExactGrower {
       }
       if (next.empty()) break;
       MRK_HIP(hipMemcpyAsync(d_tables.p, h_tables.p, table_bytes, hipMemcpyHostToDevice, st));
-      train_launch_exact_route(ctx, st, tr.d_cells.as<float>(), tr.rows, node_of, d_route, ids[0], n);
-      if (va.given) train_launch_exact_route(ctx, st, va.d_cells.as<float>(), va.rows, d_vnode_of.as<uint16_t>(), d_route, ids[0], n);
+      train_launch_exact_route(ctx, st, tr.d_cells.as<float>(), tr.rows, node_of, d_route, ids[0], n, d_masks, n_masks, cat.cat_idx, cat.cat_tables);
+      if (va.given)
+        train_launch_exact_route(ctx, st, va.d_cells.as<float>(), va.rows, d_vnode_of.as<uint16_t>(), d_route, ids[0], n, d_masks, n_masks, cat.cat_idx, cat.cat_tables);
       if (search_next) {
         const ExactPart pt{d_route, d_seg[buf].as<ExactSeg>(), ids[0], n, next[0], (int)next.size(), d_par.as<ExactSeg>(), d_seg[buf ^ 1].as<ExactSeg>(),
                            d_tcount.as<unsigned>(), d_lbase.as<unsigned>(), d_lend.as<unsigned>(), d_perm[out].as<int>()};

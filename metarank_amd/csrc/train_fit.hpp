@@ -23,7 +23,7 @@ struct TrainSet {
   std::vector<int64_t> offsets;
   EvalBins by_size;
   DevBuf d_bins, d_labels, d_off, d_wave, d_group, d_score, d_best;   // d_score, d_best: reserved by mrk_train_set, first written by train_fit
-  DevBuf d_cells, d_order;          // tree_method "exact" (step 2e) in place of d_bins: the f32 matrix [cols][rows]; the training set: every column's rows by (value, row)
+  DevBuf d_cells, d_order;          // tree_method "exact" (step 2e) in place of d_bins (the training set, step 2ec: d_bins holds the "c" columns' bytes, [n_cat][rows]): the f32 matrix [cols][rows]; the training set: every column's rows by (value, row)
   std::vector<double> gains;        // the validation set: what eval.hip reads (eval_pack_labels, relpow)
   std::vector<uint8_t> rel;
   std::vector<double> scores;       // at the best iteration, after the fit
@@ -40,6 +40,7 @@ struct TrainState {
   std::vector<int32_t> is_cat;              // per column
   bool any_cat = false;
   DevBuf d_bounds, d_bound_off, d_nbins, d_is_cat, d_cat_idx, d_cat_tables;
+  DevBuf d_cat_cols, d_cat_of;              // step 2ec: the "c" columns ascending; per column its index among them or -1
   TrainSet set[2];
   int iterations_run = 0;
   std::vector<double> history;

@@ -24,7 +24,7 @@ TrainConfig train_parse_config(const char *text, size_t len) {
   static const char *known[] = {"iterations", "learningRate", "ndcgCutoff", "maxDepth", "seed", "numLeaves", "sampling", "debias", "max_bin", "truncation",
                                 "sigma", "min_data_in_leaf", "min_sum_hessian", "lambda_l2", "early_stopping", "categorical", "max_cat_to_onehot",
                                 "max_cat_threshold", "cat_smooth", "cat_l2", "min_data_per_group", "backend", "lambda", "gamma", "min_child_weight", "position_bias",
-                                "feature_types", "tree_method"};
+                                "feature_types", "tree_method", "enable_categorical"};
   for (auto &kv : root.obj) {
     bool ok = false;
     for (const char *k : known) ok = ok || kv.first == k;
@@ -40,7 +40,7 @@ TrainConfig train_parse_config(const char *text, size_t len) {
   {  // a key of the other backend is refused, not ignored: it would be a setting that silently does nothing
     static const char *lgb_only[] = {"numLeaves", "min_data_in_leaf", "min_sum_hessian", "lambda_l2", "max_cat_to_onehot", "max_cat_threshold", "cat_smooth", "cat_l2",
                                      "min_data_per_group"};
-    static const char *xgb_only[] = {"lambda", "gamma", "min_child_weight", "feature_types", "tree_method"};
+    static const char *xgb_only[] = {"lambda", "gamma", "min_child_weight", "feature_types", "tree_method", "enable_categorical"};
     auto refuse = [&](const char *key, const char *backend) {
       const json::Value *v = root.find(key);
       if (v && !v->is_null()) range(std::string(key) + " is not a key of the " + backend + " backend");
@@ -168,8 +168,14 @@ TrainConfig train_parse_config(const char *text, size_t len) {
       if (v->str == "exact") c.tree_method = TRAIN_TREE_EXACT;
       else if (v->str != "hist") range("tree_method = '" + v->str + "' (hist or exact)");
     }
-  if (c.tree_method == TRAIN_TREE_EXACT && !c.categorical.empty())
-    throw StatusError(MRK_ERR_UNSUPPORTED, "train config: tree_method 'exact' has no categorical splits: feature_types holds a 'c'");
+  if (const json::Value *v = root.find("enable_categorical"))
+    if (!v->is_null()) {   // (backend "xgboost": refused above under the other) XGBoost's own spelling: steps 2ec / 5ec under tree_method "exact"
+      if (v->type != json::Type::Bool) bad("'enable_categorical' is not a Boolean");
+      if (c.tree_method != TRAIN_TREE_EXACT) range("enable_categorical is a key of tree_method 'exact' alone: 'hist' trains a 'c' column without it");
+      c.enable_categorical = v->b;
+    }
+  if (c.tree_method == TRAIN_TREE_EXACT && !c.categorical.empty() && !c.enable_categorical)
+    throw StatusError(MRK_ERR_UNSUPPORTED, "train config: tree_method 'exact' has no categorical splits: feature_types holds a 'c' (set enable_categorical)");
   if (c.debias) throw StatusError(MRK_ERR_UNSUPPORTED, "train config: debias carries neither the number of positions nor the norm: use position_bias");
   if (c.num_leaves > TRAIN_MAX_LEAVES)
     throw StatusError(MRK_ERR_UNSUPPORTED, "train config: numLeaves = " + std::to_string(c.num_leaves) + " (limit " + std::to_string(TRAIN_MAX_LEAVES) + ")");
@@ -384,12 +390,16 @@ int64_t train_level_cap(const TrainConfig &cfg, int64_t rows) { return std::max<
 
 // step 2e / 5e: no bins and no histograms.  Per cell the f32 value (4) and - the training set - three permutations (the sorted order every
 // tree starts from and the two a level's partition goes between); per (column, tile) a triple of sums (24), a left count (4) and two
-// edge records (2 x 48); per (column, node of a level) the NaN sums, the base (24 each), a record (48) and the partition's two counts
+// edge records (2 x 48); per (column, node of a level) the NaN sums, the base (24 each), a record (48) and the partition's two counts.
+// enable_categorical (steps 2ec / 5ec), per "c" column: a byte per training cell, 256 triples of sums (24) and a mask (32) per node of
+// the widest level; per such node 32 more behind its record and 32 in the routing table; the two small per-column tables
 static double train_exact_bytes(const TrainConfig &cfg, int which, double rows, double cols, double groups, int64_t rows_) {
   const double per_row = (which == 0 && cfg.position_bias ? 67.0 : 51.0) * rows + 2.0 * rows, group_lists = 12.0 * groups;
   if (which == 1) return 4.0 * rows * cols + per_row + group_lists + (9.0 * rows + 8.0 * groups);
   const double tiles = std::ceil(rows / 1024.0), cap = (double)train_level_cap(cfg, rows_);
-  return 16.0 * rows * cols + per_row + group_lists + cols * tiles * 124.0 + cols * cap * 104.0 + cap * 256.0;
+  const double n_cat = (double)cfg.categorical.size();
+  const double by_runs = n_cat > 0.0 ? n_cat * (rows + cap * (256.0 * 24.0 + 32.0)) + cap * 64.0 + (n_cat + cols) * 4.0 : 0.0;
+  return 16.0 * rows * cols + per_row + group_lists + cols * tiles * 124.0 + cols * cap * 104.0 + cap * 256.0 + by_runs;
 }
 
 double train_fit_bytes(const TrainConfig &cfg, int which, int64_t rows_, int cols, int64_t n_groups_) {

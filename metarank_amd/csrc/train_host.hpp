@@ -62,6 +62,7 @@ struct TrainConfig {
   int bias_positions = 32;
   double bias_norm = 1.0;
   int tree_method = 0;                // backend "xgboost", "tree_method": 0 "hist" (steps 2x, 5x), 1 "exact" (steps 2e, 5e: no bins, max_bin unused)
+  bool enable_categorical = false;    // tree_method "exact", "enable_categorical": "c" entries of feature_types are trained (steps 2ec, 5ec; max_bin - 2 kept categories)
 };
 constexpr int TRAIN_BACKEND_LIGHTGBM = 0, TRAIN_BACKEND_XGBOOST = 1;
 constexpr int TRAIN_TREE_HIST = 0, TRAIN_TREE_EXACT = 1;
@@ -73,7 +74,8 @@ constexpr int TRAIN_XGB_MAX_DEPTH = 15;     // a node id is a u16: a complete tr
 // feature_types (backend "xgboost"): not an array or an entry that is no string: MRK_ERR_PARSE; an entry other than "q" / "c":
 // MRK_ERR_INVALID_ARG.  Its "c" entries become `categorical` (steps 2cx, 5cx)
 // tree_method (backend "xgboost"): not a string: MRK_ERR_PARSE; a string other than "hist" / "exact": MRK_ERR_INVALID_ARG; "exact" with a
-// "c" in feature_types: MRK_ERR_UNSUPPORTED
+// "c" in feature_types: MRK_ERR_UNSUPPORTED - unless enable_categorical is true (not a Boolean: MRK_ERR_PARSE; under "hist", spelled or
+// defaulted, where it would do nothing: MRK_ERR_INVALID_ARG; backend "lightgbm": MRK_ERR_INVALID_ARG)
 // position_bias (either backend): not an object, a key inside other than positions / norm or one that is no number: MRK_ERR_PARSE;
 // positions outside 1 ... TRAIN_MAX_GROUP, norm negative or not finite: MRK_ERR_INVALID_ARG
 TrainConfig train_parse_config(const char *json, size_t len);

@@ -10,7 +10,7 @@ device phases, per scan (the record read back after every split is a stream sync
 host's book-keeping); the restatement (tests/train_reference.py) for ONE iteration on the first --ref-groups groups of the same data on
 this host; and, if sklearn is importable, HistGradientBoostingRegressor's time per tree on the same matrix (a regressor on the labels:
 context only, another objective).  No threshold: nothing was measured before this tool existed.
---categorical N declares the last N columns categorical (their cells rounded to ids 0 ... 49): the split search of those columns is
+--categorical N (with --tree-method exact it sets enable_categorical and counts steps 2ec / 5ec's launches) declares the last N columns categorical (their cells rounded to ids 0 ... 49): the split search of those columns is
 include/mrk.h's step 5c, the restatement and sklearn then see the rounded columns as numbers.
 --backend xgboost [--depth D] fits the same matrix with the level-wise grower (include/mrk.h steps 2x, 5x, 6x, 7x; --leaves is unused):
 the phases are then train_level_hist, train_level_scan (scan + pick), train_level_split (the per-tree start and one routing pass per
@@ -51,6 +51,7 @@ LEVEL_TIMERS = ("train_bin", "train_grad", "train_level_hist", "train_level_scan
 # and - when the children are searched too - the partition (4)
 EXACT_TIMERS = ("train_bin", "train_sort", "train_grad", "train_exact_sums", "train_exact_candidates", "train_exact_route", "train_exact_partition",
                 "train_level_readback", "train_apply", "train_eval")
+EXACT_CAT_TIMERS = ("train_exact_cat_sums", "train_exact_cat_scan")       # --categorical N with it (steps 2ec, 5ec): one launch each per searched level
 BIAS_TIMERS = ("train_grad_bias", "train_pos_sum", "train_bias_readback")   # step 3b: the biased LambdaRank kernels, the position sums, their copy back
 COLS = 24
 
@@ -86,6 +87,7 @@ def main():
     xgb = a.backend == "xgboost"
     by_order = xgb and a.tree_method == "exact"
     timers = (EXACT_TIMERS if by_order else LEVEL_TIMERS if xgb else TIMERS) + (BIAS_TIMERS if a.position_bias else ())
+    timers += EXACT_CAT_TIMERS if by_order and a.categorical else ()
     ctx = M.Context(0)
     X, y, off = synth.synthetic_ranking_rows(a.groups, a.min_items, a.max_items, COLS, seed=0)
     rows = int(off[-1])
@@ -101,6 +103,8 @@ def main():
         X[:, cats] = np.clip(np.rint((X[:, cats] + 3.0) * (49.0 / 6.0)), 0.0, 49.0)
         if xgb:                                                           # (this backend names them per column: steps 2cx, 5cx)
             cfg["feature_types"] = ["c" if c in cats else "q" for c in range(COLS)]
+            if by_order:
+                cfg["enable_categorical"] = True
         else:
             cfg["categorical"] = cats
     out = {"groups": a.groups, "rows": rows, "items_per_group": [a.min_items, a.max_items], "columns": COLS, "iterations": a.iterations, "leaves": a.leaves,
@@ -259,9 +263,12 @@ def finish_exact(a, ctx, out, parts, hist, bound):
     counts = {name: int(parts[name][1]) for name in EXACT_TIMERS}
     out["launches"] = {"per_phase": counts, "bound_trees_x_depth": bound, "sums": counts["train_exact_sums"], "candidates": counts["train_exact_candidates"],
                        "partitions": counts["train_exact_partition"], "record_readbacks": counts["train_level_readback"]}
-    out["launches"]["within_bound"] = all(out["launches"][k] <= bound for k in ("sums", "candidates", "partitions", "record_readbacks"))
-    device_ms = sum(parts[name][0] for name in EXACT_TIMERS if name not in ("train_bin", "train_sort"))
-    out["phase_ms"] = {name: parts[name][0] for name in EXACT_TIMERS}
+    names = EXACT_TIMERS + (EXACT_CAT_TIMERS if a.categorical else ())
+    for name in names[len(EXACT_TIMERS):]:                                # one launch each per level that is searched
+        out["launches"][name[len("train_exact_"):]] = counts[name] = int(parts[name][1])
+    out["launches"]["within_bound"] = all(v <= bound for k, v in out["launches"].items() if k not in ("per_phase", "bound_trees_x_depth"))
+    device_ms = sum(parts[name][0] for name in names if name not in ("train_bin", "train_sort"))
+    out["phase_ms"] = {name: parts[name][0] for name in names}
     out["fit_device_phases_ms"] = device_ms
     out["fit_host_and_sync_ms_per_readback"] = (out["fit_call_ms"] - device_ms) / max(counts["train_level_readback"], 1)
     out["fit_ms_per_tree"] = out["fit_call_ms"] / max(hist["iterations_run"], 1)
