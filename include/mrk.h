@@ -592,8 +592,20 @@ int mrk_encoder_load(mrk_ctx *ctx, const uint8_t *weights, size_t len, const cha
  * MRK_ENCODER_FP16 (opt-in; BASELINE config 5's "fp16"): fp16 weights and operands on the matrix cores, f32 accumulation -
  * pooled cosines within 3e-3 of an fp32 run of the graph; about 1 % of a 500-tree forest's scores move by more than 1e-5 and
  * a third of the requests see a pair of candidates swapped (bench.py's config-5 line reports it per run).
- * MRK_ENCODER_AUTO: accepted for hosts built against ABI <= 7 (where it chose by call size); it is MRK_ENCODER_F32 now. */
-enum { MRK_ENCODER_FP16 = 0, MRK_ENCODER_F32 = 1, MRK_ENCODER_AUTO = 2 };
+ * MRK_ENCODER_AUTO: accepted for hosts built against ABI <= 7 (where it chose by call size); it is MRK_ENCODER_F32 now.
+ * MRK_ENCODER_SPLIT (opt-in): the four dense products of a layer (QKV, attention output, FFN 1, FFN 2) on the bf16 matrix
+ * instruction (v_mfma_f32_32x32x16_bf16) with each f32 operand written as a sum of two round-to-nearest-even bf16 terms,
+ * x = x1 + x2: a product is a1 w1 + (a1 w2 + a2 w1), three bf16 products accumulated in f32 (the term a2 w2, ~2^-16 of the
+ * product, is dropped).  The weights are split once at load into two bf16 planes, the activations in the kernel; embeddings,
+ * LayerNorm, attention, GELU (libm erf), pooling, pooler and classifier are those of MRK_ENCODER_F32, and the activations
+ * between the kernels are f32.  Promises: hidden states and logits within the bounds the f32 handle is held to against the
+ * fp32 graph (2e-4 / 5e-4 at the test models); and, as with MRK_ENCODER_F32, one canonical accumulation order per output
+ * element, so a sequence's embedding is the same bits alone, in any batch, padded or packed, and as a row of
+ * mrk_index_build_texts.  Not promised: the bits of the reference's fp32 session or of an MRK_ENCODER_F32 handle - results
+ * differ from those in the last bits - nor a given speed (DESIGN has what was measured).  A non-finite activation or weight
+ * gives a non-finite result, not necessarily the one f32 arithmetic gives (inf - bf16(inf) is NaN).
+ * Any other value: MRK_ERR_INVALID_ARG. */
+enum { MRK_ENCODER_FP16 = 0, MRK_ENCODER_F32 = 1, MRK_ENCODER_AUTO = 2, MRK_ENCODER_SPLIT = 3 };
 int mrk_encoder_load_ex(mrk_ctx *ctx, const uint8_t *weights, size_t len, const char *tokenizer_json, size_t tok_len, int heads,
                         int precision, mrk_encoder **out);
 int mrk_encoder_get_info(mrk_encoder *enc, mrk_encoder_info *info);

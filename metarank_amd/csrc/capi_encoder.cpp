@@ -30,7 +30,8 @@ uint16_t to_half(float f) {
 }
 
 // Validates the checkpoint against the BertModel layout, converts and uploads it (one device allocation).
-void build_encoder(mrk_encoder &e, const Checkpoint &ck, bool f32) {
+void build_encoder(mrk_encoder &e, const Checkpoint &ck, int precision) {
+  const bool f32 = precision == MRK_ENCODER_F32 || precision == MRK_ENCODER_AUTO, split = precision == MRK_ENCODER_SPLIT;
   auto get = [&](const std::string &name) -> const HostTensor & {
     auto it = ck.tensors.find(name);
     if (it == ck.tensors.end()) throw StatusError(MRK_ERR_PARSE, "encoder weights: tensor " + name + " is missing (BERT-family graphs only)");
@@ -60,6 +61,11 @@ void build_encoder(mrk_encoder &e, const Checkpoint &ck, bool f32) {
     throw StatusError(MRK_ERR_UNSUPPORTED, "encoder: hidden " + std::to_string(sh.hidden) + " / heads " + std::to_string(sh.heads) + " / intermediate " +
                       std::to_string(sh.inter) + " is outside the supported shapes (head size 32 or 64, widths multiple of 64, hidden <= 1024)");
   const int H = sh.hidden, I = sh.inter;
+  // (every shape accepted above is one the split product takes; should either range move, a split handle is refused here, with the
+  //  sizes - it never runs in another arithmetic)
+  if (split && !(gemm_split_takes(3 * H, H) && gemm_split_takes(H, H) && gemm_split_takes(I, H) && gemm_split_takes(H, I)))
+    throw StatusError(MRK_ERR_UNSUPPORTED, "encoder: precision split takes products with N % 64 == 0 and K % 32 == 0; hidden " + std::to_string(H) +
+                      " / intermediate " + std::to_string(I) + " has one outside that");
 
   // host image: fp16 block then f32 block, every tensor 256-byte aligned
   std::vector<uint16_t> hs;
@@ -139,6 +145,50 @@ void build_encoder(mrk_encoder &e, const Checkpoint &ck, bool f32) {
     for (auto &o : lo) d.layers32.push_back(LayerDev32{mb + o.wqkv, mb + o.wo, mb + o.w1, mb + o.w2});
     if (sh.classifier) d.pool_w32 = mb + o_pw;
   }
+  if (split) {
+    // what stays f32 beside the vectors: the embedding tables and the pooler (one allocation, 256-byte aligned tensors) ...
+    std::vector<float> es;
+    auto put_e = [&](const HostTensor &t) { size_t off = es.size(); es.insert(es.end(), t.data.begin(), t.data.end()); es.resize((es.size() + 63) / 64 * 64); return off; };
+    const size_t e_word = put_e(word), e_pos = put_e(get("embeddings.position_embeddings.weight")), e_type = put_e(get("embeddings.token_type_embeddings.weight"));
+    const size_t e_pw = sh.classifier ? put_e(get("pooler.dense.weight")) : 0;
+    e.weights32.reserve(es.size() * 4);
+    MRK_HIP(hipMemcpy(e.weights32.p, es.data(), es.size() * 4, hipMemcpyHostToDevice));
+    const float *eb = e.weights32.as<float>();
+    d.word32 = eb + e_word; d.pos32 = eb + e_pos; d.type32 = eb + e_type;
+    if (sh.classifier) d.pool_w32 = eb + e_pw;
+    // ... and the bf16 planes of the four matrices of every layer: plane p of an [N, K] matrix at its offset + p N K, [out, in]
+    // rows as in the checkpoint - a lane's 16-byte load is 8 consecutive k of one output row (encoder_split.hip)
+    std::vector<uint16_t> ps;
+    auto put_p = [&](const std::vector<const HostTensor *> &parts) {
+      size_t numel = 0;
+      for (const HostTensor *t : parts) numel += t->data.size();
+      const size_t off = ps.size();
+      ps.resize(off + (SPLIT_PLANES * numel + 127) / 128 * 128);
+      size_t at = off;
+      for (const HostTensor *t : parts)
+        for (float v : t->data) {
+          uint16_t terms[SPLIT_PLANES];
+          split_bf16(v, terms);
+          for (int q = 0; q < SPLIT_PLANES; ++q) ps[at + q * numel] = terms[q];
+          ++at;
+        }
+      return off;
+    };
+    struct SplitOff { size_t wqkv, wo, w1, w2; };
+    std::vector<SplitOff> off(sh.layers);
+    for (int l = 0; l < sh.layers; ++l) {
+      const std::string p = "encoder.layer." + std::to_string(l) + ".";
+      const size_t qkv = put_p({&get(p + "attention.self.query.weight"), &get(p + "attention.self.key.weight"), &get(p + "attention.self.value.weight")});
+      const size_t wo = put_p({&get(p + "attention.output.dense.weight")}), w1 = put_p({&get(p + "intermediate.dense.weight")}), w2 = put_p({&get(p + "output.dense.weight")});
+      off[l] = SplitOff{qkv, wo, w1, w2};
+    }
+    e.weights_split.reserve(ps.size() * 2);
+    MRK_HIP(hipMemcpy(e.weights_split.p, ps.data(), ps.size() * 2, hipMemcpyHostToDevice));
+    e.device_bytes += (int64_t)(es.size() * 4 + ps.size() * 2);
+    const uint16_t *pb = e.weights_split.as<uint16_t>();
+    for (const SplitOff &o : off) d.layers_split.push_back(LayerSplit{pb + o.wqkv, pb + o.wo, pb + o.w1, pb + o.w2});
+    d.split = true;
+  }
 }
 
 constexpr size_t GRAPH_MAX_TOKENS = 8192, GRAPH_MAX_CACHED = 256;
@@ -151,7 +201,10 @@ void drop_graphs(mrk_encoder &e) {
 // Which arithmetic a handle's calls run in is a property of the HANDLE (mrk_encoder_load_ex), never of the size of a call:
 // the f32 kernels give a sequence the same bits whatever batch it travels in, so a request's scores do not depend on how
 // many concurrent callers mrk_rank's combining front merged.  (ABI <= 7 had a size-based MRK_ENCODER_AUTO; it is f32 now.)
-bool call_in_f32(const mrk_encoder &e) { return e.precision != MRK_ENCODER_FP16; }
+// A split handle (MRK_ENCODER_SPLIT) is not "f32" here: it keeps no f32 matrices, and its arithmetic - f32 activations, the dense
+// products on the bf16 instruction - is e.dev.split, set once at load.  It shares the f32 handle's property all the same: one
+// canonical order per output element, the same bits in every batch.
+bool call_in_f32(const mrk_encoder &e) { return e.precision == MRK_ENCODER_F32 || e.precision == MRK_ENCODER_AUTO; }
 
 // one forward pass over a padded id batch; `out` is host memory sized by the mode
 void run_encoder(mrk_encoder &e, const int32_t *ids, const int32_t *types, const int32_t *mask, int n, int seq, int mode, float *out, bool f32) {
@@ -222,7 +275,7 @@ void run_encoder(mrk_encoder &e, const int32_t *ids, const int32_t *types, const
   // mrk_profile_enable: the forward pass (embedding lookup ... pooling / classifier, no copies) between two events on the
   // encoder's own stream, accumulated under the name "encoder" (bench.py: the dominant launch sequence of config 5)
   hipEvent_t ev_a = nullptr, ev_b = nullptr;
-  const bool timed = e.ctx->profile && !(switches().encoder_graph && !e.dev.f32) && hipEventCreate(&ev_a) == hipSuccess && hipEventCreate(&ev_b) == hipSuccess;
+  const bool timed = e.ctx->profile && !(switches().encoder_graph && !e.dev.f32_activations()) && hipEventCreate(&ev_a) == hipSuccess && hipEventCreate(&ev_b) == hipSuccess;
   EncoderDest dst;
   dst.h_out = e.h_out.p;
   dst.out_n = out_n;
@@ -234,7 +287,7 @@ void run_encoder(mrk_encoder &e, const int32_t *ids, const int32_t *types, const
   // Opt-in (MRK_ENCODER_GRAPH=1): measured 0.230 vs 0.240 ms for a 9-token query -- the forward pass of a small batch
   // is bound by the dependent-kernel chain, not by launch overhead -- and rocprofv3's kernel tracing crashes inside
   // the HIP runtime when a captured graph is launched.
-  const bool use_graphs = switches().encoder_graph && !e.dev.f32;
+  const bool use_graphs = switches().encoder_graph && !e.dev.f32_activations();
   if (use_graphs && M <= GRAPH_MAX_TOKENS) {
     // (a packed batch's launch geometry depends on its token count and its longest sequence)
     const std::tuple<int, int, int> key(n, packed ? -(int)M : seq, mode * 4096 + (packed ? max_len : 0));
@@ -428,13 +481,14 @@ int mrk_encoder_load_ex(mrk_ctx *ctx, const uint8_t *weights, size_t len, const 
                         int precision, mrk_encoder **out) {
   return guard([&] {
     need(ctx && weights && tokenizer_json && out, "mrk_encoder_load: null argument");
-    need(precision == MRK_ENCODER_FP16 || precision == MRK_ENCODER_F32 || precision == MRK_ENCODER_AUTO, "mrk_encoder_load_ex: unknown precision");
+    need(precision == MRK_ENCODER_FP16 || precision == MRK_ENCODER_F32 || precision == MRK_ENCODER_AUTO || precision == MRK_ENCODER_SPLIT,
+         "mrk_encoder_load_ex: unknown precision");
     std::unique_ptr<mrk_encoder> e(new mrk_encoder);
     e->tok = Tokenizer::from_json(tokenizer_json, tok_len);
     Checkpoint ck = read_checkpoint(weights, len);
     if (heads > 0) ck.heads = heads;
     MRK_HIP(hipSetDevice(ctx->device));
-    build_encoder(*e, ck, precision != MRK_ENCODER_FP16);   // (f32 keeps the matrices as f32 too)
+    build_encoder(*e, ck, precision);   // (f32 keeps the matrices as f32 too, split as bf16 planes)
     e->precision = precision;
     MRK_HIP(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
     e->ctx = ctx;

@@ -959,7 +959,7 @@ __global__ __launch_bounds__(256) void attention_f32_kernel(const float *__restr
 
 void encoder_reserve(const EncoderDev &enc, EncoderScratch &sc, int n, int seq) {
   const size_t M = (size_t)n * seq, H = enc.shape.hidden, I = enc.shape.inter;
-  const size_t w = enc.f32 ? 4 : 2;  // bytes per activation between the products
+  const size_t w = enc.f32_activations() ? 4 : 2;  // bytes per activation between the products
   sc.x.reserve(M * H * 4);
   sc.xh.reserve(M * H * 2);
   sc.qkv.reserve(M * 3 * H * w);
@@ -982,14 +982,24 @@ static void forward_impl(const EncoderDev &enc, EncoderScratch &sc, int n, int s
   uint16_t *xh = sc.xh.as<uint16_t>(), *qkv = sc.qkv.as<uint16_t>(), *ctx = sc.ctx.as<uint16_t>(), *mid = sc.mid.as<uint16_t>();
   const int row_blocks = (M + 3) / 4;
   const float scale = 1.0f / sqrtf((float)DH);
-  if (enc.f32) {  // precision f32 (mrk_encoder_load_ex): the fp32 graph's arithmetic; qkv / ctx / mid hold f32 here
+  if (enc.f32_activations()) {  // precision f32 (mrk_encoder_load_ex): the fp32 graph's arithmetic; qkv / ctx / mid hold f32 here
     float *qf = sc.qkv.as<float>(), *cf = sc.ctx.as<float>(), *mf = sc.mid.as<float>();
     hipLaunchKernelGGL(embed_ln_kernel<float>, dim3(row_blocks), dim3(256), 0, s, ids, types, pos_ids, M, seq, H, sh.vocab, sh.type_vocab, enc.word32, enc.pos32,
                        enc.type32, enc.embg, enc.embb, sh.eps, x, (_Float16 *)xh);
+    // the four dense products of a layer: a split handle's on the bf16 instruction from its planes (encoder_split.hip), an f32
+    // handle's on the f32 one.  Everything between them - attention, LayerNorm, the f32 activations - is the same pass.
+    static_assert(DENSE_NONE == EPI32_NONE && DENSE_GELU == EPI32_GELU && DENSE_RES == EPI32_RES, "one numbering of the epilogues");
+    auto dense = [&](int epi, const float *A, const float *w32, const uint16_t *planes, const float *bias, const float *res, float *out, int N, int K) {
+      if (enc.split) gemm_split(epi, A, planes, bias, res, out, M, N, K, s);
+      else if (epi == EPI32_GELU) launch_gemm_f32<EPI32_GELU>(A, w32, bias, res, out, M, N, K, s);
+      else if (epi == EPI32_RES) launch_gemm_f32<EPI32_RES>(A, w32, bias, res, out, M, N, K, s);
+      else launch_gemm_f32<EPI32_NONE>(A, w32, bias, res, out, M, N, K, s);
+    };
     for (size_t l = 0; l < enc.layers.size(); ++l) {
       const LayerDev &L = enc.layers[l];
-      const LayerDev32 &W = enc.layers32[l];
-      launch_gemm_f32<EPI32_NONE>(x, W.wqkv, L.bqkv, nullptr, qf, M, 3 * H, H, s);
+      const LayerDev32 W = enc.split ? LayerDev32{} : enc.layers32[l];
+      const LayerSplit P = enc.split ? enc.layers_split[l] : LayerSplit{};
+      dense(EPI32_NONE, x, W.wqkv, P.wqkv, L.bqkv, nullptr, qf, 3 * H, H);
       const dim3 ag32((seq + 15) / 16, (sh.heads + ATT_HEADS - 1) / ATT_HEADS, n);
       if (switches().encoder_f32_mfma && DH == 32)
         hipLaunchKernelGGL((attention_f32_mfma_kernel<32>), ag32, dim3(64 * ATT_HEADS), 0, s, (const float *)qf, mask, cu, seq, H, sh.heads, scale, cf);
@@ -998,10 +1008,10 @@ static void forward_impl(const EncoderDev &enc, EncoderScratch &sc, int n, int s
       else
         hipLaunchKernelGGL(attention_f32_kernel, dim3((seq + 3) / 4, sh.heads, n), dim3(256), (size_t)4 * seq * sizeof(float), s, (const float *)qf, mask, cu, seq, H,
                            DH, scale, cf);
-      launch_gemm_f32<EPI32_RES>(cf, W.wo, L.bo, x, y, M, H, H, s);
+      dense(EPI32_RES, cf, W.wo, P.wo, L.bo, x, y, H, H);
       hipLaunchKernelGGL(ln_kernel, dim3(row_blocks), dim3(256), 0, s, (const float *)y, M, H, L.ln1g, L.ln1b, sh.eps, x, (_Float16 *)xh);
-      launch_gemm_f32<EPI32_GELU>(x, W.w1, L.b1, nullptr, mf, M, I, H, s);
-      launch_gemm_f32<EPI32_RES>(mf, W.w2, L.b2, x, y, M, H, I, s);
+      dense(EPI32_GELU, x, W.w1, P.w1, L.b1, nullptr, mf, I, H);
+      dense(EPI32_RES, mf, W.w2, P.w2, L.b2, x, y, H, I);
       hipLaunchKernelGGL(ln_kernel, dim3(row_blocks), dim3(256), 0, s, (const float *)y, M, H, L.ln2g, L.ln2b, sh.eps, x, (_Float16 *)xh);
     }
     MRK_HIP(hipGetLastError());
@@ -1038,7 +1048,7 @@ void encoder_classify(const EncoderDev &enc, EncoderScratch &sc, int n, int seq,
   if (n <= 0) return;
   const int H = enc.shape.hidden;
   const int32_t *cu = M_packed > 0 ? sc.ids.as<int32_t>() + 3 * (size_t)M_packed : nullptr;
-  if (enc.f32)
+  if (enc.f32_activations())   // f32 and split: the f32 pooler
     hipLaunchKernelGGL(classify_kernel<float>, dim3(n), dim3(256), (H + 4) * sizeof(float), s, (const float *)sc.x.as<float>(), cu, seq, H, enc.pool_w32, enc.pool_b,
                        enc.cls_w, enc.cls_b, d_out);
   else

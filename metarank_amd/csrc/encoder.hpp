@@ -9,6 +9,7 @@
 #include <tuple>
 #include <vector>
 
+#include "device_types.hpp"
 #include "runtime.hpp"
 #include "tokenizer.hpp"
 
@@ -47,6 +48,41 @@ struct LayerDev32 {
   const float *wqkv, *wo, *w1, *w2;              // f32 [out, in]
 };
 
+// Precision split (mrk_encoder_load_ex(MRK_ENCODER_SPLIT), encoder_split.hip): an f32 value as a sum of bf16 terms
+// x = x1 + x2 (+ x3), x1 = bf16_rne(x), x2 = bf16_rne(x - x1), ...; a product as the sum of the leading term products on the
+// bf16 matrix instruction, accumulated in f32.  SPLIT_PRODUCTS = 3: a1 w1 + (a1 w2 + a2 w1), two planes per operand;
+// 6 adds a2 w2 + a1 w3 + a3 w1 and a third plane.  The ONE place the rounding is written: weights at load (host) and
+// activations in the kernel (device) go through split_bf16.
+constexpr int SPLIT_PRODUCTS = 3;
+constexpr int SPLIT_PLANES = SPLIT_PRODUCTS == 3 ? 2 : 3;
+static_assert(SPLIT_PRODUCTS == 3 || SPLIT_PRODUCTS == 6, "three or six term products");
+
+MRK_HD inline uint32_t split_f32_bits(float x) { union { float f; uint32_t u; } v; v.f = x; return v.u; }
+MRK_HD inline float split_bits_f32(uint32_t u) { union { float f; uint32_t u; } v; v.u = u; return v.f; }
+// round to nearest even onto the upper 16 bits; the result still as f32 bits (low half zero).  An infinity stays itself, a finite
+// value past the largest bf16 becomes one (as rounding should); a NaN is answered with the quiet NaN, whatever its payload - the
+// integer sum would turn some payloads into a finite value.
+MRK_HD inline uint32_t bf16_rne_bits(float x) {
+  const uint32_t u = split_f32_bits(x);
+  const uint32_t r = (u + 0x7fffu + ((u >> 16) & 1u)) & 0xffff0000u;
+  return x != x ? 0x7fc00000u : r;
+}
+// t[p] = the p-th bf16 term of x.  An infinite x has x - x1 = NaN: a non-finite operand gives a non-finite product, not
+// necessarily the f32 product's infinity.
+MRK_HD inline void split_bf16(float x, uint16_t (&t)[SPLIT_PLANES]) {
+  float rest = x;
+  for (int p = 0; p < SPLIT_PLANES; ++p) {
+    const uint32_t b = bf16_rne_bits(rest);
+    t[p] = (uint16_t)(b >> 16);
+    rest = rest - split_bits_f32(b);   // exact: b agrees with `rest` in sign, exponent and leading mantissa bits
+  }
+}
+
+// the bf16 planes of a split handle's four matrices: plane p of an [N, K] matrix at pointer + p * N * K, each [out, in]
+struct LayerSplit {
+  const uint16_t *wqkv, *wo, *w1, *w2;
+};
+
 struct EncoderDev {
   EncoderShape shape;
   const uint16_t *word, *pos, *type;             // fp16 embedding tables
@@ -57,6 +93,9 @@ struct EncoderDev {
   bool f32 = false;                              // precision f32: the fields below are set and the forward pass uses them
   const float *word32 = nullptr, *pos32 = nullptr, *type32 = nullptr, *pool_w32 = nullptr;
   std::vector<LayerDev32> layers32;
+  bool split = false;                            // precision split: word32 / pos32 / type32 / pool_w32 and layers_split are set; f32 stays false
+  std::vector<LayerSplit> layers_split;
+  bool f32_activations() const { return f32 || split; }   // what lies between the kernels is f32 (qkv, ctx, mid)
 };
 
 // activations of one forward call (grow-only, owned by the encoder handle)
@@ -77,6 +116,13 @@ void encoder_forward_packed(const EncoderDev &enc, EncoderScratch &s, int n, int
 void encoder_meanpool(const EncoderDev &enc, EncoderScratch &s, int n, int seq, int M_packed, float *d_out, hipStream_t stream);
 // pooler + classifier on the [CLS] row: -> out f32 [n] (device)
 void encoder_classify(const EncoderDev &enc, EncoderScratch &s, int n, int seq, int M_packed, float *d_out, hipStream_t stream);
+
+// encoder_split.hip: out[M, N] = A[M, K] W[N, K]^T + bias (+ GELU | + res) with W given as bf16 planes (LayerSplit) and A
+// split into bf16 terms on the way into LDS.  N % 64 == 0, K % 32 == 0 (gemm_split_takes).
+enum { DENSE_NONE = 0, DENSE_GELU = 1, DENSE_RES = 2 };
+inline bool gemm_split_takes(int N, int K) { return N > 0 && K > 0 && N % 64 == 0 && K % 32 == 0; }
+void gemm_split(int epilogue, const float *A, const uint16_t *W_planes, const float *bias, const float *res, float *out, int M, int N, int K,
+                hipStream_t stream);
 
 struct KnnTable;  // knn.hpp
 
@@ -102,7 +148,8 @@ struct EncoderMarks {
 // `dst`.  The caller holds e.mu, has sized every buffer and has set e.dev.f32.
 void encoder_enqueue(mrk_encoder &e, const void *h_ids, size_t id_words, int n, int seq, int M_packed, int mode, const EncoderDest &dst,
                      const EncoderMarks &marks);
-// ... and what surrounds it for a caller outside capi_encoder.cpp (under e.mu): the arithmetic a handle's calls run in, and
+// ... and what surrounds it for a caller outside capi_encoder.cpp (under e.mu): whether a handle's calls run in the f32 kernels
+// (false for an fp16 handle and for a split one, whose arithmetic is e.dev.split, fixed at load), and
 // the activation buffers + the device id buffer sized for M tokens / id_words words (captured graphs are dropped when one moves)
 bool encoder_calls_in_f32(const mrk_encoder &e);
 void encoder_reserve_call(mrk_encoder &e, size_t M, size_t id_words);
@@ -123,7 +170,8 @@ struct mrk_encoder {
   mrk::Tokenizer tok;
   mrk::EncoderDev dev;
   mrk::DevBuf weights;     // one allocation: fp16 matrices then f32 vectors
-  mrk::DevBuf weights32;   // precision f32: the matrices once more, as f32
+  mrk::DevBuf weights32;   // precision f32: the matrices once more, as f32 (split: the embedding tables and the pooler only)
+  mrk::DevBuf weights_split;  // precision split: the bf16 planes of the layers' matrices
   mrk::EncoderScratch scratch;
   mrk::PinBuf h_ids, h_out;  // pinned staging of one call
   hipStream_t stream = nullptr;
@@ -132,6 +180,6 @@ struct mrk_encoder {
   int64_t device_bytes = 0;
   // EmbeddingCache: query text -> embedding (FieldMatchBiencoderFeature.scala:96-99)
   std::map<std::string, std::vector<float>> cache;
-  int precision = 0;       // MRK_ENCODER_FP16 | _F32 (mrk_encoder_load_ex; _AUTO = _F32)
+  int precision = 0;       // MRK_ENCODER_FP16 | _F32 | _SPLIT (mrk_encoder_load_ex; _AUTO = _F32)
   std::atomic<int> refs{1};
 };

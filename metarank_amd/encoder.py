@@ -73,12 +73,15 @@ class HipEncoder:
                  precision: str | None = None):
         """precision (mrk_encoder_load_ex): "f32" (default, what mrk_encoder_load uses: f32 operands on the f32-input matrix
         instruction - the fp32 ONNX session's arithmetic, batch-independent bits; `f32=True` is the same), "f16" (opt-in:
-        fp16 operands on the matrix cores, ~3.5x faster per packed batch, cosines within 3e-3), "auto" (ABI <= 7 name: f32 now)"""
+        fp16 operands on the matrix cores, ~3.5x faster per packed batch, cosines within 3e-3), "auto" (ABI <= 7 name: f32 now),
+        "split" (opt-in, MRK_ENCODER_SPLIT: the dense products as three bf16 products of two-term bf16 splits of the f32
+        operands, f32 accumulation - within the f32 handle's error bounds of the fp32 graph and batch-independent bits like it,
+        but not its bits)"""
         self.ctx = ctx or default_context()
         tj = tokenizer_json.encode() if isinstance(tokenizer_json, str) else tokenizer_json
         self._h = C.c_void_p()
         self.precision = precision or ("f16" if f32 is False else "f32")
-        code = {"f16": 0, "f32": 1, "auto": 2}[self.precision]
+        code = {"f16": 0, "f32": 1, "auto": 2, "split": 3}[self.precision]
         N.check(N.lib().mrk_encoder_load_ex(self.ctx.handle, weights, len(weights), tj, len(tj), heads, code, C.byref(self._h)))
         info = N.mrk_encoder_info()
         N.check(N.lib().mrk_encoder_get_info(self._h, C.byref(info)))

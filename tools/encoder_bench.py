@@ -31,12 +31,110 @@ def timeit(fn, reps, warm=3):
     return np.array(ts)
 
 
+BF16_PEAK_TFLOPS = 2500.0   # dense bf16 matrix peak of the MI355X
+
+
+def compare(reps):
+    """One packed forward pass (mrk_encoder_embed_ids) in all three precisions, same process, same inputs, the precisions taken in
+    turn inside every repetition: HIP events around the forward pass (mrk_profile_enable's "encoder" timer), median of `reps`.
+    split_product_tflops = the bf16 work of the dense products (SPLIT_PRODUCTS = 3 products of 2 M N K each) over the WHOLE pass -
+    a lower bound of the split kernel's own rate; the kernel's share of peak comes from a kernel trace of --precision split."""
+    import metarank_amd as M
+    ctx = M.Context(0)
+    ctx.profile_enable(True)
+    out = {}
+    rng = np.random.default_rng(9)
+    for name, shape, n, lo, hi in (("minilm_c5_batch", dict(layers=6, hidden=384, heads=12, inter=1536), 3840, 0, 0),
+                                   ("bert_base_384_tokens", dict(layers=12, hidden=768, heads=12, inter=3072), 12, 16, 48)):
+        tj = synth.wordpiece_tokenizer_json(vocab_size=2000, max_length=128)
+        blob = synth.bert_safetensors(synth.synthetic_bert(**shape), shape["heads"])
+        if lo:   # n sequences of lo .. hi random tokens
+            lens = rng.integers(lo, hi + 1, size=n); lens[0] = hi
+            ids = rng.integers(5, 2000, size=(n, hi)).astype(np.int32); ty = np.zeros_like(ids)
+            m = (np.arange(hi)[None, :] < lens[:, None]).astype(np.int32)
+        else:    # bench.py --workload c5: one device batch's queries
+            ids, ty, m = HipTokenizer(tj).encode_batch(synth.synthetic_queries(n, seed=3))
+        encs = {p: HipEncoder(blob, tj, ctx=ctx, precision=p) for p in ("f32", "f16", "split")}
+        ms = {p: [] for p in encs}
+        emb = {}
+        for r in range(3 + reps):
+            for p, e in encs.items():
+                t0 = ctx.profile_get("encoder")[0]
+                emb[p] = e.embed_ids(ids, ty, m)
+                if r >= 3:
+                    ms[p].append(ctx.profile_get("encoder")[0] - t0)
+        tokens, H, I, L = int(m.sum()), shape["hidden"], shape["inter"], shape["layers"]
+        dense = 2.0 * tokens * L * (4 * H * H + 2 * H * I)
+        med = {p: float(np.median(v)) for p, v in ms.items()}
+        out[name] = {"tokens": tokens, "sequences": int(n), "ms": med, "ms_min_max": {p: [float(min(v)), float(max(v))] for p, v in ms.items()},
+                     "split_vs_f32_time": med["split"] / med["f32"], "split_product_tflops_whole_pass": 3 * dense / med["split"] / 1e9,
+                     "frac_of_bf16_peak_whole_pass": 3 * dense / med["split"] / 1e9 / BF16_PEAK_TFLOPS,
+                     "max_abs_embedding_diff_vs_f32": {p: float(np.abs(emb[p] - emb["f32"]).max()) for p in ("f16", "split")}}
+        for e in encs.values():
+            e.close()
+    out["ranking_vs_f32"] = rank_agreement(ctx)
+    ctx.close()
+    return out
+
+
+def rank_agreement(ctx, requests=96, items=100, catalogue=5000, sessions=500, trees=500):
+    """bench.py's config 5 in small (24 Ranklens columns + the bi-encoder cosine, a 500-tree forest): how far an fp16 and a split
+    handle move the f32 handle's scores and order - INTEGRATION.md's pair of figures."""
+    import itertools
+    import metarank_amd as M
+    from workloads import ranklens
+    ranker = M.HipRanker(ranklens.c5_config(), ctx)
+    tj = synth.wordpiece_tokenizer_json(vocab_size=2000, max_length=128)
+    blob = synth.bert_safetensors(synth.synthetic_bert(), 12)
+    put = {"double": ranker.put_double, "string": ranker.put_string, "string_list": ranker.put_string_list, "double_list": ranker.put_double_list,
+           "counter": ranker.put_counter, "periodic": ranker.put_periodic, "bounded_list": ranker.put_bounded_list}
+    for kind, key, value in itertools.chain(ranklens.generate_state(catalogue, sessions), ranklens.c5_embeddings(catalogue)):
+        put[kind](key, value)
+    ranker.flush()
+    def with_queries(evs, seed):
+        for ev, q in zip(evs, synth.synthetic_queries(len(evs), seed=seed)):
+            ev["fields"] = [{"name": "query", "value": q}]
+        return evs
+    encs = {p: HipEncoder(blob, tj, ctx=ctx, precision=p) for p in ("f32", "f16", "split")}
+    ranker.bind_encoder("title_match", encs["f32"])
+    sample = ranker.prepare("xgboost", with_queries(ranklens.generate_requests(64, 100, catalogue, sessions, seed=ranklens.SEED + 99), 77))
+    sample.run(None)
+    _, _, sm = sample.fetch(matrix=True)
+    sample.close()
+    model = synth.synthetic_lgbm_model(n_trees=trees, n_features=ranker.dim("xgboost"), num_leaves=16, max_depth=8, quantiles=ranklens.column_quantiles(sm, n=49),
+                                       missing="per_feature")
+    booster = M.HipBooster(model, M.LIGHTGBM, ctx)
+    evs = with_queries(ranklens.generate_requests(requests, items, catalogue, sessions, seed=ranklens.SEED + 1), 100)
+    res = {}
+    for p, e in encs.items():
+        ranker.bind_encoder("title_match", e)
+        b = ranker.prepare("xgboost", evs)
+        b.run(booster)
+        s, o, _ = b.fetch()
+        res[p] = (s.copy(), o.copy(), list(b.offsets))
+        b.close()
+    s32, o32, offs = res["f32"]
+    out = {"requests": requests, "items": int(len(s32)), "trees": trees}
+    for p in ("f16", "split"):
+        s, o, _ = res[p]
+        out[p] = {"scores_over_1e-5": int((np.abs(s - s32) > 1e-5).sum()), "max_abs_score_diff": float(np.abs(s - s32).max()),
+                  "reordered_requests": sum(1 for r in range(requests) if not np.array_equal(o[offs[r]:offs[r + 1]], o32[offs[r]:offs[r + 1]]))}
+    booster.close()
+    for e in encs.values():
+        e.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--json", action="store_true")
-    ap.add_argument("--precision", choices=["f16", "f32"], default="f16")
+    ap.add_argument("--precision", choices=["f16", "f32", "split"], default="f16")
     ap.add_argument("--quick", action="store_true", help="single query + the c5 batch (3 840 queries) only")
+    ap.add_argument("--compare", type=int, default=0, metavar="REPS", help="f32 / f16 / split side by side (see compare()), nothing else")
     a = ap.parse_args()
+    if a.compare:
+        print(json.dumps(compare(a.compare)))
+        return
     w = synth.synthetic_bert(classifier=True)
     tj = synth.wordpiece_tokenizer_json(vocab_size=2000, max_length=128)
     enc = HipEncoder(synth.bert_safetensors(w, 12), tj, precision=a.precision)
