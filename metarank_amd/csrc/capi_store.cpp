@@ -284,6 +284,14 @@ int mrk_debug_fused_shape(int n_req, int max_items, int *out3) {
   out3[2] = s.slices;
   return MRK_OK;
 }
+// ... and split_launch_plan under the switches as they stand: out = {SplitKernel, workgroups, threads per workgroup}
+int mrk_debug_split_plan(int M, int N, int K, int *out3) {
+  const mrk::SplitPlan p = mrk::split_launch_plan(M, N, K, mrk::switches().encoder_split_skinny);
+  out3[0] = (int)p.kernel;
+  out3[1] = (int)p.workgroups;
+  out3[2] = p.threads;
+  return MRK_OK;
+}
 // rank_plan.hpp through the C ABI, for tests without a device, under the DEFAULT switches but for the three the table varies.
 // in[24] = {n_req, candidates per request, the largest request's table entries, its median values, compact_tables, overrides,
 // want_matrix, normalises, n_prep, dim | model: present, bit-vector image, f64, thr_cap, n_views, rt_doubles, max_chunk_bytes,

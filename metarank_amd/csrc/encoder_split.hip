@@ -11,9 +11,11 @@
 // every smaller one.  k is walked in ascending steps of 16 (one MFMA's depth); step s adds, in this order,
 //     C0 += a1 w1 [16 s .. 16 s + 15];   C1 += a1 w2 [same k];   C1 += a2 w1;   (six products: C1 += a2 w2; += a1 w3; += a3 w1)
 // and after the last step the element is (C0 + C1), then bias, then GELU / residual.  The weight rows are the instruction's A
-// operand, the token rows its B operand, in every launch.  There is ONE kernel body; the launch shapes below differ in how
-// many 32 x 32 blocks a wavefront owns and in how many wavefronts share the staging, never in an element's chain - so a token's
-// bits depend on neither the tile it fell into nor the batch it travelled in (tests/test_encoder_split_gpu.py).
+// operand, the token rows its B operand, in every launch.  The tile kernel has ONE body; its launch shapes differ in how
+// many 32 x 32 blocks a wavefront owns and in how many wavefronts share the staging, never in an element's chain, and the
+// one-request kernel (gemm_split_skinny_kernel) hands the same two accumulators from wavefront to wavefront - so a token's bits
+// depend on neither the kernel, nor the tile it fell into, nor the batch it travelled in (tests/test_encoder_split_gpu.py,
+// tests/test_encoder_split_skinny_gpu.py).
 //
 // Tile and LDS: a workgroup of WR x WC wavefronts computes a (32 WR TM) x (32 WC TN) tile.  Per 32-wide k block it stages the
 // bf16 planes of its A rows and W rows in LDS as [plane][row][32 + 8]: the 80-byte row stride keeps every 16-byte fragment read
@@ -25,6 +27,8 @@
 #include <hip/hip_runtime.h>
 
 #include "encoder.hpp"
+#include "launch_shape.hpp"
+#include "switches.hpp"
 
 namespace mrk {
 namespace {
@@ -175,18 +179,144 @@ __global__ __launch_bounds__(64 * WR * WC, 2) void gemm_split_kernel(const float
       }
 }
 
+// The same product for M <= 32 rows - ONE request's query on a split handle (mrk_rank with a bi- / cross-encoder field_match), where
+// the critical path is what counts.  One workgroup per 32 x 32 block of the output (N / 32 of them); its four wavefronts own a quarter
+// of K each (S = K / 64 steps of 16) and continue ONE pair of accumulators in turn, wavefront 0 first, handing C0 and C1 over through
+// LDS (8 KB, the kernel's only LDS and barriers) - the chain of gemm_split_kernel, hence its bits.
+//
+// Nothing is staged: a lane's 16-byte load of a W plane (row l & 31, k 16 s + 8 (l >> 5) .. + 7) IS the instruction's A fragment, and
+// its two 16-byte loads of the f32 activations at the same place become the B fragments through split_bf16, in registers.  That split
+// is the expensive part (~14 VALU operations per element, 8 elements per lane and step - several times the step's three MFMAs), so
+// it is kept off the chain: every wavefront holds two groups of up to SKINNY_G steps in registers, asks for both at once when
+// the kernel starts (every wavefront's loads are in flight from the first cycle) and splits them as they arrive, all four wavefronts
+// side by side, BEFORE it waits for its turn.  Up to 2 SKINNY_G steps per wavefront (K <= 128 SKINNY_G) the turn itself is MFMAs
+// only.  A longer share walks on in groups inside the turn: the next group's loads fly during the MFMAs of the one at hand, its split
+// waits on them.  The first group is the ragged one (S - SKINNY_G (groups - 1) steps, wave-uniform guards), every later one is whole.
+constexpr int SKINNY_G = NP == 2 ? 8 : 4;
+
+template <int EPI>
+__global__ __launch_bounds__(256) void gemm_split_skinny_kernel(const float *__restrict__ A, const uint16_t *__restrict__ W, const float *__restrict__ bias,
+                                                                const float *__restrict__ res, float *__restrict__ out, int M, int N, int K) {
+  constexpr int G = SKINNY_G;
+  __shared__ floatx4 hand[8][64];   // C0 then C1, four registers a row: 16 bytes per lane, conflict-free both ways
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int fr = lane & 31, fk = (lane >> 5) * 8, fg = (lane >> 5) * 4;
+  const int n0 = blockIdx.x * 32, S = K / 64;
+  const int groups = (S + G - 1) / G, first = S - G * (groups - 1);
+  const size_t plane = (size_t)N * K;
+  const uint16_t *wrow = W + (size_t)(n0 + fr) * K + wave * S * 16 + fk;
+  const float *arow = A + (size_t)(fr < M ? fr : M - 1) * K + wave * S * 16 + fk;   // rows past M repeat the last one and are never stored
+
+  // steps s0 .. s0 + n - 1 of the wavefront's share: W fragments as they are, A as f32
+  auto fetch = [&](uintx4 (&fw)[G][NP], floatx4 (&ra)[G][2], int s0, int n) {
+#pragma unroll
+    for (int t = 0; t < G; ++t)
+      if (t < n) {
+#pragma unroll
+        for (int p = 0; p < NP; ++p) fw[t][p] = *(const uintx4 *)(wrow + p * plane + 16 * (s0 + t));
+        ra[t][0] = *(const floatx4 *)(arow + 16 * (s0 + t));
+        ra[t][1] = *(const floatx4 *)(arow + 16 * (s0 + t) + 4);
+      }
+  };
+  // ... A's 8 consecutive k of a step into the bf16 fragment of every plane (element e in bits 16 (e & 1) of word e / 2)
+  auto split = [&](const floatx4 (&ra)[G][2], uintx4 (&fa)[G][NP], int n) {
+#pragma unroll
+    for (int t = 0; t < G; ++t)
+      if (t < n) {
+        uint16_t b[8][NP];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) split_bf16(ra[t][e >> 2][e & 3], b[e]);
+#pragma unroll
+        for (int p = 0; p < NP; ++p)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) fa[t][p][q] = (uint32_t)b[2 * q][p] | ((uint32_t)b[2 * q + 1][p] << 16);
+      }
+  };
+  floatx16 c0, c1;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) c0[r] = c1[r] = 0.f;
+  // ... and their term products in the canonical order
+  auto steps = [&](const uintx4 (&fw)[G][NP], const uintx4 (&fa)[G][NP], int n) {
+#pragma unroll
+    for (int t = 0; t < G; ++t)
+      if (t < n) {
+        bf16x8 w[NP], a[NP];
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+          w[p] = __builtin_bit_cast(bf16x8, fw[t][p]);
+          a[p] = __builtin_bit_cast(bf16x8, fa[t][p]);
+        }
+        c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w[0], a[0], c0, 0, 0, 0);     // a1 w1
+        c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w[1], a[0], c1, 0, 0, 0);     // a1 w2
+        c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w[0], a[1], c1, 0, 0, 0);     // a2 w1
+        if constexpr (NP == 3) {
+          c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w[1], a[1], c1, 0, 0, 0);   // a2 w2
+          c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w[2], a[0], c1, 0, 0, 0);   // a1 w3
+          c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w[0], a[2], c1, 0, 0, 0);   // a3 w1
+        }
+      }
+  };
+
+  uintx4 w0[G][NP], w1[G][NP], a0[G][NP], a1[G][NP];   // group 0, 2, 4 ... lives in w0 / a0, group 1, 3, ... in w1 / a1
+  floatx4 r0[G][2], r1[G][2];
+  fetch(w0, r0, 0, first);
+  if (groups > 1) fetch(w1, r1, first, G);
+  split(r0, a0, first);
+  if (groups > 1) split(r1, a1, G);
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    if (wave == w) {
+      if (w > 0) {
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          const floatx4 h0 = hand[v][lane], h1 = hand[4 + v][lane];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) { c0[4 * v + e] = h0[e]; c1[4 * v + e] = h1[e]; }
+        }
+      }
+      steps(w0, a0, first);
+      for (int g = 1; g < groups; g += 2) {   // group g from w1 / a1, then group g + 1 from w0 / a0
+        if (g + 1 < groups) fetch(w0, r0, first + G * g, G);
+        steps(w1, a1, G);
+        if (g + 1 < groups) {
+          split(r0, a0, G);
+          if (g + 2 < groups) fetch(w1, r1, first + G * (g + 1), G);
+          steps(w0, a0, G);
+          if (g + 2 < groups) split(r1, a1, G);
+        }
+      }
+      if (w < 3) {
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          hand[v][lane] = floatx4{c0[4 * v], c0[4 * v + 1], c0[4 * v + 2], c0[4 * v + 3]};
+          hand[4 + v][lane] = floatx4{c1[4 * v], c1[4 * v + 1], c1[4 * v + 2], c1[4 * v + 3]};
+        }
+      }
+    }
+    if (w < 3) __syncthreads();
+  }
+  if (wave != 3) return;
+  // D[weight row][token], as in gemm_split_kernel: the lane owns token fr; registers 4 v .. 4 v + 3 are weight rows 8 v + fg .. + 3
+#pragma unroll
+  for (int v = 0; v < 4; ++v) {
+    floatx4 quad;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) quad[e] = c0[4 * v + e] + c1[4 * v + e];
+    store_split_quad<EPI>(quad, fr, n0 + 8 * v + fg, M, N, bias, res, out);
+  }
+}
+
+// split_launch_plan (launch_shape.hpp) decides, nothing here does
 template <int EPI>
 void launch_gemm_split(const float *A, const uint16_t *W, const float *bias, const float *res, float *out, int M, int N, int K, hipStream_t s) {
-  // <= 32 rows (one request's query): two wavefronts, one 32 x 32 block each - the shortest life a workgroup can have here
-  if (M <= 32) {
-    hipLaunchKernelGGL((gemm_split_kernel<1, 2, 1, 1, false, EPI>), dim3(N / 64), dim3(128), 0, s, A, W, bias, res, out, M, N, K);
-    return;
+  const SplitPlan p = split_launch_plan(M, N, K, switches().encoder_split_skinny);
+  const dim3 grid(p.workgroups), block(p.threads);
+  switch (p.kernel) {
+    case SPLIT_SKINNY: hipLaunchKernelGGL((gemm_split_skinny_kernel<EPI>), grid, block, 0, s, A, W, bias, res, out, M, N, K); break;
+    case SPLIT_TILE_32x64: hipLaunchKernelGGL((gemm_split_kernel<1, 2, 1, 1, false, EPI>), grid, block, 0, s, A, W, bias, res, out, M, N, K); break;
+    case SPLIT_TILE_64: hipLaunchKernelGGL((gemm_split_kernel<2, 2, 1, 1, true, EPI>), grid, block, 0, s, A, W, bias, res, out, M, N, K); break;
+    case SPLIT_TILE_128: hipLaunchKernelGGL((gemm_split_kernel<2, 2, 2, 2, true, EPI>), grid, block, 0, s, A, W, bias, res, out, M, N, K); break;
   }
-  // 128 x 128 tiles once the grid covers the chip with them (one workgroup per CU), 64 x 64 tiles otherwise
-  const bool big = N % 128 == 0 && (size_t)((M + 127) / 128) * (N / 128) >= 256;
-  auto grid_of = [&](int bm, int bn) { return dim3((unsigned)(8 * (((M + bm - 1) / bm + 7) / 8) * (N / bn))); };
-  if (big) hipLaunchKernelGGL((gemm_split_kernel<2, 2, 2, 2, true, EPI>), grid_of(128, 128), dim3(256), 0, s, A, W, bias, res, out, M, N, K);
-  else hipLaunchKernelGGL((gemm_split_kernel<2, 2, 1, 1, true, EPI>), grid_of(64, 64), dim3(256), 0, s, A, W, bias, res, out, M, N, K);
 }
 
 }  // namespace

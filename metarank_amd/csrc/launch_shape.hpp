@@ -117,4 +117,24 @@ inline size_t rank_one_walk_lds_bytes(int cols, bool f64, size_t chunk_bytes, in
 }
 constexpr size_t RANK_ONE_LDS_CAP = 96 * 1024;   // what mrk_rank's one-launch kernels keep to (rank_plan.hpp plan_rank)
 
+// Which kernel a dense product of a split-bf16 encoder handle runs, and its grid (encoder_split.hip launch_gemm_split; N % 64 == 0,
+// K % 32 == 0).  One request's query (M <= 32 rows) takes the skinny kernel - one 32 x 32 block per workgroup, K over its four
+// wavefronts, so K % 64 == 0 - unless MRK_ENCODER_SPLIT_SKINNY=0 (`skinny`), which leaves it the 32 x 64 tile of two wavefronts.  More rows:
+// 128 x 128 tiles once the grid covers the chip with them (one workgroup per CU), 64 x 64 tiles otherwise, both on the XCD fold's grid.
+enum SplitKernel { SPLIT_SKINNY = 0, SPLIT_TILE_32x64 = 1, SPLIT_TILE_64 = 2, SPLIT_TILE_128 = 3 };
+struct SplitPlan {
+  SplitKernel kernel;
+  unsigned workgroups;
+  int threads;
+};
+inline SplitPlan split_launch_plan(int M, int N, int K, bool skinny) {
+  if (M <= 32) {
+    if (skinny && K % 64 == 0) return {SPLIT_SKINNY, (unsigned)(N / 32), 256};
+    return {SPLIT_TILE_32x64, (unsigned)(N / 64), 128};
+  }
+  const bool big = N % 128 == 0 && (size_t)((M + 127) / 128) * (N / 128) >= 256;
+  const int bm = big ? 128 : 64;
+  return {big ? SPLIT_TILE_128 : SPLIT_TILE_64, (unsigned)(8 * (((M + bm - 1) / bm + 7) / 8) * (N / bm)), 256};
+}
+
 }  // namespace mrk

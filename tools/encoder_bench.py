@@ -77,6 +77,49 @@ def compare(reps):
     return out
 
 
+SINGLE_SHAPES = {"minilm_l6": dict(layers=6, hidden=384, heads=12, inter=1536), "bert_base": dict(layers=12, hidden=768, heads=12, inter=3072)}
+
+
+def single(reps, shapes):
+    """One request's query - ONE sequence of 9 and of 32 tokens - on an f32 handle and on a split handle with MRK_ENCODER_SPLIT_SKINNY=0
+    (the 32 x 64 tile) and =1 (gemm_split_skinny_kernel): same process, the three taken in turn inside every repetition, HIP events
+    around the forward pass (the "encoder" timer), 3 warm-ups, median [min, max] in ms.  The two split runs must give the same bits."""
+    import metarank_amd as M
+    from metarank_amd import _native
+    ctx = M.Context(0)
+    ctx.profile_enable(True)
+    rng = np.random.default_rng(9)
+    tj = synth.wordpiece_tokenizer_json(vocab_size=2000, max_length=128)
+    out = {}
+    for name in shapes:
+        shape = SINGLE_SHAPES[name]
+        blob = synth.bert_safetensors(synth.synthetic_bert(**shape), shape["heads"])
+        encs = {"f32": HipEncoder(blob, tj, ctx=ctx, precision="f32"), "split": HipEncoder(blob, tj, ctx=ctx, precision="split")}
+        for n in (9, 32):
+            ids = rng.integers(5, 2000, size=(1, n)).astype(np.int32); ty = np.zeros_like(ids); m = np.ones_like(ids)
+            runs = (("f32", "f32", None), ("split_tile", "split", "0"), ("split_skinny", "split", "1"))
+            ms, emb = {r[0]: [] for r in runs}, {}
+            for r in range(3 + reps):
+                for key, handle, switch in runs:
+                    if switch is not None:
+                        os.environ["MRK_ENCODER_SPLIT_SKINNY"] = switch
+                        _native.reload_switches()
+                    t0 = ctx.profile_get("encoder")[0]
+                    emb[key] = encs[handle].embed_ids(ids, ty, m)
+                    if r >= 3:
+                        ms[key].append(ctx.profile_get("encoder")[0] - t0)
+            os.environ.pop("MRK_ENCODER_SPLIT_SKINNY", None)
+            _native.reload_switches()
+            out[f"{name}_{n}_tokens"] = {"ms": {k: float(np.median(v)) for k, v in ms.items()}, "ms_min_max": {k: [float(min(v)), float(max(v))] for k, v in ms.items()},
+                                         "skinny_vs_tile_time": float(np.median(ms["split_skinny"]) / np.median(ms["split_tile"])),
+                                         "same_bits_skinny_and_tile": bool(np.array_equal(emb["split_skinny"].view(np.uint32), emb["split_tile"].view(np.uint32))),
+                                         "max_abs_embedding_diff_vs_f32": float(np.abs(emb["split_skinny"] - emb["f32"]).max())}
+        for e in encs.values():
+            e.close()
+    ctx.close()
+    return out
+
+
 def rank_agreement(ctx, requests=96, items=100, catalogue=5000, sessions=500, trees=500):
     """bench.py's config 5 in small (24 Ranklens columns + the bi-encoder cosine, a 500-tree forest): how far an fp16 and a split
     handle move the f32 handle's scores and order - INTEGRATION.md's pair of figures."""
@@ -131,7 +174,12 @@ def main():
     ap.add_argument("--precision", choices=["f16", "f32", "split"], default="f16")
     ap.add_argument("--quick", action="store_true", help="single query + the c5 batch (3 840 queries) only")
     ap.add_argument("--compare", type=int, default=0, metavar="REPS", help="f32 / f16 / split side by side (see compare()), nothing else")
+    ap.add_argument("--single", type=int, default=0, metavar="REPS", help="one 9- and one 32-token query: f32 / split on the 32 x 64 tile / split on the skinny kernel (see single()), nothing else")
+    ap.add_argument("--shape", choices=sorted(SINGLE_SHAPES), default=None, help="--single: this shape only (a kernel trace per shape)")
     a = ap.parse_args()
+    if a.single:
+        print(json.dumps(single(a.single, [a.shape] if a.shape else list(SINGLE_SHAPES))))
+        return
     if a.compare:
         print(json.dumps(compare(a.compare)))
         return
