@@ -604,6 +604,11 @@ int mrk_encoder_load(mrk_ctx *ctx, const uint8_t *weights, size_t len, const cha
  * mrk_index_build_texts.  Not promised: the bits of the reference's fp32 session or of an MRK_ENCODER_F32 handle - results
  * differ from those in the last bits - nor a given speed (DESIGN has what was measured).  A non-finite activation or weight
  * gives a non-finite result, not necessarily the one f32 arithmetic gives (inf - bf16(inf) is NaN).
+ * Two experiment switches of the environment touch a split handle and no other:
+ * MRK_ENCODER_SPLIT_SKINNY=0 runs its <= 32-row products on the 32 x 64 tile instead of the one-request kernel (same bits);
+ * MRK_ENCODER_SPLIT_ATTENTION=1 (default 0) runs its attention on the bf16 instruction as well - scale Q K^T and P V as split
+ * products in the same canonical order, the softmax in f32 - with the same two promises (the bounds, and bits that do not
+ * depend on the batch) and other last bits than with 0.  With 0 or unset the handle launches attention as described above.
  * Any other value: MRK_ERR_INVALID_ARG. */
 enum { MRK_ENCODER_FP16 = 0, MRK_ENCODER_F32 = 1, MRK_ENCODER_AUTO = 2, MRK_ENCODER_SPLIT = 3 };
 int mrk_encoder_load_ex(mrk_ctx *ctx, const uint8_t *weights, size_t len, const char *tokenizer_json, size_t tok_len, int heads,

@@ -75,6 +75,7 @@ static Switches read_switches() {
   s.semantic_window = std::max(0, std::min(64, num("MRK_SEMANTIC_WINDOW", 4)));
   s.encoder_f32_mfma = flag("MRK_ENCODER_F32_MFMA", true);
   s.encoder_split_skinny = flag("MRK_ENCODER_SPLIT_SKINNY", true);
+  s.encoder_split_attention = flag("MRK_ENCODER_SPLIT_ATTENTION", false);
   s.als_stage_max = std::max(0, num("MRK_ALS_STAGE_MAX", 0));
   return s;
 }

@@ -242,14 +242,14 @@ void run_encoder(mrk_encoder &e, const int32_t *ids, const int32_t *types, const
   // every buffer is sized before anything is enqueued: a captured graph holds raw pointers, so a buffer that
   // moves invalidates the graphs recorded so far
   const void *before[] = {e.h_ids.p, e.h_out.p, e.scratch.ids.p, e.scratch.x.p, e.scratch.xh.p, e.scratch.qkv.p,
-                          e.scratch.ctx.p, e.scratch.mid.p, e.scratch.y.p, e.scratch.out.p};
+                          e.scratch.ctx.p, e.scratch.mid.p, e.scratch.y.p, e.scratch.out.p, e.scratch.kv.p};
   e.h_ids.reserve(id_words * 4);
   e.h_out.reserve(out_n * 4);
   e.scratch.ids.reserve(id_words * 4);
   e.scratch.out.reserve(out_n * 4);
   encoder_reserve(e.dev, e.scratch, 1, (int)M);
   const void *after[] = {e.h_ids.p, e.h_out.p, e.scratch.ids.p, e.scratch.x.p, e.scratch.xh.p, e.scratch.qkv.p,
-                         e.scratch.ctx.p, e.scratch.mid.p, e.scratch.y.p, e.scratch.out.p};
+                         e.scratch.ctx.p, e.scratch.mid.p, e.scratch.y.p, e.scratch.out.p, e.scratch.kv.p};
   if (memcmp(before, after, sizeof before) != 0) drop_graphs(e);
 
   int32_t *h = e.h_ids.as<int32_t>();
@@ -370,10 +370,10 @@ void encoder_enqueue(mrk_encoder &e, const void *h_ids, size_t id_words, int n, 
 bool encoder_calls_in_f32(const mrk_encoder &e) { return call_in_f32(e); }
 
 void encoder_reserve_call(mrk_encoder &e, size_t M, size_t id_words) {
-  const void *before[] = {e.scratch.ids.p, e.scratch.x.p, e.scratch.xh.p, e.scratch.qkv.p, e.scratch.ctx.p, e.scratch.mid.p, e.scratch.y.p};
+  const void *before[] = {e.scratch.ids.p, e.scratch.x.p, e.scratch.xh.p, e.scratch.qkv.p, e.scratch.ctx.p, e.scratch.mid.p, e.scratch.y.p, e.scratch.kv.p};
   e.scratch.ids.reserve(id_words * 4);
   encoder_reserve(e.dev, e.scratch, 1, (int)M);
-  const void *after[] = {e.scratch.ids.p, e.scratch.x.p, e.scratch.xh.p, e.scratch.qkv.p, e.scratch.ctx.p, e.scratch.mid.p, e.scratch.y.p};
+  const void *after[] = {e.scratch.ids.p, e.scratch.x.p, e.scratch.xh.p, e.scratch.qkv.p, e.scratch.ctx.p, e.scratch.mid.p, e.scratch.y.p, e.scratch.kv.p};
   if (memcmp(before, after, sizeof before) != 0) drop_graphs(e);
 }
 

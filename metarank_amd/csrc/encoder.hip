@@ -344,8 +344,7 @@ bool launch_skinny(const _Float16 *A, const _Float16 *W, const float *bias, cons
 // Packed batches (cu != nullptr): sequence b owns rows [cu[b], cu[b + 1]), every one of them live.  The arithmetic of a
 // query row is the same in both: dead keys contribute exact zeros, whole dead key blocks leave the running state untouched.
 // A workgroup is ATT_HEADS independent wavefronts, one head each (no LDS, no barrier): a batch of 3 840 nine-token
-// queries is 46 080 wavefronts, and dispatching them four to a workgroup is cheaper than one by one.
-constexpr int ATT_HEADS = 4;
+// queries is 46 080 wavefronts, and dispatching them four to a workgroup is cheaper than one by one (ATT_HEADS, encoder.hpp).
 template <int DH>
 __global__ __launch_bounds__(64 * ATT_HEADS) void attention_kernel(const _Float16 *__restrict__ qkv, const int32_t *__restrict__ mask, const int32_t *__restrict__ cu,
                                                                   int seq_pad, int H, int heads, float scale, _Float16 *__restrict__ ctx) {
@@ -955,10 +954,17 @@ __global__ __launch_bounds__(256) void attention_f32_kernel(const float *__restr
   }
 }
 
+// a split handle's attention goes to attention_split: only under MRK_ENCODER_SPLIT_ATTENTION=1, which no other precision looks at;
+// a head size that kernel does not take stays where it is today
+bool split_attention_on(const EncoderDev &enc) {
+  return enc.split && switches().encoder_split_attention && attention_split_takes(enc.shape.hidden / enc.shape.heads);
+}
+
 }  // namespace
 
 void encoder_reserve(const EncoderDev &enc, EncoderScratch &sc, int n, int seq) {
   const size_t M = (size_t)n * seq, H = enc.shape.hidden, I = enc.shape.inter;
+  if (split_attention_on(enc)) sc.kv.reserve(attention_split_kv_bytes(M, H));
   const size_t w = enc.f32_activations() ? 4 : 2;  // bytes per activation between the products
   sc.x.reserve(M * H * 4);
   sc.xh.reserve(M * H * 2);
@@ -995,13 +1001,18 @@ static void forward_impl(const EncoderDev &enc, EncoderScratch &sc, int n, int s
       else if (epi == EPI32_RES) launch_gemm_f32<EPI32_RES>(A, w32, bias, res, out, M, N, K, s);
       else launch_gemm_f32<EPI32_NONE>(A, w32, bias, res, out, M, N, K, s);
     };
+    const bool split_attention = split_attention_on(enc);
+    if (split_attention && sc.kv.cap < attention_split_kv_bytes(M, H))   // (the switch moved between encoder_reserve and here)
+      throw StatusError(MRK_ERR_DEVICE, "encoder: the K / V planes of split attention were not reserved");
     for (size_t l = 0; l < enc.layers.size(); ++l) {
       const LayerDev &L = enc.layers[l];
       const LayerDev32 W = enc.split ? LayerDev32{} : enc.layers32[l];
       const LayerSplit P = enc.split ? enc.layers_split[l] : LayerSplit{};
       dense(EPI32_NONE, x, W.wqkv, P.wqkv, L.bqkv, nullptr, qf, 3 * H, H);
       const dim3 ag32((seq + 15) / 16, (sh.heads + ATT_HEADS - 1) / ATT_HEADS, n);
-      if (switches().encoder_f32_mfma && DH == 32)
+      if (split_attention)   // MRK_ENCODER_SPLIT_ATTENTION=1: this product too on the bf16 instruction (encoder_split.hip)
+        attention_split(qf, sc.kv.as<uint16_t>(), mask, cu, n, seq, M, H, sh.heads, scale, cf, s);
+      else if (switches().encoder_f32_mfma && DH == 32)
         hipLaunchKernelGGL((attention_f32_mfma_kernel<32>), ag32, dim3(64 * ATT_HEADS), 0, s, (const float *)qf, mask, cu, seq, H, sh.heads, scale, cf);
       else if (switches().encoder_f32_mfma && DH == 64)
         hipLaunchKernelGGL((attention_f32_mfma_kernel<64>), ag32, dim3(64 * ATT_HEADS), 0, s, (const float *)qf, mask, cu, seq, H, sh.heads, scale, cf);

@@ -101,6 +101,7 @@ struct EncoderDev {
 // activations of one forward call (grow-only, owned by the encoder handle)
 struct EncoderScratch {
   DevBuf ids, x, xh, qkv, ctx, mid, y, out;
+  DevBuf kv;   // a split handle with MRK_ENCODER_SPLIT_ATTENTION=1: the bf16 planes of a layer's K and V (attention_split)
 };
 
 // encoder.hip ------------------------------------------------------------------------------------
@@ -123,6 +124,15 @@ enum { DENSE_NONE = 0, DENSE_GELU = 1, DENSE_RES = 2 };
 inline bool gemm_split_takes(int N, int K) { return N > 0 && K > 0 && N % 64 == 0 && K % 32 == 0; }
 void gemm_split(int epilogue, const float *A, const uint16_t *W_planes, const float *bias, const float *res, float *out, int M, int N, int K,
                 hipStream_t stream);
+
+// Attention of a split handle with MRK_ENCODER_SPLIT_ATTENTION=1 (encoder_split.hip): both products of a head as split products on
+// the bf16 instruction, the softmax in f32.  qkv f32 [M, 3 H]; kv_planes = EncoderScratch::kv, the bf16 planes of K and V that the
+// call writes first ([plane][M][2 H]); mask / cu / seq as attention_f32_mfma_kernel takes them; ctx f32 [M, H].  Head size 32 or 64.
+constexpr int ATT_HEADS = 4;   // heads (wavefronts) per workgroup of every attention kernel
+inline bool attention_split_takes(int head_size) { return head_size == 32 || head_size == 64; }
+inline size_t attention_split_kv_bytes(size_t M, size_t H) { return (size_t)SPLIT_PLANES * M * 2 * H * sizeof(uint16_t); }
+void attention_split(const float *qkv, uint16_t *kv_planes, const int32_t *mask, const int32_t *cu, int n, int seq, int M, int H, int heads,
+                     float scale, float *ctx, hipStream_t stream);
 
 struct KnnTable;  // knn.hpp
 

@@ -1,4 +1,5 @@
-// The dense products of an encoder loaded with MRK_ENCODER_SPLIT, on gfx950's bf16 matrix instruction.
+// The dense products of an encoder loaded with MRK_ENCODER_SPLIT, on gfx950's bf16 matrix instruction - and, under
+// MRK_ENCODER_SPLIT_ATTENTION=1, its attention (attention_split_kernel, further down).
 //
 // Arithmetic: an f32 operand is a sum of bf16 terms (split_bf16, encoder.hpp: x1 = bf16_rne(x), x2 = bf16_rne(x - x1), ...),
 // a product the sum of the leading term products, every one of them v_mfma_f32_32x32x16_bf16 with f32 accumulation:
@@ -25,6 +26,9 @@
 // the MFMAs, as in gemm_f32_mfma32_kernel; the split of A happens between the two barriers, from registers.
 // The products are computed transposed, as in the f32 kernels: a lane ends up with 4 consecutive output columns of one token.
 #include <hip/hip_runtime.h>
+
+#include <cfloat>
+#include <cmath>
 
 #include "encoder.hpp"
 #include "launch_shape.hpp"
@@ -319,6 +323,203 @@ void launch_gemm_split(const float *A, const uint16_t *W, const float *bias, con
   }
 }
 
+// ---- attention of a split handle (MRK_ENCODER_SPLIT_ATTENTION=1): S = scale Q K^T and O = softmax(S + mask) V as split products.
+//
+// Where K and V are split: ONCE per layer, by split_kv_kernel, into bf16 planes in global memory ([plane][token][K of all heads | V of
+// all heads], EncoderScratch::kv) - every query block of a sequence reads the same K / V rows, and a wavefront that split them in its
+// own registers would spend ~14 VALU operations an element on each of them again (S / 32 times per row).  One head per wavefront means
+// the wavefronts of a workgroup share no K / V, so LDS planes would be shared by nobody; the planes in memory are shared by every query
+// block, and the attention kernel needs neither LDS nor a barrier.  Q is split once per wavefront in registers, P once per key block.
+//
+// The kernel: one wavefront per (32 queries, head, sequence), ATT_HEADS wavefronts (heads) per workgroup, as attention_kernel /
+// attention_f32_mfma_kernel.  Scores are computed transposed, S^T = K Q^T: K rows are the instruction's A operand (a lane's 16-byte
+// load of a K plane - key l & 31, d 16 t + 8 (l >> 5) .. + 7 - IS the fragment), the query's Q terms the B operand, the contraction
+// walks the head dimension in DH / 16 steps.  A lane then owns query column l & 31 and 16 of the block's 32 keys (register 4 v + e =
+// key 8 v + 4 (l >> 5) + e): the softmax is a per-lane reduction plus one exchange with lane ^ 32, f32 with libm expf, running maximum
+// and sum over key blocks of 32, and registers 8 c .. 8 c + 7, split, are the B fragment of step c of O^T = V^T P^T - k slot j of that
+// step stands for key 16 c + 8 (j >> 2) + 4 (l >> 5) + (j & 3) on both operands, so step c covers exactly keys 16 c .. 16 c + 15 of the block
+// and the contraction ascends in steps of 16 keys.  V^T's fragment (row d = l & 31, those 8 keys) is gathered from the V planes with
+// eight 2-byte loads: 32 consecutive lanes read 64 consecutive bytes of one key's row.
+//
+// Canonical order, both products, a = the query side (Q, P), b = the key side (K, V): C0 += a1 b1, C1 += a1 b2, C1 += a2 b1 per step,
+// two accumulators from +0.  S^T = scale (C0 + C1) per key block; O keeps its C0 and C1 across key blocks, both rescaled by the running
+// maximum's exp(m_old - m_new) as attention_f32_mfma_kernel rescales its one, and ends as (C0 + C1) / l.
+//
+// What a (sequence, head, query)'s bits depend on: its own sequence.  Key blocks start at the sequence's first token, in the padded
+// and the packed form alike; a key past the sequence's end or with mask 0 gets probability +0 in both planes, i.e. +0 terms into
+// accumulators that hold +0 or a sum; a block without a live key (the sequence's own mask decides, uniformly over the wavefront)
+// leaves the state untouched; a live block always runs both of its 16-key steps.  A query column never meets another column's data.
+// The next key block's K fragments are loaded before the softmax of the block at hand and fly under it; the V gathers of a step are
+// issued before the split of its probabilities.
+__global__ __launch_bounds__(256) void split_kv_kernel(const float *__restrict__ qkv, uint16_t *__restrict__ kv, int M, int H) {
+  const int per_row = 2 * H / 8;   // pieces of 8 consecutive elements of a token's [K | V]
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (size_t)M * per_row) return;
+  const size_t m = i / per_row;
+  const int j = (int)(i % per_row) * 8;
+  const float *src = qkv + m * 3 * H + H + j;
+  const floatx4 lo = *(const floatx4 *)src, hi = *(const floatx4 *)(src + 4);
+  uint16_t t[8][NP];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) split_bf16(e < 4 ? lo[e] : hi[e - 4], t[e]);
+#pragma unroll
+  for (int p = 0; p < NP; ++p) {
+    uintx4 w;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) w[q] = (uint32_t)t[2 * q][p] | ((uint32_t)t[2 * q + 1][p] << 16);
+    *(uintx4 *)(kv + ((size_t)p * M + m) * 2 * H + j) = w;
+  }
+}
+
+// 8 f32 values as the bf16 fragment of every plane (element e in bits 16 (e & 1) of word e / 2)
+__device__ __forceinline__ void split_fragment(const float (&x)[8], bf16x8 (&f)[NP]) {
+  uint16_t t[8][NP];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) split_bf16(x[e], t[e]);
+#pragma unroll
+  for (int p = 0; p < NP; ++p) {
+    uintx4 w;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) w[q] = (uint32_t)t[2 * q][p] | ((uint32_t)t[2 * q + 1][p] << 16);
+    f[p] = __builtin_bit_cast(bf16x8, w);
+  }
+}
+
+// one step of the canonical order: a = the query side (B operand), b = the key side (A operand)
+__device__ __forceinline__ void split_step(floatx16 &c0, floatx16 &c1, const bf16x8 (&b)[NP], const bf16x8 (&a)[NP]) {
+  c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b[0], a[0], c0, 0, 0, 0);     // a1 b1
+  c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b[1], a[0], c1, 0, 0, 0);     // a1 b2
+  c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b[0], a[1], c1, 0, 0, 0);     // a2 b1
+  if constexpr (NP == 3) {
+    c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b[1], a[1], c1, 0, 0, 0);   // a2 b2
+    c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b[2], a[0], c1, 0, 0, 0);   // a1 b3
+    c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b[0], a[2], c1, 0, 0, 0);   // a3 b1
+  }
+}
+
+template <int DH>
+__global__ __launch_bounds__(64 * ATT_HEADS, 2) void attention_split_kernel(const float *__restrict__ qkv, const uint16_t *__restrict__ kv,
+                                                                        const int32_t *__restrict__ mask, const int32_t *__restrict__ cu, int seq_pad,
+                                                                        int M, int H, int heads, float scale, float *__restrict__ ctx) {
+  constexpr int KS = DH / 16, DB = DH / 32;   // steps of S^T's contraction; 32-row blocks of O^T
+  const int lane = threadIdx.x & 63, c = lane & 31, g = lane >> 5;
+  const int q0 = blockIdx.x * 32, head = blockIdx.y * ATT_HEADS + __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), b = blockIdx.z;
+  if (head >= heads) return;
+  const size_t first = cu ? (size_t)cu[b] : (size_t)b * seq_pad;
+  const int seq = cu ? cu[b + 1] - cu[b] : seq_pad;
+  if (q0 >= seq) return;   // (packed: the grid covers the longest sequence)
+  const int32_t *mrow = mask ? mask + first : nullptr;
+  // wavefront-uniform bases (scalar registers) and 32-bit lane offsets from them: a key's row lies < max_pos x 2 H elements past `first`
+  const uint32_t kvrow = 2u * H;
+  const size_t plane = (size_t)M * kvrow;
+  const uint16_t *kbase[NP], *vbase[NP];
+#pragma unroll
+  for (int p = 0; p < NP; ++p) {
+    kbase[p] = kv + p * plane + first * kvrow + head * DH;
+    vbase[p] = kbase[p] + H;
+  }
+
+  bf16x8 qf[KS][NP];
+  {
+    const int qi = q0 + c < seq ? q0 + c : seq - 1;   // rows past the sequence repeat its last one and are never stored
+    const float *q = qkv + (first + qi) * 3 * H + head * DH + 8 * g;
+#pragma unroll
+    for (int t = 0; t < KS; ++t) {
+      const floatx4 lo = *(const floatx4 *)(q + 16 * t), hi = *(const floatx4 *)(q + 16 * t + 4);
+      const float x[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+      split_fragment(x, qf[t]);
+    }
+  }
+  // the K fragments of the key block at k0: key k0 + c (past the end: the last key, its scores are masked below)
+  auto load_k = [&](bf16x8 (&kf)[KS][NP], int k0) {
+    const uint32_t at = (uint32_t)(k0 + c < seq ? k0 + c : seq - 1) * kvrow + 8 * g;
+#pragma unroll
+    for (int t = 0; t < KS; ++t)
+#pragma unroll
+      for (int p = 0; p < NP; ++p) kf[t][p] = *(const bf16x8 *)(kbase[p] + (at + 16 * t));
+  };
+
+  floatx16 o0[DB], o1[DB];
+#pragma unroll
+  for (int d = 0; d < DB; ++d)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) o0[d][r] = o1[d][r] = 0.f;
+  float m_run = -INFINITY, l_run = 0.f;
+  bf16x8 kf[KS][NP];
+  load_k(kf, 0);
+  for (int k0 = 0; k0 < seq; k0 += 32) {
+    floatx16 s0, s1;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) s0[r] = s1[r] = 0.f;
+#pragma unroll
+    for (int t = 0; t < KS; ++t) split_step(s0, s1, kf[t], qf[t]);
+    if (k0 + 32 < seq) load_k(kf, k0 + 32);
+    float p[16];
+    float bm = -FLT_MAX;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int key = k0 + 8 * (r >> 2) + 4 * g + (r & 3);
+      const bool live = key < seq && (mrow == nullptr || mrow[key < seq ? key : seq - 1] != 0);
+      p[r] = live ? (s0[r] + s1[r]) * scale : -FLT_MAX;
+      bm = fmaxf(bm, p[r]);
+    }
+    bm = fmaxf(bm, __shfl_xor(bm, 32, 64));
+    // a block of dead keys leaves the state untouched, as in attention_f32_mfma_kernel (liveness does not depend on the query: the
+    // branch is uniform); a sequence without any live key ends as 0 * inf = NaN, like that kernel's and the fp32 oracle's
+    if (bm == -FLT_MAX) continue;
+    const float m_new = fmaxf(m_run, bm);
+    const float alpha = expf(m_run - m_new);
+    float ls = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      p[r] = p[r] == -FLT_MAX ? 0.f : expf(p[r] - m_new);
+      ls += p[r];
+    }
+    ls += __shfl_xor(ls, 32, 64);
+    l_run = l_run * alpha + ls;
+    m_run = m_new;
+#pragma unroll
+    for (int d = 0; d < DB; ++d)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        o0[d][r] *= alpha;
+        o1[d][r] *= alpha;
+      }
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      // V^T's fragments of the step: slot j = key k0 + 16 s + 8 (j >> 2) + 4 g + (j & 3), the key of register 8 s + j of p
+      bf16x8 vf[DB][NP];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int key = k0 + 16 * s + 8 * (j >> 2) + 4 * g + (j & 3);
+        const uint32_t at = (uint32_t)(key < seq ? key : seq - 1) * kvrow + c;   // past the end: the last key, its probability is +0
+#pragma unroll
+        for (int d = 0; d < DB; ++d)
+#pragma unroll
+          for (int pl = 0; pl < NP; ++pl) vf[d][pl][j] = __builtin_bit_cast(__bf16, vbase[pl][at + 32 * d]);
+      }
+      bf16x8 pf[NP];
+      const float x[8] = {p[8 * s], p[8 * s + 1], p[8 * s + 2], p[8 * s + 3], p[8 * s + 4], p[8 * s + 5], p[8 * s + 6], p[8 * s + 7]};
+      split_fragment(x, pf);
+#pragma unroll
+      for (int d = 0; d < DB; ++d) split_step(o0[d], o1[d], vf[d], pf);
+    }
+  }
+  if (q0 + c >= seq) return;
+  const float inv = 1.0f / l_run;   // (l_run == 0: no live key at all -> 0 * inf = NaN)
+  float *dst = ctx + (first + q0 + c) * H + head * DH;
+  // O^T[d][query]: registers 4 v .. 4 v + 3 are d = 32 block + 8 v + 4 g .. + 3 of the lane's query
+#pragma unroll
+  for (int d = 0; d < DB; ++d)
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      floatx4 quad;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) quad[e] = (o0[d][4 * v + e] + o1[d][4 * v + e]) * inv;
+      *(floatx4 *)(dst + 32 * d + 8 * v + 4 * g) = quad;
+    }
+}
+
 }  // namespace
 
 void gemm_split(int epilogue, const float *A, const uint16_t *W_planes, const float *bias, const float *res, float *out, int M, int N, int K,
@@ -328,6 +529,18 @@ void gemm_split(int epilogue, const float *A, const uint16_t *W_planes, const fl
   if (epilogue == DENSE_GELU) launch_gemm_split<DENSE_GELU>(A, W_planes, bias, res, out, M, N, K, s);
   else if (epilogue == DENSE_RES) launch_gemm_split<DENSE_RES>(A, W_planes, bias, res, out, M, N, K, s);
   else launch_gemm_split<DENSE_NONE>(A, W_planes, bias, res, out, M, N, K, s);
+}
+
+void attention_split(const float *qkv, uint16_t *kv_planes, const int32_t *mask, const int32_t *cu, int n, int seq, int M, int H, int heads,
+                     float scale, float *ctx, hipStream_t s) {
+  const int DH = heads > 0 ? H / heads : 0;
+  if (!attention_split_takes(DH) || n <= 0 || seq <= 0 || M <= 0)
+    throw StatusError(MRK_ERR_UNSUPPORTED, "encoder: split attention takes head sizes 32 and 64, got " + std::to_string(DH));
+  const SplitAttentionPlan p = split_attention_plan(n, seq, M, H, heads);
+  hipLaunchKernelGGL(split_kv_kernel, dim3(p.split_workgroups), dim3(p.split_threads), 0, s, qkv, kv_planes, M, H);
+  const dim3 grid(p.query_blocks, p.head_groups, p.sequences), block(p.threads);
+  if (DH == 32) hipLaunchKernelGGL((attention_split_kernel<32>), grid, block, 0, s, qkv, kv_planes, mask, cu, seq, M, H, heads, scale, ctx);
+  else hipLaunchKernelGGL((attention_split_kernel<64>), grid, block, 0, s, qkv, kv_planes, mask, cu, seq, M, H, heads, scale, ctx);
 }
 
 }  // namespace mrk

@@ -137,4 +137,20 @@ inline SplitPlan split_launch_plan(int M, int N, int K, bool skinny) {
   return {big ? SPLIT_TILE_128 : SPLIT_TILE_64, (unsigned)(8 * (((M + bm - 1) / bm + 7) / 8) * (N / bm)), 256};
 }
 
+// The two launches of a split handle's attention step under MRK_ENCODER_SPLIT_ATTENTION=1 (encoder_split.hip attention_split): the
+// pre-pass that writes the bf16 planes of K and V - one lane per 8 consecutive elements of a token's [K | V], 2 H / 8 of them a token -
+// and the attention kernel's grid: 32 query rows per wavefront (one 32 x 32 x 16 block; `seq` is the padded width, or the longest
+// sequence of a packed batch), `heads_per_group` heads = wavefronts per workgroup, one grid layer per sequence.
+struct SplitAttentionPlan {
+  unsigned split_workgroups;
+  int split_threads;
+  unsigned query_blocks, head_groups, sequences;
+  int threads;
+};
+inline SplitAttentionPlan split_attention_plan(int n, int seq, int M, int H, int heads, int heads_per_group = 4) {
+  const size_t pieces = (size_t)M * (size_t)(2 * H / 8);
+  return {(unsigned)((pieces + 255) / 256), 256, (unsigned)((seq + 31) / 32), (unsigned)((heads + heads_per_group - 1) / heads_per_group), (unsigned)n,
+          64 * heads_per_group};
+}
+
 }  // namespace mrk

@@ -65,7 +65,8 @@ struct Switches {
   int semantic_window = 4;     // MRK_SEMANTIC_WINDOW=k: mrk_index_build_texts runs windows of about k pieces in length order (rows still land in input order; measured faster); 0: input order
   bool encoder_f32_mfma = true;  // MRK_ENCODER_F32_MFMA=0: the f32 products / attention on the vector unit (the test instrument)
   bool encoder_split_skinny = true;  // MRK_ENCODER_SPLIT_SKINNY=0: a split handle's <= 32-row products on the 32 x 64 tile instead of gemm_split_skinny_kernel (same bits; A/B runs)
-  int als_stage_max = 0;       // MRK_ALS_STAGE_MAX=n: the ALS sweeps stage the gathered factor rows of rows of up to n entries in LDS (0: what 16 KiB hold; smaller: tests reach the gather path)
+  bool encoder_split_attention = false;  // MRK_ENCODER_SPLIT_ATTENTION=1: a split handle's attention on the bf16 instruction too (attention_split_kernel); 0: attention_f32_mfma_kernel, as before
+  int als_stage_max = 0;      // MRK_ALS_STAGE_MAX=n: the ALS sweeps stage the gathered factor rows of rows of up to n entries in LDS (0: what 16 KiB hold; smaller: tests reach the gather path)
 };
 const Switches &switches();
 void reload_switches();

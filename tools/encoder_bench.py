@@ -120,6 +120,45 @@ def single(reps, shapes):
     return out
 
 
+ATTENTION_TOKENS = 8192   # tokens of a batch of attention(): 256 sequences of 32, 64 of 128, 16 of 512
+
+
+def attention(reps, shapes):
+    """A split handle's packed batch of ATTENTION_TOKENS tokens in sequences of 32, 128 and 512 with MRK_ENCODER_SPLIT_ATTENTION=0
+    (attention_f32_mfma_kernel) and =1 (attention_split_kernel): same process, the two taken in turn inside every repetition, HIP
+    events around the forward pass (the "encoder" timer), 3 warm-ups, median [min, max] in ms."""
+    import metarank_amd as M
+    from metarank_amd import _native
+    ctx = M.Context(0)
+    ctx.profile_enable(True)
+    rng = np.random.default_rng(9)
+    tj = synth.wordpiece_tokenizer_json(vocab_size=2000, max_length=512)
+    out = {}
+    for name in shapes:
+        shape = SINGLE_SHAPES[name]
+        enc = HipEncoder(synth.bert_safetensors(synth.synthetic_bert(**shape), shape["heads"]), tj, ctx=ctx, precision="split")
+        for seq in (32, 128, 512):
+            ids = rng.integers(5, 2000, size=(ATTENTION_TOKENS // seq, seq)).astype(np.int32); ty = np.zeros_like(ids); m = np.ones_like(ids)
+            ms, emb = {"0": [], "1": []}, {}
+            for r in range(3 + reps):
+                for switch in ms:
+                    os.environ["MRK_ENCODER_SPLIT_ATTENTION"] = switch
+                    _native.reload_switches()
+                    t0 = ctx.profile_get("encoder")[0]
+                    emb[switch] = enc.embed_ids(ids, ty, m)
+                    if r >= 3:
+                        ms[switch].append(ctx.profile_get("encoder")[0] - t0)
+            os.environ.pop("MRK_ENCODER_SPLIT_ATTENTION", None)
+            _native.reload_switches()
+            out[f"{name}_{seq}_tokens"] = {"sequences": int(ids.shape[0]), "ms": {k: float(np.median(v)) for k, v in ms.items()},
+                                           "ms_min_max": {k: [float(min(v)), float(max(v))] for k, v in ms.items()},
+                                           "switch_1_vs_0_time": float(np.median(ms["1"]) / np.median(ms["0"])),
+                                           "max_abs_embedding_diff_1_vs_0": float(np.abs(emb["1"] - emb["0"]).max())}
+        enc.close()
+    ctx.close()
+    return out
+
+
 def rank_agreement(ctx, requests=96, items=100, catalogue=5000, sessions=500, trees=500):
     """bench.py's config 5 in small (24 Ranklens columns + the bi-encoder cosine, a 500-tree forest): how far an fp16 and a split
     handle move the f32 handle's scores and order - INTEGRATION.md's pair of figures."""
@@ -176,7 +215,11 @@ def main():
     ap.add_argument("--compare", type=int, default=0, metavar="REPS", help="f32 / f16 / split side by side (see compare()), nothing else")
     ap.add_argument("--single", type=int, default=0, metavar="REPS", help="one 9- and one 32-token query: f32 / split on the 32 x 64 tile / split on the skinny kernel (see single()), nothing else")
     ap.add_argument("--shape", choices=sorted(SINGLE_SHAPES), default=None, help="--single: this shape only (a kernel trace per shape)")
+    ap.add_argument("--attention", type=int, default=0, metavar="REPS", help="a split handle's 8 192-token batch at 32, 128 and 512 tokens a sequence with MRK_ENCODER_SPLIT_ATTENTION=0 and =1 (see attention()), nothing else; --shape as for --single")
     a = ap.parse_args()
+    if a.attention:
+        print(json.dumps(attention(a.attention, [a.shape] if a.shape else list(SINGLE_SHAPES))))
+        return
     if a.single:
         print(json.dumps(single(a.single, [a.shape] if a.shape else list(SINGLE_SHAPES))))
         return
