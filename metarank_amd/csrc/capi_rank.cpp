@@ -206,7 +206,7 @@ static int shard_chunk(const mrk_batch &b, int count) { return (int)mrk_shard_ch
 
 static void sort_batch(mrk_batch &b) {
   mrk_ctx *ctx = b.ctx;
-  launch_sort(ctx, b.view, b.hb.max_items);
+  b.ran.sort_form = launch_sort(ctx, b.view, b.hb.max_items);
   if (b.big.empty()) return;
   ScopedKernelTimer timer(ctx, "sort");
   for (auto &br : b.big) {

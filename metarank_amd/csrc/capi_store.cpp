@@ -386,6 +386,16 @@ int mrk_debug_batch_launch(mrk_batch *b, int64_t *out10) {
   });
 }
 
+/* not part of include/mrk.h: the ordering launch of a batch's last run - *out = 0 none (a one-launch run, no sort asked), 1 sort_kernel,
+ * 2 the wavefront-per-request sort_wave_kernel */
+int mrk_debug_batch_order(mrk_batch *b, int64_t *out) {
+  return guard([&] {
+    if (!b || !out) throw StatusError(MRK_ERR_INVALID_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(b->bmu);
+    *out = b->ran.sort_form;
+  });
+}
+
 /* not part of include/mrk.h, host only: the arithmetic of the two rules above - out2 = {1 if a table with `insertions` inserted
  * tokens over a column whose largest token id is `max_token` fits the compact entry (features.hpp compact_table_ok), the dynamic
  * LDS bytes of a fused launch (launch_shape.hpp fused_lds_bytes)} */

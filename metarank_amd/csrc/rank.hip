@@ -188,6 +188,55 @@ sort_kernel(BatchDev b, int cap) {
   for (int i = tid; i < n; i += SORT_THREADS) b.order[rq.item_begin + i] = s_idx[i];
 }
 
+// A batch whose largest request has <= SORT_WAVE_MAX candidates (every batch of 100-candidate requests): one WAVEFRONT per
+// request, four requests per workgroup, the keys in registers - no LDS, no barrier.  Lane l holds the keys of candidates l and
+// l + 64; candidate j's key comes to every lane through the scalar registers (readlane of its owner's two halves) and both of the
+// lane's counters take sort_wave_step's increments: sort_kernel's counting rule, so the count is the position in the stable order.
+// sort_kernel spends 256 lanes and a chain of n LDS round trips on such a request, and 2.44 of its 4 wavefronts have no candidate.
+constexpr int SORT_WAVE_REQS = SORT_THREADS / 64;   // requests per workgroup
+static_assert(SORT_WAVE_MAX == 2 * 64, "sort_wave_kernel keeps exactly two keys per lane of a 64-lane wavefront");
+
+__device__ __forceinline__ unsigned long long wave_key_of(unsigned long long v, int lane) {
+  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, lane), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), lane);
+  return (unsigned long long)hi << 32 | lo;
+}
+
+__global__ void __launch_bounds__(SORT_THREADS)
+sort_wave_kernel(BatchDev b) {
+  // (readfirstlane: the request is the wavefront's, so its descriptor and the loop bounds below live in scalar registers)
+  const int r = (int)blockIdx.x * SORT_WAVE_REQS + __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+  if (r >= b.n_req) return;
+  const int lane = (int)threadIdx.x & 63;
+  const ReqDev rq = b.reqs[r];
+  const int n = rq.n_items;
+  if (n <= 0 || n > SORT_WAVE_MAX) return;   // (the host launches this kernel only when no request of the batch is larger)
+  const int i0 = lane, i1 = lane + 64;
+  const unsigned long long mine0 = i0 < n ? sort_key(b.scores[rq.item_begin + i0]) : ~0ull;
+  const unsigned long long mine1 = i1 < n ? sort_key(b.scores[rq.item_begin + i1]) : ~0ull;
+  int before0 = 0, before1 = 0;
+  // Four keys a round, so that the reads of the next keys do not wait on this key's compares.  The bounds are n rounded up to whole
+  // rounds (<= 64, <= 128): a pad's key ~0 precedes no candidate (no score's key is ~0: asc_key), and a pad lane's counts are not stored.
+  const int n4 = (n + 3) & ~3, n_lo = n4 < 64 ? n4 : 64;
+  for (int j0 = 0; j0 < n_lo; j0 += 4) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const SortWaveStep s = sort_wave_step(mine0, i0, mine1, i1, wave_key_of(mine0, j0 + u), j0 + u);
+      before0 += s.lo;
+      before1 += s.hi;
+    }
+  }
+  for (int j0 = 64; j0 < n4; j0 += 4) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const SortWaveStep s = sort_wave_step(mine0, i0, mine1, i1, wave_key_of(mine1, j0 + u - 64), j0 + u);
+      before0 += s.lo;
+      before1 += s.hi;
+    }
+  }
+  if (i0 < n) b.order[rq.item_begin + before0] = i0;
+  if (i1 < n) b.order[rq.item_begin + before1] = i1;
+}
+
 // ---------------------------------------------------------------- Normalize.scale over one matrix column
 // ml/onnx/Normalize.scala:13-45, applied by the bi-/cross-encoder field_match features to the request's raw values
 // (FieldMatchBiencoderFeature.scala:107, FieldMatchCrossEncoderFeature.scala:111).  One workgroup per request.
@@ -492,14 +541,22 @@ void launch_status_or(hipStream_t stream, const int32_t *all, int world, int n_r
 }
 
 // max_items: the batch's largest request (requests of more than SORT_MAX_ITEMS are ordered by bigsort.hip)
-void launch_sort(mrk_ctx *ctx, const BatchDev &b, int max_items) {
-  if (b.n_req <= 0) return;
+// Returns the kernel launched: 0 none, 1 sort_kernel, 2 sort_wave_kernel (no request of more than SORT_WAVE_MAX candidates).
+int launch_sort(mrk_ctx *ctx, const BatchDev &b, int max_items) {
+  if (b.n_req <= 0) return 0;
+  if (max_items <= SORT_WAVE_MAX) {
+    ScopedKernelTimer timer(ctx, "sort");
+    hipLaunchKernelGGL(sort_wave_kernel, dim3((b.n_req + SORT_WAVE_REQS - 1) / SORT_WAVE_REQS), dim3(SORT_THREADS), 0, ctx->launch, b);
+    MRK_HIP(hipGetLastError());
+    return 2;
+  }
   int cap = 64;
   while (cap < std::min(max_items, SORT_MAX_ITEMS)) cap <<= 1;
   const size_t lds = cap <= SORT_COUNT_MAX ? (size_t)cap * 8 : (size_t)cap * 12;
   ScopedKernelTimer timer(ctx, "sort");
   hipLaunchKernelGGL(sort_kernel, dim3(b.n_req), dim3(SORT_THREADS), lds, ctx->launch, b, cap);
   MRK_HIP(hipGetLastError());
+  return 1;
 }
 
 }  // namespace mrk

@@ -59,6 +59,7 @@ struct mrk_batch {
     bool split_sized = false;
     size_t lds = 0, rt_bytes = 0;
     uint32_t thr_cap = 0;
+    int sort_form = 0;   // (mrk_debug_batch_order) the ordering launch: 0 none, 1 sort_kernel, 2 sort_wave_kernel
   } ran;
 };
 

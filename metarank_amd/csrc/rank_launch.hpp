@@ -12,7 +12,7 @@ namespace mrk {
 // rank.hip
 void launch_prepass(mrk_ctx *ctx, const StoreDev &st, const ProgramDev &prog, const BatchDev &b, uint32_t max_req_entries, void *jit_fn);
 void launch_assemble(mrk_ctx *ctx, const StoreDev &st, const ProgramDev &prog, const BatchDev &b);
-void launch_sort(mrk_ctx *ctx, const BatchDev &b, int max_items);
+int launch_sort(mrk_ctx *ctx, const BatchDev &b, int max_items);
 void launch_status_or(hipStream_t stream, const int32_t *all, int world, int n_req, int32_t *status);
 void launch_normalize(mrk_ctx *ctx, const BatchDev &b, int dim, int col, int mode);
 void launch_normalize_big(mrk_ctx *ctx, const BatchDev &b, int dim, int col, int item_begin, int n, int *order, void *scratch);

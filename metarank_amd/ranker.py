@@ -171,6 +171,14 @@ class Batch:
         N.check(fn(self._h, out))
         return dict(zip(("entry_bytes", "lds", "kernel", "qualifies", "tab_entries", "vals_cap", "threads", "thr_cap", "rt_bytes", "split"), [int(x) for x in out]))
 
+    def order_info(self) -> dict:
+        """the batch's last run (mrk_debug_batch_order): sort 0 = no ordering launch, 1 = sort_kernel, 2 = the wavefront-per-request kernel"""
+        fn = N.lib().mrk_debug_batch_order
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]
+        out = C.c_int64(0)
+        N.check(fn(self._h, C.byref(out)))
+        return {"sort": int(out.value)}
+
     def close(self):
         if self._h:
             N.lib().mrk_batch_free(self._h)
