@@ -544,7 +544,8 @@ int mrk_sync(mrk_ctx *ctx);            /* hipStreamSynchronize on the context st
 void *mrk_stream(mrk_ctx *ctx);        /* the hipStream_t all work is enqueued on     */
 
 /* HIP-event timing of the kernels launched by the last mrk_batch_run / predict call on this ctx.
- * names: scorer "score", assembly "assemble", request pre-pass "prepass", sort "sort".
+ * names: scorer "score", assembly "assemble", request pre-pass "prepass", sort "sort", the device medians of numeric
+ * `diversity` features over more than 4 096 values "median" (one timed span around all their launches for a batch).
  * Enable with mrk_profile_enable(ctx, 1); returns accumulated ms and launch count since enable. */
 int mrk_profile_enable(mrk_ctx *ctx, int on);
 int mrk_profile_get(mrk_ctx *ctx, const char *kernel, double *total_ms, int64_t *launches);

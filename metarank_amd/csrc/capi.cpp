@@ -76,6 +76,7 @@ static Switches read_switches() {
   s.encoder_f32_mfma = flag("MRK_ENCODER_F32_MFMA", true);
   s.encoder_split_skinny = flag("MRK_ENCODER_SPLIT_SKINNY", true);
   s.encoder_split_attention = flag("MRK_ENCODER_SPLIT_ATTENTION", false);
+  s.diversity_select = flag("MRK_DIVERSITY_SELECT", true);
   s.als_stage_max = std::max(0, num("MRK_ALS_STAGE_MAX", 0));
   return s;
 }

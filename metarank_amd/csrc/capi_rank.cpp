@@ -58,6 +58,7 @@ void build_batch(mrk_ctx *ctx, const Program &prog, const mrk_request *reqs, int
   Store &store = *ctx->store;
   MRK_HIP(hipSetDevice(ctx->device));
   HostBatch &hb = b.hb;
+  hb.device_median = switches().diversity_select;   // (run_batch / run_values launch select.hip's kernels in front of every stand-alone pre-pass)
   resolve_requests(prog, store, reqs, n_req, ids, hb);
   b.ctx = ctx;
   b.prog = &prog;
@@ -133,6 +134,13 @@ void build_batch(mrk_ctx *ctx, const Program &prog, const mrk_request *reqs, int
       big_bytes = std::max(big_bytes, big_sort_scratch_bytes(hb.reqs[r].n_items));
     }
   if (big_bytes) b.d_sort.reserve(big_bytes);  // one scratch: the big requests of a batch are sorted one after the other on its stream
+  if (!hb.select.entries.empty()) {   // the device medians' scratch, sized from the plan's bounds; its entries go up once per load
+    const size_t entry_bytes = hb.select.entries.size() * sizeof(SelectEntry);
+    b.d_select.reserve(SelectLayout(hb.select).bytes);
+    b.h_select.reserve(entry_bytes);
+    memcpy(b.h_select.p, hb.select.entries.data(), entry_bytes);
+    MRK_HIP(hipMemcpyAsync(b.d_select.p, b.h_select.p, entry_bytes, hipMemcpyHostToDevice, b.s()));
+  }
   b.sh = BatchShape{};
   b.sh.n_req = n_req;
   b.sh.total_items = T;
@@ -185,6 +193,7 @@ static void assemble_matrix(mrk_batch &b, const StoreDev &st, const ProgramDev &
   if (b.sh.fused_ok) {
     launch_rank_fused(ctx, st, pd, b.view, b.sh.fused_entries, b.sh.fused_vals, b.sh.fused_threads, b.sh.fused_split, jit_matrix_fn ? 1 : b.sh.fused_slices, nullptr, nullptr, true, jit_matrix_fn);
   } else {
+    launch_diversity_select(ctx, st, pd, b.view, b.hb.select, b.d_select.p);
     launch_prepass(ctx, st, pd, b.view, b.sh.fused_entries, nullptr);
     launch_assemble(ctx, st, pd, b.view);
   }
@@ -301,6 +310,7 @@ void run_batch(mrk_batch &b, mrk_model *model, int lo, int hi, bool sort, bool d
         b.ran.lds = launch_rank_fused(ctx, st, pd, b.view, sh.fused_entries, sh.fused_vals, sh.fused_threads, sh.fused_split, sh.fused_slices, &q, b.d_cells.as<uint16_t>(), f64, jit_fn,
                                       b.ran.rt_bytes, b.ran.entry_bytes, split_kernel);
       } else {
+        launch_diversity_select(ctx, st, pd, b.view, b.hb.select, b.d_select.p);
         launch_prepass(ctx, st, pd, b.view, sh.fused_entries, jit_prep_fn);
         launch_assemble_cells(ctx, st, pd, b.view, q, b.d_cells.as<uint16_t>(), f64, jit_fn, sh.fused_entries, jit_rt_fn, jit_rt_fn ? model->qs_sig.rt_total : 0u);
       }

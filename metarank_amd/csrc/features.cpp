@@ -1051,10 +1051,12 @@ void resolve_requests(const Program &prog, Store &store, const mrk_request *reqs
     const char *s = reqs[r].item_ids[i];
     return s ? std::string_view(s) : std::string_view("");
   };
-  // Flat ids: the device resolves the slots and the host sizes the pre-pass tables from bounds.  One exception: a numeric
-  // `diversity` over more candidates than the pre-pass sorts needs the exact count of present values, i.e. the slots.
+  hb.select.clear();
+  // Flat ids: the device resolves the slots and the host sizes the pre-pass tables from bounds.  One exception, and only where no
+  // device median follows (hb.device_median): a numeric `diversity` over more candidates than the pre-pass sorts, taken by the
+  // host, needs the exact count of present values, i.e. the slots.
   bool device_ids = ids != nullptr;
-  if (device_ids)
+  if (device_ids && !hb.device_median)
     for (const HostOp &ho : prog.host_ops)
       if (ho.def->type == FType::Diversity)
         for (int r = 0; r < n_req && device_ids; ++r)
@@ -1150,7 +1152,7 @@ void resolve_requests(const Program &prog, Store &store, const mrk_request *reqs
   // pressure there, only the longer walks) its 0.8 % back (LOG.md round 18)
   auto vocab_bound = [&](ColRef c) -> uint64_t { return c.tag >= 0 && c.tag < (int)item_table.cols.size() ? 2ull * item_table.cols[(size_t)c.tag].distinct : 0u; };
   auto col_max_token = [&](ColRef c) -> uint32_t { return c.tag >= 0 && c.tag < (int)item_table.cols.size() ? item_table.cols[(size_t)c.tag].max_token : 0u; };
-  struct Worker { std::vector<Override> overrides; int max_items = 0, max_doubles = 0; std::vector<double> enc; bool compact = true; };
+  struct Worker { std::vector<Override> overrides; int max_items = 0, max_doubles = 0; std::vector<double> enc; bool compact = true; std::vector<std::pair<int, int>> select; };
   std::vector<Worker> workers((size_t)std::max(1, n_workers));
   std::vector<uint64_t> req_entries((size_t)n_req, 0);  // hash-table entries of every request (its tables are contiguous)
   // one request: everything but the position of its tables in the arena
@@ -1342,11 +1344,18 @@ void resolve_requests(const Program &prog, Store &store, const mrk_request *reqs
         uint64_t tokens = 0;
         int taken = 0, doubles = 0;
         int mode = -1;  // -1 undecided, 0 other, 1 string, 2 double
-        if (device_ids) {  // bounds: the first `top` candidates all present, each with the longest list the column ever held
+        // More candidates than the device pre-pass sorts in LDS, and a device median follows: select.hip takes the entry - by this
+        // bound, not by the data, so nothing is walked or counted here (a string column is sized from the same bounds as under flat ids)
+        const bool select = hb.device_median && std::min(f.div_top, rq.n_items) > PREP_MAX_VALUES;
+        if (device_ids || select) {  // bounds: the first `top` candidates all present, each with the longest list the column ever held
           doubles = std::min(f.div_top, rq.n_items);
           tokens = (uint64_t)doubles * col_max_len(pe.item_col);
         }
-        for (int i = 0; !device_ids && i < rq.n_items && taken < f.div_top; ++i) {
+        if (select) {
+          wk.select.emplace_back(r, ho.prep_base);
+          doubles = 0;
+        }
+        for (int i = 0; !device_ids && !select && i < rq.n_items && taken < f.div_top; ++i) {
           HostCell c = host_cell(store, SC_ITEM, hb.item_slot[begin + i], pe.item_col);
           if (c.tag == TAG_MISSING) continue;
           if (mode < 0) mode = (c.tag == TAG_STRING || c.tag == TAG_STRING_LIST) ? 1 : (c.tag == TAG_DOUBLE ? 2 : 0);
@@ -1357,7 +1366,8 @@ void resolve_requests(const Program &prog, Store &store, const mrk_request *reqs
         }
         PrepOut &po = hb.prep_out[(size_t)r * prog.prep.size() + ho.prep_base];
         if (doubles > PREP_MAX_VALUES) {
-          // More values than the device pre-pass sorts in LDS (`top` above 4 096 over that many present candidates): the host
+          // More values than the device pre-pass sorts in LDS (`top` above 4 096 over that many present candidates) and no device
+          // median (MRK_DIVERSITY_SELECT=0, or a caller without select.hip's launch): the host
           // holds the same values in its mirror (this path runs with host-resolved slots) and takes the median itself -
           // commons-math Percentile(50), LEGACY estimation, NaN removed (DiversityFeature.scala:113-126), the arithmetic of
           // rank_device.hpp median_of - and hands it over as a finished pre-pass result.
@@ -1499,7 +1509,9 @@ void resolve_requests(const Program &prog, Store &store, const mrk_request *reqs
     hb.max_items = std::max(hb.max_items, wk.max_items);
     hb.max_doubles = std::max(hb.max_doubles, wk.max_doubles);
     hb.compact_tables = hb.compact_tables && wk.compact;
+    for (const auto &e : wk.select) hb.select.add(e.first, e.second, hb.reqs[(size_t)e.first].n_items, prog.prep[(size_t)e.second].top);
   }
+  if (!hb.select.fits()) throw StatusError(MRK_ERR_UNSUPPORTED, "batch has more numeric diversity medians over 4 096 values than the device select takes (65 535 entries, 2^32 values)");
   for (const CrossValue &c : cross_values)
     if (c.v == c.v) hb.overrides.push_back({(uint32_t)(hb.reqs[c.req].item_begin + c.item), (uint32_t)c.dst, c.v});
   hb.arena_entries = arena;

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "rank.hpp"
+#include "select.hpp"
 #include "store.hpp"
 
 struct mrk_encoder;
@@ -135,6 +136,11 @@ struct HostBatch {
   int max_items = 0;              // largest request
   int total_items = 0;
   bool device_ids = false;        // item_slot / item_req are left to the device (resolve.hip): the batch came with flat ids
+  // Set by the CALLER before resolve_requests: the batch pipeline runs select.hip's kernels over `select` before the pre-pass
+  // (capi_rank.cpp, MRK_DIVERSITY_SELECT).  false - a caller that launches no such kernel, or the switch at 0: the host takes the
+  // median of a numeric diversity over more values than the pre-pass sorts from its mirror, as before that kernel.
+  bool device_median = false;
+  SelectPlan select;              // the (request, numeric-diversity entry) pairs with min(top, n_items) > PREP_MAX_VALUES
 };
 
 // The compact 4-byte entry of the pre-pass tables (table32_device.hpp: 20 bits of token id, 11 of count) holds a table when

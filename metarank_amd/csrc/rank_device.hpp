@@ -787,7 +787,7 @@ __device__ __forceinline__ void prepass_request(const StoreDev &st, const Prog &
   MRK_PHASE(sc.clk, sc.acc[1]);
   // ---- diversity (DiversityFeature.scala:72-103), PREP_GROUP entries at a time
   for (int e0 = 0; e0 < n_prep;) {
-    if (prog.prep[e0].kind != PREP_DIVERSITY || po_out[e0].preset) { ++e0; continue; }  // (preset: the host took this entry's median)
+    if (prog.prep[e0].kind != PREP_DIVERSITY || po_out[e0].preset) { ++e0; continue; }  // (preset: select.hip or the host took this entry's median)
     int ent[PREP_GROUP];
     int n = 0, e1 = e0;
     for (; e1 < n_prep && n < PREP_GROUP; ++e1) {

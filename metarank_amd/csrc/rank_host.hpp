@@ -28,6 +28,8 @@ struct mrk_batch {
   bool fetch_enqueued = false;          // the download of d_out into h_out is on the stream behind the last run
   mrk::DevBuf d_cells;            // the scorer's binned tile (bit-vector models), grow-only
   mrk::DevBuf d_sort;                        // scratch of the multi-workgroup sort (bigsort.hip)
+  mrk::DevBuf d_select;                      // scratch of the numeric diversity medians over more values than the pre-pass sorts (select.hip; SelectLayout of hb.select)
+  mrk::PinBuf h_select;                      // ... the staging copy of its entries
   mrk::DevBuf d_norm_order;                  // norm: position over a request of more than SORT_MAX_ITEMS candidates: its column's order
   mrk::DevBuf d_gather;                      // mrk_batch_gather_scores: the scores of every rank
   mrk::DevBuf d_gather_status;               // item-sharded runs: the status words of every rank ([world][n_req]) before they are OR-ed

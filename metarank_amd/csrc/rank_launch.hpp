@@ -5,6 +5,7 @@
 #include "qs_device.hpp"
 #include "rank.hpp"
 #include "runtime.hpp"
+#include "select.hpp"
 #include "sort_device.hpp"   // SortSrc
 
 namespace mrk {
@@ -34,6 +35,8 @@ void launch_rank_serve_walk(mrk_ctx *ctx, hipStream_t stream, const StoreDev &st
 // bigsort.hip
 void launch_big_sort(mrk_ctx *ctx, hipStream_t stream, const SortSrc &src, int n, int *out_order, void *scratch);
 size_t big_sort_scratch_bytes(int n);
+// select.hip
+void launch_diversity_select(mrk_ctx *ctx, const StoreDev &st, const ProgramDev &prog, const BatchDev &b, const SelectPlan &plan, void *scratch);
 // score.hip
 void launch_score_batch(mrk_ctx *ctx, mrk_model *m, const double *d_x, int rows, int cols, double *d_out,
                         int *d_status, const uint32_t *d_row_req);

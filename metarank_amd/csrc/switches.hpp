@@ -66,6 +66,7 @@ struct Switches {
   bool encoder_f32_mfma = true;  // MRK_ENCODER_F32_MFMA=0: the f32 products / attention on the vector unit (the test instrument)
   bool encoder_split_skinny = true;  // MRK_ENCODER_SPLIT_SKINNY=0: a split handle's <= 32-row products on the 32 x 64 tile instead of gemm_split_skinny_kernel (same bits; A/B runs)
   bool encoder_split_attention = false;  // MRK_ENCODER_SPLIT_ATTENTION=1: a split handle's attention on the bf16 instruction too (attention_split_kernel); 0: attention_f32_mfma_kernel, as before
+  bool diversity_select = true;  // MRK_DIVERSITY_SELECT=0: the HOST takes the median of a numeric diversity over more values than the pre-pass sorts (walk + std::sort of its mirror, as before select.hip; A/B runs)
   int als_stage_max = 0;      // MRK_ALS_STAGE_MAX=n: the ALS sweeps stage the gathered factor rows of rows of up to n entries in LDS (0: what 16 KiB hold; smaller: tests reach the gather path)
 };
 const Switches &switches();
